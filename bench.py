@@ -20,6 +20,13 @@ Contract: one JSON line on stdout from rank 0.  Launched by the driver as
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 `python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment re-executes itself under torch.distributed.run
 with N ranks (dist.launch_plan); it exits with an error if fewer than N GPUs are visible or WORLD_SIZE != N.
+
+A plain run does what the headline needs: set up, warm up, time the K steps, the PCoA on the result, one line.  --full adds
+everything else the line can carry (CPU baseline and parity sample, Householder and band eigensolvers, standalone and fp32
+rooflines, sustained legs, the int8 path, the uint8 / bitset / CSR / PLINK boundaries, configs[0], [2] and [3] on one GPU,
+PCIe rates); --no-extras and --no-cpu-baseline trim a --full run.  --dump-outputs DIR writes what the timed path returned
+after its last step (S, the principal coordinates, their eigenvalues) as DIR/<name>.npy: the inputs are seeded, so two
+builds can be compared output for output.
 """
 import argparse
 import ctypes
@@ -75,6 +82,24 @@ def cpu_baseline(x_dev, n, budget_s=20.0):
             "blas_note": "best-effort numpy/OpenBLAS sgemm X^T X on %d variants" % nb}, s_ref, sample
 
 
+def dump_outputs(path, s, comps, lam, budget=60 * 10**6):
+    """--dump-outputs: what a caller of the timed path receives -- S after the last step (int64 counts, exact in float64), the
+    principal coordinates and their eigenvalues -- as <path>/<name>.npy.  An S over `budget` bytes is written as a fixed,
+    seeded sample of its rows (gram_rows, and their indices in gram_row_index)."""
+    os.makedirs(path, exist_ok=True)
+    out = {"components": np.asarray(comps, dtype=np.float64), "eigenvalues": np.asarray(lam, dtype=np.float64)}
+    room = budget - sum(a.nbytes for a in out.values())
+    if s.size * 8 <= room:
+        out["gram"] = s.astype(np.float64)
+    else:
+        k = int(min(s.shape[0], max(1, room // (8 * (s.shape[1] + 1)))))
+        rows = np.sort(np.random.default_rng(SEED).choice(s.shape[0], size=k, replace=False))
+        out["gram_rows"] = s[rows].astype(np.float64)
+        out["gram_row_index"] = rows.astype(np.float64)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def pmc_for(key):
     """HBM traffic per 10^6 variants from rocprofv3 --pmc passes.  k-bits kernels: profiles/gram_pmc_live.json, written by
     `tools/gpu_round.sh <tag> pmclive` from the tree it ran on and named by that tree's source hash; a file of another
@@ -114,10 +139,15 @@ def main():
     ap.add_argument("--ld", type=int, default=0,
                     help="row pitch of the resident fp32 tile in floats (0 = packed: ld = samples).  pcoa.h: a pitch that is a "
                          "multiple of 32 floats starts every row on a 128-byte line")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline (CPU baseline, other kernels, input boundaries, "
+                         "configurations and eigensolvers; minutes): off by default")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned after its last step as DIR/<name>.npy (float64, <= 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--pcoa-reps", type=int, default=3)
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the reference-only extras (uint8 input, config-0 CSR job, PCIe rates, Householder timing)")
+                    help="--full: skip the reference-only extras (uint8 input, config-0 CSR job, PCIe rates, Householder timing)")
     ap.add_argument("--allreduce", choices=["native", "torch"], default="native",
                     help="N>1: native = RCCL communicator inside libpcoa_hip (in-place int32), torch = "
                          "export -> torch.distributed.all_reduce -> import")
@@ -140,6 +170,8 @@ def main():
     ap.add_argument("--sustained-seconds", type=float, default=2.0,
                     help="extras: length of the additional sustained run (same step, >= this many seconds of timed region)")
     args = ap.parse_args()
+    extras = args.full and not args.no_extras
+    cpu_base = args.full and not args.no_cpu_baseline
 
     import torch
     import torch.distributed as td
@@ -431,19 +463,22 @@ def main():
             comps, lam, nz = eng.compute(2)
             pcoa.append(1e3 * (time.perf_counter() - t1))
         tim2 = eng.timings()
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, eng.gram(), comps, lam)
         # the dense (gap-independent) eigensolver on the same S, for reference
-        pcoa_hh = []
-        with P.PcoaEngine(n, device=local_rank, eig="householder") as eng_hh:
-            eng_hh.load_gram(eng.gram())
-            for _ in range(0 if args.no_extras else 2):
-                t1 = time.perf_counter()
-                comps_hh, lam_hh, _ = eng_hh.compute(2)
-                pcoa_hh.append(1e3 * (time.perf_counter() - t1))
-            tim_hh = eng_hh.timings()
+        pcoa_hh, tim_hh = [], None
+        if extras:
+            with P.PcoaEngine(n, device=local_rank, eig="householder") as eng_hh:
+                eng_hh.load_gram(eng.gram())
+                for _ in range(2):
+                    t1 = time.perf_counter()
+                    comps_hh, lam_hh, _ = eng_hh.compute(2)
+                    pcoa_hh.append(1e3 * (time.perf_counter() - t1))
+                tim_hh = eng_hh.timings()
         # the gap-independent Krylov path (r06): Lanczos as the band iteration from the start (block width num_pc + 2), which is
         # what the engine falls back to for clustered leading eigenvalues before the dense solver
         pcoa_band, band_steps, agree_band = [], None, None
-        if not args.no_extras:
+        if extras:
             with P.PcoaEngine(n, device=local_rank, eig="band") as eng_b:
                 eng_b.load_gram(eng.gram())
                 for _ in range(3):
@@ -452,7 +487,7 @@ def main():
                     pcoa_band.append(1e3 * (time.perf_counter() - t1))
                 band_steps = int(eng_b.timings()["lanczos_block_steps"])
             agree_band = float(max(np.linalg.norm(comps[:, c] - comps_b[:, c] * np.sign(np.dot(comps[:, c], comps_b[:, c]))) for c in range(2)))
-        agree = None if args.no_extras else float(max(
+        agree = None if not extras else float(max(
             np.linalg.norm(comps[:, c] - comps_hh[:, c] * np.sign(np.dot(comps[:, c], comps_hh[:, c]))) for c in range(2)))
         out = {
             "metric": METRIC, "value": value, "unit": "variants/s", "n_gpus": world, "steps": args.steps,
@@ -497,18 +532,18 @@ def main():
             "pcoa_wall_ms_householder": float(min(pcoa_hh)) if pcoa_hh else None,
             "pcoa_householder_breakdown_ms": {k: 1e3 * tim_hh[k] / 2 for k in
                                               ("center_seconds", "tridiag_seconds", "eig_seconds",
-                                               "backtransform_seconds")},
+                                               "backtransform_seconds")} if tim_hh is not None else None,
             "pcoa_paths_max_vector_diff": agree,
             "pcoa_wall_ms_band_lanczos": float(min(pcoa_band)) if pcoa_band else None, "band_lanczos_basis_vectors": band_steps,
             "pcoa_band_vs_default_max_vector_diff": agree_band,
             "eigenvalues": [float(t) for t in lam], "nonzero_rows": int(nz),
             "device": dev_name, "cu_count": cus,
             # what tools/pmc_live.py needs to turn per-process counter totals into per-variant traffic
-            "pmc_manifest": {"source_hash": pkg("_lib").source_hash(), "no_extras": bool(args.no_extras),
+            "pmc_manifest": {"source_hash": pkg("_lib").source_hash(), "no_extras": not extras,
                              "fp32_variants_through_the_engine": int((args.warmup + args.steps) * v) if args.scaling == "weak" else None,
                              "pipeline": bool(info["pipeline"])},
         }
-        if not args.no_extras and info["pipeline"]:
+        if extras and info["pipeline"]:
             # the two kernels STANDALONE (each alone on the whole chip, strictly serial on one stream): what their own
             # rooflines look like without the other kernel beside them -- three steps on a PCOA_FLAG_NO_PIPELINE engine
             with P.PcoaEngine(n, device=local_rank, gram_kernel=args.gram_kernel, pipeline=False, operand=args.operand) as es:
@@ -560,7 +595,7 @@ def main():
                 alone = out["roofline_standalone"]["pre_pass" if obj.get("bound") == "hbm" else "contraction"]
                 obj["alone_on_the_chip"] = {"avg_launch_ms": alone["avg_launch_ms"], "achieved": alone["achieved"],
                                             "frac": alone["frac"], "source": "roofline_standalone (same run, same box)"}
-        if not args.no_extras and world == 1:
+        if extras and world == 1:
             # the same step, sustained: a timed region of >= --sustained-seconds (boost clocks, thermal state and a 53-ms
             # burst are different things); S would pass int32 on the way, so the int64 fold is part of it, as in a real
             # whole-genome stream
@@ -580,7 +615,7 @@ def main():
             one_step(steps - 1)
             finish_job()
             fence()
-        if not args.no_extras:
+        if extras:
             # north_star's literal kernel: the fp32-MFMA Gram (v_mfma_f32_32x32x2_f32) on a slice of the same batch, so that
             # the record carries its roofline fraction too ("at >= 40 % fp32-MFMA roofline")
             vf = int(min(131072, resident))
@@ -599,7 +634,7 @@ def main():
                 "variants_per_s": vf / f32_s if f32_s > 0 else 0.0, "variants": vf, "kernel": "gram_f32_kernel<4>",
                 "avg_launch_ms": 1e3 * f32_s,
                 "note": "gram_kernel=f32 (PCOA_FLAG_GRAM_F32_MFMA) on the first %d variants of the batch; not the default path" % vf}
-        if world == 1 and not args.no_extras:
+        if world == 1 and extras:
             # the int8-MFMA path (tiles with carrier multiplicities; forced here on the binary cohort: same kernels, same bytes):
             # pre-pass and contraction in series (r06 tried the pre-pass on a stream of its own with two workspaces: the two
             # kernels do not co-reside -- the contraction's waves hold every register of a CU -- and the step stayed the sum)
@@ -618,7 +653,7 @@ def main():
                                 "pack_ms_per_step": 1e3 * ti8["pack_seconds"] / steps, "gram_ms_per_step": 1e3 * ti8["gram_kernel_seconds"] / steps,
                                 "note": "PCOA_FLAG_GRAM_I8_MFMA on the same fp32 batch: pack fp32 -> int8 (HBM-bound) + v_mfma_i32_32x32x32_i8; "
                                         "in series on the ctx stream (pcoa.h: this path is not pipelined)"}
-        if world == 1 and not args.no_extras:
+        if world == 1 and extras:
             # the production input format (one byte per genotype): same contraction, 4x cheaper pre-pass
             x1 = x[:min(v, resident)]          # the extras below work on the first resident batch
             x8 = x1.to(torch.uint8)
@@ -679,11 +714,11 @@ def main():
             del bits
             out["csr_boundary"] = csr_boundary(P, torch, dev, local_rank, n, x1, s_dense, steps, args.operand)
             out["plink_bed_boundary"] = plink_bed_boundary(P, torch, dev, local_rank, n, x1, s_dense, steps, args.operand)
-        if world == 1 and not args.no_extras and args.config2_variants > 0:
+        if world == 1 and extras and args.config2_variants > 0:
             # BASELINE configs[2] on ONE GPU: the whole 40 M-variant cohort as carrier bitsets (12.6 GB, resident), one job
             out["config2_one_gpu_bits"] = config2_one_gpu_bits(P, synth, torch, dev, local_rank, n, args.config2_variants,
                                                                args.operand)
-        if world == 1 and not args.no_extras:
+        if world == 1 and extras:
             # BASELINE configs[0] stand-in: BRCA1-sized region (2,500 variants) through the faithful CSR boundary
             # (pcoa_accumulate_calls, host arrays), end to end: H2D + densify + Gram + finalize + PCoA + D2H
             v1 = 2500
@@ -704,7 +739,7 @@ def main():
                 tt1 = e1.timings()
             # the same job on the CPU restatement at 4 threads (= the reference's local[4]) -- baseline only
             cpu_c0 = None
-            if not args.no_cpu_baseline:
+            if cpu_base:
                 sys.path.insert(0, os.path.join(ROOT, "oracle"))
                 oracle = importlib.import_module("variants_pca_oracle")
                 prev = oracle.num_threads()
@@ -724,7 +759,7 @@ def main():
                 "wall_ms": float(min(walls[1:])), "wall_ms_all": walls,
                 "eig_method": {1: "lanczos", 2: "householder"}.get(tt1["eig_method"], "?"),
                 "eigenvalues": [float(t) for t in l1], "cpu_local4": cpu_c0}
-        if world == 1 and not args.no_extras:
+        if world == 1 and extras:
             # PCIe-inclusive rates (host tiles through the staging path): noted, never `value`
             hv = min(v, resident, 131072)
             xh = x[:hv].cpu().numpy()
@@ -741,7 +776,7 @@ def main():
                             "pcoa_accumulate_bits with is_device_ptr=0)" % hv)
             out["pcie_inclusive"] = pcie
             del xh, xh8, xhb
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and cpu_base:
             base, s_ref, sample = cpu_baseline(x[:min(v, resident)], n)
             out["cpu_baseline"] = base
             # the CPU sample doubles as an end-of-run parity check of the measured path
@@ -750,7 +785,7 @@ def main():
             out["parity_vs_cpu_sample"] = bool(np.array_equal(eng.gram(), s_ref))
         else:
             out["cpu_baseline"] = None
-        if world == 1 and not args.no_extras and args.config3_samples > 0:
+        if world == 1 and extras and args.config3_samples > 0:
             # BASELINE configs[3] at FULL size on this one GPU, by wall-clock (the reference cannot hold N > 46,340 at all,
             # VariantsPca.scala:176-177, :185).  Last of the extras: the resident fp32 batches are released first (S alone is 40 GB).
             x1 = None   # (a view of the resident batches)

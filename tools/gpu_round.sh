@@ -22,7 +22,7 @@ for s in $STEPS; do
       echo "tests exit $?" | tee -a $OUT/summary.txt; grep -E "passed|failed|error" $OUT/tests.log | tail -3 | tee -a $OUT/summary.txt
       grep -E "^(FAILED|ERROR)|PCoA wall" $OUT/tests.log | head -40 | tee -a $OUT/summary.txt ;;
     bench)
-      timeout 900 python bench.py --gpus 1 --steps 5 --warmup 2 > $OUT/bench.json 2> $OUT/bench.err
+      timeout 900 python bench.py --gpus 1 --steps 5 --warmup 2 --full > $OUT/bench.json 2> $OUT/bench.err
       echo "bench exit $?" | tee -a $OUT/summary.txt; cat $OUT/bench.json | tee -a $OUT/summary.txt; tail -5 $OUT/bench.err ;;
     pmcf32)
       for c in FETCH_SIZE WRITE_SIZE; do
@@ -64,10 +64,10 @@ for s in $STEPS; do
         echo "tests $AB_VAR=$t exit $?: $(tail -1 $OUT/tests_$t.log)" | tee -a $OUT/summary.txt
       done ;;
     benchf32)
-      timeout 900 python bench.py --gpus 1 --steps 5 --warmup 2 --gram-kernel f32 --no-cpu-baseline > $OUT/bench_f32.json 2> $OUT/bench_f32.err
+      timeout 900 python bench.py --gpus 1 --steps 5 --warmup 2 --gram-kernel f32 --full --no-cpu-baseline > $OUT/bench_f32.json 2> $OUT/bench_f32.err
       echo "bench f32 exit $?" | tee -a $OUT/summary.txt; cat $OUT/bench_f32.json | tee -a $OUT/summary.txt; tail -5 $OUT/bench_f32.err ;;
     prof)
-      ( cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OLDPWD/$OUT/prof -o trace -- python $OLDPWD/bench.py --gpus 1 --steps 3 --warmup 1 --no-cpu-baseline > $OLDPWD/$OUT/prof_bench.json 2> $OLDPWD/$OUT/prof.err )
+      ( cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OLDPWD/$OUT/prof -o trace -- python $OLDPWD/bench.py --gpus 1 --steps 3 --warmup 1 --full --no-cpu-baseline > $OLDPWD/$OUT/prof_bench.json 2> $OLDPWD/$OUT/prof.err )
       echo "prof exit $?" | tee -a $OUT/summary.txt
       find $OUT/prof -name "*kernel_stats*" | head -3 | while read f; do echo "--- $f"; head -25 "$f" | cut -c1-220; done | tee -a $OUT/summary.txt
       # keep the merge-back small: drop the raw per-dispatch trace if it is large
