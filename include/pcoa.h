@@ -207,6 +207,54 @@ int pcoa_strip_matvec(pcoa_ctx* ctx, const double* v, const double* means, doubl
 int pcoa_strip_set_centering(pcoa_ctx* ctx, const double* means, double matrix_mean);
 int pcoa_strip_matvec_device(pcoa_ctx* ctx, const double* v_dev, double* y_dev);
 
+/* ---- layout of S over the engines of one job ------------------------------------------------------------------------
+ * FULL: every engine holds a whole N x N partial S (4 N^2 bytes) for its share of the variants; the partials are reduced
+ * into engine 0 (peer copies: engine 0 stages one more 4 N^2 matrix when the engines sit on different devices, RCCL
+ * otherwise).  STRIPS: engine g holds S[:, col0_g .. col0_g + cols_g) (pcoa_create_strip, 4 N cols_g bytes), is fed EVERY
+ * variant, and nothing is reduced; computePca is pcoa_compute_strips.  A strip contraction computes N x cols, both
+ * triangles, so the strips together do about twice the matrix-core work per variant of the full layout's upper triangle. */
+#define PCOA_LAYOUT_AUTO   0
+#define PCOA_LAYOUT_FULL   1
+#define PCOA_LAYOUT_STRIPS 2
+#define PCOA_LAYOUT_FREE_FRACTION 0.9   /* share of an engine's free bytes the auto rule lets S (+ staging) take */
+
+/* Pure function (no GPU): the layout for N samples on n_engines engines.
+ *   request PCOA_LAYOUT_FULL / _STRIPS: that layout.  PCOA_LAYOUT_AUTO with 1 < n_engines <= N: STRIPS exactly when the
+ *   full layout does not fit, i.e. when for some engine g   4 N^2 (+ 4 N^2 more on engine 0: the reduce staging)
+ *   > PCOA_LAYOUT_FREE_FRACTION * free_bytes[g];  FULL otherwise.  Always FULL with one engine (one strip needs the same
+ *   4 N^2 bytes) and when n_engines > N.  The rule is about
+ *   memory only -- which layout is faster at a size where both fit has not been measured.
+ *   free_bytes[g]: the bytes engine g may use (needed for AUTO only).  Engines that share a device split it: a device with
+ *   F free bytes and m engines gives each F / m (the hosts fill it so, from pcoa_device_memory).
+ * On STRIPS, col0_out[g] / cols_out[g] (n_engines entries each) receive the column ranges: balanced, every inner cut rounded
+ * to the nearest multiple of 256 (the contraction's tile width) when that keeps it strictly between the cut before it and
+ * N, and the plain cuts N g / n_engines if some strip would still be empty (the same ranges as strips.strip_ranges).  On FULL
+ * they are not written.  PCOA_ERR_INVALID_ARG for a bad request, N or n_engines <= 0, or STRIPS with n_engines > N. */
+int pcoa_plan_layout(int32_t n_samples, int32_t n_engines, const int64_t* free_bytes, int32_t request, int32_t* layout_out,
+                     int32_t* col0_out, int32_t* cols_out);
+
+/* hipMemGetInfo on device `device_ordinal` (the calling thread's current device is left as it was).  Either pointer may be
+ * NULL.  PCOA_ERR_NO_DEVICE / PCOA_ERR_HIP without a usable device. */
+int pcoa_device_memory(int32_t device_ordinal, int64_t* free_out, int64_t* total_out);
+
+/* computePca (VariantsPca.scala:198-231) over the strip owners of ONE process; they may share a device or sit on several.
+ * owners[0 .. n_owners) must be strip owners of the same N whose ranges, in array order, tile [0, N) without gap or
+ * overlap, else PCOA_ERR_INVALID_ARG.  Errors are reported on owners[0] (pcoa_last_error names a failing owner's index).
+ *   rowSums (:206-211): each owner's exact int64 column sums land in one N-vector on owners[0] (the lead): in place on the
+ *     same device, by peer copy from another; the matrix mean, the non-zero rows and the means rowSums / N follow on the
+ *     lead and the means are copied once into every owner's resident centring buffer (as pcoa_strip_set_centering).
+ *   principal components (:224-227): the lead's Lanczos (as pcoa_lanczos_with_matvec) with a built-in product: every owner
+ *     waits on an event for v (a peer copy when it sits on another device), multiplies its strip on its own stream and
+ *     writes its piece straight to y + col0 of the lead's vector (a peer-mapped pointer where peer access exists, else a
+ *     local piece + a peer copy); the lead's stream waits on every owner's event.  No host synchronisation per step beyond
+ *     the Lanczos iteration's own.  The additions are those of pcoa_strip_matvec_device in the same order: eigenvalues and
+ *     components equal, bit for bit, strips.compute_pca_over_strips over the same owners.
+ *   N < 32 (below the Lanczos path): the strips are read into one N x N matrix on the host, loaded into a temporary full
+ *     engine on the lead's device and solved by pcoa_compute -- the single engine's result by construction.
+ * Outputs as pcoa_compute: [num_pc][N] sign-normalised columns, the eigenvalues, the non-zero rows.  Synchronising. */
+int pcoa_compute_strips(pcoa_ctx* const* owners, int32_t n_owners, int32_t num_pc, double* out_components,
+                        double* out_eigenvalues, int32_t* nonzero_rows_out);
+
 /* Replaces: VariantsPcaDriver.stop (VariantsPca.scala:283-285). */
 void pcoa_destroy(pcoa_ctx* ctx);
 

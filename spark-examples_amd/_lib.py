@@ -31,6 +31,10 @@ PCOA_FLAG_EIG_LANCZOS = 0x40
 PCOA_FLAG_NO_PIPELINE = 0x80
 PCOA_FLAG_OPERAND_FP4 = 0x100
 PCOA_FLAG_EIG_BAND = 0x200
+PCOA_LAYOUT_AUTO = 0
+PCOA_LAYOUT_FULL = 1
+PCOA_LAYOUT_STRIPS = 2
+PCOA_LAYOUT_FREE_FRACTION = 0.9
 MATVEC_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p)
 PCOA_BED_HOST_ASYNC = 2
 PCOA_CALLS_DEVICE_PTR = 1
@@ -107,6 +111,9 @@ _SIGNATURES = [
     ("pcoa_strip_matvec", ctypes.c_int, [_vp, _vp, _vp, ctypes.c_double, _vp]),
     ("pcoa_strip_set_centering", ctypes.c_int, [_vp, _vp, ctypes.c_double]),
     ("pcoa_strip_matvec_device", ctypes.c_int, [_vp, _vp, _vp]),
+    ("pcoa_plan_layout", ctypes.c_int, [_i32, _i32, _vp, _i32, ctypes.POINTER(_i32), _vp, _vp]),
+    ("pcoa_device_memory", ctypes.c_int, [_i32, ctypes.POINTER(_i64), ctypes.POINTER(_i64)]),
+    ("pcoa_compute_strips", ctypes.c_int, [_vp, _i32, _i32, _vp, _vp, ctypes.POINTER(_i32)]),
     ("pcoa_destroy", None, [_vp]),
     ("pcoa_last_error", ctypes.c_char_p, [_vp]),
     ("pcoa_reset", ctypes.c_int, [_vp]),

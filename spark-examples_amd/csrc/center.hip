@@ -224,6 +224,20 @@ __global__ __launch_bounds__(256) void strip_finish_kernel(const double* __restr
   }
 }
 
+// pcoa_compute_strips: the column sums of one owner land in the LEAD's N-vectors at the owner's columns -- exact int64 (what
+// stats_kernel reduces) and as doubles (what col_means_kernel divides) -- the bands added in the order strip_finish_kernel
+// adds them.  The pointers are the lead's buffers (same device) or owner-local ones that the caller peer-copies.
+__global__ __launch_bounds__(256) void strip_col_sums_gather_kernel(const int64_t* __restrict__ partial, int32_t cols,
+                                                                    int32_t bands, int64_t* __restrict__ out_i64,
+                                                                    double* __restrict__ out_f64) {
+  const int jj = blockIdx.x * 256 + threadIdx.x;
+  if (jj >= cols) return;
+  int64_t acc = 0;
+  for (int b = 0; b < bands; ++b) acc += partial[(int64_t)b * cols + jj];
+  out_i64[jj] = acc;
+  out_f64[jj] = (double)acc;
+}
+
 }  // namespace
 
 int64_t strip_ws_doubles(int32_t n, int32_t cols) {
@@ -256,6 +270,38 @@ hipError_t launch_strip_matvec(const int32_t* s32, const int64_t* s64_or_null, i
     hipLaunchKernelGGL((strip_band_kernel<true, false>), grid, dim3(256), 0, stream, s32, s64_or_null, n, col0, cols, v, means,
                        matrix_mean, ws + cols);
   hipLaunchKernelGGL(strip_finish_kernel<true>, dim3((unsigned)((cols + 255) / 256)), dim3(256), 0, stream, ws + cols, cols, bands, ws);
+  return hipGetLastError();
+}
+
+hipError_t launch_strip_col_sums_to(const int32_t* s32, const int64_t* s64_or_null, int32_t n, int32_t cols, double* ws,
+                                    int64_t* out_i64, double* out_f64, hipStream_t stream) {
+  const int bands = (n + STRIP_BAND - 1) / STRIP_BAND;
+  const dim3 grid((unsigned)((cols + 1023) / 1024), (unsigned)bands);
+  if (s64_or_null)
+    hipLaunchKernelGGL((strip_band_kernel<false, true>), grid, dim3(256), 0, stream, s32, s64_or_null, n, 0, cols, nullptr, nullptr,
+                       0.0, ws + cols);
+  else
+    hipLaunchKernelGGL((strip_band_kernel<false, false>), grid, dim3(256), 0, stream, s32, s64_or_null, n, 0, cols, nullptr, nullptr,
+                       0.0, ws + cols);
+  hipLaunchKernelGGL(strip_col_sums_gather_kernel, dim3((unsigned)((cols + 255) / 256)), dim3(256), 0, stream,
+                     reinterpret_cast<const int64_t*>(ws + cols), cols, bands, out_i64, out_f64);
+  return hipGetLastError();
+}
+
+hipError_t launch_strip_matvec_to(const int32_t* s32, const int64_t* s64_or_null, int32_t n, int32_t col0, int32_t cols,
+                                  const double* v, const double* means, double matrix_mean, double* ws, double* y_out,
+                                  hipStream_t stream) {
+  const int bands = (n + STRIP_BAND - 1) / STRIP_BAND;
+  const dim3 grid((unsigned)((cols + 1023) / 1024), (unsigned)bands);
+  if (s64_or_null)
+    hipLaunchKernelGGL((strip_band_kernel<true, true>), grid, dim3(256), 0, stream, s32, s64_or_null, n, col0, cols, v, means,
+                       matrix_mean, ws + cols);
+  else
+    hipLaunchKernelGGL((strip_band_kernel<true, false>), grid, dim3(256), 0, stream, s32, s64_or_null, n, col0, cols, v, means,
+                       matrix_mean, ws + cols);
+  // the same finish as launch_strip_matvec (bands in order), its output pointed at the gathered vector
+  hipLaunchKernelGGL(strip_finish_kernel<true>, dim3((unsigned)((cols + 255) / 256)), dim3(256), 0, stream, ws + cols, cols, bands,
+                     y_out);
   return hipGetLastError();
 }
 

@@ -179,6 +179,15 @@ hipError_t launch_strip_col_sums(const int32_t* s32, const int64_t* s64_or_null,
 // matrix in the reference's operation order (VariantsPca.scala:216-221), from the strip's column (S is symmetric)
 hipError_t launch_strip_matvec(const int32_t* s32, const int64_t* s64_or_null, int32_t n, int32_t col0, int32_t cols,
                                const double* v, const double* means, double matrix_mean, double* ws, hipStream_t stream);
+// pcoa_compute_strips: the column sums as exact int64 and as doubles into out_i64[0..cols) / out_f64[0..cols) (any buffers
+// on the ws's device, e.g. the lead's N-vectors at the owner's columns)
+hipError_t launch_strip_col_sums_to(const int32_t* s32, const int64_t* s64_or_null, int32_t n, int32_t cols, double* ws,
+                                    int64_t* out_i64, double* out_f64, hipStream_t stream);
+// launch_strip_matvec with the piece written to y_out[0..cols) (a device pointer the ws's device can write: same device or
+// peer-mapped) instead of ws[0..cols); bit-identical values
+hipError_t launch_strip_matvec_to(const int32_t* s32, const int64_t* s64_or_null, int32_t n, int32_t col0, int32_t cols,
+                                  const double* v, const double* means, double matrix_mean, double* ws, double* y_out,
+                                  hipStream_t stream);
 
 // ---- symmetric eigensolver (eig.hip) ----------------------------------------------------------
 struct EigWorkspace {

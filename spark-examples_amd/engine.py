@@ -455,3 +455,63 @@ class PcoaEngine(object):
 
     def reset_timings(self):
         self._check(self._lib.pcoa_reset_timings(self._ctx))
+
+
+# ---------------------------------------------------------------------------------------------- layout of S (pcoa.h)
+LAYOUTS = {"auto": L.PCOA_LAYOUT_AUTO, "full": L.PCOA_LAYOUT_FULL, "strips": L.PCOA_LAYOUT_STRIPS}
+
+
+def plan_layout(n_samples, n_engines, free_bytes=None, request="auto"):
+    """pcoa_plan_layout (no GPU): ("full", None) or ("strips", [(col0, cols), ..] per engine).  free_bytes: the bytes each
+    engine may use (engines sharing a device split it, see engine_free_bytes); needed for "auto" only."""
+    lib = L.load()
+    if request not in LAYOUTS:
+        raise ValueError("layout must be auto, full or strips")
+    k = int(n_engines)
+    fb = None
+    if free_bytes is not None:
+        fb = np.ascontiguousarray(free_bytes, dtype=np.int64)
+        if fb.shape != (k,):
+            raise ValueError("free_bytes needs one entry per engine")
+    col0 = np.zeros(max(k, 1), dtype=np.int32)
+    cols = np.zeros(max(k, 1), dtype=np.int32)
+    out = ctypes.c_int32(0)
+    rc = lib.pcoa_plan_layout(int(n_samples), k, _ptr(fb) if fb is not None else None, LAYOUTS[request], ctypes.byref(out),
+                              _ptr(col0), _ptr(cols))
+    if rc != L.PCOA_OK:
+        raise PcoaError(rc, lib.pcoa_last_error(None).decode(errors="replace"))
+    if out.value == L.PCOA_LAYOUT_FULL:
+        return "full", None
+    return "strips", [(int(a), int(b)) for a, b in zip(col0[:k], cols[:k])]
+
+
+def device_memory(device):
+    """(free, total) bytes of a device (pcoa_device_memory: hipMemGetInfo)."""
+    lib = L.load()
+    fr, tot = ctypes.c_int64(0), ctypes.c_int64(0)
+    rc = lib.pcoa_device_memory(int(device), ctypes.byref(fr), ctypes.byref(tot))
+    if rc != L.PCOA_OK:
+        raise PcoaError(rc, lib.pcoa_last_error(None).decode(errors="replace"))
+    return int(fr.value), int(tot.value)
+
+
+def engine_free_bytes(device_of_engine, free_of_device):
+    """The free_bytes of plan_layout: engine g gets the free bytes of its device divided by the engines on that device."""
+    devs = [int(d) for d in device_of_engine]
+    return [int(free_of_device(d)) // devs.count(d) for d in devs]
+
+
+def compute_strips(owners, num_pc=2):
+    """computePca over the strip owners of this process (pcoa_compute_strips): `owners` are PcoaEngine(strip=...) whose ranges
+    tile [0, N) in list order; they may share a device.  Returns (components [N, k], eigenvalues [k], nonzero_rows) as
+    PcoaEngine.compute does."""
+    if not owners:
+        raise ValueError("no strip owners")
+    lead = owners[0]
+    n, k = lead.n, int(num_pc)
+    arr = (ctypes.c_void_p * len(owners))(*[o._ctx.value for o in owners])
+    comps = np.zeros((max(k, 1), n), dtype=np.float64)
+    lam = np.zeros(max(k, 1), dtype=np.float64)
+    nz = ctypes.c_int32(0)
+    lead._check(lead._lib.pcoa_compute_strips(arr, len(owners), k, _ptr(comps), _ptr(lam), ctypes.byref(nz)))
+    return np.ascontiguousarray(comps[:k].T), lam[:k].copy(), int(nz.value)

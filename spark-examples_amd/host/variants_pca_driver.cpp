@@ -72,6 +72,8 @@ struct Conf {  // PcaConf / GenomicsConf (GenomicsConf.scala:31-101), same flag 
   int gpus = 1;                       // --gpus k: k host threads, one engine per device, variants dealt by contiguous ranges
   std::vector<int> gpu_map;           // --gpu-map a,b,..: device ordinal of each engine (default: --gpu, --gpu + 1, ..)
   std::string reduce = "auto";        // --reduce auto|rccl|peer: all-reduce over RCCL / peer copies + int64 adds
+  std::string layout = "auto";        // --layout auto|full|strips: S whole on every engine (variants dealt, then reduced) or
+                                      // tiled by columns (every engine fed every variant, no reduction); auto: pcoa_plan_layout
   std::string plink_decode = "device";  // --plink-decode device|host: where the 2-bit codes become carrier bits
   long stream_rows = 131072;          // --stream-rows: variants per block of the streaming PLINK reader (four blocks are page-locked: 328 MB at N = 2504)
   bool no_stream = false;             // --no-stream: a single PLINK fileset / VCF through the in-memory path (whole data set, then carrier lists)
@@ -122,6 +124,7 @@ Conf parse(int argc, char** argv) {
       while (std::getline(ss, tok, ',')) c.gpu_map.push_back(std::atoi(tok.c_str()));
     }
     else if (a == "--reduce") c.reduce = one(i);
+    else if (a == "--layout") c.layout = one(i);
     else if (a == "--plink-decode") c.plink_decode = one(i);
     else if (a == "--stream-rows") c.stream_rows = std::atol(one(i).c_str());
     else if (a == "--no-stream") c.no_stream = true;
@@ -146,6 +149,8 @@ Conf parse(int argc, char** argv) {
     for (int g = 0; g < c.gpus; ++g) c.gpu_map.push_back(c.gpu + g);
   if ((int)c.gpu_map.size() != c.gpus) die("--gpu-map must name exactly --gpus devices");
   if (c.reduce != "auto" && c.reduce != "rccl" && c.reduce != "peer") die("--reduce takes auto, rccl or peer");
+  if (c.layout != "auto" && c.layout != "full" && c.layout != "strips") die("--layout takes auto, full or strips");
+  if (c.layout == "strips" && c.reduce == "rccl") die("--layout strips has no reduction step: it cannot take --reduce rccl");
   if (c.plink_decode != "device" && c.plink_decode != "host") die("--plink-decode takes device or host");
   if (c.stream_rows < 1) die("--stream-rows must be >= 1");
   return c;
@@ -1049,20 +1054,31 @@ void stream_plink_shard(const Conf& conf, const PlinkMeta& m, int g, int k, pcoa
 // k engines, fed by k host threads, reduced into engine 0 (VariantsPca.scala:190: reduceByKey).  RCCL where every engine has
 // a device of its own and the collective runtime binds; else peer copies + int64 adds (pcoa_gram_reduce_from), which also work
 // with several engines on ONE device (--gpu-map 0,0: the way this path is tested on a single-GPU box).
-pcoa_ctx* run_engines(const Conf& conf, int32_t n, const std::function<void(int, int, pcoa_ctx*)>& feed, std::string* how,
-                      double* feed_seconds, const std::function<void(const std::vector<pcoa_ctx*>&)>& prepare) {
+//
+// The strip layout (`strips`: one column range per engine) has no reduction: engine g is a strip owner of
+// S[:, col0_g .. col0_g + cols_g) and is fed EVERY variant -- feed(g, 0, 1, ..): its thread runs the whole ingest road --,
+// and all k owners come back.  Otherwise feed(g, g, k, ..) gives engine g its shard and only engine 0 comes back.
+std::vector<pcoa_ctx*> run_engines(const Conf& conf, int32_t n, const std::vector<std::pair<int32_t, int32_t>>& strips,
+                                   const std::function<void(int, int, int, pcoa_ctx*)>& feed, std::string* how,
+                                   double* feed_seconds, const std::function<void(const std::vector<pcoa_ctx*>&)>& prepare) {
   const int k = conf.gpus;
+  const bool tiled = !strips.empty();
   std::vector<pcoa_ctx*> ctx((size_t)k, nullptr);
-  for (int g = 0; g < k; ++g)
-    if (pcoa_create(&ctx[(size_t)g], n, conf.gpu_map[(size_t)g], PCOA_FLAG_DEFAULT) != PCOA_OK)
-      die("pcoa_create on device " + std::to_string(conf.gpu_map[(size_t)g]) + ": " + pcoa_last_error(nullptr));
+  for (int g = 0; g < k; ++g) {
+    const int rc = tiled ? pcoa_create_strip(&ctx[(size_t)g], n, strips[(size_t)g].first, strips[(size_t)g].second,
+                                             conf.gpu_map[(size_t)g], PCOA_FLAG_DEFAULT)
+                         : pcoa_create(&ctx[(size_t)g], n, conf.gpu_map[(size_t)g], PCOA_FLAG_DEFAULT);
+    if (rc != PCOA_OK)
+      die(std::string(tiled ? "pcoa_create_strip" : "pcoa_create") + " on device " + std::to_string(conf.gpu_map[(size_t)g]) +
+          ": " + pcoa_last_error(nullptr));
+  }
   // operand buffers and the computePca workspace now, not inside the first accumulate calls (pcoa_reserve: the warm-up a Spark
   // executor runs once per GPU)
   for (int g = 0; g < k; ++g) check(ctx[(size_t)g], pcoa_reserve(ctx[(size_t)g], (int64_t)1 << 20, g == 0 ? conf.num_pc : 0), "pcoa_reserve");
   bool distinct = true;
   for (int a = 0; a < k; ++a)
     for (int b = a + 1; b < k; ++b) distinct = distinct && conf.gpu_map[(size_t)a] != conf.gpu_map[(size_t)b];
-  bool use_rccl = k > 1 && (conf.reduce == "rccl" || (conf.reduce == "auto" && distinct));
+  bool use_rccl = !tiled && k > 1 && (conf.reduce == "rccl" || (conf.reduce == "auto" && distinct));
   if (use_rccl && !distinct) die("--reduce rccl needs a device of its own for every engine");
   uint8_t uid[128] = {0};
   if (use_rccl && pcoa_comm_unique_id(uid) != PCOA_OK) {
@@ -1075,7 +1091,7 @@ pcoa_ctx* run_engines(const Conf& conf, int32_t n, const std::function<void(int,
   const auto t_feed = std::chrono::steady_clock::now();  // engines exist: from here to the reduced S is the job
   for (int g = 0; g < k; ++g)
     th.emplace_back([&, g] {
-      feed(g, k, ctx[(size_t)g]);
+      feed(g, tiled ? 0 : g, tiled ? 1 : k, ctx[(size_t)g]);
       if (use_rccl) {  // every rank reaches the collective from its own thread
         void* comm = nullptr;
         int rc = pcoa_comm_init(ctx[(size_t)g], uid, g, k, &comm);
@@ -1089,16 +1105,23 @@ pcoa_ctx* run_engines(const Conf& conf, int32_t n, const std::function<void(int,
     for (int g = 0; g < k; ++g)
       if (rccl_rc[(size_t)g] != PCOA_OK) die(std::string("all-reduce over RCCL: ") + pcoa_last_error(ctx[(size_t)g]));
     *how = "RCCL all-reduce over " + std::to_string(k) + " engines";
+  } else if (tiled) {
+    *how = "strip layout: " + std::to_string(k) + " owner(s), each fed every variant, no reduction; columns";
+    for (int g = 0; g < k; ++g)
+      *how += (g ? ", [" : " [") + std::to_string(strips[(size_t)g].first) + ", " +
+              std::to_string(strips[(size_t)g].first + strips[(size_t)g].second) + ") on device " +
+              std::to_string(conf.gpu_map[(size_t)g]);
   } else if (k > 1) {
     for (int g = 1; g < k; ++g) check(ctx[0], pcoa_gram_reduce_from(ctx[0], ctx[(size_t)g]), "reduce");
     *how = "peer reduction of " + std::to_string(k) + " engines into engine 0";
   } else {
     *how = "one engine";
   }
-  check(ctx[0], pcoa_gram_finalize(ctx[0]), "getSimilarityMatrix");
+  for (int g = 0; g < (tiled ? k : 1); ++g) check(ctx[(size_t)g], pcoa_gram_finalize(ctx[(size_t)g]), "getSimilarityMatrix");
   *feed_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_feed).count();
+  if (tiled) return ctx;
   for (int g = 1; g < k; ++g) pcoa_destroy(ctx[(size_t)g]);
-  return ctx[0];
+  return {ctx[0]};
 }
 
 int main(int argc, char** argv) {
@@ -1253,6 +1276,42 @@ int main(int argc, char** argv) {
   }
   if (sample_idx.empty()) sample_idx.push_back(0);
 
+  // the layout of S (pcoa_plan_layout; the rule is in pcoa.h): decided before any engine exists.  auto with k > 1 asks every
+  // device of --gpu-map for its free memory (engines sharing a device split it) and keeps the full layout where it fits or
+  // where the devices cannot be asked (engine creation then reports why)
+  std::vector<std::pair<int32_t, int32_t>> strips;   // empty: the full layout
+  {
+    const int k = conf.gpus;
+    int32_t request = conf.layout == "full" ? PCOA_LAYOUT_FULL : conf.layout == "strips" ? PCOA_LAYOUT_STRIPS : PCOA_LAYOUT_AUTO;
+    if (request == PCOA_LAYOUT_STRIPS && k > n)
+      die("--layout strips: " + std::to_string(k) + " owners for " + std::to_string(n) + " samples; every owner needs a column");
+    std::vector<int64_t> free_bytes((size_t)k, 0);
+    if (request == PCOA_LAYOUT_AUTO && k > 1 && k <= n) {   // (one engine: full, without asking a device)
+      std::map<int, int64_t> dev_free;
+      for (int d : conf.gpu_map) {
+        int64_t fr = 0;
+        if (dev_free.count(d)) continue;
+        if (pcoa_device_memory(d, &fr, nullptr) != PCOA_OK) {
+          request = PCOA_LAYOUT_FULL;
+          break;
+        }
+        dev_free[d] = fr;
+      }
+      for (int g = 0; g < k && request == PCOA_LAYOUT_AUTO; ++g)
+        free_bytes[(size_t)g] = dev_free[conf.gpu_map[(size_t)g]] /
+                                (int64_t)std::count(conf.gpu_map.begin(), conf.gpu_map.end(), conf.gpu_map[(size_t)g]);
+    }
+    std::vector<int32_t> col0((size_t)k), cols((size_t)k);
+    int32_t layout = PCOA_LAYOUT_FULL;
+    if (pcoa_plan_layout(n, k, free_bytes.data(), request, &layout, col0.data(), cols.data()) != PCOA_OK)
+      die(std::string("pcoa_plan_layout: ") + pcoa_last_error(nullptr));
+    if (layout == PCOA_LAYOUT_STRIPS) {
+      if (conf.reduce == "rccl") die("the strip layout has no reduction step: it cannot take --reduce rccl");
+      for (int g = 0; g < k; ++g) strips.emplace_back(col0[(size_t)g], cols[(size_t)g]);
+    }
+  }
+  const int per_owner = strips.empty() ? 1 : conf.gpus;   // every owner ingests every variant: its counts are k-fold
+
   // getSimilarityMatrix (:182-191) and computePca (:198-231) on the GPU(s)
   // The RDD[Seq[Int]] rows go over as what they are: carrier lists (pcoa_accumulate_calls_ex).  The device checks the
   // range of every index and finds a list that names a callset twice -- mergeDatasets can produce one when a key occurs
@@ -1262,15 +1321,16 @@ int main(int argc, char** argv) {
   StreamStats stream_stats;
   std::atomic<int64_t> fed_as_bits{0}, fed_as_lists{0}, joined_rows{0};
   std::vector<unsigned char*> blocks;  // page-locked blocks of the streaming reader, four per engine (filled by `prepare`)
-  // engine g of k takes the contiguous range shard_range(g, k, rows) -- the reference's partitions (:184)
-  std::function<void(int, int, pcoa_ctx*)> feed = [&](int g, int k, pcoa_ctx* ctx) {
+  // engine g takes shard `shard` of `k`: the contiguous range shard_range(shard, k, rows) -- the reference's partitions (:184);
+  // under the strip layout every engine takes shard 0 of 1, i.e. every variant
+  std::function<void(int, int, int, pcoa_ctx*)> feed = [&](int g, int shard, int k, pcoa_ctx* ctx) {
     if (stream_plink) {
       unsigned char* const four[4] = {blocks[(size_t)(4 * g)], blocks[(size_t)(4 * g + 1)], blocks[(size_t)(4 * g + 2)], blocks[(size_t)(4 * g + 3)]};
-      stream_plink_shard(conf, plink, g, k, ctx, &stream_stats, four);
+      stream_plink_shard(conf, plink, shard, k, ctx, &stream_stats, four);
       return;
     }
     CarrierFeeder feeder;   // one per engine thread
-    const unsigned feed_threads = std::max(1u, std::min<unsigned>(conf.ingest_threads > 0 ? (unsigned)conf.ingest_threads : std::thread::hardware_concurrency(), 16u) / (unsigned)k);
+    const unsigned feed_threads = std::max(1u, std::min<unsigned>(conf.ingest_threads > 0 ? (unsigned)conf.ingest_threads : std::thread::hardware_concurrency(), 16u) / (unsigned)conf.gpus);
     struct Tally {   // the engines' totals, for the stderr line
       CarrierFeeder& f; std::atomic<int64_t>& bits; std::atomic<int64_t>& lists;
       ~Tally() { bits += f.rows_as_bits; lists += f.rows_as_lists; }
@@ -1278,7 +1338,7 @@ int main(int argc, char** argv) {
     if (stream_join) {   // pass 2: key partitions q = g, g + k, ..: read back, join / merge, feed
       std::vector<int32_t> idx;
       std::vector<int64_t> offs;
-      for (int q = g; q < spill.parts; q += k) {
+      for (int q = shard; q < spill.parts; q += k) {
         std::vector<std::vector<Variant>> sets;
         for (int sset = 0; sset < spill.sets; ++sset) sets.push_back(spill.read(sset, q));
         std::vector<std::vector<int32_t>> rows;
@@ -1319,7 +1379,7 @@ int main(int argc, char** argv) {
       return;
     }
     int64_t ra, rb;
-    shard_range(g, k, (int64_t)row_offsets.size() - 1, &ra, &rb);
+    shard_range(shard, k, (int64_t)row_offsets.size() - 1, &ra, &rb);
     if (rb <= ra) return;
     feeder.feed(ctx, conf, n, sample_idx.data(), row_offsets.data() + ra, rb - ra, feed_threads);
   };
@@ -1341,7 +1401,7 @@ int main(int argc, char** argv) {
     for (int g = 0; g < conf.gpus; ++g) {
       unsigned char* b = blocks[(size_t)(4 * g)];
       int64_t r0 = 0, r1 = 0;
-      shard_range(g, conf.gpus, (int64_t)plink.keep.size(), &r0, &r1);
+      shard_range(strips.empty() ? g : 0, strips.empty() ? conf.gpus : 1, (int64_t)plink.keep.size(), &r0, &r1);
       const int64_t wrows = std::max<int64_t>(1, std::min<int64_t>(conf.stream_rows, r1 - r0));   // never more than the shard itself
       std::memset(b, ref_a1 ? 0x00 : 0xFF, (size_t)wrows * plink.bpv);
       pcoa_ctx* e = engines[(size_t)g];
@@ -1352,33 +1412,46 @@ int main(int argc, char** argv) {
     }
     warmup_s = now_s() - tw0;
   };
-  pcoa_ctx* ctx = run_engines(conf, n, feed, &how, &feed_s, prepare);
+  const std::vector<pcoa_ctx*> owners = run_engines(conf, n, strips, feed, &how, &feed_s, prepare);
+  pcoa_ctx* const ctx = owners[0];
   if (stream_join) {
     std::fprintf(stderr, "%zu variant set(s) through %d key partitions: %lld records, %.1f MB of spill files in %s\n",
                  conf.input_path.size(), spill.parts, (long long)spilled_records, spill.bytes / 1e6, spill.dir.c_str());
     spill.remove_all();
   }
   for (unsigned char* b : blocks) (void)pcoa_host_free_pinned(b);
-  check(ctx, pcoa_gram_finalize(ctx), "getSimilarityMatrix");
+  for (pcoa_ctx* o : owners) check(o, pcoa_gram_finalize(o), "getSimilarityMatrix");
   {
     struct rusage ru;
     getrusage(RUSAGE_SELF, &ru);
     if (stream_plink)
       std::fprintf(stderr, "Streamed %lld variants x %d samples from %s.bed in %.3f s = %.1f M variants/s (ingest -> reduced S; engines "
                    "already created and a warm-up block of %.3f s per run -- first-use allocation, code-object load -- NOT included; %s; "
-                   "slowest shard: reads %.3f s, feed calls %.3f s; %s decode); peak RSS %.0f MB\n", (long long)stream_stats.variants, n,
-                   plink.prefix.c_str(), feed_s, stream_stats.variants / feed_s / 1e6, warmup_s, how.c_str(), stream_stats.read_s,
+                   "slowest shard: reads %.3f s, feed calls %.3f s; %s decode); peak RSS %.0f MB\n", (long long)stream_stats.variants / per_owner, n,
+                   plink.prefix.c_str(), feed_s, stream_stats.variants / per_owner / feed_s / 1e6, warmup_s, how.c_str(), stream_stats.read_s,
                    stream_stats.feed_s, conf.plink_decode.c_str(), ru.ru_maxrss / 1024.0);
     else
       std::fprintf(stderr, "getSimilarityMatrix: %zu variants in %.3f s (%s%s; %lld rows as carrier bitsets, %lld as carrier lists); peak RSS %.0f MB\n",
-                   stream_join ? (size_t)joined_rows.load() : stream_vcf ? (size_t)streamed_variants : row_offsets.size() - 1, feed_s, how.c_str(),
+                   stream_join ? (size_t)(joined_rows.load() / per_owner) : stream_vcf ? (size_t)(streamed_variants / per_owner) : row_offsets.size() - 1,
+                   feed_s, how.c_str(),
                    stream_join ? "; sets streamed into key-partitioned spill files, joined one partition at a time" :
-                   stream_vcf ? "; the VCF streamed block by block: read + parse + feed" : "", (long long)fed_as_bits.load(),
-                   (long long)fed_as_lists.load(), ru.ru_maxrss / 1024.0);
+                   stream_vcf ? "; the VCF streamed block by block: read + parse + feed" : "", (long long)(fed_as_bits.load() / per_owner),
+                   (long long)(fed_as_lists.load() / per_owner), ru.ru_maxrss / 1024.0);
   }
   if (!conf.dump_similarity.empty()) {  // all N^2 entries, as matrix.iterator emits them (:189)
     std::vector<int64_t> sim((size_t)n * (size_t)n);
-    check(ctx, pcoa_gram_read_i64(ctx, sim.data()), "dump-similarity");
+    if (strips.empty()) {
+      check(ctx, pcoa_gram_read_i64(ctx, sim.data()), "dump-similarity");
+    } else {   // each owner's [N][cols] into its columns
+      std::vector<int64_t> part;
+      for (size_t g = 0; g < owners.size(); ++g) {
+        const int32_t c0 = strips[g].first, w = strips[g].second;
+        part.resize((size_t)n * (size_t)w);
+        check(owners[g], pcoa_gram_read_i64(owners[g], part.data()), "dump-similarity");
+        for (int32_t r = 0; r < n; ++r)
+          std::copy(part.begin() + (size_t)r * w, part.begin() + (size_t)(r + 1) * w, sim.begin() + (size_t)r * n + c0);
+      }
+    }
     std::ofstream out(conf.dump_similarity, std::ios::binary);
     out.write(reinterpret_cast<const char*>(sim.data()), (std::streamsize)(sim.size() * sizeof(int64_t)));
     if (!out) die("cannot write " + conf.dump_similarity);
@@ -1387,7 +1460,10 @@ int main(int argc, char** argv) {
     die("computePca emits exactly PC1 and PC2 (VariantsPca.scala:229-230); --num-pc must be >= 2");
   std::vector<double> comps((size_t)conf.num_pc * (size_t)n), lam((size_t)conf.num_pc);
   int32_t nonzero = 0;
-  check(ctx, pcoa_compute(ctx, conf.num_pc, comps.data(), lam.data(), &nonzero), "computePca");
+  if (strips.empty())
+    check(ctx, pcoa_compute(ctx, conf.num_pc, comps.data(), lam.data(), &nonzero), "computePca");
+  else
+    check(ctx, pcoa_compute_strips(owners.data(), (int32_t)owners.size(), conf.num_pc, comps.data(), lam.data(), &nonzero), "computePca");
   std::printf("Non zero rows in matrix: %d / %d.\n", nonzero, n);
 
   // emitResult (:233-246)
@@ -1413,9 +1489,18 @@ int main(int argc, char** argv) {
 
   // reportIoStats (:48) / stop (:49)
   pcoa_timings t;
-  if (pcoa_get_timings(ctx, &t) == PCOA_OK)
+  if (pcoa_get_timings(ctx, &t) == PCOA_OK) {
+    double gram_s = t.gram_kernel_seconds;   // (strip layout: summed over the owners)
+    for (size_t g = 1; g < owners.size(); ++g) {
+      pcoa_timings tg;
+      if (pcoa_get_timings(owners[g], &tg) == PCOA_OK) gram_s += tg.gram_kernel_seconds;
+    }
     std::fprintf(stderr, "Variants accumulated: %lld; Gram kernel %.3f ms; PCoA %.3f ms\n", (long long)t.gram_variants,
-                 1e3 * t.gram_kernel_seconds, 1e3 * t.compute_total_seconds);
-  pcoa_destroy(ctx);
+                 1e3 * gram_s, 1e3 * t.compute_total_seconds);
+    if (!strips.empty())
+      std::fprintf(stderr, "computePca over %zu strip owners: %d Lanczos steps (each one product over every owner)\n", owners.size(),
+                   t.lanczos_steps);
+  }
+  for (pcoa_ctx* o : owners) pcoa_destroy(o);
   return 0;
 }

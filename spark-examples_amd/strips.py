@@ -150,9 +150,12 @@ def gather_concat_device(pieces, widths, group=None):
     return torch.cat([g[:w] for g, w in zip(got, widths)])
 
 
-def compute_pca_over_strips(owners, num_pc=2, group=None, max_steps=512, tol=1e-11, first_check=12, trace=None):
+def compute_pca_over_strips(owners, num_pc=2, group=None, max_steps=512, tol=1e-11, first_check=12, trace=None,
+                            host_exchange=False):
     """computePca for strip owners.  `owners`: this rank's owners in column order; over all ranks (in rank order) the
     strips must tile [0, N).  Returns (components [N, k] sign-normalised unit columns, eigenvalues [k], nonzero_rows).
+    host_exchange=True: engines multiply host vectors (pcoa_strip_matvec) and the pieces travel as host arrays -- for a
+    process group whose backend cannot all-gather device tensors (gloo); the products are the same bits.
     MLlib ranks components by |lambda| (singular values of the covariance); B = J S J is positive semi-definite up to
     rounding, so the largest eigenvalues are taken, as the engine's Lanczos path does."""
     if not owners:
@@ -172,7 +175,15 @@ def compute_pca_over_strips(owners, num_pc=2, group=None, max_steps=512, tol=1e-
     # Engines keep everything of the iteration on the device (row means uploaded once; vector, Krylov basis and
     # re-orthogonalisation on the GPU; all-gather of device tensors).  xp = torch on that path, numpy for the stand-ins.
     on_device = all(hasattr(o, "strip_matvec_device") for o in owners)
-    if on_device:
+    if on_device and host_exchange:
+        import torch
+
+        def matvec(v):
+            vh = v.double().cpu().numpy()
+            y = gather_concat([o.strip_matvec(vh, means, matrix_mean) for o in owners], group)
+            return torch.from_numpy(y).to(v.device)
+
+    elif on_device:
         import torch
         dev = torch.device("cuda", int(getattr(owners[0], "device", 0)))
         for o in owners:

@@ -285,6 +285,10 @@ class PcaConf(object):
         p.add_argument("--spark-output-layout", action="store_true",
                        help="write <output-path>-pca.tsv as the DIRECTORY Spark's saveAsTextFile leaves (part-00000 + _SUCCESS, "
                             "VariantsPca.scala:241-245) instead of one file of that name")
+        p.add_argument("--layout", choices=["auto", "full", "strips"], default="auto",
+                       help="full: every rank a whole partial S over its share of the variants, then the all-reduce; strips: "
+                            "rank r owns the columns strip_ranges(N, K)[r] of S and reads every variant, nothing is reduced; "
+                            "auto: strips only when K > 1 and S does not fit (pcoa_plan_layout)")
         p.add_argument("--dump-similarity", type=str, default=None,
                        help="write S (N x N int64, little-endian, row-major) to this file (parity tests)")
         a = p.parse_args(list(arguments))
@@ -430,6 +434,36 @@ class VariantsPcaDriver(object):
             native.close()
         return self.engine, tele
 
+    # the strip layout (pcoa_plan_layout): this rank owns S[:, col0:col0+cols] and is fed EVERY variant (no shard_calls);
+    # nothing is reduced.  Returns the owner.
+    def getSimilarityMatrixStrip(self, callsets, strip, device):
+        self.engine = calculate_similarity_matrix(callsets, len(self.indexes), engine=PcoaEngine(len(self.indexes), device=device,
+                                                                                                 strip=strip))
+        return self.engine
+
+    # computePca over the strips of all ranks (every rank calls it: the exchange is collective).  One process:
+    # pcoa_compute_strips; several: strips.compute_pca_over_strips over the process group (host vectors over gloo).
+    def computePcaOverStrips(self, owner, world, host_exchange=False):
+        from . import engine as E
+        from . import strips
+        n = len(self.indexes)
+        if world == 1:
+            comps, _, nonzero = E.compute_strips([owner], self.conf.numPc)
+        elif n < 32:   # below the Lanczos path: the strips assembled on every rank, solved by a full engine
+            full = PcoaEngine(n, device=owner.device)
+            try:
+                full.load_gram(gather_strips(owner))
+                comps, _, nonzero = full.compute(self.conf.numPc)
+            finally:
+                full.close()
+        else:
+            comps, _, nonzero = strips.compute_pca_over_strips([owner], self.conf.numPc, host_exchange=host_exchange)
+        print("Non zero rows in matrix: %d / %d." % (nonzero, n))  # :208
+        if comps.shape[1] < 2:
+            raise IndexError("computePca emits exactly PC1 and PC2 (VariantsPca.scala:229-230); --num-pc must be >= 2")
+        reverse = dict((v, k) for (k, v) in self.indexes.items())
+        return [(reverse[i], float(comps[i, 0]), float(comps[i, 1])) for i in range(n)]
+
     # getSimilarityMatrixStream, VariantsPca.scala:262-279 (not called by the reference's main): the same S through
     # upper-triangle pair emission + mirror, i.e. only the keys with a non-zero count exist
     def getSimilarityMatrixStream(self, callsets):
@@ -544,6 +578,38 @@ def multi_gpu_plan(conf, args, env, device_count, python=None):
     return dist.launch_plan(conf.gpus, env, device_count, [os.path.abspath(__file__)] + list(args), python=python or sys.executable)
 
 
+def gather_strips(owner):
+    """The N x N matrix from the [N][cols] strips of every rank, in rank order (all_gather_object: for dumps and tiny N)."""
+    import torch.distributed as td
+    local = owner.gram()
+    if not (td.is_available() and td.is_initialized()) or td.get_world_size() == 1:
+        return local
+    got = [None] * td.get_world_size()
+    td.all_gather_object(got, local)
+    return np.concatenate(got, axis=1)
+
+
+def resolve_layout(conf, n, world, devices):
+    """--layout -> None (full) or the column ranges of the strips (pcoa_plan_layout).  auto asks every device for its free
+    memory (engines sharing a device split it) and keeps the full layout where it fits, with one rank, or where the devices
+    cannot be asked."""
+    from . import engine as E
+    if conf.layout == "strips" and world > n:
+        raise SystemExit("VariantsPcaDriver: --layout strips: %d owners for %d samples; every owner needs a column" % (world, n))
+    request = conf.layout
+    free = None
+    if request == "auto":
+        if world == 1 or world > n:
+            return None
+        try:
+            mem = dict((d, E.device_memory(d)[0]) for d in set(devices))
+        except E.PcoaError:
+            return None
+        free = E.engine_free_bytes(devices, lambda d: mem[d])
+    layout, ranges = E.plan_layout(n, world, free, request)
+    return ranges if layout == "strips" else None
+
+
 def main(args):
     """VariantsPcaDriver.main (VariantsPca.scala:38-50)."""
     conf = PcaConf(args)
@@ -580,6 +646,34 @@ def main(args):
     driver = VariantsPcaDriver(conf, indexes, names, data)
     filtered = [driver.filterDataset(d) for d in driver.data]
     calls_rdd = driver.getCallsRdd(filtered)
+    n = len(driver.indexes)
+    if world > 1:
+        import torch.distributed as td
+        devices = [int(t) for t in conf.rank_devices.split(",")] if conf.rank_devices else list(range(world))
+        decided = [resolve_layout(conf, n, world, devices) if rank == 0 else None]
+        td.broadcast_object_list(decided, src=0)      # every rank takes rank 0's decision (free memory differs by the moment)
+        ranges = decided[0]
+    else:
+        ranges = resolve_layout(conf, n, 1, [conf.gpu])
+    if ranges is not None:
+        owner = driver.getSimilarityMatrixStrip(calls_rdd, ranges[rank], local_rank if world > 1 else conf.gpu)
+        if rank == 0:
+            sys.stderr.write("strip layout: %d owner(s), each fed every variant, no reduction; columns %s\n"
+                             % (world, ", ".join("[%d, %d) on device %d" % (c0, c0 + w, d) for (c0, w), d in
+                                                 zip(ranges, devices if world > 1 else [conf.gpu]))))
+        if conf.dump_similarity:
+            s = gather_strips(owner)
+            if rank == 0:
+                s.astype("<i8").tofile(conf.dump_similarity)
+        result = driver.computePcaOverStrips(owner, world, host_exchange=world > 1 and conf.dist_backend == "gloo")
+        if rank == 0:
+            driver.emitResult(result)
+            driver.reportIoStats(sys.stderr)
+        if world > 1:
+            td.barrier()
+            td.destroy_process_group()
+        driver.stop()
+        return 0
     if world > 1:
         sim_matrix, tele = driver.getSimilarityMatrixSharded(calls_rdd, rank, world, local_rank, conf.allreduce)
         if rank == 0:
