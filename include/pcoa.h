@@ -472,6 +472,31 @@ int pcoa_center_read_f64(pcoa_ctx* ctx, double* out_b_nxn, double* out_row_sums,
 int pcoa_compute(pcoa_ctx* ctx, int32_t num_pc, double* out_components, double* out_eigenvalues,
                  int32_t* out_nonzero_rows);
 
+/* Out-of-sample projection: places samples that took no part in the PCA onto a reference cohort's principal coordinates
+ * (the Nystrom / Gower extension of computePca's output).  The reference's coordinate of sample i is row i of pca.toArray
+ * (VariantsPca.scala:224-230): entry u_c[i] of a unit eigenvector of the double-centred B, and B u_c = lambda_c u_c gives
+ * u_c[i] = (sum_j B(i, j) u_c[j]) / lambda_c.  A sample q to place gets its centred similarity row in place of B(i, .):
+ *   x(j, q) = S(j, q) of cross (variants where reference sample j and q both carry), j in [0, ref->n)
+ *   m_q     = (sum_j x(j, q)) / N_ref          (exact integer sum, one division: rowSums / rowCount, :206-215)
+ *   b(q, j) = ((x(j, q) - m_q) - mean_j) + mm  (mean_j = rowSums_ref(j) / N_ref and mm = matrixMean of ref: the values
+ *                                               pcoa_compute used on ref, bit for bit; the operation order of :216-221)
+ *   coord(q, c) = (sum_j b(q, j) u_c[j]) / lambda_c   (j in fixed band order: deterministic, no floating-point atomics)
+ * A reference sample projected this way lands on u_c[i] + r_c[i] / lambda_c, r_c = B u_c - lambda_c u_c the residual the
+ * eigensolver verified before returning the pair.
+ *   ref:   a full engine (pcoa_create) whose finalized S is the reference Gram.
+ *   cross: a strip owner (pcoa_create_strip) with cross->n >= ref->n, fed the same variants: its rows [0, ref->n) are ref's
+ *          samples in ref's order, its columns the samples to place (new ones, or reference ones).  It may sit on another
+ *          device (the N_ref-double means travel by peer copy).
+ *   components / eigenvalues: what pcoa_compute(ref, num_pc, ..) returned (host arrays, the same layout: [num_pc][ref->n]).
+ *   out_coords: [num_pc][cols] column-major, the layout of out_components: component c of column q at out_coords[q + c*cols].
+ * The pass reads rows [0, ref->n) of the strip once for the column sums and once per chunk of up to 8 components (num_pc = 2:
+ * once).  PCOA_ERR_INVALID_ARG for a NULL pointer, num_pc outside (0, ref->n], cross->n < ref->n, ref a strip owner, cross not
+ * one, or an eigenvalue that is zero or not finite; PCOA_ERR_STATE when an engine cannot serve (an input check of its
+ * accumulation failed).  Errors are reported on ref.  Synchronising; neither S is modified.
+ * Extends: computePca's output (VariantsPca.scala:224-246) to samples outside the matrix it decomposed. */
+int pcoa_project(pcoa_ctx* ref, pcoa_ctx* cross, int32_t num_pc, const double* components, const double* eigenvalues,
+                 double* out_coords);
+
 /* ---- instrumentation ------------------------------------------------------------------------- */
 
 /* Synchronises and fills *out.  Replaces: reportIoStats' role of printing what was processed

@@ -114,6 +114,7 @@ _SIGNATURES = [
     ("pcoa_plan_layout", ctypes.c_int, [_i32, _i32, _vp, _i32, ctypes.POINTER(_i32), _vp, _vp]),
     ("pcoa_device_memory", ctypes.c_int, [_i32, ctypes.POINTER(_i64), ctypes.POINTER(_i64)]),
     ("pcoa_compute_strips", ctypes.c_int, [_vp, _i32, _i32, _vp, _vp, ctypes.POINTER(_i32)]),
+    ("pcoa_project", ctypes.c_int, [_vp, _vp, _i32, _vp, _vp, _vp]),
     ("pcoa_destroy", None, [_vp]),
     ("pcoa_last_error", ctypes.c_char_p, [_vp]),
     ("pcoa_reset", ctypes.c_int, [_vp]),

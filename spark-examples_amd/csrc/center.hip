@@ -238,7 +238,151 @@ __global__ __launch_bounds__(256) void strip_col_sums_gather_kernel(const int64_
   out_f64[jj] = (double)acc;
 }
 
+// pcoa_project: the out-of-sample (Nystrom / Gower) step over rows [0, n_ref) of a strip whose columns are the samples to place.
+// Column q's centred similarity to reference sample j is b(q, j) = ((x(j, q) - m_q) - mean_j) + mm with m_q = colsum_q / n_ref,
+// and the pass accumulates sum_j b(q, j) u_c[j] for the K components of one chunk.  The decomposition of strip_band_kernel: a
+// workgroup takes 1024 columns x a band of 256 rows, a lane the four columns lane + 64 q, rows prefetched STRIP_NB deep, the
+// band's mean_j and u_c[j] staged in LDS; 4 K fp64 accumulators per lane.  Rows of a band in order, one partial per (band,
+// component, column): [bands][K][cols], added in band order by project_finish_kernel -- deterministic, no float atomics, and
+// the additions of a component do not depend on K or on the other columns.
+template <int K, bool HAS64>
+__global__ __launch_bounds__(256) void project_band_kernel(const int32_t* __restrict__ s32, const int64_t* __restrict__ s64,
+                                                           int32_t n_ref, int32_t cols, const double* __restrict__ colsum,
+                                                           const double* __restrict__ means, double mmean,
+                                                           const double* __restrict__ u /* [K][n_ref] */,
+                                                           double* __restrict__ partial /* [bands][K][cols] */) {
+#pragma clang fp contract(off)
+  __shared__ double ms[STRIP_BAND], us[K][STRIP_BAND];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int band = blockIdx.y;
+  const int i0 = band * STRIP_BAND, i1 = min(n_ref, i0 + STRIP_BAND);
+  const int rows = i1 - i0;
+  for (int r = threadIdx.x; r < STRIP_BAND; r += 256) {
+    ms[r] = r < rows ? means[i0 + r] : 0.0;
+#pragma unroll
+    for (int c = 0; c < K; ++c) us[c][r] = r < rows ? u[(int64_t)c * n_ref + i0 + r] : 0.0;
+  }
+  __syncthreads();
+  const int jbase = (blockIdx.x * 4 + wave) * 256 + lane;
+  if (jbase - lane >= cols) return;   // wave-uniform
+  auto run = [&](auto full_tag) {
+    constexpr bool FULL = decltype(full_tag)::value;
+    bool ok[4];
+    double mq[4], acc[K][4];
+    const double rc = (double)n_ref;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int j = jbase + 64 * q;
+      ok[q] = FULL || j < cols;
+      mq[q] = ok[q] ? colsum[j] / rc : 0.0;   // exact integer sum, one division (rowSums / rowCount, :206-215)
+#pragma unroll
+      for (int c = 0; c < K; ++c) acc[c][q] = 0.0;
+    }
+    const int64_t base = (int64_t)i0 * cols + jbase;
+    struct Row { int32_t lo[4]; int64_t hi[HAS64 ? 4 : 1]; };
+    auto load_row = [&](int r, Row& b) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int64_t idx = base + (int64_t)r * cols + 64 * q;
+        b.lo[q] = (FULL || ok[q]) ? s32[idx] : 0;
+        if constexpr (HAS64) b.hi[q] = (FULL || ok[q]) ? s64[idx] : 0;
+      }
+    };
+    auto use_row = [&](int r, const Row& b) {
+      const double mi = ms[r];
+      double uc[K];
+#pragma unroll
+      for (int c = 0; c < K; ++c) uc[c] = us[c][r];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const double data = HAS64 ? (double)((int64_t)b.lo[q] + b.hi[HAS64 ? q : 0]) : (double)b.lo[q];
+        double t = data - mq[q];
+        t = t - mi;
+        t = t + mmean;
+#pragma unroll
+        for (int c = 0; c < K; ++c) acc[c][q] += t * uc[c];
+      }
+    };
+    Row buf[STRIP_NB];
+#pragma unroll
+    for (int b = 0; b < STRIP_NB; ++b)
+      if (b < rows) load_row(b, buf[b]);
+    int k = 0;
+    for (; k + 2 * STRIP_NB <= rows; k += STRIP_NB) {
+#pragma unroll
+      for (int b = 0; b < STRIP_NB; ++b) {
+        use_row(k + b, buf[b]);
+        load_row(k + b + STRIP_NB, buf[b]);
+      }
+    }
+#pragma unroll
+    for (int b = 0; b < STRIP_NB; ++b)
+      if (k + b < rows) {
+        use_row(k + b, buf[b]);
+        if (k + b + STRIP_NB < rows) load_row(k + b + STRIP_NB, buf[b]);
+      }
+    k += STRIP_NB;
+#pragma unroll
+    for (int b = 0; b < STRIP_NB; ++b)
+      if (k + b < rows) use_row(k + b, buf[b]);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      if (!ok[q]) continue;
+#pragma unroll
+      for (int c = 0; c < K; ++c) partial[((int64_t)band * K + c) * cols + jbase + 64 * q] = acc[c][q];
+    }
+  };
+  if (jbase - lane + 256 <= cols) run(std::true_type{});
+  else run(std::false_type{});
+}
+
+// out[(c0 + c) * cols + jj] = (sum over bands, in order, of the partials) / lambda_{c0 + c}
+__global__ __launch_bounds__(256) void project_finish_kernel(const double* __restrict__ partial, int32_t cols, int32_t bands,
+                                                             int32_t k, const double* __restrict__ lam, double* __restrict__ out) {
+#pragma clang fp contract(off)
+  const int jj = blockIdx.x * 256 + threadIdx.x;
+  const int c = blockIdx.y;
+  if (jj >= cols) return;
+  double acc = 0.0;
+  for (int b = 0; b < bands; ++b) acc += partial[((int64_t)b * k + c) * cols + jj];
+  out[(int64_t)c * cols + jj] = acc / lam[c];
+}
+
 }  // namespace
+
+int64_t project_ws_doubles(int32_t n_ref, int32_t cols, int32_t k) {
+  const int64_t bands = ((int64_t)n_ref + STRIP_BAND - 1) / STRIP_BAND;
+  return bands * (int64_t)k * cols;
+}
+
+int project_chunk(int32_t remaining) {
+  return remaining >= 8 ? 8 : remaining >= 4 ? 4 : remaining >= 2 ? 2 : 1;
+}
+
+hipError_t launch_project(const int32_t* s32, const int64_t* s64_or_null, int32_t n_ref, int32_t cols, const double* colsum,
+                          const double* means, double matrix_mean, const double* u, int32_t k, const double* lam, double* ws,
+                          double* out, hipStream_t stream) {
+  const int bands = (n_ref + STRIP_BAND - 1) / STRIP_BAND;
+  const dim3 grid((unsigned)((cols + 1023) / 1024), (unsigned)bands);
+#define PCOA_PROJECT_LAUNCH(KK)                                                                                               \
+  if (s64_or_null)                                                                                                            \
+    hipLaunchKernelGGL((project_band_kernel<KK, true>), grid, dim3(256), 0, stream, s32, s64_or_null, n_ref, cols, colsum,   \
+                       means, matrix_mean, u, ws);                                                                            \
+  else                                                                                                                        \
+    hipLaunchKernelGGL((project_band_kernel<KK, false>), grid, dim3(256), 0, stream, s32, s64_or_null, n_ref, cols, colsum,  \
+                       means, matrix_mean, u, ws);
+  switch (k) {
+    case 1: PCOA_PROJECT_LAUNCH(1) break;
+    case 2: PCOA_PROJECT_LAUNCH(2) break;
+    case 4: PCOA_PROJECT_LAUNCH(4) break;
+    case 8: PCOA_PROJECT_LAUNCH(8) break;
+    default: return hipErrorInvalidValue;
+  }
+#undef PCOA_PROJECT_LAUNCH
+  hipLaunchKernelGGL(project_finish_kernel, dim3((unsigned)((cols + 255) / 256), (unsigned)k), dim3(256), 0, stream, ws, cols,
+                     bands, k, lam, out);
+  return hipGetLastError();
+}
 
 int64_t strip_ws_doubles(int32_t n, int32_t cols) {
   const int64_t bands = ((int64_t)n + STRIP_BAND - 1) / STRIP_BAND;

@@ -226,6 +226,8 @@ struct pcoa_ctx {
   double* strip_means = nullptr;   // [n] rowSums / N, resident between the mat-vecs of one computePca (pcoa_strip_set_centering)
   double strip_matrix_mean = 0.0;
   bool strip_centering_set = false;
+  double* proj_ws = nullptr;       // pcoa_project on a strip owner: reference means, components, eigenvalues, partials, result (lazy)
+  int64_t proj_ws_cap = 0;
   int device = 0;
   uint32_t flags = 0;
   int num_cu = 256;
@@ -1542,7 +1544,7 @@ void pcoa_destroy(pcoa_ctx* c) {
   if (c->hw) (void)hipHostFree(c->hw);
   if (c->ws.host_rec) (void)hipHostFree(c->ws.host_rec);
   void* bufs[] = {c->s32, c->s64, c->s64_spare, c->narrow_flag, c->zeros, c->err_flag, c->tile, c->csr_idx, c->csr_offs, c->thr_dev,
-                  c->sample_pop, c->xfer, c->coll, c->fb_flags, c->strip_ws, c->strip_means, c->pack_buf, c->lanczos_ws, c->sym_part, c->ws.a, c->ws.d, c->ws.e, c->ws.tau, c->ws.q, c->ws.w, c->ws.lam,
+                  c->sample_pop, c->xfer, c->coll, c->fb_flags, c->strip_ws, c->strip_means, c->proj_ws, c->pack_buf, c->lanczos_ws, c->sym_part, c->ws.a, c->ws.d, c->ws.e, c->ws.tau, c->ws.q, c->ws.w, c->ws.lam,
                   c->ws.z, c->ws.wy, c->ws.scratch, c->ws.iscratch, c->row_sums, c->colmean, c->stats, c->nz,
                   c->out_dev};
   for (void* b : bufs)
@@ -2894,6 +2896,103 @@ int pcoa_strip_matvec_device(pcoa_ctx* c, const double* v_dev, double* y_dev) {
   }
   HIP_TRY(c, hipMemcpyAsync(y_dev, c->strip_ws, sizeof(double) * (size_t)c->s_cols, hipMemcpyDeviceToDevice, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));  // y_dev is ready for the caller's own stream / collective
+  return PCOA_OK;
+}
+
+// ---- out-of-sample projection -------------------------------------------------------------------------------------------
+// pcoa_project: the reference's centring is recomputed on ref with the kernels pcoa_compute runs (row sums -> stats ->
+// rowSums / N), so mean_j and the matrix mean are its values bit for bit; the means travel to cross's device once, the column
+// sums over rows [0, n_ref) of cross's strip give m_q, and the projection pass reads the strip once per chunk of components.
+namespace {
+// a failed input check of either engine: the engine cannot serve a projection (its S is invalid until pcoa_reset)
+int project_engine_state(pcoa_ctx* report, pcoa_ctx* c, const char* who, int rc) {
+  if (rc == PCOA_ERR_INDEX_RANGE || rc == PCOA_ERR_INVALID_ARG) rc = PCOA_ERR_STATE;
+  return fail(report, rc, std::string("project: ") + who + ": " + c->last_error);
+}
+}  // namespace
+
+int pcoa_project(pcoa_ctx* ref, pcoa_ctx* cross, int32_t num_pc, const double* components, const double* eigenvalues,
+                 double* out_coords) {
+  if (!cross) return fail(ref, PCOA_ERR_INVALID_ARG, "project: cross is NULL");
+  CHECK_CTX(ref);
+  if (!components || !eigenvalues || !out_coords)
+    return fail(ref, PCOA_ERR_INVALID_ARG, "project: components, eigenvalues or out_coords is NULL");
+  if (ref->is_strip)
+    return fail(ref, PCOA_ERR_INVALID_ARG, "project: ref is a strip owner; the reference must be a full engine (pcoa_create) -- "
+                                           "a reference solved over strips is not supported");
+  if (!cross->is_strip) return fail(ref, PCOA_ERR_INVALID_ARG, "project: cross is not a strip owner (pcoa_create_strip)");
+  const int32_t n_ref = ref->n, cols = cross->s_cols;
+  if (cross->n < n_ref)
+    return fail(ref, PCOA_ERR_INVALID_ARG, "project: cross has N = " + std::to_string(cross->n) + " rows, fewer than ref's " +
+                                               std::to_string(n_ref));
+  if (num_pc <= 0 || num_pc > n_ref)
+    return fail(ref, PCOA_ERR_INVALID_ARG, "project: num_pc = " + std::to_string(num_pc) + " out of range (0, n = " +
+                                               std::to_string(n_ref) + "]");
+  for (int32_t c = 0; c < num_pc; ++c)
+    if (eigenvalues[c] == 0.0 || !std::isfinite(eigenvalues[c]))
+      return fail(ref, PCOA_ERR_INVALID_ARG, "project: eigenvalue " + std::to_string(c) + " is zero or not finite");
+
+  // cross: S complete and clean; its buffers sized before ref writes into them
+  HIP_TRY(ref, hipSetDevice(cross->device));
+  int rc = finalize_impl(cross);
+  if (rc == PCOA_OK) rc = check_device_flags(cross);
+  if (rc != PCOA_OK) return project_engine_state(ref, cross, "cross", rc);
+  const int32_t k_max = project_chunk(num_pc);
+  const int64_t off_u = n_ref, off_lam = off_u + (int64_t)num_pc * n_ref, off_out = off_lam + num_pc,
+                off_part = off_out + (int64_t)num_pc * cols;
+  const int64_t need = off_part + project_ws_doubles(n_ref, cols, k_max);
+  if ((rc = ensure(cross, &cross->proj_ws, &cross->proj_ws_cap, need)) != PCOA_OK) return fail(ref, rc, "project: cross: " + cross->last_error);
+  if ((rc = ensure(cross, &cross->strip_ws, &cross->strip_ws_cap, strip_ws_doubles(n_ref, cols))) != PCOA_OK)
+    return fail(ref, rc, "project: cross: " + cross->last_error);
+  double* const means_x = cross->proj_ws;
+
+  // ref: the centring pcoa_compute used (VariantsPca.scala:206-215), then its means to cross
+  HIP_TRY(ref, hipSetDevice(ref->device));
+  rc = finalize_impl(ref);
+  if (rc == PCOA_OK) rc = check_device_flags(ref);
+  if (rc != PCOA_OK) return project_engine_state(ref, ref, "ref", rc);
+  if ((rc = ensure_workspace(ref, 1)) != PCOA_OK) return rc;
+  const int sym_min = debug_knobs().symv_sym_min_n > 0 ? debug_knobs().symv_sym_min_n : 16384;
+  const bool sym_form = !ref->s64 && n_ref >= sym_min && (n_ref & 3) == 0;   // exact integer row sums either way
+  if (sym_form && (rc = ensure(ref, &ref->sym_part, &ref->sym_part_cap, (int64_t)symv_sym_workspace_doubles(n_ref))) != PCOA_OK)
+    return rc;
+  {
+    ScopedTimer t(ref, T_CENTER);
+    if (sym_form)
+      HIP_TRY(ref, launch_row_sums_sym(ref->s32, n_ref, ref->sym_part, ref->row_sums, reinterpret_cast<int64_t*>(ref->stats + 2),
+                                       ref->stream));
+    HIP_TRY(ref, launch_center(ref->s32, ref->s64, n_ref, ref->row_sums, ref->stats, ref->nz, nullptr, ref->stream, sym_form));
+    HIP_TRY(ref, launch_col_means(ref->row_sums, n_ref, ref->colmean, ref->stream));
+  }
+  HIP_TRY(ref, hipMemcpyAsync(ref->hw->st, ref->stats, 2 * sizeof(double), hipMemcpyDeviceToHost, ref->stream));
+  if (ref->device == cross->device)
+    HIP_TRY(ref, hipMemcpyAsync(means_x, ref->colmean, sizeof(double) * (size_t)n_ref, hipMemcpyDeviceToDevice, ref->stream));
+  else
+    HIP_TRY(ref, hipMemcpyPeerAsync(means_x, cross->device, ref->colmean, ref->device, sizeof(double) * (size_t)n_ref, ref->stream));
+  HIP_TRY(ref, hipStreamSynchronize(ref->stream));
+  const double matrix_mean = ref->hw->st[1];
+
+  // cross: m_q from the column sums over rows [0, n_ref), then the components in chunks of 8 / 4 / 2 / 1
+  HIP_TRY(ref, hipSetDevice(cross->device));
+  double* const ws = cross->proj_ws;
+  HIP_TRY(ref, hipMemcpyAsync(ws + off_u, components, sizeof(double) * (size_t)num_pc * (size_t)n_ref, hipMemcpyHostToDevice,
+                              cross->stream));
+  HIP_TRY(ref, hipMemcpyAsync(ws + off_lam, eigenvalues, sizeof(double) * (size_t)num_pc, hipMemcpyHostToDevice, cross->stream));
+  {
+    ScopedTimer t(cross, T_CENTER);
+    HIP_TRY(ref, launch_strip_col_sums(cross->s32, cross->s64, n_ref, cols, cross->strip_ws, cross->stream));
+    for (int32_t c0 = 0; c0 < num_pc;) {
+      const int32_t k = project_chunk(num_pc - c0);
+      HIP_TRY(ref, launch_project(cross->s32, cross->s64, n_ref, cols, cross->strip_ws, means_x, matrix_mean,
+                                  ws + off_u + (int64_t)c0 * n_ref, k, ws + off_lam + c0, ws + off_part,
+                                  ws + off_out + (int64_t)c0 * cols, cross->stream));
+      c0 += k;
+    }
+  }
+  HIP_TRY(ref, hipMemcpyAsync(out_coords, ws + off_out, sizeof(double) * (size_t)num_pc * (size_t)cols, hipMemcpyDeviceToHost,
+                              cross->stream));
+  HIP_TRY(ref, hipStreamSynchronize(cross->stream));
+  HIP_TRY(ref, hipSetDevice(ref->device));
   return PCOA_OK;
 }
 

@@ -189,6 +189,16 @@ hipError_t launch_strip_matvec_to(const int32_t* s32, const int64_t* s64_or_null
                                   const double* v, const double* means, double matrix_mean, double* ws, double* y_out,
                                   hipStream_t stream);
 
+// pcoa_project (center.hip): rows [0, n_ref) of a strip, columns = the samples to place.  colsum[jj] = sum_{i < n_ref} S(i, jj)
+// (launch_strip_col_sums with n = n_ref), means / matrix_mean = the reference's centring, u = k components [k][n_ref], lam = their
+// k eigenvalues (device).  out[c * cols + jj] = (sum_j b(jj, j) u_c[j]) / lam[c], b in the reference's operation order.
+// k must be 1, 2, 4 or 8 (project_chunk picks the chunk); ws: project_ws_doubles(n_ref, cols, k) doubles.
+int64_t project_ws_doubles(int32_t n_ref, int32_t cols, int32_t k);
+int project_chunk(int32_t remaining);
+hipError_t launch_project(const int32_t* s32, const int64_t* s64_or_null, int32_t n_ref, int32_t cols, const double* colsum,
+                          const double* means, double matrix_mean, const double* u, int32_t k, const double* lam, double* ws,
+                          double* out, hipStream_t stream);
+
 // ---- symmetric eigensolver (eig.hip) ----------------------------------------------------------
 struct EigWorkspace {
   double* a;        // [n][n] in: symmetric matrix B; out: reflector vectors in rows (row k, cols k+1..n-1)

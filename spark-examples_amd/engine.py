@@ -447,6 +447,22 @@ class PcoaEngine(object):
         self._check(self._lib.pcoa_compute(self._ctx, k, _ptr(comps), _ptr(lam), ctypes.byref(nz)))
         return np.ascontiguousarray(comps[:k].T), lam[:k].copy(), int(nz.value)
 
+    def project(self, cross, components, eigenvalues):
+        """Places the columns of the strip owner `cross` onto this engine's principal coordinates (pcoa_project): `components`
+        [N, k] and `eigenvalues` [k] are what compute(k) returned, cross's rows [0, N) are this engine's samples in order.
+        Returns the coordinates [cross.cols, k] (the layout of compute's components)."""
+        comps = np.asarray(components, dtype=np.float64)
+        lam = np.ascontiguousarray(eigenvalues, dtype=np.float64)
+        if comps.ndim != 2 or comps.shape[0] != self.n or lam.shape != (comps.shape[1],):
+            raise ValueError("components must be [N = %d, k] and eigenvalues [k]" % self.n)
+        if not isinstance(cross, PcoaEngine):
+            raise TypeError("cross must be a PcoaEngine")
+        k = comps.shape[1]
+        u = np.ascontiguousarray(comps.T)   # [k][N]: the column-major layout pcoa_compute writes
+        out = np.zeros((max(k, 1), cross.cols), dtype=np.float64)
+        self._check(self._lib.pcoa_project(self._ctx, cross._ctx, k, _ptr(u), _ptr(lam), _ptr(out)))
+        return np.ascontiguousarray(out[:k].T)
+
     # ------------------------------------------------------------------ instrumentation
     def timings(self):
         t = L.PcoaTimings()

@@ -84,7 +84,21 @@ struct Conf {  // PcaConf / GenomicsConf (GenomicsConf.scala:31-101), same flag 
                                         // VariantsPca.scala:241-245) instead of one file of that name
   std::string carrier_format = "auto";  // --carrier-format auto|lists|bits (r06): how RDD[Seq[Int]] rows cross to the engine -- auto: a block
                                         // whose mean list is longer than N / 32 entries goes over as carrier bitsets (fewer bytes), else as lists
+  std::vector<std::string> project_input_path;  // --project-input-path: VCFs whose samples are placed onto the PCA of --input-path
+                                                // (pcoa_project); their callsets follow the reference's, variants matched by join / merge
 };
+
+const char* kUsage =
+    "usage: variants_pca_driver --input-path <file.vcf[.gz]> [more] | <prefix>.bed [options]\n"
+    "  reference flags: --output-path P --num-pc K --references R.. --all-references --min-allele-frequency F\n"
+    "                   --debug-datasets --bases-per-partition B --num-reduce-partitions P --variant-set-id ..\n"
+    "  engine flags:    --gpu D --gpus K --gpu-map a,b,.. --reduce auto|rccl|peer --layout auto|full|strips\n"
+    "                   --carrier-format auto|lists|bits --plink-decode device|host --plink-ref-allele a1|a2 --stream-rows R\n"
+    "                   --no-stream --join-partitions P --spill-dir D --spark-output-layout --ingest-threads T\n"
+    "                   --parse-only --dump-similarity FILE\n"
+    "  --project-input-path <file.vcf[.gz]> [more]\n"
+    "                   place these samples onto the principal coordinates of the --input-path cohort instead of\n"
+    "                   decomposing the union (one GPU, VCF inputs, full layout)\n";
 
 [[noreturn]] void die(const std::string& m) {
   std::cerr << "VariantsPcaDriver: " << m << std::endl;
@@ -104,6 +118,11 @@ Conf parse(int argc, char** argv) {
   for (int i = 1; i < argc; ++i) {
     const std::string a = argv[i];
     if (a == "--input-path") list(i, c.input_path);
+    else if (a == "--project-input-path") {
+      list(i, c.project_input_path);
+      if (c.project_input_path.empty()) die("--project-input-path needs at least one file");
+    }
+    else if (a == "--help" || a == "-h") { std::fputs(kUsage, stdout); std::exit(0); }
     else if (a == "--references") list(i, c.references);
     else if (a == "--variant-set-id") list(i, c.variant_set_id);
     else if (a == "--output-path") c.output_path = one(i);
@@ -1051,6 +1070,59 @@ void stream_plink_shard(const Conf& conf, const PlinkMeta& m, int g, int k, pcoa
   st->feed_s = std::max(st->feed_s, feed_s);
 }
 
+// --project-input-path: every joined row goes to BOTH engines as one carrier bitset of all N samples, packed once -- the
+// reference engine (N_ref samples) ignores the bits of samples >= N_ref (pcoa_accumulate_bits), the strip owner over columns
+// [N_ref, N) takes them all.  A row that names a callset twice cannot be a bitset: refused.
+struct ProjectionFeeder {
+  pcoa_ctx* ref = nullptr;
+  pcoa_ctx* cross = nullptr;
+  uint32_t* pin = nullptr;
+  int64_t rows_fed = 0;
+  ~ProjectionFeeder() { if (pin) (void)pcoa_host_free_pinned(pin); }
+  void feed(int n, const int32_t* idx, const int64_t* offs, int64_t rows, unsigned threads) {
+    const int64_t words = ((int64_t)n + 31) / 32;
+    if (!pin) {
+      void* q = nullptr;
+      if (pcoa_host_alloc_pinned((size_t)CarrierFeeder::kChunkRows * (size_t)words * 4, &q) != PCOA_OK) die("pcoa_host_alloc_pinned failed");
+      pin = static_cast<uint32_t*>(q);
+    }
+    for (int64_t r0 = 0; r0 < rows; r0 += CarrierFeeder::kChunkRows) {
+      const int64_t r1 = std::min(rows, r0 + CarrierFeeder::kChunkRows);
+      if (!CarrierFeeder::pack(idx, offs, r0, r1, n, words, pin, threads))
+        die("--project-input-path: a joined variant names a callset twice; a carrier bitset cannot carry that multiplicity");
+      check(ref, pcoa_accumulate_bits(ref, pin, r1 - r0, words, 0), "getSimilarityMatrix (reference)");
+      check(cross, pcoa_accumulate_bits(cross, pin, r1 - r0, words, 0), "getSimilarityMatrix (projected samples)");
+    }
+    rows_fed += rows;
+  }
+};
+
+// --project-input-path: what cannot be served is refused before any file is read or any device is touched
+void check_projection_conf(const Conf& conf) {
+  if (conf.project_input_path.empty()) return;
+  if (conf.gpus > 1) die("--project-input-path runs on one GPU: it cannot take --gpus " + std::to_string(conf.gpus));
+  if (conf.layout == "strips") die("--project-input-path needs the reference's S whole on one engine: it cannot take --layout strips");
+  if (conf.carrier_format == "lists") die("--project-input-path feeds both engines carrier bitsets: it cannot take --carrier-format lists");
+  std::set<std::string> stems;
+  auto stem_of = [](const std::string& path) {
+    std::string stem = path.substr(path.find_last_of('/') == std::string::npos ? 0 : path.find_last_of('/') + 1);
+    stem = stem.substr(0, stem.find('.'));
+    std::replace(stem.begin(), stem.end(), '-', '_');
+    return stem;
+  };
+  for (const auto& p : conf.input_path) {
+    if (is_plink_path(p)) die("--project-input-path needs VCF inputs on both sides: " + p + " is a PLINK fileset");
+    stems.insert(stem_of(p));
+  }
+  for (const auto& p : conf.project_input_path) {
+    if (is_plink_path(p)) die("--project-input-path needs VCF inputs on both sides: " + p + " is a PLINK fileset");
+    const std::string st = stem_of(p);
+    if (!stems.insert(st).second)
+      die("--project-input-path: callset-id collision: " + p + " has the set id '" + st + "' of an earlier input (callset ids are "
+          "<set id>-<column>); rename the file");
+  }
+}
+
 // k engines, fed by k host threads, reduced into engine 0 (VariantsPca.scala:190: reduceByKey).  RCCL where every engine has
 // a device of its own and the collective runtime binds; else peer copies + int64 adds (pcoa_gram_reduce_from), which also work
 // with several engines on ONE device (--gpu-map 0,0: the way this path is tested on a single-GPU box).
@@ -1124,12 +1196,38 @@ std::vector<pcoa_ctx*> run_engines(const Conf& conf, int32_t n, const std::vecto
   return {ctx[0]};
 }
 
+// emitResult (:233-246): name, dataset, pc1, pc2 sorted by name on stdout (+ <output-path>-pca.tsv)
+struct OutRow { std::string name, dataset; double pc1, pc2; };
+void emit_result(const Conf& conf, std::vector<OutRow>& rows) {
+  std::stable_sort(rows.begin(), rows.end(), [](const OutRow& a, const OutRow& b) { return a.name < b.name; });
+  for (const auto& r : rows)
+    std::printf("%s\t%s\t%s\t%s\n", r.name.c_str(), r.dataset.c_str(), java_double(r.pc1).c_str(), java_double(r.pc2).c_str());
+  if (!conf.output_path.empty()) {
+    std::string target = conf.output_path + "-pca.tsv";
+    if (conf.spark_output) {   // what resultRDD.saveAsTextFile(outputPath) leaves (:241-245): a directory; like Spark, an existing one is an error
+      if (::mkdir(target.c_str(), 0777) != 0) die("output directory " + target + " already exists (or cannot be created)");
+      std::ofstream(target + "/_SUCCESS");
+      target += "/part-00000";
+    }
+    std::ofstream out(target);
+    for (const auto& r : rows)
+      out << r.name << "\t" << java_double(r.pc1) << "\t" << java_double(r.pc2) << "\t" << r.dataset << "\n";
+  }
+}
+
 int main(int argc, char** argv) {
   const auto t_start = std::chrono::steady_clock::now();
   Conf conf = parse(argc, argv);
   if (conf.input_path.empty())
     die("--input-path <file.vcf[.gz]> [more files] or one PLINK fileset (<prefix>.bed) is required: the Google Genomics API the reference read "
         "from has been shut down");
+  // --project-input-path: those sets follow the reference's, so their callsets take the indexes [N_ref, N) (the concatenation
+  // rule below) and their variants are matched by the join / merge of all sets
+  check_projection_conf(conf);
+  const bool projecting = !conf.project_input_path.empty();
+  const size_t n_ref_inputs = conf.input_path.size();
+  conf.input_path.insert(conf.input_path.end(), conf.project_input_path.begin(), conf.project_input_path.end());
+  int32_t n_ref = 0;
   // VariantsCommon (VariantsCommon.scala:33-66): callset index/name maps + one dataset per variant set
   std::vector<Dataset> data;
   std::vector<std::string> ids, names;
@@ -1173,7 +1271,7 @@ int main(int argc, char** argv) {
   std::string stream_stem;
   std::vector<Region> stream_regions;
   int64_t streamed_variants = 0;
-  if (conf.input_path.size() > 1) std::printf("Running PCA on %zu datasets.\n", conf.input_path.size());
+  if (n_ref_inputs > 1) std::printf("Running PCA on %zu datasets.\n", n_ref_inputs);
   for (size_t k = 0; k < conf.input_path.size() && !stream_plink; ++k) {
     std::vector<Region> regions;
     if (!conf.all_references && !conf.references.empty())
@@ -1200,9 +1298,10 @@ int main(int argc, char** argv) {
     }
     ids.insert(ids.end(), data.back().ids.begin(), data.back().ids.end());
     names.insert(names.end(), data.back().names.begin(), data.back().names.end());
+    if (k + 1 == n_ref_inputs) n_ref = (int32_t)ids.size();
   }
   const int32_t n = (int32_t)ids.size();
-  std::printf("Matrix size: %d.\n", n);
+  std::printf("Matrix size: %d.\n", projecting ? n_ref : n);
   if (n == 0) die("no samples");
 
   // streamed join / merge, pass 1: every set once through the parser threads into its key partitions' spill files
@@ -1321,6 +1420,7 @@ int main(int argc, char** argv) {
   StreamStats stream_stats;
   std::atomic<int64_t> fed_as_bits{0}, fed_as_lists{0}, joined_rows{0};
   std::vector<unsigned char*> blocks;  // page-locked blocks of the streaming reader, four per engine (filled by `prepare`)
+  ProjectionFeeder* proj_feeder = nullptr;   // --project-input-path: every row to both engines (feed below)
   // engine g takes shard `shard` of `k`: the contiguous range shard_range(shard, k, rows) -- the reference's partitions (:184);
   // under the strip layout every engine takes shard 0 of 1, i.e. every variant
   std::function<void(int, int, int, pcoa_ctx*)> feed = [&](int g, int shard, int k, pcoa_ctx* ctx) {
@@ -1335,6 +1435,10 @@ int main(int argc, char** argv) {
       CarrierFeeder& f; std::atomic<int64_t>& bits; std::atomic<int64_t>& lists;
       ~Tally() { bits += f.rows_as_bits; lists += f.rows_as_lists; }
     } tally{feeder, fed_as_bits, fed_as_lists};
+    auto give = [&](const int32_t* idx, const int64_t* offs, int64_t rows) {
+      if (proj_feeder) proj_feeder->feed(n, idx, offs, rows, feed_threads);
+      else feeder.feed(ctx, conf, n, idx, offs, rows, feed_threads);
+    };
     if (stream_join) {   // pass 2: key partitions q = g, g + k, ..: read back, join / merge, feed
       std::vector<int32_t> idx;
       std::vector<int64_t> offs;
@@ -1351,7 +1455,7 @@ int main(int argc, char** argv) {
           offs.push_back((int64_t)idx.size());
         }
         if (offs.size() > 1) {
-          feeder.feed(ctx, conf, n, idx.data(), offs.data(), (int64_t)offs.size() - 1, feed_threads);
+          give(idx.data(), offs.data(), (int64_t)offs.size() - 1);
           joined_rows += (int64_t)offs.size() - 1;
         }
       }
@@ -1371,7 +1475,7 @@ int main(int argc, char** argv) {
           offs.push_back((int64_t)idx.size());
         }
         if (offs.size() > 1) {
-          feeder.feed(ctx, conf, n, idx.data(), offs.data(), (int64_t)offs.size() - 1, feed_threads);
+          give(idx.data(), offs.data(), (int64_t)offs.size() - 1);
           streamed_variants += (int64_t)offs.size() - 1;
         }
       };
@@ -1381,7 +1485,7 @@ int main(int argc, char** argv) {
     int64_t ra, rb;
     shard_range(shard, k, (int64_t)row_offsets.size() - 1, &ra, &rb);
     if (rb <= ra) return;
-    feeder.feed(ctx, conf, n, sample_idx.data(), row_offsets.data() + ra, rb - ra, feed_threads);
+    give(sample_idx.data(), row_offsets.data() + ra, rb - ra);
   };
   std::string how;
   double feed_s = 0, warmup_s = 0;
@@ -1412,6 +1516,60 @@ int main(int argc, char** argv) {
     }
     warmup_s = now_s() - tw0;
   };
+  if (projecting) {
+    // PCA of the reference cohort on a full engine over N_ref, the other samples placed onto it (pcoa_project) from a strip owner
+    // over columns [N_ref, N): the cross block S[0:N_ref, N_ref:N] (and the rows below it, unused)
+    const int32_t n_new = n - n_ref;
+    if (n_ref <= 0 || n_new <= 0) die("--project-input-path: both the reference and the projected inputs need samples");
+    if (conf.num_pc < 2) die("computePca emits exactly PC1 and PC2 (VariantsPca.scala:229-230); --num-pc must be >= 2");
+    pcoa_ctx* ref = nullptr;
+    pcoa_ctx* cross = nullptr;
+    if (pcoa_create(&ref, n_ref, conf.gpu, PCOA_FLAG_DEFAULT) != PCOA_OK) die(std::string("pcoa_create: ") + pcoa_last_error(nullptr));
+    if (pcoa_create_strip(&cross, n, n_ref, n_new, conf.gpu, PCOA_FLAG_DEFAULT) != PCOA_OK)
+      die(std::string("pcoa_create_strip: ") + pcoa_last_error(nullptr));
+    check(ref, pcoa_reserve(ref, (int64_t)1 << 20, conf.num_pc), "pcoa_reserve");
+    check(cross, pcoa_reserve(cross, (int64_t)1 << 20, 0), "pcoa_reserve");
+    ProjectionFeeder pf;
+    pf.ref = ref;
+    pf.cross = cross;
+    proj_feeder = &pf;
+    const double t0 = now_s();
+    feed(0, 0, 1, ref);
+    check(ref, pcoa_gram_finalize(ref), "getSimilarityMatrix");
+    check(cross, pcoa_gram_finalize(cross), "getSimilarityMatrix");
+    feed_s = now_s() - t0;
+    if (stream_join) spill.remove_all();
+    std::fprintf(stderr, "getSimilarityMatrix: %lld variants in %.3f s (reference engine over %d samples, strip owner over columns "
+                 "[%d, %d) of %d; every row packed once as a carrier bitset for both)\n", (long long)pf.rows_fed, feed_s, n_ref, n_ref, n, n);
+    if (!conf.dump_similarity.empty()) {   // the reference's S (N_ref x N_ref)
+      std::vector<int64_t> sim((size_t)n_ref * (size_t)n_ref);
+      check(ref, pcoa_gram_read_i64(ref, sim.data()), "dump-similarity");
+      std::ofstream out(conf.dump_similarity, std::ios::binary);
+      out.write(reinterpret_cast<const char*>(sim.data()), (std::streamsize)(sim.size() * sizeof(int64_t)));
+      if (!out) die("cannot write " + conf.dump_similarity);
+    }
+    std::vector<double> comps((size_t)conf.num_pc * (size_t)n_ref), lam((size_t)conf.num_pc), coords((size_t)conf.num_pc * (size_t)n_new);
+    int32_t nonzero = 0;
+    check(ref, pcoa_compute(ref, conf.num_pc, comps.data(), lam.data(), &nonzero), "computePca");
+    std::printf("Non zero rows in matrix: %d / %d.\n", nonzero, n_ref);
+    check(ref, pcoa_project(ref, cross, conf.num_pc, comps.data(), lam.data(), coords.data()), "project");
+    std::printf("Projected %d samples onto %d principal components of %d reference samples.\n", n_new, conf.num_pc, n_ref);
+    std::vector<OutRow> rows;
+    for (int32_t i = 0; i < n; ++i) {
+      const bool r = i < n_ref;
+      const size_t at = r ? (size_t)i : (size_t)(i - n_ref), ld = r ? (size_t)n_ref : (size_t)n_new;
+      const std::vector<double>& v = r ? comps : coords;
+      rows.push_back({names[(size_t)i], ids[(size_t)i].substr(0, ids[(size_t)i].find('-')), v[at], v[at + ld]});
+    }
+    emit_result(conf, rows);
+    pcoa_timings t;
+    if (pcoa_get_timings(ref, &t) == PCOA_OK)
+      std::fprintf(stderr, "Variants accumulated: %lld; Gram kernel %.3f ms; PCoA %.3f ms\n", (long long)t.gram_variants,
+                   1e3 * t.gram_kernel_seconds, 1e3 * t.compute_total_seconds);
+    pcoa_destroy(cross);
+    pcoa_destroy(ref);
+    return 0;
+  }
   const std::vector<pcoa_ctx*> owners = run_engines(conf, n, strips, feed, &how, &feed_s, prepare);
   pcoa_ctx* const ctx = owners[0];
   if (stream_join) {
@@ -1467,25 +1625,11 @@ int main(int argc, char** argv) {
   std::printf("Non zero rows in matrix: %d / %d.\n", nonzero, n);
 
   // emitResult (:233-246)
-  struct Row { std::string name, dataset; double pc1, pc2; };
-  std::vector<Row> rows;
+  std::vector<OutRow> rows;
   for (int32_t i = 0; i < n; ++i)
     rows.push_back({names[(size_t)i], ids[(size_t)i].substr(0, ids[(size_t)i].find('-')), comps[(size_t)i],
                     comps[(size_t)i + (size_t)n]});
-  std::stable_sort(rows.begin(), rows.end(), [](const Row& a, const Row& b) { return a.name < b.name; });
-  for (const auto& r : rows)
-    std::printf("%s\t%s\t%s\t%s\n", r.name.c_str(), r.dataset.c_str(), java_double(r.pc1).c_str(), java_double(r.pc2).c_str());
-  if (!conf.output_path.empty()) {
-    std::string target = conf.output_path + "-pca.tsv";
-    if (conf.spark_output) {   // what resultRDD.saveAsTextFile(outputPath) leaves (:241-245): a directory; like Spark, an existing one is an error
-      if (::mkdir(target.c_str(), 0777) != 0) die("output directory " + target + " already exists (or cannot be created)");
-      std::ofstream(target + "/_SUCCESS");
-      target += "/part-00000";
-    }
-    std::ofstream out(target);
-    for (const auto& r : rows)
-      out << r.name << "\t" << java_double(r.pc1) << "\t" << java_double(r.pc2) << "\t" << r.dataset << "\n";
-  }
+  emit_result(conf, rows);
 
   // reportIoStats (:48) / stop (:49)
   pcoa_timings t;

@@ -291,6 +291,10 @@ class PcaConf(object):
                             "auto: strips only when K > 1 and S does not fit (pcoa_plan_layout)")
         p.add_argument("--dump-similarity", type=str, default=None,
                        help="write S (N x N int64, little-endian, row-major) to this file (parity tests)")
+        p.add_argument("--project-input-path", type=str, nargs="+", default=None,
+                       help="VCFs whose samples are placed onto the principal coordinates of the --input-path cohort "
+                            "(pcoa_project) instead of decomposing the union: their callsets follow the reference's, variants "
+                            "are matched by the join / merge of all sets; one GPU, VCF inputs, full layout")
         a = p.parse_args(list(arguments))
         self.__dict__.update(vars(a))
         self.numPc = a.num_pc
@@ -354,12 +358,12 @@ class VariantsPcaDriver(object):
     indexes: callset id -> 0..N-1 in callset-list order, names: callset id -> name
     (VariantsCommon.scala:44-47; the ordering rule is preserved)."""
 
-    def __init__(self, conf, indexes, names, data):
+    def __init__(self, conf, indexes, names, data, matrix_size=None):
         self.conf = conf
         self.indexes = dict(indexes)
         self.names = dict(names)
         self.data = data  # list of datasets, each a list of variant dicts (or ('csr', idx, offs))
-        print("Matrix size: %d." % len(self.indexes))  # VariantsCommon.scala:48
+        print("Matrix size: %d." % (len(self.indexes) if matrix_size is None else matrix_size))  # VariantsCommon.scala:48
         self.engine = None
 
     # filterDataset, VariantsPca.scala:96-108
@@ -610,9 +614,89 @@ def resolve_layout(conf, n, world, devices):
     return ranges if layout == "strips" else None
 
 
+def check_projection_conf(conf):
+    """--project-input-path: what cannot be served is refused before any file is read or any device is touched."""
+    from . import ingest
+    if conf.gpus > 1:
+        raise SystemExit("VariantsPcaDriver: --project-input-path runs on one GPU: it cannot take --gpus %d" % conf.gpus)
+    if conf.layout == "strips":
+        raise SystemExit("VariantsPcaDriver: --project-input-path needs the reference's S whole on one engine: it cannot take "
+                         "--layout strips")
+    if conf.synthetic or not conf.inputPath:
+        raise SystemExit("VariantsPcaDriver: --project-input-path needs VCF inputs on both sides (--input-path)")
+    stems = set()
+    for k, path in enumerate(list(conf.inputPath) + list(conf.project_input_path)):
+        if path.endswith(".npz") or path[-4:] in (".bed", ".bim", ".fam"):
+            raise SystemExit("VariantsPcaDriver: --project-input-path needs VCF inputs on both sides: %s is not a VCF" % path)
+        stem = ingest.set_id_of(path)
+        if k >= len(conf.inputPath) and stem in stems:
+            raise SystemExit("VariantsPcaDriver: --project-input-path: callset-id collision: %s has the set id '%s' of an earlier "
+                             "input (callset ids are <set id>-<column>); rename the file" % (path, stem))
+        stems.add(stem)
+
+
+def main_projection(conf):
+    """--project-input-path: the PCA of the --input-path cohort on a full engine over N_ref, the other samples placed onto it
+    (pcoa_project) from a strip owner over columns [N_ref, N).  Lists go to the strip whole and, filtered to indexes < N_ref,
+    to the reference engine."""
+    from . import ingest
+    ref_paths, proj_paths = list(conf.inputPath), list(conf.project_input_path)
+    refs = None if conf.all_references else conf.references
+    if len(ref_paths) > 1:
+        print("Running PCA on %d datasets." % len(ref_paths))  # VariantsCommon.scala:57
+    indexes, names, data, used = {}, {}, [], set()
+    n_ref = 0
+    for k, path in enumerate(ref_paths + proj_paths):
+        set_id = ingest.set_id_of(path, k, used)
+        ids, nm, variants = ingest.load_vcf_records(path, parse_refs(refs, k), set_id=set_id)
+        base = len(indexes)
+        for i, cid in enumerate(ids):
+            indexes[cid] = base + i
+        names.update(nm)
+        data.append(variants)
+        if k + 1 == len(ref_paths):
+            n_ref = len(indexes)
+    n = len(indexes)
+    driver = VariantsPcaDriver(conf, indexes, names, data, matrix_size=n_ref)
+    if n_ref == 0 or n == n_ref:
+        raise SystemExit("VariantsPcaDriver: --project-input-path: both the reference and the projected inputs need samples")
+    if conf.numPc < 2:
+        raise IndexError("computePca emits exactly PC1 and PC2 (VariantsPca.scala:229-230); --num-pc must be >= 2")
+    filtered = [driver.filterDataset(d) for d in driver.data]
+    rows = driver.getCallsRdd(filtered)
+    for r in rows:
+        if len(set(r)) != len(r):
+            raise SystemExit("VariantsPcaDriver: --project-input-path: a joined variant names a callset twice; a carrier bitset "
+                             "cannot carry that multiplicity")
+    ref = PcoaEngine(n_ref, device=conf.gpu)
+    cross = PcoaEngine(n, device=conf.gpu, strip=(n_ref, n - n_ref))
+    driver.engine = ref
+    try:
+        calculate_similarity_matrix([[i for i in r if i < n_ref] for r in rows], n_ref, engine=ref)
+        calculate_similarity_matrix(rows, n, engine=cross)
+        if conf.dump_similarity:
+            ref.gram().astype("<i8").tofile(conf.dump_similarity)
+        comps, lam, nonzero = ref.compute(conf.numPc)
+        print("Non zero rows in matrix: %d / %d." % (nonzero, n_ref))  # :208
+        coords = ref.project(cross, comps, lam)
+        print("Projected %d samples onto %d principal components of %d reference samples." % (n - n_ref, conf.numPc, n_ref))
+        reverse = dict((v, k) for (k, v) in indexes.items())
+        result = [(reverse[i], float(comps[i, 0]), float(comps[i, 1])) for i in range(n_ref)]
+        result += [(reverse[n_ref + q], float(coords[q, 0]), float(coords[q, 1])) for q in range(n - n_ref)]
+        driver.emitResult(result)
+        driver.reportIoStats(sys.stderr)
+    finally:
+        cross.close()
+        driver.stop()
+    return 0
+
+
 def main(args):
     """VariantsPcaDriver.main (VariantsPca.scala:38-50)."""
     conf = PcaConf(args)
+    if conf.project_input_path:
+        check_projection_conf(conf)
+        return main_projection(conf)
     rank, world = 0, 1
     if conf.gpus > 1 or "WORLD_SIZE" in os.environ:
         import torch  # plumbing: rendezvous and the device count
