@@ -140,7 +140,12 @@ typedef struct pcoa_timings {
   int32_t lanczos_block_steps;  /* band-Lanczos fallback (clustered leading eigenvalues): columns (= mat-vecs) it processed in
                                    the last pcoa_compute / pcoa_lanczos_with_matvec, thick restarts included; 0 = the
                                    single-vector iteration sufficed                                                          */
-  int32_t reserved_r06;
+  int32_t eig_dense_form;       /* launch forms the last pcoa_compute's dense solve of the N x N matrix B took, a bit set chosen
+                                   by the launchers: 1 fused Householder step (8 <= N <= 6,784), 2 that step
+                                   with more than 64 KiB of dynamic LDS (N >= 2,731), 4 two-kernel step (2 <= N <= 7,
+                                   N >= 6,785), 8 bisection from LDS (N <= 4,080), 16 inverse iteration from LDS
+                                   (N <= 3,490), 32 inverse iteration with one workgroup per vector, 64 blocked compact-WY
+                                   back-transform (N >= 130).  0 when eig_method != 2                                        */
 } pcoa_timings;
 #define PCOA_TIMINGS_R03_BYTES 192  /* offsetof(pcoa_timings, csr_stage_seconds): what pcoa_get_timings writes */
 

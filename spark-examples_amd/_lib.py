@@ -84,7 +84,7 @@ class PcoaTimings(ctypes.Structure):
         ("reduce_int32_calls", ctypes.c_int64),
         ("narrowed_to_int32", ctypes.c_int64),
         ("lanczos_block_steps", ctypes.c_int32),
-        ("reserved_r06", ctypes.c_int32),
+        ("eig_dense_form", ctypes.c_int32),
     ]
 
 

@@ -218,7 +218,7 @@ __global__ __launch_bounds__(256) void tridiag_update_kernel(double* __restrict_
 // back-transform.  Rows are dealt to workgroups by ABSOLUTE index (row i -> workgroup i mod gridDim, so XCD i mod 8
 // whatever k is): a row's 20 KB stay in the same XCD's L2 from step to step instead of migrating as the trailing block
 // shrinks.  Same formulas as tridiag_hw_kernel / tridiag_update_kernel; only the order of the reductions differs.
-// LDS: 3 (n - k) doubles (v_{k-1}, w_{k-1}, v_k), i.e. n <= 2,730 without raising the dynamic-LDS limit, n <= 6,800 with.
+// LDS: 3 (n - k) doubles (v_{k-1}, w_{k-1}, v_k), i.e. n <= 2,730 without raising the dynamic-LDS limit, n <= 6,784 with.
 constexpr int FT = 512;  // threads of a fused-step workgroup: 8 waves share one copy of the three vectors
 __global__ __launch_bounds__(FT) void tridiag_fused_kernel(double* __restrict__ a, int n, int k, double* __restrict__ d,
                                                             double* __restrict__ e, double* __restrict__ tau,
@@ -402,7 +402,7 @@ __global__ __launch_bounds__(256) void bisect_kernel(const double* __restrict__ 
 // pseudo-random start, re-orthogonalisation inside clusters).  The recurrences are serial in i,
 // so lane 0 of a single wave runs them; norms and axpys use all 64 lanes.
 // scratch: dl[n] dd[n] du[n] du2[n] y[n]; with use_lds the five arrays and the pivots live in
-// dynamic LDS (44 n bytes, n <= ~3600), which cuts the latency of every step of the serial chain.
+// dynamic LDS (44 n + 16 bytes, n <= 3,490), which cuts the latency of every step of the serial chain.
 __global__ __launch_bounds__(64) void invit_kernel(const double* __restrict__ d, const double* __restrict__ e,
                                                    int n, const double* __restrict__ lam, int k,
                                                    double* __restrict__ z, double* __restrict__ scratch,
@@ -696,14 +696,14 @@ __global__ __launch_bounds__(256) void wy_apply_kernel(const double* __restrict_
 
 }  // namespace
 
-hipError_t launch_tridiagonalize(const EigWorkspace& ws, int32_t n, hipStream_t stream) {
+hipError_t launch_tridiagonalize(const EigWorkspace& ws, int32_t n, hipStream_t stream, int32_t* form) {
   if (n <= 0) return hipErrorInvalidValue;
   if (n == 1) {
     hipLaunchKernelGGL(tridiag_hw_kernel, dim3(1), dim3(HW_T), 0, stream, ws.a, n, 0, ws.d, ws.e, ws.tau, ws.q,
                        ws.w);
     return hipGetLastError();
   }
-  // Fused form (one launch per column) while v_{k-1}, w_{k-1}, v_k fit the LDS: n <= 6,800.  ws.w is 2 n doubles and
+  // Fused form (one launch per column) while v_{k-1}, w_{k-1}, v_k fit the LDS: n <= 6,784.  ws.w is 2 n doubles and
   // ws.scratch 6 n: q is double-buffered in ws.w, the current reflector in ws.scratch.
   const size_t lds_full = 3 * (size_t)n * sizeof(double);
   int kf = 0;  // columns [0, kf) take the fused kernel
@@ -717,6 +717,7 @@ hipError_t launch_tridiagonalize(const EigWorkspace& ws, int32_t n, hipStream_t 
         raised = true;
       }
     }
+    if (form) *form |= EIG_FORM_FUSED | (lds_full > 64 * 1024 ? EIG_FORM_FUSED_BIG_LDS : 0);
     kf = n - 2;  // steps 0 .. n-3 generate a reflector; step n-2 only closes d / e (tridiag_hw_kernel below)
     double* qb[2] = {ws.w, ws.w + n};
     double* vb[2] = {ws.scratch, ws.scratch + n};
@@ -736,6 +737,7 @@ hipError_t launch_tridiagonalize(const EigWorkspace& ws, int32_t n, hipStream_t 
     err = hipMemcpyAsync(ws.q, qb[(kf - 1) & 1], sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, stream);
     if (err != hipSuccess) return err;
   }
+  if (form && kf == 0) *form |= EIG_FORM_TWO_KERNEL;
   for (int k = kf; k <= n - 2; ++k) {
     const int hw_threads = HW_T;  // 256 threads were measured slower (7.6 vs 6.0 us per step at N = 2504)
     hipLaunchKernelGGL(tridiag_hw_kernel, dim3(1), dim3(hw_threads), 0, stream, ws.a, n, k, ws.d, ws.e, ws.tau,
@@ -750,13 +752,14 @@ hipError_t launch_tridiagonalize(const EigWorkspace& ws, int32_t n, hipStream_t 
 }
 
 hipError_t launch_bisect(const EigWorkspace& ws, int32_t n, const int32_t* idx_host, int32_t count,
-                         double* lam_out_dev, hipStream_t stream) {
+                         double* lam_out_dev, hipStream_t stream, int32_t* form) {
   if (count <= 0) return hipSuccess;
   hipError_t err = hipMemcpyAsync(ws.iscratch, idx_host, sizeof(int32_t) * count, hipMemcpyHostToDevice, stream);
   if (err != hipSuccess) return err;
   const size_t lds_full = sizeof(double) * (32 + 2 * (size_t)n);
   const int use_lds = lds_full <= 64 * 1024;
   const size_t lds = use_lds ? lds_full : sizeof(double) * 32;
+  if (form && use_lds) *form |= EIG_FORM_BISECT_LDS;
   hipLaunchKernelGGL(bisect_kernel, dim3((unsigned)count), dim3(256), lds, stream, ws.d, ws.e, n, ws.iscratch,
                      lam_out_dev, use_lds);
   return hipGetLastError();
@@ -782,7 +785,7 @@ hipError_t invit_lds_bytes(int32_t n, size_t* lds_out) {
 }  // namespace
 
 hipError_t launch_inverse_iteration(const EigWorkspace& ws, int32_t n, const double* lam_sel_host, int32_t k,
-                                    hipStream_t stream) {
+                                    hipStream_t stream, int32_t* form) {
   // selected eigenvalues go to ws.lam[0..k) (the candidates there have been consumed by the host)
   hipError_t err = hipMemcpyAsync(ws.lam, lam_sel_host, sizeof(double) * k, hipMemcpyHostToDevice, stream);
   if (err != hipSuccess) return err;
@@ -801,6 +804,7 @@ hipError_t launch_inverse_iteration(const EigWorkspace& ws, int32_t n, const dou
       for (int p = 0; p < c; ++p)
         if (std::fabs(lam_sel_host[c] - lam_sel_host[p]) <= 1e-2 * big) { separate = false; break; }
   }
+  if (form) *form |= (use_lds ? EIG_FORM_INVIT_LDS : 0) | (separate ? EIG_FORM_INVIT_PER_VECTOR : 0);
   hipLaunchKernelGGL(invit_kernel, dim3(separate ? (unsigned)k : 1u), dim3(64), lds, stream, ws.d, ws.e, n,
                      ws.lam, k, ws.z, ws.scratch, ws.iscratch, use_lds);
   return hipGetLastError();
@@ -816,7 +820,7 @@ hipError_t launch_inverse_iteration_dev(const EigWorkspace& ws, int32_t n, int32
 }
 
 hipError_t launch_backtransform(const EigWorkspace& ws, int32_t n, int32_t k, int sign_normalize,
-                                int apply_reflectors, double* out_dev, hipStream_t stream) {
+                                int apply_reflectors, double* out_dev, hipStream_t stream, int32_t* form) {
   // blocked form when a WY workspace exists (ws.wy: nblk * (2 * BT * BT) + nslices * k * BT doubles) and there are enough
   // reflectors for it to pay; the serial kernel then only normalises
   const int nref = n - 2;
@@ -835,6 +839,7 @@ hipError_t launch_backtransform(const EigWorkspace& ws, int32_t n, int32_t k, in
                          nslices, t, ypart, ws.z, k);
     }
     apply_reflectors = 0;
+    if (form) *form |= EIG_FORM_WY_BACKTRANSFORM;
   }
   hipLaunchKernelGGL(backtransform_kernel, dim3((unsigned)k), dim3(HW_T), 0, stream, ws.a, n, ws.tau, ws.z,
                      sign_normalize, apply_reflectors, out_dev);

@@ -369,6 +369,7 @@ struct pcoa_ctx {
   int64_t sym_part_cap = 0;
   int64_t lanczos_cap = 0;         // doubles
   int32_t eig_method = 0;          // of the last pcoa_compute: 1 = Lanczos, 2 = Householder
+  int32_t eig_dense_form = 0;      // EIG_FORM_* bits of the last pcoa_compute's dense solve of B (0 unless eig_method == 2)
   int32_t lanczos_steps = 0;
 
   // timings
@@ -2664,6 +2665,7 @@ int pcoa_compute(pcoa_ctx* c, int32_t num_pc, double* out_components, double* ou
   std::vector<double> sel((size_t)num_pc);
   bool have_vectors = false;
   c->eig_method = 0;
+  c->eig_dense_form = 0;
   c->lanczos_steps = 0;
   if (try_lanczos) {
     // fast path: Lanczos on B for the k wanted pairs, accepted only with a verified residual
@@ -2706,7 +2708,7 @@ int pcoa_compute(pcoa_ctx* c, int32_t num_pc, double* out_components, double* ou
     }
     {
       ScopedTimer t(c, T_TRIDIAG);
-      HIP_TRY(c, launch_tridiagonalize(c->ws, n, c->stream));
+      HIP_TRY(c, launch_tridiagonalize(c->ws, n, c->stream, &c->eig_dense_form));
     }
     // candidates: the k algebraically largest and the k smallest eigenvalues of T; MLlib ranks by the
     // singular values of Cov, i.e. by |lambda| (B = J S J is PSD up to rounding, so normally the largest)
@@ -2717,7 +2719,7 @@ int pcoa_compute(pcoa_ctx* c, int32_t num_pc, double* out_components, double* ou
     std::vector<double> cand(idx.size());
     {
       ScopedTimer t(c, T_EIG);
-      HIP_TRY(c, launch_bisect(c->ws, n, idx.data(), (int32_t)idx.size(), c->ws.lam, c->stream));
+      HIP_TRY(c, launch_bisect(c->ws, n, idx.data(), (int32_t)idx.size(), c->ws.lam, c->stream, &c->eig_dense_form));
       HIP_TRY(c, hipMemcpyAsync(cand.data(), c->ws.lam, sizeof(double) * cand.size(), hipMemcpyDeviceToHost,
                                 c->stream));
     }
@@ -2735,13 +2737,13 @@ int pcoa_compute(pcoa_ctx* c, int32_t num_pc, double* out_components, double* ou
     }
     {
       ScopedTimer t(c, T_EIG);
-      HIP_TRY(c, launch_inverse_iteration(c->ws, n, sel.data(), num_pc, c->stream));
+      HIP_TRY(c, launch_inverse_iteration(c->ws, n, sel.data(), num_pc, c->stream, &c->eig_dense_form));
     }
   }
   {
     ScopedTimer t(c, T_BACK);
     HIP_TRY(c, launch_backtransform(c->ws, n, num_pc, (c->flags & PCOA_FLAG_NO_SIGN_NORM) ? 0 : 1,
-                                    have_vectors ? 0 : 1, c->out_dev, c->stream));
+                                    have_vectors ? 0 : 1, c->out_dev, c->stream, have_vectors ? nullptr : &c->eig_dense_form));
   }
   HIP_TRY(c, hipMemcpyAsync(out_components, c->out_dev, sizeof(double) * (size_t)num_pc * (size_t)n,
                             hipMemcpyDeviceToHost, c->stream));
@@ -2796,6 +2798,7 @@ int lanczos_over(pcoa_ctx* c, int32_t num_pc, const LanczosMatvec& mv, double* o
     return fail(c, PCOA_ERR_NOT_CONVERGED, "Lanczos did not reach a verified residual (tiny spectral gaps?); there is no dense "
                                            "fallback for an operator the engine does not hold");
   c->eig_method = 1;
+  c->eig_dense_form = 0;
   HIP_TRY(c, launch_backtransform(c->ws, n, num_pc, (c->flags & PCOA_FLAG_NO_SIGN_NORM) ? 0 : 1, 0, c->out_dev, c->stream));
   HIP_TRY(c, hipMemcpyAsync(out_components, c->out_dev, sizeof(double) * (size_t)num_pc * (size_t)n, hipMemcpyDeviceToHost,
                             c->stream));
@@ -3309,6 +3312,7 @@ int pcoa_get_timings_sized(pcoa_ctx* c, pcoa_timings* out_user, size_t out_size)
   out->reduce_int32_calls = c->reduce_i32_calls;
   out->narrowed_to_int32 = c->narrowed;
   out->lanczos_block_steps = c->lanczos_block_steps;
+  out->eig_dense_form = c->eig_dense_form;
   std::memcpy(out_user, out, std::min(out_size, sizeof(full)));
   return PCOA_OK;
 }

@@ -200,6 +200,14 @@ hipError_t launch_project(const int32_t* s32, const int64_t* s64_or_null, int32_
                           double* out, hipStream_t stream);
 
 // ---- symmetric eigensolver (eig.hip) ----------------------------------------------------------
+// launch forms of the dense solver (pcoa_timings.eig_dense_form, include/pcoa.h)
+constexpr int32_t EIG_FORM_FUSED = 1;              // tridiagonalisation: fused step, one launch per column
+constexpr int32_t EIG_FORM_FUSED_BIG_LDS = 2;      // ... with more than 64 KiB of dynamic LDS
+constexpr int32_t EIG_FORM_TWO_KERNEL = 4;         // tridiagonalisation: tridiag_hw_kernel + tridiag_update_kernel per column
+constexpr int32_t EIG_FORM_BISECT_LDS = 8;         // bisection reads d / e^2 from LDS
+constexpr int32_t EIG_FORM_INVIT_LDS = 16;         // inverse iteration keeps its LU factors in LDS
+constexpr int32_t EIG_FORM_INVIT_PER_VECTOR = 32;  // inverse iteration: one workgroup per vector
+constexpr int32_t EIG_FORM_WY_BACKTRANSFORM = 64;  // blocked compact-WY back-transform
 struct EigWorkspace {
   double* a;        // [n][n] in: symmetric matrix B; out: reflector vectors in rows (row k, cols k+1..n-1)
   double* d;        // [n]   diagonal of T
@@ -232,19 +240,20 @@ size_t symv_sym_workspace_doubles(int32_t n);
 hipError_t launch_row_sums_sym(const int32_t* s32, int32_t n, double* sym_part, double* row_sums, int64_t* row_sums_i64,
                                hipStream_t stream);
 void launch_centred_matvec(const EigWorkspace& ws, int32_t n, const double* x, double* y, hipStream_t stream);  // one y = B x (test hook)
-hipError_t launch_tridiagonalize(const EigWorkspace& ws, int32_t n, hipStream_t stream);
+// form (optional): the launcher ORs in the EIG_FORM_* bits (pcoa.h, pcoa_timings.eig_dense_form) of the form it launched
+hipError_t launch_tridiagonalize(const EigWorkspace& ws, int32_t n, hipStream_t stream, int32_t* form = nullptr);
 // eigenvalues with ascending indices idx[0..count) of T -> lam_out[0..count) (device)
 hipError_t launch_bisect(const EigWorkspace& ws, int32_t n, const int32_t* idx_host, int32_t count,
-                         double* lam_out_dev, hipStream_t stream);
+                         double* lam_out_dev, hipStream_t stream, int32_t* form = nullptr);
 // eigenvectors of T for lam_sel[0..k) (host values) -> ws.z
 hipError_t launch_inverse_iteration(const EigWorkspace& ws, int32_t n, const double* lam_sel_host, int32_t k,
-                                    hipStream_t stream);
+                                    hipStream_t stream, int32_t* form = nullptr);
 // the same with lam_sel already in ws.lam[0..k) on the device (one workgroup, vectors in sequence)
 hipError_t launch_inverse_iteration_dev(const EigWorkspace& ws, int32_t n, int32_t k, hipStream_t stream);
 // ws.z <- Q * ws.z (if apply_reflectors), normalise, sign-normalise (optional); out_dev[c*n + i] column-major
 size_t wy_workspace_doubles(int32_t n, int32_t k);
 hipError_t launch_backtransform(const EigWorkspace& ws, int32_t n, int32_t k, int sign_normalize,
-                                int apply_reflectors, double* out_dev, hipStream_t stream);
+                                int apply_reflectors, double* out_dev, hipStream_t stream, int32_t* form = nullptr);
 
 // ---- Lanczos fast path (eig_lanczos.hip) ------------------------------------------------------
 size_t lanczos_workspace_doubles(int32_t n, int32_t k, int32_t mmax);

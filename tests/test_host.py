@@ -58,6 +58,27 @@ def test_header_is_plain_c_and_a_c_client_links_against_the_library(tmp_path):
     assert "gfx950" in run.stdout
 
 
+def test_timings_struct_layout_matches_the_header(tmp_path):
+    """_lib.PcoaTimings mirrors pcoa_timings field by field: the offsets of the fields read by name (eig_dense_form, the last,
+    among them) and the size must equal the C compiler's."""
+    import ctypes
+    import shutil
+    import subprocess
+    gcc = shutil.which("gcc")
+    if not gcc:
+        pytest.skip("gcc not available")
+    timings = load_pkg("_lib").PcoaTimings
+    names = ["eig_method", "lanczos_block_steps", "eig_dense_form"]
+    src = tmp_path / "layout.c"
+    src.write_text('#include <stddef.h>\n#include <stdio.h>\n#include "pcoa.h"\nint main(void) {\n' +
+                   "".join('  printf("%%zu\\n", offsetof(pcoa_timings, %s));\n' % f for f in names) +
+                   '  printf("%zu\\n", sizeof(pcoa_timings));\n  return 0;\n}\n')
+    exe = str(tmp_path / "layout")
+    subprocess.check_call([gcc, "-std=c99", "-I", os.path.join(ROOT, "include"), str(src), "-o", exe])
+    got = [int(x) for x in subprocess.check_output([exe]).split()]
+    assert got == [getattr(timings, f).offset for f in names] + [ctypes.sizeof(timings)]
+
+
 def test_no_cpu_fallback_without_a_gpu():
     import torch
     if torch.cuda.is_available():
