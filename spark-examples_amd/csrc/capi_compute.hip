@@ -1,0 +1,784 @@
+// capi_compute.hip -- computePca on the device: centring, the eigensolvers and their workspace, the strip layout, and the
+// out-of-sample projection.
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <string>
+
+#include "pcoa_ctx.h"
+
+using namespace pcoa;
+
+namespace pcoa {
+
+int ensure_workspace(pcoa_ctx* c, int32_t k) {
+  const int64_t n = c->n;
+  if (!c->ws_ready) {
+    // ws.a (the N x N fp64 matrix B) is allocated lazily by ensure_b(): the Lanczos path evaluates B on the fly
+    HIP_TRY(c, dev_alloc((void**)&c->colmean, sizeof(double) * (size_t)n, c->device));
+    HIP_TRY(c, dev_alloc((void**)&c->ws.d, sizeof(double) * (size_t)n, c->device));
+    HIP_TRY(c, dev_alloc((void**)&c->ws.e, sizeof(double) * (size_t)n, c->device));
+    HIP_TRY(c, dev_alloc((void**)&c->ws.tau, sizeof(double) * (size_t)n, c->device));
+    HIP_TRY(c, dev_alloc((void**)&c->ws.q, sizeof(double) * (size_t)n, c->device));
+    HIP_TRY(c, dev_alloc((void**)&c->ws.w, sizeof(double) * (size_t)(2 * n), c->device));
+    HIP_TRY(c, dev_alloc((void**)&c->ws.scratch, sizeof(double) * (size_t)(6 * n), c->device));
+    HIP_TRY(c, dev_alloc((void**)&c->ws.iscratch, sizeof(int32_t) * (size_t)(2 * n + 64), c->device));
+    HIP_TRY(c, dev_alloc((void**)&c->row_sums, sizeof(double) * (size_t)n, c->device));
+    HIP_TRY(c, dev_alloc((void**)&c->stats, sizeof(double) * (size_t)(2 + n), c->device));
+    HIP_TRY(c, dev_alloc((void**)&c->nz, sizeof(int32_t) * 4, c->device));
+    HIP_TRY(c, hipMemsetAsync(c->ws.tau, 0, sizeof(double) * (size_t)n, c->stream));
+    HIP_TRY(c, hipMemsetAsync(c->ws.e, 0, sizeof(double) * (size_t)n, c->stream));
+    c->ws_ready = true;
+  }
+  if (k > c->kmax) {
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (c->ws.lam) dev_free(c->ws.lam);
+    if (c->ws.z) dev_free(c->ws.z);
+    if (c->out_dev) dev_free(c->out_dev);
+    if (c->ws.wy) dev_free(c->ws.wy);
+    if (c->ws.host_rec) (void)hipHostFree(c->ws.host_rec);
+    c->ws.lam = nullptr; c->ws.z = nullptr; c->out_dev = nullptr; c->ws.wy = nullptr; c->kmax = 0;
+    c->ws.host_rec = nullptr; c->ws.host_rec_cap = 0;
+    {  // pinned landing zone of the Lanczos check record (without it the read-back goes through pageable memory)
+      const size_t cap = 4 * (size_t)k + 16;
+      if (hipHostMalloc((void**)&c->ws.host_rec, sizeof(double) * cap, hipHostMallocDefault) == hipSuccess)
+        c->ws.host_rec_cap = cap;
+      else {
+        (void)hipGetLastError();
+        c->ws.host_rec = nullptr;
+      }
+    }
+    HIP_TRY(c, dev_alloc((void**)&c->ws.wy, sizeof(double) * wy_workspace_doubles(c->n, k), c->device));
+    HIP_TRY(c, dev_alloc((void**)&c->ws.lam, sizeof(double) * (size_t)(2 * k + 8), c->device));
+    HIP_TRY(c, dev_alloc((void**)&c->ws.z, sizeof(double) * (size_t)((int64_t)k * n), c->device));
+    HIP_TRY(c, dev_alloc((void**)&c->out_dev, sizeof(double) * (size_t)((int64_t)k * n), c->device));
+    c->kmax = k;
+  }
+  return PCOA_OK;
+}
+
+int ensure_b(pcoa_ctx* c) {
+  if (c->ws.a) return PCOA_OK;
+  const int64_t n = c->n;
+  HIP_TRY(c, dev_alloc((void**)&c->ws.a, sizeof(double) * (size_t)(n * n), c->device));
+  return PCOA_OK;
+}
+
+}  // namespace pcoa
+
+namespace {
+
+// the body of pcoa_lanczos_with_matvec / pcoa_compute_strips: c's Lanczos over the operator mv (c's device is current)
+int lanczos_over(pcoa_ctx* c, int32_t num_pc, const LanczosMatvec& mv, double* out_components, double* out_eigenvalues,
+                 int32_t* steps_out) {
+  const int32_t n = c->n;
+  int rc = ensure_workspace(c, num_pc);
+  if (rc != PCOA_OK) return rc;
+  const int32_t mmax = std::min<int32_t>(n, 512);
+  if ((rc = ensure(c, &c->lanczos_ws, &c->lanczos_cap, (int64_t)lanczos_workspace_doubles(n, num_pc, mmax))) != PCOA_OK) return rc;
+  std::vector<double> sel((size_t)num_pc);
+  int conv = 0, steps = 0;
+  {
+    ScopedTimer t(c, T_LANCZOS);
+    EigWorkspace wl = c->ws;
+    wl.a = nullptr;
+    wl.s32 = nullptr;
+    wl.s64 = nullptr;
+    wl.band_only = (c->flags & PCOA_FLAG_EIG_BAND) != 0;
+    int band = 0;
+    HIP_TRY(c, lanczos_topk(wl, c->lanczos_ws, n, num_pc, mmax, 1e-11, sel.data(), &conv, &steps, c->stream, &mv, &band));
+    c->lanczos_block_steps = band;
+  }
+  c->lanczos_steps = steps;
+  if (steps_out) *steps_out = steps;
+  if (!conv)
+    return fail(c, PCOA_ERR_NOT_CONVERGED, "Lanczos did not reach a verified residual (tiny spectral gaps?); there is no dense "
+                                           "fallback for an operator the engine does not hold");
+  c->eig_method = 1;
+  c->eig_dense_form = 0;
+  HIP_TRY(c, launch_backtransform(c->ws, n, num_pc, (c->flags & PCOA_FLAG_NO_SIGN_NORM) ? 0 : 1, 0, c->out_dev, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(out_components, c->out_dev, sizeof(double) * (size_t)num_pc * (size_t)n, hipMemcpyDeviceToHost,
+                            c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  for (size_t i = 0; i < (size_t)num_pc * (size_t)n; ++i)
+    if (!std::isfinite(out_components[i])) return fail(c, PCOA_ERR_NOT_CONVERGED, "non-finite eigenvector entry");
+  if (out_eigenvalues)
+    for (int32_t t = 0; t < num_pc; ++t) out_eigenvalues[t] = sel[(size_t)t];
+  return PCOA_OK;
+}
+
+// a failed input check of either engine: the engine cannot serve a projection (its S is invalid until pcoa_reset)
+int project_engine_state(pcoa_ctx* report, pcoa_ctx* c, const char* who, int rc) {
+  if (rc == PCOA_ERR_INDEX_RANGE || rc == PCOA_ERR_INVALID_ARG) rc = PCOA_ERR_STATE;
+  return fail(report, rc, std::string("project: ") + who + ": " + c->last_error);
+}
+
+// computePca over the strips when N < 32 (no Lanczos): the strips assembled on the host into one full engine on the lead's
+// device, whose pcoa_compute is then the single engine's by construction
+int compute_strips_small(pcoa_ctx* const* owners, int32_t n_owners, int32_t num_pc, double* out_components,
+                         double* out_eigenvalues, int32_t* nonzero_rows_out) {
+  pcoa_ctx* lead = owners[0];
+  const int32_t n = lead->n;
+  std::vector<int64_t> s((size_t)n * (size_t)n), part;
+  for (int32_t i = 0; i < n_owners; ++i) {
+    pcoa_ctx* o = owners[i];
+    part.assign((size_t)n * (size_t)o->s_cols, 0);
+    const int rc = pcoa_gram_read_i64(o, part.data());
+    if (rc != PCOA_OK) return fail(lead, rc, "compute_strips: owner " + std::to_string(i) + ": " + o->last_error);
+    for (int32_t r = 0; r < n; ++r)
+      for (int32_t j = 0; j < o->s_cols; ++j) s[(size_t)r * n + o->strip_col0 + j] = part[(size_t)r * o->s_cols + j];
+  }
+  pcoa_ctx* tmp = nullptr;
+  int rc = pcoa_create(&tmp, n, lead->device, lead->flags);
+  if (rc != PCOA_OK) return fail(lead, rc, std::string("compute_strips: temporary engine: ") + pcoa_last_error(nullptr));
+  rc = pcoa_gram_load_i64(tmp, s.data());
+  if (rc == PCOA_OK) rc = pcoa_compute(tmp, num_pc, out_components, out_eigenvalues, nonzero_rows_out);
+  if (rc != PCOA_OK) lead->last_error = "compute_strips: temporary engine: " + tmp->last_error;
+  pcoa_destroy(tmp);
+  (void)hipSetDevice(lead->device);
+  return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pcoa_center_read_f64(pcoa_ctx* c, double* out_b, double* out_row_sums, int32_t* out_nonzero_rows,
+                         double* out_matrix_mean) {
+  CHECK_CTX(c);
+  if (c->is_strip) return fail(c, PCOA_ERR_STATE, "a strip owner holds N x cols of S: use pcoa_strip_col_sums / pcoa_strip_matvec");
+  int rc = finalize_impl(c);
+  if (rc != PCOA_OK) return rc;
+  if ((rc = check_device_flags(c)) != PCOA_OK) return rc;
+  rc = ensure_workspace(c, 1);
+  if (rc != PCOA_OK) return rc;
+  if (out_b && (rc = ensure_b(c)) != PCOA_OK) return rc;
+  const size_t n = (size_t)c->n;
+  {
+    ScopedTimer t(c, T_CENTER);
+    HIP_TRY(c, launch_center(c->s32, c->s64, c->n, c->row_sums, c->stats, c->nz, out_b ? c->ws.a : nullptr,
+                             c->stream));
+  }
+  if (out_b) HIP_TRY(c, hipMemcpyAsync(out_b, c->ws.a, sizeof(double) * n * n, hipMemcpyDeviceToHost, c->stream));
+  if (out_row_sums)
+    HIP_TRY(c, hipMemcpyAsync(out_row_sums, c->row_sums, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(c->hw->st, c->stats, 2 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(&c->hw->nz, c->nz, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if (out_nonzero_rows) *out_nonzero_rows = c->hw->nz;
+  if (out_matrix_mean) *out_matrix_mean = c->hw->st[1];
+  return PCOA_OK;
+}
+
+int pcoa_compute(pcoa_ctx* c, int32_t num_pc, double* out_components, double* out_eigenvalues,
+                 int32_t* out_nonzero_rows) {
+  CHECK_CTX(c);
+  const int32_t n = c->n;
+  if (num_pc <= 0 || num_pc > n) {
+    char buf[128];
+    std::snprintf(buf, sizeof(buf), "num_pc = %d out of range (0, n = %d]", num_pc, n);  // MLlib require(k > 0 && k <= n)
+    return fail(c, PCOA_ERR_INVALID_ARG, buf);
+  }
+  if (!out_components) return fail(c, PCOA_ERR_INVALID_ARG, "out_components is NULL");
+  if (c->is_strip)
+    return fail(c, PCOA_ERR_STATE, "a strip owner holds N x cols of S: the eigensolve over strips is driven by the host "
+                                   "(pcoa_strip_col_sums / pcoa_strip_matvec; spark-examples_amd/strips.py)");
+  int rc = finalize_impl(c);
+  if (rc != PCOA_OK) return rc;
+  rc = check_device_flags(c);
+  if (rc != PCOA_OK) return rc;
+  rc = ensure_workspace(c, num_pc);
+  if (rc != PCOA_OK) return rc;
+
+  struct WallEvents {  // back to the pool on every path out of this function
+    pcoa_ctx* c;
+    hipEvent_t w0, w1;
+    ~WallEvents() {
+      if (w0) c->pool.push_back(w0);
+      if (w1) c->pool.push_back(w1);
+    }
+  } wall{c, get_event(c), get_event(c)};
+  hipEvent_t w0 = wall.w0, w1 = wall.w1;
+  if (w0) (void)hipEventRecord(w0, c->stream);
+
+  const bool force_householder = (c->flags & PCOA_FLAG_EIG_HOUSEHOLDER) != 0;
+  const bool force_lanczos = (c->flags & PCOA_FLAG_EIG_LANCZOS) != 0;
+  const bool try_lanczos = !force_householder && n >= 32;
+  // The Lanczos path evaluates B on the fly inside its matvec (bit-identical entries, half the bytes, no N x N fp64
+  // matrix); B is only materialised for the dense solver.  PCOA_EXPLICIT_CENTER=1 restores the materialised form.
+  const bool explicit_b = !try_lanczos || debug_knobs().explicit_center != 0;
+  if (explicit_b && (rc = ensure_b(c)) != PCOA_OK) return rc;
+  // large N: row sums and mat-vec read only the upper triangle of S (half the bytes; rowsums_sym_tiles_kernel,
+  // symv_sym_tiles_kernel)
+  const int sym_min = debug_knobs().symv_sym_min_n > 0 ? debug_knobs().symv_sym_min_n : 16384;
+  const bool sym_form = !explicit_b && !c->s64 && n >= sym_min && (n & 3) == 0;
+  if (sym_form && (rc = ensure(c, &c->sym_part, &c->sym_part_cap, (int64_t)symv_sym_workspace_doubles(n))) != PCOA_OK) return rc;
+  {
+    ScopedTimer t(c, T_CENTER);
+    if (sym_form)
+      HIP_TRY(c, launch_row_sums_sym(c->s32, n, c->sym_part, c->row_sums, reinterpret_cast<int64_t*>(c->stats + 2), c->stream));
+    HIP_TRY(c, launch_center(c->s32, c->s64, n, c->row_sums, c->stats, c->nz, explicit_b ? c->ws.a : nullptr,
+                             c->stream, sym_form));
+    HIP_TRY(c, launch_col_means(c->row_sums, n, c->colmean, c->stream));
+  }
+  c->ws.s32 = c->s32;
+  c->ws.s64 = c->s64;
+  c->ws.colmean = c->colmean;
+  c->ws.stats = c->stats;
+  bool b_ready = explicit_b;
+  std::vector<double> sel((size_t)num_pc);
+  bool have_vectors = false;
+  c->eig_method = 0;
+  c->eig_dense_form = 0;
+  c->lanczos_steps = 0;
+  if (try_lanczos) {
+    // fast path: Lanczos on B for the k wanted pairs, accepted only with a verified residual
+    const int32_t mmax = std::min<int32_t>(n, 512);
+    const int64_t need = (int64_t)lanczos_workspace_doubles(n, num_pc, mmax);
+    rc = ensure(c, &c->lanczos_ws, &c->lanczos_cap, need);
+    if (rc != PCOA_OK) return rc;
+    int conv = 0, steps = 0;
+    {
+      ScopedTimer t(c, T_LANCZOS);
+      EigWorkspace wl = c->ws;
+      if (!b_ready) wl.a = nullptr;  // implicit form
+      wl.sym_part = (sym_form && !wl.a) ? c->sym_part : nullptr;
+      c->matvec_form = wl.a ? 2 : wl.sym_part ? 1 : 0;
+      wl.band_only = (c->flags & PCOA_FLAG_EIG_BAND) != 0;
+      int band = 0;
+      HIP_TRY(c, lanczos_topk(wl, c->lanczos_ws, n, num_pc, mmax, 1e-11, sel.data(), &conv, &steps, c->stream, nullptr, &band));
+      c->lanczos_block_steps = band;
+    }
+    c->lanczos_steps = steps;
+    if (conv) {
+      have_vectors = true;
+      c->eig_method = 1;
+    } else if (force_lanczos) {
+      return fail(c, PCOA_ERR_NOT_CONVERGED, "Lanczos did not reach a verified residual (PCOA_FLAG_EIG_LANCZOS set)");
+    } else if (n > 16384) {
+      return fail(c, PCOA_ERR_NOT_CONVERGED,
+                  "Lanczos did not reach a verified residual and the dense O(N^3) fallback is disabled above "
+                  "N = 16384 (set PCOA_FLAG_EIG_HOUSEHOLDER to force it)");
+    }
+  }
+  if (!have_vectors) {
+    // exact, gap-independent path: Householder tridiagonalisation + bisection + inverse iteration
+    c->eig_method = 2;
+    if (!b_ready) {  // the dense solver needs B in memory
+      if ((rc = ensure_b(c)) != PCOA_OK) return rc;
+      ScopedTimer t(c, T_CENTER);
+      HIP_TRY(c, launch_center(c->s32, c->s64, n, c->row_sums, c->stats, c->nz, c->ws.a, c->stream));
+      b_ready = true;
+    }
+    {
+      ScopedTimer t(c, T_TRIDIAG);
+      HIP_TRY(c, launch_tridiagonalize(c->ws, n, c->stream, &c->eig_dense_form));
+    }
+    // candidates: the k algebraically largest and the k smallest eigenvalues of T; MLlib ranks by the
+    // singular values of Cov, i.e. by |lambda| (B = J S J is PSD up to rounding, so normally the largest)
+    std::vector<int32_t> idx;
+    for (int32_t t = 0; t < num_pc; ++t) idx.push_back(n - 1 - t);
+    for (int32_t t = 0; t < num_pc; ++t)
+      if (t < n - num_pc) idx.push_back(t);
+    std::vector<double> cand(idx.size());
+    {
+      ScopedTimer t(c, T_EIG);
+      HIP_TRY(c, launch_bisect(c->ws, n, idx.data(), (int32_t)idx.size(), c->ws.lam, c->stream, &c->eig_dense_form));
+      HIP_TRY(c, hipMemcpyAsync(cand.data(), c->ws.lam, sizeof(double) * cand.size(), hipMemcpyDeviceToHost,
+                                c->stream));
+    }
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    std::vector<int> order(cand.size());
+    for (size_t i = 0; i < order.size(); ++i) order[i] = (int)i;
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) {
+      const double fa = std::fabs(cand[a]), fb = std::fabs(cand[b]);
+      if (fa != fb) return fa > fb;
+      return cand[a] > cand[b];
+    });
+    for (int32_t t = 0; t < num_pc; ++t) {
+      if (!std::isfinite(cand[order[t]])) return fail(c, PCOA_ERR_NOT_CONVERGED, "non-finite eigenvalue");
+      sel[(size_t)t] = cand[order[t]];
+    }
+    {
+      ScopedTimer t(c, T_EIG);
+      HIP_TRY(c, launch_inverse_iteration(c->ws, n, sel.data(), num_pc, c->stream, &c->eig_dense_form));
+    }
+  }
+  {
+    ScopedTimer t(c, T_BACK);
+    HIP_TRY(c, launch_backtransform(c->ws, n, num_pc, (c->flags & PCOA_FLAG_NO_SIGN_NORM) ? 0 : 1,
+                                    have_vectors ? 0 : 1, c->out_dev, c->stream, have_vectors ? nullptr : &c->eig_dense_form));
+  }
+  HIP_TRY(c, hipMemcpyAsync(out_components, c->out_dev, sizeof(double) * (size_t)num_pc * (size_t)n,
+                            hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(&c->hw->nz, c->nz, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+  if (w1) (void)hipEventRecord(w1, c->stream);
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if (w0 && w1) {
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, w0, w1) == hipSuccess) c->compute_total = (double)ms * 1e-3;
+  }
+  for (int32_t t = 0; t < num_pc; ++t) {
+    for (int32_t i = 0; i < n; ++i)
+      if (!std::isfinite(out_components[(size_t)t * n + i]))
+        return fail(c, PCOA_ERR_NOT_CONVERGED, "non-finite eigenvector entry");
+  }
+  if (out_eigenvalues)
+    for (int32_t t = 0; t < num_pc; ++t) out_eigenvalues[t] = sel[(size_t)t];
+  if (out_nonzero_rows) *out_nonzero_rows = c->hw->nz;
+  return PCOA_OK;
+}
+
+// Top-k eigenpairs of a symmetric operator the CALLER applies (r04): the engine's Lanczos -- Krylov basis, CGS2, the Ritz
+// problem by bisection + inverse iteration, acceptance only on the TRUE residual -- with y = B v supplied through a callback
+// on device vectors.  The strip-owner layout (B tiled over GPUs, one all-gather per product) runs its computePca through this,
+// so that no linear algebra happens outside these kernels (VERDICT r03 Weak 5).  Works on any ctx (its N, its GPU, its
+// stream); S is not touched.
+int pcoa_lanczos_with_matvec(pcoa_ctx* c, int32_t num_pc, pcoa_matvec_fn fn, void* user, double* out_components,
+                             double* out_eigenvalues, int32_t* steps_out) {
+  CHECK_CTX(c);
+  const int32_t n = c->n;
+  if (!fn || !out_components) return fail(c, PCOA_ERR_INVALID_ARG, "fn or out_components is NULL");
+  if (num_pc <= 0 || num_pc > n) return fail(c, PCOA_ERR_INVALID_ARG, "num_pc must be in (0, n]");
+  if (n < 32) return fail(c, PCOA_ERR_INVALID_ARG, "the Lanczos path needs N >= 32");
+  LanczosMatvec mv = [&](const double* v, double* y) { return fn(user, v, y); };
+  return lanczos_over(c, num_pc, mv, out_components, out_eigenvalues, steps_out);
+}
+
+int pcoa_strip_info(const pcoa_ctx* c, int32_t* col0_out, int32_t* cols_out) {
+  if (!c) return fail(nullptr, PCOA_ERR_INVALID_ARG, "ctx is NULL");
+  if (col0_out) *col0_out = c->strip_col0;
+  if (cols_out) *cols_out = c->s_cols;
+  return c->is_strip ? 1 : 0;
+}
+
+int pcoa_strip_col_sums(pcoa_ctx* c, double* out_cols) {
+  CHECK_CTX(c);
+  if (!c->is_strip) return fail(c, PCOA_ERR_STATE, "not a strip owner (pcoa_create_strip)");
+  if (!out_cols) return fail(c, PCOA_ERR_INVALID_ARG, "out_cols is NULL");
+  int rc = finalize_impl(c);
+  if (rc != PCOA_OK) return rc;
+  if ((rc = check_device_flags(c)) != PCOA_OK) return rc;
+  const int64_t need = strip_ws_doubles(c->n, c->s_cols);
+  if ((rc = ensure(c, &c->strip_ws, &c->strip_ws_cap, need)) != PCOA_OK) return rc;
+  {
+    ScopedTimer t(c, T_CENTER);
+    HIP_TRY(c, launch_strip_col_sums(c->s32, c->s64, c->n, c->s_cols, c->strip_ws, c->stream));
+  }
+  HIP_TRY(c, hipMemcpyAsync(out_cols, c->strip_ws, sizeof(double) * (size_t)c->s_cols, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return PCOA_OK;
+}
+
+int pcoa_strip_matvec(pcoa_ctx* c, const double* v, const double* means, double matrix_mean, double* y_out) {
+  CHECK_CTX(c);
+  if (!c->is_strip) return fail(c, PCOA_ERR_STATE, "not a strip owner (pcoa_create_strip)");
+  if (!v || !means || !y_out) return fail(c, PCOA_ERR_INVALID_ARG, "v, means or y_out is NULL");
+  int rc = finalize_impl(c);
+  if (rc != PCOA_OK) return rc;
+  if ((rc = check_device_flags(c)) != PCOA_OK) return rc;  // never multiply by an S that an input check has invalidated
+  const int64_t need = strip_ws_doubles(c->n, c->s_cols) + 2 * (int64_t)c->n;
+  if ((rc = ensure(c, &c->strip_ws, &c->strip_ws_cap, need)) != PCOA_OK) return rc;
+  double* v_dev = c->strip_ws + strip_ws_doubles(c->n, c->s_cols);
+  double* m_dev = v_dev + c->n;
+  HIP_TRY(c, hipMemcpyAsync(v_dev, v, sizeof(double) * (size_t)c->n, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(m_dev, means, sizeof(double) * (size_t)c->n, hipMemcpyHostToDevice, c->stream));
+  {
+    ScopedTimer t(c, T_LANCZOS);
+    HIP_TRY(c, launch_strip_matvec(c->s32, c->s64, c->n, c->strip_col0, c->s_cols, v_dev, m_dev, matrix_mean, c->strip_ws,
+                                   c->stream));
+  }
+  HIP_TRY(c, hipMemcpyAsync(y_out, c->strip_ws, sizeof(double) * (size_t)c->s_cols, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return PCOA_OK;
+}
+
+int pcoa_strip_set_centering(pcoa_ctx* c, const double* means, double matrix_mean) {
+  CHECK_CTX(c);
+  if (!c->is_strip) return fail(c, PCOA_ERR_STATE, "not a strip owner (pcoa_create_strip)");
+  if (!means) return fail(c, PCOA_ERR_INVALID_ARG, "means is NULL");
+  if (!c->strip_means) HIP_TRY(c, dev_alloc((void**)&c->strip_means, sizeof(double) * (size_t)c->n, c->device));
+  HIP_TRY(c, hipMemcpyAsync(c->strip_means, means, sizeof(double) * (size_t)c->n, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));  // the caller's array may go away
+  c->strip_matrix_mean = matrix_mean;
+  c->strip_centering_set = true;
+  return PCOA_OK;
+}
+
+int pcoa_strip_matvec_device(pcoa_ctx* c, const double* v_dev, double* y_dev) {
+  CHECK_CTX(c);
+  if (!c->is_strip) return fail(c, PCOA_ERR_STATE, "not a strip owner (pcoa_create_strip)");
+  if (!v_dev || !y_dev) return fail(c, PCOA_ERR_INVALID_ARG, "v_dev or y_dev is NULL");
+  if (!c->strip_centering_set) return fail(c, PCOA_ERR_STATE, "pcoa_strip_set_centering has not been called");
+  int rc = finalize_impl(c);
+  if (rc != PCOA_OK) return rc;
+  if ((rc = check_device_flags(c)) != PCOA_OK) return rc;
+  const int64_t need = strip_ws_doubles(c->n, c->s_cols) + 2 * (int64_t)c->n;
+  if ((rc = ensure(c, &c->strip_ws, &c->strip_ws_cap, need)) != PCOA_OK) return rc;
+  {
+    ScopedTimer t(c, T_LANCZOS);
+    HIP_TRY(c, launch_strip_matvec(c->s32, c->s64, c->n, c->strip_col0, c->s_cols, v_dev, c->strip_means, c->strip_matrix_mean,
+                                   c->strip_ws, c->stream));
+  }
+  HIP_TRY(c, hipMemcpyAsync(y_dev, c->strip_ws, sizeof(double) * (size_t)c->s_cols, hipMemcpyDeviceToDevice, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));  // y_dev is ready for the caller's own stream / collective
+  return PCOA_OK;
+}
+
+// ---- out-of-sample projection -------------------------------------------------------------------------------------------
+// pcoa_project: the reference's centring is recomputed on ref with the kernels pcoa_compute runs (row sums -> stats ->
+// rowSums / N), so mean_j and the matrix mean are its values bit for bit; the means travel to cross's device once, the column
+// sums over rows [0, n_ref) of cross's strip give m_q, and the projection pass reads the strip once per chunk of components.
+
+int pcoa_project(pcoa_ctx* ref, pcoa_ctx* cross, int32_t num_pc, const double* components, const double* eigenvalues,
+                 double* out_coords) {
+  if (!cross) return fail(ref, PCOA_ERR_INVALID_ARG, "project: cross is NULL");
+  CHECK_CTX(ref);
+  if (!components || !eigenvalues || !out_coords)
+    return fail(ref, PCOA_ERR_INVALID_ARG, "project: components, eigenvalues or out_coords is NULL");
+  if (ref->is_strip)
+    return fail(ref, PCOA_ERR_INVALID_ARG, "project: ref is a strip owner; the reference must be a full engine (pcoa_create) -- "
+                                           "a reference solved over strips is not supported");
+  if (!cross->is_strip) return fail(ref, PCOA_ERR_INVALID_ARG, "project: cross is not a strip owner (pcoa_create_strip)");
+  const int32_t n_ref = ref->n, cols = cross->s_cols;
+  if (cross->n < n_ref)
+    return fail(ref, PCOA_ERR_INVALID_ARG, "project: cross has N = " + std::to_string(cross->n) + " rows, fewer than ref's " +
+                                               std::to_string(n_ref));
+  if (num_pc <= 0 || num_pc > n_ref)
+    return fail(ref, PCOA_ERR_INVALID_ARG, "project: num_pc = " + std::to_string(num_pc) + " out of range (0, n = " +
+                                               std::to_string(n_ref) + "]");
+  for (int32_t c = 0; c < num_pc; ++c)
+    if (eigenvalues[c] == 0.0 || !std::isfinite(eigenvalues[c]))
+      return fail(ref, PCOA_ERR_INVALID_ARG, "project: eigenvalue " + std::to_string(c) + " is zero or not finite");
+
+  // cross: S complete and clean; its buffers sized before ref writes into them
+  HIP_TRY(ref, hipSetDevice(cross->device));
+  int rc = finalize_impl(cross);
+  if (rc == PCOA_OK) rc = check_device_flags(cross);
+  if (rc != PCOA_OK) return project_engine_state(ref, cross, "cross", rc);
+  const int32_t k_max = project_chunk(num_pc);
+  const int64_t off_u = n_ref, off_lam = off_u + (int64_t)num_pc * n_ref, off_out = off_lam + num_pc,
+                off_part = off_out + (int64_t)num_pc * cols;
+  const int64_t need = off_part + project_ws_doubles(n_ref, cols, k_max);
+  if ((rc = ensure(cross, &cross->proj_ws, &cross->proj_ws_cap, need)) != PCOA_OK) return fail(ref, rc, "project: cross: " + cross->last_error);
+  if ((rc = ensure(cross, &cross->strip_ws, &cross->strip_ws_cap, strip_ws_doubles(n_ref, cols))) != PCOA_OK)
+    return fail(ref, rc, "project: cross: " + cross->last_error);
+  double* const means_x = cross->proj_ws;
+
+  // ref: the centring pcoa_compute used (VariantsPca.scala:206-215), then its means to cross
+  HIP_TRY(ref, hipSetDevice(ref->device));
+  rc = finalize_impl(ref);
+  if (rc == PCOA_OK) rc = check_device_flags(ref);
+  if (rc != PCOA_OK) return project_engine_state(ref, ref, "ref", rc);
+  if ((rc = ensure_workspace(ref, 1)) != PCOA_OK) return rc;
+  const int sym_min = debug_knobs().symv_sym_min_n > 0 ? debug_knobs().symv_sym_min_n : 16384;
+  const bool sym_form = !ref->s64 && n_ref >= sym_min && (n_ref & 3) == 0;   // exact integer row sums either way
+  if (sym_form && (rc = ensure(ref, &ref->sym_part, &ref->sym_part_cap, (int64_t)symv_sym_workspace_doubles(n_ref))) != PCOA_OK)
+    return rc;
+  {
+    ScopedTimer t(ref, T_CENTER);
+    if (sym_form)
+      HIP_TRY(ref, launch_row_sums_sym(ref->s32, n_ref, ref->sym_part, ref->row_sums, reinterpret_cast<int64_t*>(ref->stats + 2),
+                                       ref->stream));
+    HIP_TRY(ref, launch_center(ref->s32, ref->s64, n_ref, ref->row_sums, ref->stats, ref->nz, nullptr, ref->stream, sym_form));
+    HIP_TRY(ref, launch_col_means(ref->row_sums, n_ref, ref->colmean, ref->stream));
+  }
+  HIP_TRY(ref, hipMemcpyAsync(ref->hw->st, ref->stats, 2 * sizeof(double), hipMemcpyDeviceToHost, ref->stream));
+  if (ref->device == cross->device)
+    HIP_TRY(ref, hipMemcpyAsync(means_x, ref->colmean, sizeof(double) * (size_t)n_ref, hipMemcpyDeviceToDevice, ref->stream));
+  else
+    HIP_TRY(ref, hipMemcpyPeerAsync(means_x, cross->device, ref->colmean, ref->device, sizeof(double) * (size_t)n_ref, ref->stream));
+  HIP_TRY(ref, hipStreamSynchronize(ref->stream));
+  const double matrix_mean = ref->hw->st[1];
+
+  // cross: m_q from the column sums over rows [0, n_ref), then the components in chunks of 8 / 4 / 2 / 1
+  HIP_TRY(ref, hipSetDevice(cross->device));
+  double* const ws = cross->proj_ws;
+  HIP_TRY(ref, hipMemcpyAsync(ws + off_u, components, sizeof(double) * (size_t)num_pc * (size_t)n_ref, hipMemcpyHostToDevice,
+                              cross->stream));
+  HIP_TRY(ref, hipMemcpyAsync(ws + off_lam, eigenvalues, sizeof(double) * (size_t)num_pc, hipMemcpyHostToDevice, cross->stream));
+  {
+    ScopedTimer t(cross, T_CENTER);
+    HIP_TRY(ref, launch_strip_col_sums(cross->s32, cross->s64, n_ref, cols, cross->strip_ws, cross->stream));
+    for (int32_t c0 = 0; c0 < num_pc;) {
+      const int32_t k = project_chunk(num_pc - c0);
+      HIP_TRY(ref, launch_project(cross->s32, cross->s64, n_ref, cols, cross->strip_ws, means_x, matrix_mean,
+                                  ws + off_u + (int64_t)c0 * n_ref, k, ws + off_lam + c0, ws + off_part,
+                                  ws + off_out + (int64_t)c0 * cols, cross->stream));
+      c0 += k;
+    }
+  }
+  HIP_TRY(ref, hipMemcpyAsync(out_coords, ws + off_out, sizeof(double) * (size_t)num_pc * (size_t)cols, hipMemcpyDeviceToHost,
+                              cross->stream));
+  HIP_TRY(ref, hipStreamSynchronize(cross->stream));
+  HIP_TRY(ref, hipSetDevice(ref->device));
+  return PCOA_OK;
+}
+
+// ---- the strip layout in one process --------------------------------------------------------------------------------------
+
+// strips.strip_ranges: balanced cuts, each rounded to the nearest multiple of 256 (the contraction's tile width) where that
+// leaves it strictly between its left neighbour and N; if some strip still ends up empty, the plain balanced cuts
+int pcoa_plan_layout(int32_t n_samples, int32_t n_engines, const int64_t* free_bytes, int32_t request, int32_t* layout_out,
+                     int32_t* col0_out, int32_t* cols_out) {
+  if (n_samples <= 0 || n_engines <= 0 || !layout_out)
+    return fail(nullptr, PCOA_ERR_INVALID_ARG, "plan_layout: n_samples and n_engines must be positive, layout_out non-NULL");
+  if (request != PCOA_LAYOUT_AUTO && request != PCOA_LAYOUT_FULL && request != PCOA_LAYOUT_STRIPS)
+    return fail(nullptr, PCOA_ERR_INVALID_ARG, "plan_layout: request must be PCOA_LAYOUT_AUTO, _FULL or _STRIPS");
+  const int64_t n = n_samples, k = n_engines;
+  int32_t layout = request;
+  if (request == PCOA_LAYOUT_AUTO) {
+    if (!free_bytes) return fail(nullptr, PCOA_ERR_INVALID_ARG, "plan_layout: auto needs free_bytes");
+    layout = PCOA_LAYOUT_FULL;
+    // one engine: a single strip needs the same 4 N^2 bytes, so it could only change the eigensolver path with the memory
+    // other processes happen to use; more engines than samples: no strip layout exists
+    if (k > 1 && k <= n) {
+      const double s_bytes = 4.0 * (double)n * (double)n;
+      for (int64_t g = 0; g < k; ++g) {
+        const double need = s_bytes + ((g == 0 && k > 1) ? s_bytes : 0.0);   // engine 0 stages a peer's S to reduce it
+        if (need > PCOA_LAYOUT_FREE_FRACTION * (double)free_bytes[g]) layout = PCOA_LAYOUT_STRIPS;
+      }
+    }
+  }
+  if (layout == PCOA_LAYOUT_STRIPS) {
+    if (k > n) return fail(nullptr, PCOA_ERR_INVALID_ARG, "plan_layout: the strip layout needs n_engines <= n_samples");
+    if (!col0_out || !cols_out) return fail(nullptr, PCOA_ERR_INVALID_ARG, "plan_layout: col0_out / cols_out are NULL");
+    constexpr int64_t align = 256;
+    std::vector<int64_t> cuts{0};
+    for (int64_t g = 1; g < k; ++g) {
+      const int64_t c = n * g / k;
+      const int64_t a = (c + align / 2) / align * align;
+      cuts.push_back(cuts.back() < a && a < n ? a : c);
+    }
+    cuts.push_back(n);
+    bool ok = true;
+    for (int64_t g = 0; g < k; ++g) ok = ok && cuts[(size_t)g + 1] > cuts[(size_t)g];
+    if (!ok)
+      for (int64_t g = 0; g <= k; ++g) cuts[(size_t)g] = n * g / k;
+    for (int64_t g = 0; g < k; ++g) {
+      col0_out[g] = (int32_t)cuts[(size_t)g];
+      cols_out[g] = (int32_t)(cuts[(size_t)g + 1] - cuts[(size_t)g]);
+    }
+  }
+  *layout_out = layout;
+  return PCOA_OK;
+}
+
+int pcoa_device_memory(int32_t device_ordinal, int64_t* free_out, int64_t* total_out) {
+  int prev = -1;
+  hipError_t e = hipGetDevice(&prev);
+  if (e == hipSuccess) e = hipSetDevice(device_ordinal);
+  size_t fr = 0, tot = 0;
+  if (e == hipSuccess) e = hipMemGetInfo(&fr, &tot);
+  if (prev >= 0) (void)hipSetDevice(prev);
+  if (e != hipSuccess) return hip_fail(nullptr, e, "pcoa_device_memory");
+  if (free_out) *free_out = (int64_t)fr;
+  if (total_out) *total_out = (int64_t)tot;
+  return PCOA_OK;
+}
+
+
+// computePca over the strip owners of ONE process (the strip layout of the compiled host): row sums gathered on the lead
+// (owners[0]), the means sent once to every owner, then the lead's Lanczos with a built-in product -- every owner multiplies
+// its strip on its own stream and writes its piece of y straight into the lead's vector.  No host round trip per step.
+int pcoa_compute_strips(pcoa_ctx* const* owners, int32_t n_owners, int32_t num_pc, double* out_components,
+                        double* out_eigenvalues, int32_t* nonzero_rows_out) {
+  if (!owners || n_owners <= 0 || !owners[0]) return fail(nullptr, PCOA_ERR_INVALID_ARG, "compute_strips: no owners");
+  pcoa_ctx* lead = owners[0];
+  CHECK_CTX(lead);
+  const int32_t n = lead->n;
+  int64_t next = 0;
+  for (int32_t i = 0; i < n_owners; ++i) {
+    const pcoa_ctx* o = owners[i];
+    const std::string who = "compute_strips: owner " + std::to_string(i);
+    if (!o) return fail(lead, PCOA_ERR_INVALID_ARG, who + " is NULL");
+    if (!o->is_strip) return fail(lead, PCOA_ERR_INVALID_ARG, who + " is not a strip owner (pcoa_create_strip)");
+    if (o->n != n) return fail(lead, PCOA_ERR_INVALID_ARG, who + " has a different N");
+    if (o->strip_col0 != next)
+      return fail(lead, PCOA_ERR_INVALID_ARG, who + " starts at column " + std::to_string(o->strip_col0) + ", expected " +
+                                                 std::to_string(next) + " (the strips must tile [0, N) in order)");
+    next += o->s_cols;
+  }
+  if (next != n) return fail(lead, PCOA_ERR_INVALID_ARG, "compute_strips: the strips end at column " + std::to_string(next) +
+                                                            ", N = " + std::to_string(n));
+  if (num_pc <= 0 || num_pc > n) return fail(lead, PCOA_ERR_INVALID_ARG, "compute_strips: num_pc must be in (0, n]");
+  if (!out_components) return fail(lead, PCOA_ERR_INVALID_ARG, "compute_strips: out_components is NULL");
+  if (n < 32) return compute_strips_small(owners, n_owners, num_pc, out_components, out_eigenvalues, nonzero_rows_out);
+  const double t0 = wall_now();
+  auto owner_failed = [&](int32_t i, int rc) {
+    if (i != 0) lead->last_error = "compute_strips: owner " + std::to_string(i) + ": " + owners[i]->last_error;
+    (void)hipSetDevice(lead->device);
+    return rc;
+  };
+  int rc = ensure_workspace(lead, num_pc);
+  if (rc != PCOA_OK) return rc;
+  int64_t* rs_i64 = reinterpret_cast<int64_t*>(lead->stats + 2);   // (launch_center's layout: behind stats[0..1])
+
+  // rowSums (:206): every owner's exact column sums into the lead's N-vectors at its columns
+  std::vector<char> peer((size_t)n_owners, 0);
+  for (int32_t i = 0; i < n_owners; ++i) {
+    pcoa_ctx* c = owners[i];
+    if (hipSetDevice(c->device) != hipSuccess) return owner_failed(i, hip_fail(c, hipGetLastError(), "hipSetDevice"));
+    if ((rc = finalize_impl(c)) != PCOA_OK || (rc = check_device_flags(c)) != PCOA_OK ||
+        (rc = ensure(c, &c->strip_ws, &c->strip_ws_cap, strip_ws_doubles(n, c->s_cols) + 2 * (int64_t)n)) != PCOA_OK)
+      return owner_failed(i, rc);
+    if (!c->strip_means) {
+      const hipError_t e = dev_alloc((void**)&c->strip_means, sizeof(double) * (size_t)n, c->device);
+      if (e != hipSuccess) return owner_failed(i, hip_fail(c, e, "allocation of the row means"));
+    }
+    const bool local = c->device == lead->device;
+    if (!local) {   // the owner writes its mat-vec pieces through a peer mapping of the lead's memory where there is one
+      int can = 0;
+      if (hipDeviceCanAccessPeer(&can, c->device, lead->device) == hipSuccess && can) {
+        const hipError_t e = hipDeviceEnablePeerAccess(lead->device, 0);
+        if (e == hipSuccess || e == hipErrorPeerAccessAlreadyEnabled) peer[(size_t)i] = 1;
+      }
+      (void)hipGetLastError();
+    }
+    int64_t* to_i64 = local ? rs_i64 + c->strip_col0 : reinterpret_cast<int64_t*>(c->strip_ws + strip_ws_doubles(n, c->s_cols));
+    double* to_f64 = local ? lead->row_sums + c->strip_col0 : c->strip_ws + strip_ws_doubles(n, c->s_cols) + n;
+    {
+      ScopedTimer t(c, T_CENTER);
+      const hipError_t e = launch_strip_col_sums_to(c->s32, c->s64, n, c->s_cols, c->strip_ws, to_i64, to_f64, c->stream);
+      if (e != hipSuccess) return owner_failed(i, hip_fail(c, e, "strip column sums"));
+    }
+    if (!local) {
+      hipError_t e = hipMemcpyPeerAsync(rs_i64 + c->strip_col0, lead->device, to_i64, c->device, sizeof(int64_t) * (size_t)c->s_cols,
+                                        c->stream);
+      if (e == hipSuccess)
+        e = hipMemcpyPeerAsync(lead->row_sums + c->strip_col0, lead->device, to_f64, c->device, sizeof(double) * (size_t)c->s_cols,
+                               c->stream);
+      if (e != hipSuccess) return owner_failed(i, hip_fail(c, e, "peer copy of the column sums"));
+    }
+  }
+  for (int32_t i = 0; i < n_owners; ++i) {   // (once per computePca)
+    pcoa_ctx* c = owners[i];
+    (void)hipSetDevice(c->device);
+    const hipError_t e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) return owner_failed(i, hip_fail(c, e, "column sums"));
+  }
+  (void)hipSetDevice(lead->device);
+  // nonZeroRows, matrixMean (:207-211) and the means rowSums / N, on the lead
+  {
+    ScopedTimer t(lead, T_CENTER);
+    HIP_TRY(lead, launch_center(nullptr, nullptr, n, lead->row_sums, lead->stats, lead->nz, nullptr, lead->stream, true));
+    HIP_TRY(lead, launch_col_means(lead->row_sums, n, lead->colmean, lead->stream));
+  }
+  double st[2] = {0, 0};
+  HIP_TRY(lead, hipMemcpyAsync(st, lead->stats, sizeof(st), hipMemcpyDeviceToHost, lead->stream));
+  HIP_TRY(lead, hipMemcpyAsync(&lead->hw->nz, lead->nz, sizeof(int32_t), hipMemcpyDeviceToHost, lead->stream));
+  // the means travel once to every owner's resident centring buffer
+  for (int32_t i = 0; i < n_owners; ++i) {
+    pcoa_ctx* c = owners[i];
+    if (c->device == lead->device)
+      HIP_TRY(lead, hipMemcpyAsync(c->strip_means, lead->colmean, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, lead->stream));
+    else
+      HIP_TRY(lead, hipMemcpyPeerAsync(c->strip_means, c->device, lead->colmean, lead->device, sizeof(double) * (size_t)n, lead->stream));
+  }
+  HIP_TRY(lead, hipStreamSynchronize(lead->stream));
+  const double matrix_mean = st[1];
+  for (int32_t i = 0; i < n_owners; ++i) {
+    owners[i]->strip_matrix_mean = matrix_mean;
+    owners[i]->strip_centering_set = true;
+  }
+
+  // the product: v ready on the lead's stream -> every owner's stream -> pieces written at y + col0 -> the lead waits
+  struct Events {
+    std::vector<hipEvent_t> ev;
+    ~Events() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
+  } evs;
+  evs.ev.assign((size_t)n_owners + 1, nullptr);
+  for (int32_t i = 0; i <= n_owners; ++i) {   // ev[0]: v ready (lead's device); ev[1 + i]: owner i done (its device)
+    const int dev = i == 0 ? lead->device : owners[i - 1]->device;
+    (void)hipSetDevice(dev);
+    const hipError_t e = hipEventCreateWithFlags(&evs.ev[(size_t)i], hipEventDisableTiming);
+    if (e != hipSuccess) {
+      (void)hipSetDevice(lead->device);
+      return hip_fail(lead, e, "hipEventCreateWithFlags");
+    }
+  }
+  (void)hipSetDevice(lead->device);
+  std::string mv_error;
+  LanczosMatvec mv = [&](const double* v, double* y) -> int {
+    auto bad = [&](hipError_t e, int32_t i, const char* what) {
+      mv_error = "compute_strips: owner " + std::to_string(i) + ": " + what + ": " + hipGetErrorString(e);
+      (void)hipSetDevice(lead->device);
+      return 1;
+    };
+    hipError_t e = hipEventRecord(evs.ev[0], lead->stream);
+    if (e != hipSuccess) return bad(e, 0, "hipEventRecord");
+    for (int32_t i = 0; i < n_owners; ++i) {
+      pcoa_ctx* c = owners[i];
+      const bool local = c->device == lead->device;
+      if ((e = hipSetDevice(c->device)) != hipSuccess) return bad(e, i, "hipSetDevice");
+      if ((e = hipStreamWaitEvent(c->stream, evs.ev[0], 0)) != hipSuccess) return bad(e, i, "hipStreamWaitEvent");
+      const double* vo = v;
+      double* dst = y + c->strip_col0;
+      double* const spare = c->strip_ws + strip_ws_doubles(n, c->s_cols);   // [n]: v on this device, [n]: y piece
+      if (!local) {
+        if ((e = hipMemcpyPeerAsync(spare, c->device, v, lead->device, sizeof(double) * (size_t)n, c->stream)) != hipSuccess)
+          return bad(e, i, "peer copy of v");
+        vo = spare;
+        if (!peer[(size_t)i]) dst = spare + n;
+      }
+      if ((e = launch_strip_matvec_to(c->s32, c->s64, n, c->strip_col0, c->s_cols, vo, c->strip_means, matrix_mean, c->strip_ws,
+                                      dst, c->stream)) != hipSuccess)
+        return bad(e, i, "strip mat-vec");
+      if (!local && !peer[(size_t)i] &&
+          (e = hipMemcpyPeerAsync(y + c->strip_col0, lead->device, dst, c->device, sizeof(double) * (size_t)c->s_cols,
+                                  c->stream)) != hipSuccess)
+        return bad(e, i, "peer copy of the piece");
+      if ((e = hipEventRecord(evs.ev[(size_t)i + 1], c->stream)) != hipSuccess) return bad(e, i, "hipEventRecord");
+    }
+    if ((e = hipSetDevice(lead->device)) != hipSuccess) return bad(e, 0, "hipSetDevice");
+    for (int32_t i = 0; i < n_owners; ++i)
+      if ((e = hipStreamWaitEvent(lead->stream, evs.ev[(size_t)i + 1], 0)) != hipSuccess) return bad(e, i, "hipStreamWaitEvent");
+    return 0;
+  };
+  int32_t steps = 0;
+  rc = lanczos_over(lead, num_pc, mv, out_components, out_eigenvalues, &steps);
+  if (rc != PCOA_OK && !mv_error.empty()) lead->last_error = mv_error;
+  if (rc != PCOA_OK) return rc;
+  if (nonzero_rows_out) *nonzero_rows_out = lead->hw->nz;
+  lead->compute_total = wall_now() - t0;
+  return PCOA_OK;
+}
+
+// Test hook: one y = B x of the centred matrix of the CURRENT S with either form of the mat-vec (0 = one wave per row over all
+// N^2 entries, 1 = upper-triangular tiles); x, y host arrays of N doubles.  N % 4 == 0 and no int64 part for form 1.
+int pcoa_debug_centred_matvec(pcoa_ctx* c, const double* x, double* y, int upper_triangle_form) {
+  CHECK_CTX(c);
+  if (!x || !y) return fail(c, PCOA_ERR_INVALID_ARG, "x or y is NULL");
+  if (c->is_strip) return fail(c, PCOA_ERR_STATE, "not available on a strip owner");
+  int rc = finalize_impl(c);
+  if (rc != PCOA_OK) return rc;
+  if ((rc = check_device_flags(c)) != PCOA_OK) return rc;
+  if ((rc = ensure_workspace(c, 1)) != PCOA_OK) return rc;
+  const int32_t n = c->n;
+  EigWorkspace wl = c->ws;
+  wl.a = nullptr;
+  wl.s32 = c->s32;
+  wl.s64 = c->s64;
+  wl.colmean = c->colmean;
+  wl.stats = c->stats;
+  wl.sym_part = nullptr;
+  if (upper_triangle_form) {
+    if (c->s64 || (n & 3)) return fail(c, PCOA_ERR_STATE, "the upper-triangle form needs N % 4 == 0 and no int64 part");
+    if ((rc = ensure(c, &c->sym_part, &c->sym_part_cap, (int64_t)symv_sym_workspace_doubles(n))) != PCOA_OK) return rc;
+    wl.sym_part = c->sym_part;
+    // the large-N form of computePca's first pass as well: row sums from the upper-triangular tiles
+    HIP_TRY(c, launch_row_sums_sym(c->s32, n, c->sym_part, c->row_sums, reinterpret_cast<int64_t*>(c->stats + 2), c->stream));
+  }
+  HIP_TRY(c, launch_center(c->s32, c->s64, n, c->row_sums, c->stats, c->nz, nullptr, c->stream, upper_triangle_form != 0));
+  HIP_TRY(c, launch_col_means(c->row_sums, n, c->colmean, c->stream));
+  double* xd = c->ws.q;   // two N-vectors of the eigensolver workspace
+  double* yd = c->ws.w;
+  HIP_TRY(c, hipMemcpyAsync(xd, x, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+  launch_centred_matvec(wl, n, xd, yd, c->stream);
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipMemcpyAsync(y, yd, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return PCOA_OK;
+}
+
+}  // extern "C"

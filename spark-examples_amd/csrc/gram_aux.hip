@@ -236,7 +236,7 @@ hipError_t launch_add_i32(int32_t* dst, const int32_t* src, int64_t count, hipSt
   return hipGetLastError();
 }
 
-// int64 total -> int32 matrix where every entry fits (narrow_s64, pcoa_capi.hip): flag[0] is raised by an entry that does
+// int64 total -> int32 matrix where every entry fits (narrow_s64): flag[0] is raised by an entry that does
 // not, the 64-bit word at flag + 2 receives max |entry|
 __global__ __launch_bounds__(256) void narrow_i64_kernel(const int64_t* __restrict__ s64, int32_t* __restrict__ s32, int64_t count,
                                                          int32_t* __restrict__ flag) {

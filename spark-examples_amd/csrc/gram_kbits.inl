@@ -119,7 +119,7 @@ __global__ __launch_bounds__(256) void pack_kbits_kernel(const T* __restrict__ x
 }
 
 // ---- persistent k-bits pre-pass fed by an LDS-DMA ring (fp32 tiles with ld % 4 == 0 and a 16-byte aligned base) ------------
-// Same output as pack_kbits_kernel<float, 4>, built to SHARE a CU with the contraction (the fp32 pipeline of pcoa_capi.hip):
+// Same output as pack_kbits_kernel<float, 4>, built to SHARE a CU with the contraction (the fp32 pipeline of fp4_setup / fp4_reserve):
 // 256 threads = one wave per SIMD, 40 VGPRs (a contraction held to 224 VGPRs per wave leaves 64 of a SIMD's 512), 4 * R KiB
 // of LDS, a fixed grid of one or two workgroups per CU that live for the whole launch.  With the FP4 operand sharing a CU
 // was negative-sum (r02: the contraction pulled 53 GB/s per CU of L2 hits through the same in-order vector-memory path);

@@ -1,0 +1,309 @@
+// pcoa_ctx.h -- what the translation units of the C ABI share (private, not installed): the engine's state (pcoa_ctx),
+// error reporting, HIP-event timing, and the helpers that cross files.  Host-side orchestration only: device memory
+// ownership, chunking (fp32 accumulators stay exact below 2^24 per launch, int32 partials are folded into int64 before 2^31),
+// stream ordering.  Who defines what:
+//   devmem.hip           the allocator (guard pages), regrow, debug_knobs
+//   operand.hip          S and its int64 fold, the operand buffers, the contractions, finalize
+//   capi_accumulate.hip  the staging ring and the input boundaries
+//   capi_reduce.hip      RCCL, reductions, export / import / read / load
+//   capi_compute.hip     the eigensolver workspace, computePca, strips, projection
+//   pcoa_capi.hip        create / destroy, errors, timings
+#pragma once
+
+#include <algorithm>
+#include <chrono>
+
+#include "pcoa_internal.h"
+
+enum TimeCat { T_GRAM = 0, T_DENSIFY, T_SYNTH, T_FINALIZE, T_CENTER, T_TRIDIAG, T_EIG, T_BACK, T_PACK, T_LANCZOS, T_ALLREDUCE, T_NCAT };
+
+struct EventPair {
+  hipEvent_t a, b;
+  int cat;
+};
+
+// A ring of two staging slots: the double-buffered host-to-device staging of a host caller's input on the copy stream
+// (pcoa_ctx::csr_stream), so that the copy of one chunk runs beside the kernels of the chunk before.  The protocol, in the
+// order a boundary goes through it (capi_accumulate.hip):
+//   staging_acquire    the next slot; the host waits for the slot's last reader (`freed`) before the slot may be rewritten
+//                      or regrown -- sizes are the boundary's own policy: it names what it needs and what to grow to
+//   (the copies, on the copy stream)
+//   staging_copied     `copied` recorded behind them; the boundary makes its consumer stream wait for it, and a synchronous
+//                      call ends with the host waiting for the last `copied`: a host input is consumed when its copy is
+//                      done, not when its kernels are
+//   staging_released   `freed` recorded behind the slot's last reader, on the stream the boundary names
+// A slot has two device buffers under one event pair (the carrier lists travel as indices + offsets; the other rings use
+// buffer 0 only), each with an optional page-locked twin for pageable sources (staging_pin).
+struct StagingRing {
+  struct Slot {
+    void* dev[2] = {nullptr, nullptr};
+    size_t dev_bytes[2] = {0, 0};
+    void* pin[2] = {nullptr, nullptr};
+    size_t pin_bytes[2] = {0, 0};
+    hipEvent_t copied = nullptr, freed = nullptr;   // H2D of the slot done / the kernels that read the slot done
+    bool used = false;
+  };
+  Slot slot[2];
+  int next = 0;   // slot[next & 1] is acquired next
+};
+
+struct pcoa_ctx {
+  int32_t n = 0;
+  // strip owner (SURVEY 8e, N beyond one HBM): the ctx holds S[:, strip_col0 .. strip_col0 + s_cols) as [n][s_cols]
+  // (both triangles, no mirror); s_cols == n and is_strip == false for the ordinary symmetric engine
+  int32_t s_cols = 0, strip_col0 = 0;
+  bool is_strip = false;
+  double* strip_ws = nullptr;      // partial sums of the strip reductions (lazy)
+  int64_t strip_ws_cap = 0;
+  double* strip_means = nullptr;   // [n] rowSums / N, resident between the mat-vecs of one computePca (pcoa_strip_set_centering)
+  double strip_matrix_mean = 0.0;
+  bool strip_centering_set = false;
+  double* proj_ws = nullptr;       // pcoa_project on a strip owner: reference means, components, eigenvalues, partials, result (lazy)
+  int64_t proj_ws_cap = 0;
+  int device = 0;
+  uint32_t flags = 0;
+  int num_cu = 256;
+  char dev_name[256] = {0};
+  hipStream_t own_stream = nullptr;
+  hipStream_t stream = nullptr;
+  std::string last_error;
+
+  // Gram state
+  int32_t* s32 = nullptr;          // [n][n] partial, upper-triangular tiles authoritative
+  int64_t* s64 = nullptr;          // [n][n] folded total (lazy), always symmetric
+  int64_t* s64_spare = nullptr;    // an int64 matrix retired by narrow_s64 (S fitted int32 again): the next fold re-uses it
+  int64_t variants_in_s32 = 0;     // variants accumulated into s32 since the last fold
+  bool dirty = false;              // s32 has contributions not yet mirrored
+  float* zeros = nullptr;          // 4 KiB of zeros
+  int32_t* err_flag = nullptr;     // device: [0] error bits, [1] max carrier multiplicity seen by the int8 pre-passes
+  // Pinned host memory where every small asynchronous read-back of the library lands (flags, multiplicity bound,
+  // statistics, the all-reduce's agreement words).  Never a stack variable or pageable memory: an async copy to
+  // pageable memory goes through the runtime's staging path and its helper thread.
+  struct HostWords {
+    int32_t flag, mmax, seen, nz;
+    int64_t coll[2];
+    double st[2];
+  };
+  HostWords* hw = nullptr;
+
+  // staging (lazy)
+  float* tile = nullptr;
+  int64_t tile_elems = 0;
+  int32_t* csr_idx = nullptr;
+  int64_t csr_idx_cap = 0;
+  int64_t* csr_offs = nullptr;
+  int64_t csr_offs_cap = 0;
+  // CSR boundary, fast path (calls_fast): two staging slots (device idx / offsets + a pinned host twin for pageable
+  // callers), a copy stream, a flag word of its own, and the chunks whose validation is still owed
+  StagingRing cs;   // buffer 0: indices (int32), buffer 1: offsets (int64)
+  hipStream_t csr_stream = nullptr;
+  int32_t* csr_flag = nullptr;        // device: bit 0 index out of range, bit 5 a carrier list repeats a callset
+  int32_t* csr_flag_host = nullptr;   // pinned
+  struct CsrPending { const int32_t* idx; const int64_t* offs; int64_t nv; int64_t kb; bool device; };
+  std::vector<CsrPending> csr_pending;  // committed provisionally into the ACTIVE operand buffer, not yet validated
+  double csr_stage_s = 0, csr_wait_s = 0;  // host seconds spent copying into pinned staging / waiting in validation
+  int64_t csr_fast_chunks = 0, csr_redo_chunks = 0;
+  // raw PLINK .bed rows (pcoa_accumulate_plink_bed, host input): two device slots filled on the copy stream (csr_stream),
+  // so that the H2D of one chunk runs beside the decode / transpose / contraction of the one before
+  StagingRing bs;   // shared with the host bitsets of pcoa_accumulate_bits
+  uint32_t* thr_dev = nullptr;
+  int64_t thr_cap = 0;
+  int32_t* sample_pop = nullptr;   // [n]
+  std::vector<int32_t> pop_offsets_dev;   // the pop_offsets sample_pop was built from (uploaded again only when they change)
+  // pcoa_accumulate_synthetic, k-bits operand (r06): the thresholds of a call travel on the copy stream into one of two slots
+  StagingRing ts;
+  int64_t* xfer = nullptr;         // exchange buffer (lazy): [n][n] int64, or [n][n] int32 for the int32 peer reduction
+  size_t xfer_bytes = 0;
+  int32_t* narrow_flag = nullptr;  // device: narrow_s64's {overflow, -, max |entry| (64 bit)}
+  int64_t reduce_i32_calls = 0, narrowed = 0, allreduce_calls = 0;
+  int32_t comm_ranks = 0, allreduce_int32 = 0, matvec_form = 0, lanczos_block_steps = 0;
+  int64_t* coll = nullptr;         // 2 int64: {variants in S32, has-S64 flag} agreed across ranks
+  int8_t* pack_buf = nullptr;      // k-blocked int8 workspace of the i8 path (lazy)
+  int64_t pack_cap = 0;            // bytes
+  bool use_i8 = true;              // packed-operand Gram (FP4 / int8) or fp32-MFMA Gram
+  int packed_mode = 0;             // 0 auto (FP4 for binary tiles, int8 otherwise), 2 int8 only, 3 FP4 only
+  // Form of the binary-tile operand in HBM: 2 = k-bits (1 bit per genotype, expanded to MX-FP4 in registers by the
+  // contraction: gram_kbits.inl; default), 1 = MX-FP4 (4 bits per genotype, PCOA_FLAG_OPERAND_FP4).  The buffer logic
+  // below counts in k-blocks of 32 variants either way; a k-bits chunk is padded to whole blocks of 128 variants.
+  int op_fmt = 2;
+  int64_t fp4_fallbacks = 0;
+  int i8_streak = 0;               // auto mode: chunks still to be sent straight to the int8 kernel after a fallback
+  // FP4 operand buffers.  Binary chunks are only PACKED when they arrive (behind what the active buffer already
+  // holds); a buffer is contracted when it is full or when S is needed (finalize / read / all-reduce / compute), so one
+  // launch carries up to the buffer's capacity whatever the size of the calls.  Two buffers exist where the fp32
+  // pipeline applies (fb_count == 2): the pre-pass of the next buffer then runs beside the contraction of the last one
+  // on disjoint CU sets (DESIGN_HISTORY.md 4.1).  Auto mode: the pre-passes of a buffer generation raise the buffer's device
+  // flag on a value other than 0 / 1, the contraction reads the same word and does nothing if it is set, and the host
+  // learns it when it next needs the buffer (fp4_resolve) and redoes the generation's chunks on the int8 kernel -- no
+  // host synchronisation per call.
+  struct Fp4Chunk { const void* x; int is_u8; int64_t nv, ld; };
+  struct Fp4Buf {
+    int8_t* p = nullptr;
+    int64_t cap_kb = 0;            // capacity in k-blocks of 32 variants (+24 of zero padding behind it)
+    int64_t kb = 0, vars = 0;      // filled: k-blocks / variants (the last k-block of a chunk may be partly empty)
+    hipStream_t fill_stream = nullptr;   // where this generation's pre-passes run (ctx stream or the masked pack stream)
+    hipEvent_t packed = nullptr, consumed = nullptr;
+    bool launched = false;         // the contraction of the last generation is queued; `consumed` tells when it is done
+    bool verify = false;           // that generation's pre-passes report non-binary values through the buffer's flag
+    int64_t launched_vars = 0;
+    std::vector<Fp4Chunk> chunks;  // device-resident inputs of the generation (kept until it is verified)
+  };
+  Fp4Buf fb[2];
+  int fb_count = 1, fb_active = 0;
+  int32_t* fb_flags = nullptr;       // device: the flag word of buffer b at fb_flags[16 * b]
+  int32_t* fb_flags_host = nullptr;  // pinned host copy, written by an async D2H behind each contraction
+  // fp32 pipeline: the pre-pass of one buffer beside the lock-step contraction of the other, on two side streams
+  bool pipe_ok = false;
+  int pipe_gram_cus = 0;
+  hipStream_t pack_stream = nullptr, gram_stream = nullptr;
+  hipEvent_t ev_fork = nullptr;
+  bool lockstep_ok = false;          // the lock-step contraction launch fits this N on the whole chip
+  int kbits_mode = 4;                // whole-chip launch form of the k-bits contraction: 4 even split, 2 lock-step, 0 split-K
+  bool coreside = false;             // fp32 pipeline, k-bits operand: ring pre-pass and whole-chip contraction share every CU
+  int coreside_mode = 4;             // launch form of that contraction: 2 lock-step where the shape fits, else 4 even split
+  int ring_wgs = 0;                  // workgroups of the ring pre-pass beside a contraction
+  int64_t lockstep_launches = 0, pipeline_launches = 0, evensplit_launches = 0;
+  int64_t pack_chunk = (int64_t)1 << 20;  // variants packed + contracted per launch pair
+  int64_t pack_launches = 0;
+  double pack_bytes = 0;
+
+  // computePca workspace (lazy)
+  bool ws_ready = false;
+  pcoa::EigWorkspace ws{};
+  double* row_sums = nullptr;      // [n]
+  double* colmean = nullptr;       // [n] rowSums / N (implicit form of B for the Lanczos path)
+  double* stats = nullptr;         // [2 + n] (sum, mean, then int64 row sums)
+  int32_t* nz = nullptr;           // [1]
+  double* out_dev = nullptr;       // [kmax][n]
+  int32_t kmax = 0;
+  double* lanczos_ws = nullptr;    // Krylov basis + scalars of the Lanczos fast path (lazy)
+  double* sym_part = nullptr;      // tile sums of the symmetric mat-vec (large N, lazy)
+  int64_t sym_part_cap = 0;
+  int64_t lanczos_cap = 0;         // doubles
+  int32_t eig_method = 0;          // of the last pcoa_compute: 1 = Lanczos, 2 = Householder
+  int32_t eig_dense_form = 0;      // EIG_FORM_* bits of the last pcoa_compute's dense solve of B (0 unless eig_method == 2)
+  int32_t lanczos_steps = 0;
+
+  // timings
+  std::vector<EventPair> pending;
+  std::vector<hipEvent_t> pool;
+  double tsec[T_NCAT] = {0};
+  int64_t gram_launches = 0;
+  int64_t gram_variants = 0;
+  double gram_flops = 0, gram_bytes = 0;
+  double compute_total = 0;
+  int gram_kind = 1;
+  int64_t max_launch = (int64_t)1 << 24;
+  int64_t fold_threshold = (int64_t)1 << 30;
+};
+
+#define HIP_TRY(ctx, expr)                                     \
+  do {                                                         \
+    hipError_t _e = (expr);                                    \
+    if (_e != hipSuccess) return hip_fail((ctx), _e, #expr);   \
+  } while (0)
+
+#define CHECK_CTX(ctx)                                                      \
+  do {                                                                      \
+    if (!(ctx)) return fail(nullptr, PCOA_ERR_INVALID_ARG, "ctx is NULL");  \
+    hipError_t _e = hipSetDevice((ctx)->device);                            \
+    if (_e != hipSuccess) return hip_fail((ctx), _e, "hipSetDevice");       \
+  } while (0)
+
+namespace pcoa {
+
+constexpr int64_t KB_I8 = 16;                             // variants per int8 k-block
+constexpr int64_t kMaxLaunchVariants = (int64_t)1 << 24;  // fp32 accumulators exact below 2^24
+constexpr int64_t kFoldThreshold = (int64_t)1 << 30;      // fold int32 partials long before 2^31
+constexpr int64_t kBatchVariants = (int64_t)1 << 22;   // variants per FP4 contraction launch (fp32 exact below 2^24)
+constexpr int64_t kBatchBytes = (int64_t)6 << 30;      // cap of an FP4 operand buffer
+constexpr int64_t kPipeVariants = (int64_t)1 << 20;    // buffer size where two buffers alternate (pipeline / lock-step)
+constexpr int64_t kCoresideMaxNpad = 16384;            // co-resident pipeline: largest padded sample count (measured up to here)
+
+inline int64_t round_up(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
+inline double wall_now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+inline size_t s_count(const pcoa_ctx* c) { return (size_t)c->n * (size_t)c->s_cols; }
+inline GramStrip strip_of(const pcoa_ctx* c) {
+  GramStrip st;
+  if (c->is_strip) { st.col0 = c->strip_col0; st.cols = c->s_cols; }
+  return st;
+}
+
+// ---- devmem.hip: every device allocation of the library goes through dev_alloc / dev_free
+hipError_t dev_alloc(void** out, size_t bytes, int device);
+void dev_free(void* p);
+int regrow(pcoa_ctx* c, void** buf, size_t bytes, bool sync_ctx_stream);
+
+// ---- pcoa_capi.hip: errors (c == nullptr: the thread's create error) and the timing events
+int fail(pcoa_ctx* c, int code, const std::string& msg);
+int hip_fail(pcoa_ctx* c, hipError_t e, const char* what);
+hipEvent_t get_event(pcoa_ctx* c);
+void drain_events(pcoa_ctx* c, bool wait);
+
+// ---- operand.hip
+int fold_now(pcoa_ctx* c);
+int ensure_xfer(pcoa_ctx* c, size_t bytes);
+int narrow_s64(pcoa_ctx* c);
+void account_gram(pcoa_ctx* c, int64_t cur, int64_t weight = 1);
+int fold_if_needed(pcoa_ctx* c, int64_t cur);
+int64_t kb_of(const pcoa_ctx* c, int64_t nv);
+int64_t fp4_target_kb(const pcoa_ctx* c);
+hipError_t launch_csr_operand(const pcoa_ctx* c, const int32_t* idx, const int64_t* offs, int64_t nv, int64_t offs_base,
+                              int8_t* dst, hipStream_t s, int64_t kb);
+int fp4_setup(pcoa_ctx* c);
+int fp4_quiesce(pcoa_ctx* c);   // (operand.hip needs it ahead of its definition too: fold_if_needed -> fp4_quiesce -> fp4_resolve -> int8_chunk -> fold_if_needed)
+int fp4_flush(pcoa_ctx* c);
+int fp4_sync_point(pcoa_ctx* c);
+int fp4_discard(pcoa_ctx* c);
+int fp4_grow(pcoa_ctx* c, int bi, int64_t kb, int64_t chunk_variants);
+int fp4_reserve(pcoa_ctx* c, int64_t kb, int64_t chunk_variants, int side_kind, bool verify, int8_t** dst,
+                hipStream_t* stream, int32_t** flag);
+void fp4_commit(pcoa_ctx* c, int64_t kb, int64_t vars);
+int gram_device(pcoa_ctx* c, const void* x_dev, int is_u8, int64_t nv, int64_t ld, bool can_defer);
+int gram_device_bits(pcoa_ctx* c, const uint32_t* bits_dev, int64_t nv, int64_t ld_words, bool can_defer);
+int check_device_flags(pcoa_ctx* c);
+int finalize_impl(pcoa_ctx* c);
+
+// ---- capi_accumulate.hip
+int csr_validate(pcoa_ctx* c);
+int staging_wait_all(pcoa_ctx* c, StagingRing& r);
+void staging_destroy(StagingRing& r);
+
+// ---- capi_compute.hip
+int ensure_workspace(pcoa_ctx* c, int32_t k);
+int ensure_b(pcoa_ctx* c);
+
+struct ScopedTimer {
+  pcoa_ctx* c;
+  EventPair p;
+  hipStream_t s;
+  bool on;
+  ScopedTimer(pcoa_ctx* ctx, int cat, hipStream_t stream = nullptr) : c(ctx), s(stream ? stream : ctx->stream), on(false) {
+    p.a = get_event(c);
+    p.b = get_event(c);
+    p.cat = cat;
+    if (p.a && p.b && hipEventRecord(p.a, s) == hipSuccess) on = true;
+  }
+  ~ScopedTimer() {
+    if (on && hipEventRecord(p.b, s) == hipSuccess) {
+      c->pending.push_back(p);
+      if (c->pending.size() > 2048) drain_events(c, true);
+    } else {
+      if (p.a) c->pool.push_back(p.a);
+      if (p.b) c->pool.push_back(p.b);
+    }
+  }
+};
+
+// *buf holds at least `need` elements (floor 1,024); its old contents are not kept
+template <typename T>
+int ensure(pcoa_ctx* c, T** buf, int64_t* cap, int64_t need) {
+  if (need <= *cap) return PCOA_OK;
+  *cap = 0;
+  const int64_t newcap = std::max<int64_t>(need, 1024);
+  const int rc = regrow(c, (void**)buf, sizeof(T) * (size_t)newcap, true);
+  if (rc == PCOA_OK) *cap = newcap;
+  return rc;
+}
+
+}  // namespace pcoa

@@ -1,6 +1,6 @@
 """Every launch form of the k-bits contraction held to an exact Gram, at the sample counts where the dispatch changes form.
 
-fp4_setup / fp4_launch (pcoa_capi.hip) pick the contraction's launch from the padded sample count: beside the next pre-pass
+fp4_setup / fp4_launch (operand.hip) pick the contraction's launch from the padded sample count: beside the next pre-pass
 (co-resident pipeline) the 224-VGPR gram_kbits_kernel as an even split (mode 4), lock-step with split-K 8 / 4 / 2 / 1
 (mode 2) or banded split-K (mode 0); alone on the chip (tail generation, finalize, serial bitsets) the one-wave-per-SIMD
 kernel as an even split or banded.  On 256 CUs ("Launch bands"):

@@ -19,7 +19,7 @@
 
 #include "../spark-examples_amd/csrc/gram_packed.hip"
 
-// the library reads its environment knobs through this accessor (pcoa_capi.hip); the harness has none
+// the library reads its environment knobs through this accessor (devmem.hip); the harness has none
 namespace pcoa {
 const DebugKnobs& debug_knobs() {
   static const DebugKnobs k;
