@@ -125,7 +125,7 @@ __global__ __launch_bounds__(256) void synth_fill_kernel(uint64_t seed, const ui
   }
 }
 
-// The same model written straight into the k-bits operand K1[blk][npad][4 words] (gram_kbits.inl): the fp32 tile -- 400 GB
+// The same model written straight into the k-bits operand K1[blk][npad][4 words] (kbits_layout.h): the fp32 tile -- 400 GB
 // for configs[3]'s 100,000 samples x 10^6 variants -- is never written or read back (r06; r05: synth_fill_kernel into a staging
 // tile + pack_kbits_kernel, 0.14 + 0.07 s of that job).  One thread = (block of 128 variants, 4 samples): 128 Philox calls,
 // whose word t decides sample 4 g + t exactly as synth_fill_kernel's does (same key, same counter, same thresholds), 64

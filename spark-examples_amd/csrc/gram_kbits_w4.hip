@@ -1,25 +1,31 @@
-// gram_kbits_w4.inl -- the k-bits contraction with ONE wave per SIMD and a hand-placed software pipeline (round 4).
-// Included twice by gram_packed.hip, like gram_kbits.inl (kernels inside its anonymous namespace, launchers inside
-// namespace pcoa); not a translation unit of its own.  Reference work it replaces: VariantsPca.scala:186-188.
+// gram_kbits_w4.hip -- the k-bits contraction with ONE wave per SIMD and a hand-placed software pipeline (round 4).
+// Reference work it replaces: VariantsPca.scala:186-188.
 //
 // Why: gram_kbits_kernel<3,2,2> issues 4.25 expansion VALU per MFMA (a 128 x 64 wave tile needs 6
 // fragments for 8 MFMAs) and hands the matrix pipe from one wave to its partner on the SIMD every 16 MFMAs; alone on the
 // chip it reaches 0.63 of the FP4 peak.  Here:
 //   * 256 threads = 4 waves as 2 x 2, one per SIMD; a wave owns a 128 x 128 block = 4 x 4 MFMA tiles, its 256 accumulator
 //     registers live in the AGPR half of the unified file.  8 fragments feed 16 MFMAs: 48 expansion VALU per k-step = 3.0
-//     per MFMA (conjugate-weight encoding of gram_kbits.inl: 5 operations per A word, 7 per B word);
+//     per MFMA (conjugate-weight encoding of gram_kbits.hip: 5 operations per A word, 7 per B word);
 //   * no phases: the wave's MFMA stream never stops.  Behind MFMA t of a k-step the wave issues its share of the NEXT
 //     k-step's expansion (2-4 VALU), which executes in the 32-cycle shadow of the MFMA (MI355X_MICROARCH.md: one wave per
 //     SIMD hides <= 5 single-issue instructions per 8-pass MFMA).  Fragments are double-buffered by k-step, the raw words
 //     by stage; nothing an MFMA reads is written within 16 MFMAs of it;
 //   * per stage (128 variants = 2 k-steps = 32 MFMAs per wave): 8 ds_read_b64, 2 global_load_lds_dwordx4, ONE s_barrier,
 //     placed directly behind an MFMA so that the barrier's round trip hides behind it.
-// LDS ring: NST stages of 8 KiB (StageBits of gram_kbits.inl: the LDS image is the global image).  Stage s+1 must have
+// LDS ring: NST stages of 8 KiB (StageBits of kbits_layout.h: the LDS image is the global image).  Stage s+1 must have
 // landed at the barrier of stage s; the DMA of stage s+NST goes into the slot of stage s behind the same barrier (every
 // wave has the words of stage s in registers by then).  The vmcnt book-keeping is constant: a wave issues its PER DMA
 // instructions every stage, clamped to the operand's last block beyond the run (harmless re-reads), so that
 // s_waitcnt vmcnt(PER * (NST - 2)) always means "my share of stage s+1 has landed".
-#ifdef PCOA_KBITS_W4_KERNELS
+#include <algorithm>
+#include <utility>
+
+#include "gram_common.h"
+#include "kbits_layout.h"
+
+namespace pcoa {
+namespace {
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
@@ -46,7 +52,7 @@ constexpr bool w4_needs_b() {  // B fragment G (column tile G) is read by some M
 }
 
 // MFMA T of a k-step: (mi, ni) = (T / 4, T % 4).  NOP wait states inside the statement, where nothing can be scheduled
-// between the pad and the instruction.  (gram_kbits.inl pads every MFMA: its late expansions write registers an MFMA issued
+// between the pad and the instruction.  (gram_kbits.hip pads every MFMA: its late expansions write registers an MFMA issued
 // a cycle later may still read.  Here nothing an MFMA reads is written within 16 MFMAs of it and the accumulators are AGPRs no
 // VALU instruction touches: NOP = 0 is bit-exact on every shape and launch of tools/exp_w4, profiles/r04a.)
 template <int T, int NOP>
@@ -111,7 +117,7 @@ __device__ __forceinline__ uint32_t w4_word(const u32x4 (&raw)[4]) {
 }
 
 // The expansion work placed behind MFMA T: fragments (A_g, B_g), g = T / 4, of the next k-step, 12 operations over four
-// gaps as 3 + 3 + 4 + 2 (conjugate weights of gram_kbits.inl: A class 0..3 -> E2M1 0.5, 1, 2, 2; B -> 2, 1, 0.5, 0.5).
+// gaps as 3 + 3 + 4 + 2 (conjugate weights of gram_kbits.hip: A class 0..3 -> E2M1 0.5, 1, 2, 2; B -> 2, 1, 0.5, 0.5).
 // w4_pin_in<T> "redefines" the words gap T reads and w4_pin_out<T> the fragments it writes: asm volatile statements keep
 // their order, so the arithmetic of gap T can neither rise above its pin_in nor sink below its pin_out.
 template <int T>
@@ -161,7 +167,7 @@ __device__ __forceinline__ void w4_gap(u32x4 (&raw)[4], FragsW4& nf) {
 // One statement that reads and "redefines" all eight fragments of a buffer: it keeps the buffer's live range unbroken across
 // the k-step in which nothing reads it, so that the register allocator never moves it -- left free (OPT & 8 without this),
 // it puts a fragment of the NEXT k-step into the registers of a fragment that died one MFMA ago, and an MFMA keeps reading its
-// A / B registers for some cycles after it has issued (gram_kbits.inl, profiles/r03g_kbits_hazards.txt).
+// A / B registers for some cycles after it has issued (gram_kbits.hip, profiles/r03g_kbits_hazards.txt).
 __device__ __forceinline__ void w4_tie(FragsW4& f) {
   asm volatile("" : "+v"(f.a[0]), "+v"(f.a[1]), "+v"(f.a[2]), "+v"(f.a[3]), "+v"(f.b[0]), "+v"(f.b[1]), "+v"(f.b[2]), "+v"(f.b[3]));
 }
@@ -177,7 +183,7 @@ __device__ __forceinline__ void w4_expand_all(u32x4 (&raw)[4], FragsW4& nf) {
 
 // raw[Q] of a slot: rows 2Q and 2Q+1 (512 bytes apart) by one ds_read2_b64.  As asm statements: the compiler's wait-count
 // pass cannot tell a ring slot being read from the slots the LDS-DMA in flight writes and would put s_waitcnt vmcnt(0) in
-// front of a plain load (gram_kbits.inl, pack_u8_kbits_ring_kernel).  The wait is the caller's (w4_wait_words).
+// front of a plain load (gram_kbits.hip, pack_u8_kbits_ring_kernel).  The wait is the caller's (w4_wait_words).
 // addr = the lane's address of row 0 (A) / row 4 (B) in that slot.
 template <int Q>
 __device__ __forceinline__ void w4_read(uint32_t addr_a, uint32_t addr_b, u32x4 (&raw)[4]) {
@@ -607,9 +613,7 @@ __global__ __launch_bounds__(256, 1) void gram_kbits_w4_kernel(const int8_t* __r
 #endif
 }
 
-#endif  // PCOA_KBITS_W4_KERNELS
-
-#ifdef PCOA_KBITS_W4_LAUNCHERS
+}  // namespace
 
 #ifdef PCOA_EXPERIMENTS
 int g_w4_variant = 0;  // harness knob
@@ -712,4 +716,4 @@ hipError_t launch_gram_kbits_w4(const int8_t* p, int64_t nv, int32_t n, int32_t*
   return hipGetLastError();
 }
 
-#endif  // PCOA_KBITS_W4_LAUNCHERS
+}  // namespace pcoa

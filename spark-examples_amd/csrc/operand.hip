@@ -217,7 +217,7 @@ int fp4_setup(pcoa_ctx* c) {
     const int64_t ntri = c->is_strip ? ntile * ((c->s_cols + 255) / 256 + 1) : ntile * (ntile + 1) / 2;
     c->kbits_mode = (ntri <= 4 * (int64_t)c->num_cu) ? 4 : 0;
     if (k.kbits_mode == 0 || k.kbits_mode == 4) c->kbits_mode = k.kbits_mode;
-    if (k.kbits_mode == 5 && c->kbits_mode == 4) c->kbits_mode = 5;   // even split per XCD k-segment (gram_kbits_w4.inl, xcd_map 5)
+    if (k.kbits_mode == 5 && c->kbits_mode == 4) c->kbits_mode = 5;   // even split per XCD k-segment (gram_kbits_w4.hip, xcd_map 5)
     if (k.kbits_mode == 2 && !c->is_strip && ls > 0) c->kbits_mode = 2;
   }
   // fp32 pipeline: the contraction of one operand buffer beside the pre-pass of the next, on two side streams.
@@ -316,7 +316,7 @@ static int fp4_launch(pcoa_ctx* c, int bi, bool overlapped, int side_kind = 1) {
       // k-bits: beside the pre-pass an even split over `pipe_gram_cus` workgroups, else the whole-chip form chosen in fp4_setup
       // (beside the short bitset transpose the even split wins: 1.07 vs 1.11 ms per step, profiles/r03zd)
       const int mode = !side ? c->kbits_mode : !c->coreside ? 4 : (side_kind == 3 ? c->kbits_mode : c->coreside_mode);
-      // The one-wave-per-SIMD kernel (512 registers per wave, gram_kbits_w4.inl) wherever the contraction has its CUs to
+      // The one-wave-per-SIMD kernel (512 registers per wave, gram_kbits_w4.hip) wherever the contraction has its CUs to
       // itself; beside the ring pre-pass the two-waves-per-SIMD kernel held to 224 registers, which leaves room for it.
       const int w4 = debug_knobs().kbits_w4;
       const bool use_w4 = w4 != 0 && (!(side && c->coreside) || w4 == 2);

@@ -1,23 +1,13 @@
-// gram_kbits.inl -- FMT 2 of gram_packed.hip: the operand stays in HBM at ONE BIT per genotype and becomes MX-FP4 only
-// in registers, on the way into the matrix cores.  Included twice by gram_packed.hip (kernels inside its anonymous
-// namespace, launchers inside namespace pcoa); not a translation unit of its own.
-//
-// Why (DESIGN_HISTORY.md 4.1): the FP4 operand costs 1.28 GB written by the pre-pass and 4.3 GB re-read by
-// the contraction per 10^6 variants at N = 2504, and that L2-hit stream is what slows the fp32 pre-pass beside it.  A
-// genotype indicator is one bit; as bits the operand is 0.33 GB written and ~1.1 GB re-read.
-//
-// Operand layout K1[V/128][Npad][4 words] ("k-bits"): the 16 bytes at K1[blk][i] are sample i's indicators for the 128
-// variants of block blk, bit b of word j = variant 128 blk + 32 j + b.  A stage of the contraction is one block: 2 panels x
-// 256 samples x 16 B = 8 KiB (the FP4 stage is 32 KiB), one global_load_lds_dwordx4 per wave, and the LDS image IS the
-// global image.  A lane's operand of one MFMA (32 FP4 values = 4 dwords) comes from ONE word:
-//     d0 = (w << 1) & M,  d1 = w & M,  d2 = (w >> 1) & M,  d3 = (w >> 2) & M,   M = 0x22222222
-// i.e. bit b of the word lands in nibble b / 4 of dword b % 4 as 0x2 = E2M1 1.0 -- 7 VALU operations per fragment.  Which
-// variant sits in which of the MFMA's 64 k-slots does not matter: X^T X takes A and B from the same words through the
-// same function, so every product pairs a variant with itself (the remark on k-order in gram_packed.hip's header).
-// The wave layout, the accumulators, the ping-pong phases and the epilogue are those of gram_packed_kernel<1, ...>;
-// a wave reads its 6 operand rows of a stage with 6 ds_read_b64 (words of both k-steps at once, 3 KiB instead of the
-// 12 KiB of ds_read_b128 fragments) and expands them while its partner on the SIMD issues MFMAs.
-#ifdef PCOA_KBITS_KERNELS
+// pack_kbits.hip -- every pre-pass into the k-bits operand K1 (kbits_layout.h: one BIT per genotype): fp32 / uint8 tiles
+// (plain, small-call, the two persistent LDS-DMA-ring forms, 8-byte loads), carrier bitsets (32 x 32 bit transposes) and
+// CSR carrier lists (global atomics, or through the LDS).  The contractions are gram_kbits.hip and gram_kbits_w4.hip.
+#include <cstdlib>
+#include <type_traits>
+
+#include "gram_common.h"
+
+namespace pcoa {
+namespace {
 
 // ---------------------------------------------------------------------------------------------- pre-passes -> K1
 // fp32 / uint8 tile -> k-bits; verifies that every value is exactly 0 or 1 (flag bit 3), like pack_fp4_kernel.
@@ -160,7 +150,7 @@ __device__ __forceinline__ void ring_rows_kbits(const char* xb, int64_t ldb, int
         bad4[s2] |= __float_as_uint(__builtin_fmaf(f, f, -f));
         w[s2][C] |= ((__float_as_uint(f) >> 23) & 1u) << t;
       }
-      // pin the conversion here (see ring_unit of gram_packed.hip)
+      // pin the conversion here (see ring_unit of pack_packed.hip)
 #pragma unroll
       for (int s2 = 0; s2 < 4; ++s2) asm volatile("" : "+v"(w[s2][C]), "+v"(bad4[s2]));
     }
@@ -606,410 +596,7 @@ __global__ __launch_bounds__(THREADS) void densify_csr_kbits_lds_kernel(const in
   for (int i = tid; i < npad; i += THREADS) dst[i] = reinterpret_cast<const uint4*>(bits)[i];
 }
 
-// ---------------------------------------------------------------------------------------------- contraction
-struct StageBits {
-  uint32_t pi[256][4];  // panel I: [sample][word]; word 2 * hi + k2 is what lane half `hi` feeds to k-step k2
-  uint32_t pj[TJ][4];   // panel J
-};
-
-// 8 DMA instructions of 1 KiB per stage, one per wave (waves 0-3: the quarters of panel I, 4-7: of panel J); a diagonal
-// tile brings in its single panel with waves 0-3 only.
-template <bool DIAG>
-__device__ __forceinline__ void issue_stage_bits(StageBits* st, const int8_t* __restrict__ p, int npad, int64_t blk,
-                                                 int col_i, int col_j, int wave, int lane) {
-  if (DIAG && wave >= 4) return;  // wave-uniform
-  const bool is_i = wave < 4;
-  const int q = wave & 3;
-  const int c0 = (is_i ? col_i : col_j) + q * 64;
-  const int8_t* src = p + ((size_t)blk * npad + c0 + lane) * 16;
-  uint32_t* dst = is_i ? &st->pi[q * 64][0] : &st->pj[q * 64][0];
-  __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)dst, 16, 0, 0);
-}
-
-// the two words (k-steps 0 and 1) of each of the wave's 4 A rows and 2 B rows: 6 ds_read_b64, conflict-free (a half-wave
-// reads 32 consecutive 16-byte slots at the same 8-byte offset, the other half the other 8 bytes)
-template <bool DIAG>
-__device__ __forceinline__ void read_words(const StageBits* st, int wm, int wn, int lane, uint2 (&raw)[6]) {
-  const int l31 = lane & 31, hi = lane >> 5;
-#pragma unroll
-  for (int mi = 0; mi < 4; ++mi)
-    raw[mi] = *reinterpret_cast<const uint2*>(&st->pi[wm * 128 + mi * 32 + l31][2 * hi]);
-#pragma unroll
-  for (int ni = 0; ni < 2; ++ni) {
-    if constexpr (DIAG) raw[4 + ni] = *reinterpret_cast<const uint2*>(&st->pi[wn * 64 + ni * 32 + l31][2 * hi]);
-    else raw[4 + ni] = *reinterpret_cast<const uint2*>(&st->pj[wn * 64 + ni * 32 + l31][2 * hi]);
-  }
-}
-
-// ENC 0: both operands as E2M1 1.0 (nibble 0x2): d_q = ((w << 1) >> q) & 0x22222222 -- 7 VALU operations per word.
-// ENC 1: conjugate weights.  E2M1 also has 0.5 (nibble 0x1) and 2.0 (nibble 0x4), and 0.5 x 2.0 = 1.0 x 1.0 = 1, both
-// exact; so bit class q = b % 4 may sit at different heights in the A and the B nibble as long as the heights add up:
-//   class   A (rows: 4 fragments per k-step)        B (columns: 2 fragments)
-//     0     w & 0x1111..        0.5                 (w << 2) & 0x4444..   2.0
-//     1     w & 0x2222..        1.0                 w & 0x2222..          1.0
-//     2     w & 0x4444..        2.0                 (w >> 2) & 0x1111..   0.5
-//     3     (w >> 1) & 0x4444.. 2.0                 (w >> 3) & 0x1111..   0.5
-// 5 operations for an A word, 7 for a B word: 34 instead of 42 per k-step.  (The sign bit of a nibble is the one height
-// that cannot be used, which is why class 3 always pays a shift.)
-template <int ENC, bool IS_B>
-__device__ __forceinline__ i32x4 expand_word_fp4(uint32_t w) {
-  i32x4 r;
-  if constexpr (ENC == 0) {
-    constexpr uint32_t M = 0x22222222u;  // E2M1 1.0 in every nibble
-    r[0] = (int)((w << 1) & M);
-    r[1] = (int)(w & M);
-    r[2] = (int)((w >> 1) & M);
-    r[3] = (int)((w >> 2) & M);
-  } else if constexpr (!IS_B) {
-    r[0] = (int)(w & 0x11111111u);
-    r[1] = (int)(w & 0x22222222u);
-    r[2] = (int)(w & 0x44444444u);
-    r[3] = (int)((w >> 1) & 0x44444444u);
-  } else {
-    r[0] = (int)((w << 2) & 0x44444444u);
-    r[1] = (int)(w & 0x22222222u);
-    r[2] = (int)((w >> 2) & 0x11111111u);
-    r[3] = (int)((w >> 3) & 0x11111111u);
-  }
-  return r;
-}
-
-// ENC 2 = ENC 1 with the expansion split over the two phases: the read phase only expands the fragments of k-step 0;
-// those of k-step 1 are expanded one per MFMA gap while the wave issues its first six MFMAs (which only need k-step 0).
-// The read phase (LDS latency + expansion) is then shorter than the partner's MFMA phase instead of longer.
-template <int ENC, int K2>
-__device__ __forceinline__ void expand_half(const uint2 (&raw)[6], FragsI8<2> (&f)[2]) {
-  constexpr int E = ENC == 0 ? 0 : 1;
-#pragma unroll
-  for (int mi = 0; mi < 4; ++mi) f[K2].a[mi] = expand_word_fp4<E, false>(K2 == 0 ? raw[mi].x : raw[mi].y);
-#pragma unroll
-  for (int ni = 0; ni < 2; ++ni) f[K2].b[ni] = expand_word_fp4<E, true>(K2 == 0 ? raw[4 + ni].x : raw[4 + ni].y);
-  // The expansion is pure arithmetic: left alone, the optimiser sinks it below the phase barrier to just in front of the
-  // MFMAs that consume it -- into the phase where the wave should do nothing but feed the matrix pipe.  An empty asm
-  // that "modifies" every fragment pins the arithmetic here, in the wave's read phase.
-#pragma unroll
-  for (int mi = 0; mi < 4; ++mi) asm volatile("" : "+v"(f[K2].a[mi]));
-#pragma unroll
-  for (int ni = 0; ni < 2; ++ni) asm volatile("" : "+v"(f[K2].b[ni]));
-}
-
-template <int ENC>
-__device__ __forceinline__ void expand_frags(uint2 (&raw)[6], FragsI8<2> (&f)[2]) {
-  expand_half<ENC, 0>(raw, f);
-  if constexpr (ENC != 2) expand_half<ENC, 1>(raw, f);
-}
-
-// fragment IDX (in the order the k-step-1 MFMAs need them: a0, b0, b1, a1, a2, a3) of k-step 1, pinned at this point of
-// the instruction stream from both sides (its input is "redefined" here, its output "used" here)
-template <int IDX>
-__device__ __forceinline__ void expand_late(uint2 (&raw)[6], FragsI8<2> (&f)[2]) {
-  constexpr int R = IDX == 0 ? 0 : IDX == 1 ? 4 : IDX == 2 ? 5 : IDX - 2;  // row of `raw`
-  asm volatile("" : "+v"(raw[R].y));
-  if constexpr (R < 4) {
-    f[1].a[R] = expand_word_fp4<1, false>(raw[R].y);
-    asm volatile("" : "+v"(f[1].a[R]));
-  } else {
-    f[1].b[R - 4] = expand_word_fp4<1, true>(raw[R].y);
-    asm volatile("" : "+v"(f[1].b[R - 4]));
-  }
-}
-
-// MFMA number T of a stage (order (k-step, mi, ni) as mfma_range), optionally with wait states in front of it INSIDE the
-// asm statement, where nothing can be scheduled between them and the instruction.
-template <int T, bool PAD>
-__device__ __forceinline__ void mfma_one(const FragsI8<2> (&f)[2], f32x16 (&acc)[4][2]) {
-  constexpr int k2 = T / 8, mi = (T % 8) / 2, ni = T % 2;
-  if constexpr (PAD)
-    asm volatile("s_nop 1\n\tv_mfma_f32_32x32x64_f8f6f4 %0, %1, %2, %0 cbsz:4 blgp:4"
-                 : "+v"(acc[mi][ni])
-                 : "v"(f[k2].a[mi]), "v"(f[k2].b[ni]));
-  else
-    asm volatile("v_mfma_f32_32x32x64_f8f6f4 %0, %1, %2, %0 cbsz:4 blgp:4" : "+v"(acc[mi][ni]) : "v"(f[k2].a[mi]), "v"(f[k2].b[ni]));
-}
-
-// MFMAs LO .. HI-1 of a stage; ENC 2: with the six late expansions behind MFMAs 0 .. 5.
-// Two hazards of mixing VALU work into an asm MFMA run, both measured (profiles/r03g_kbits_hazards.txt), neither padded by
-// the compiler because it cannot see an MFMA inside an asm statement:
-//  * an MFMA that issues in the cycle after a VALU instruction comes back with the first two registers of its
-//    accumulator wrong (rows 0, 1, 4, 5 of its 32 x 32 tile): MFMA 6 directly behind the last late expansion (~7,000 of
-//    6.3 M entries of S at configs[1] size, group-1 waves only), and, once that one was padded, MFMA 0 / 8 behind
-//    compiler-placed moves at small shapes.  One wait state is enough (measured); every MFMA of this schedule carries two,
-//    inside its own asm statement where nothing can be scheduled between them and the instruction (free behind another
-//    MFMA: the pipe is busy for 32 cycles anyway);
-//  * an MFMA reads its A / B registers for several cycles after it has issued: a late expansion must never be allocated
-//    to the registers of a k-step-0 fragment that died an instruction ago, so all of k-step 0 is kept alive until its last
-//    MFMA has issued.
-template <int ENC, int LO, int HI, int T = LO>
-__device__ __forceinline__ void mfma_run(uint2 (&raw)[6], FragsI8<2> (&f)[2], f32x16 (&acc)[4][2]) {
-  if constexpr (ENC != 2) {
-    mfma_range<1, 2, 4, LO, HI>(f, acc);
-  } else if constexpr (T < HI) {
-    mfma_one<T, true>(f, acc);
-    if constexpr (T < 6) expand_late<T>(raw, f);
-    if constexpr (T == 7)
-      asm volatile("" ::"v"(f[0].a[0]), "v"(f[0].a[1]), "v"(f[0].a[2]), "v"(f[0].a[3]), "v"(f[0].b[0]), "v"(f[0].b[1]));
-    mfma_run<ENC, LO, HI, T + 1>(raw, f, acc);
-  }
-}
-
-// One stage of the ping-pong schedule (pp_stage of gram_packed.hip with the operand expanded in registers).  The phases,
-// the barriers and the vmcnt book-keeping are the same; PER_WAVE = 1 DMA instruction per wave and stage.
-template <int NST, int BUF, int GRP, bool IDLE, int LEFT, bool DIAG, int ENC>
-__device__ __forceinline__ void ppb_stage(StageBits* lds, const int8_t* __restrict__ p, int npad, int64_t blk_begin, int s,
-                                          int ns, int col_i, int col_j, int wave, int lane, int wm, int wn,
-                                          f32x16 (&acc)[4][2], FragsI8<2> (&f)[2], uint2 (&raw)[6]) {
-  constexpr int PER_WAVE = 1;
-  constexpr int D = NST - 1;
-  constexpr int TOT = 16;  // MFMAs per wave and stage
-  const bool more = s + D < ns;
-  if constexpr (GRP == 0) {
-    // ---- phase 2s: read + expand stage s, issue the DMA of stage s+D
-    if constexpr (!IDLE) read_words<DIAG>(&lds[BUF], wm, wn, lane, raw);
-    __builtin_amdgcn_sched_barrier(0);
-    if (more) issue_stage_bits<DIAG>(&lds[(BUF + D) % NST], p, npad, blk_begin + s + D, col_i, col_j, wave, lane);
-    __builtin_amdgcn_sched_barrier(0);
-    if constexpr (!IDLE) expand_frags<ENC>(raw, f);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    raw_barrier();
-    // ---- phase 2s+1: the MFMAs of stage s
-    if constexpr (!IDLE) {
-      asm volatile("s_nop 1");  // VALU-written operands -> MFMA (the barrier covers it; this makes it unconditional)
-      __builtin_amdgcn_s_setprio(1);
-      mfma_run<ENC, 0, TOT - LEFT>(raw, f, acc);
-      __builtin_amdgcn_s_setprio(0);
-    }
-  } else {
-    // ---- phase 2s: issue the DMA of stage s+D, then the MFMAs of stage s-1
-    if (more) issue_stage_bits<DIAG>(&lds[(BUF + D) % NST], p, npad, blk_begin + s + D, col_i, col_j, wave, lane);
-    __builtin_amdgcn_sched_barrier(0);
-    if constexpr (!IDLE) {
-      if (s > 0) {
-        asm volatile("s_nop 1");
-        __builtin_amdgcn_s_setprio(1);
-        mfma_run<ENC, 0, TOT - LEFT>(raw, f, acc);
-        __builtin_amdgcn_s_setprio(0);
-      }
-    }
-    raw_barrier();
-    // ---- phase 2s+1: (the leftover MFMAs of stage s-1, then) read + expand stage s
-    if constexpr (!IDLE) {
-      if constexpr (LEFT > 0) {
-        if (s > 0) {
-          __builtin_amdgcn_s_setprio(2);
-          mfma_run<ENC, TOT - LEFT, TOT>(raw, f, acc);
-          __builtin_amdgcn_s_setprio(0);
-          __builtin_amdgcn_sched_barrier(0);
-        }
-      }
-      read_words<DIAG>(&lds[BUF], wm, wn, lane, raw);
-      expand_frags<ENC>(raw, f);
-    }
-  }
-  // end of phase 2s+1: stage s+1 must have landed (own share), only the DMA of stage s+2.. may stay in flight
-  if (s + 1 < ns) {
-    const int rem = ns - 2 - s;
-    const int keep = rem < D - 1 ? rem : D - 1;
-    if (keep >= 5) wait_vmcnt<(D >= 6 ? 5 * PER_WAVE : 0)>();
-    else if (keep == 4) wait_vmcnt<(D >= 5 ? 4 * PER_WAVE : 0)>();
-    else if (keep == 3) wait_vmcnt<(D >= 4 ? 3 * PER_WAVE : 0)>();
-    else if (keep == 2) wait_vmcnt<(D >= 3 ? 2 * PER_WAVE : 0)>();
-    else if (keep == 1) wait_vmcnt<(D >= 2 ? PER_WAVE : 0)>();
-    else wait_vmcnt<0>();
-  }
-  if constexpr (GRP == 1) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  raw_barrier();
-  if constexpr (GRP == 0 && !IDLE && LEFT > 0) {  // group 0's leftover MFMAs of stage s, into phase 2(s+1)
-    __builtin_amdgcn_s_setprio(2);
-    mfma_run<ENC, TOT - LEFT, TOT>(raw, f, acc);
-    __builtin_amdgcn_s_setprio(0);
-    __builtin_amdgcn_sched_barrier(0);
-  }
-}
-
-template <int NST, int GRP, bool IDLE, int LEFT, bool DIAG, int ENC, int... Is>
-__device__ __forceinline__ void ppb_round(StageBits* lds, const int8_t* __restrict__ p, int npad, int64_t blk_begin, int s,
-                                          int ns, int count, int col_i, int col_j, int wave, int lane, int wm, int wn,
-                                          f32x16 (&acc)[4][2], FragsI8<2> (&f)[2], uint2 (&raw)[6],
-                                          std::integer_sequence<int, Is...>) {
-  ((Is < count ? ppb_stage<NST, Is, GRP, IDLE, LEFT, DIAG, ENC>(lds, p, npad, blk_begin, s + Is, ns, col_i, col_j, wave, lane, wm,
-                                                           wn, acc, f, raw)
-               : (void)0),
-   ...);
-}
-
-template <int NST, int GRP, bool IDLE, int LEFT, bool DIAG, int ENC>
-__device__ __forceinline__ void ppb_loop(StageBits* lds, const int8_t* __restrict__ p, int npad, int64_t blk_begin, int ns,
-                                         int col_i, int col_j, int wave, int lane, int wm, int wn,
-                                         f32x16 (&acc)[4][2]) {
-  FragsI8<2> f[2];
-  uint2 raw[6];
-  // prologue: stages 0 .. NST-2 go in flight; stage 0 must have landed before group 0 reads it in phase 0
-#pragma unroll
-  for (int i = 0; i < NST - 1; ++i)
-    if (i < ns) issue_stage_bits<DIAG>(&lds[i], p, npad, blk_begin + i, col_i, col_j, wave, lane);
-  if (ns > 1 && NST > 2) wait_vmcnt<(NST > 2 ? 1 : 0)>();
-  else wait_vmcnt<0>();
-  raw_barrier();
-  int s = 0;
-  for (; s + NST - 1 < ns; s += NST)
-    ppb_round<NST, GRP, IDLE, LEFT, DIAG, ENC>(lds, p, npad, blk_begin, s, ns, NST, col_i, col_j, wave, lane, wm, wn, acc, f,
-                                          raw, std::make_integer_sequence<int, NST>{});
-  if (s < ns)
-    ppb_round<NST, GRP, IDLE, LEFT, DIAG, ENC>(lds, p, npad, blk_begin, s, ns, ns - s, col_i, col_j, wave, lane, wm, wn, acc, f,
-                                          raw, std::make_integer_sequence<int, NST - 1>{});
-  if constexpr (GRP == 1 && !IDLE) {  // phase 2*ns: group 1's MFMAs of the last stage, nobody to wait for
-    asm volatile("s_nop 1");
-    mfma_run<ENC, 0, 16>(raw, f, acc);
-  }
-}
-
-// Work decomposition: xcd_map 0 / 1 / 2 as gram_packed_kernel (legacy split-K, split-K with one k-slice per XCD,
-// lock-step); xcd_map 4 = even split: `nwork` = ntri * nstages (tile, stage) units in tile-major order are cut into
-// gridDim.x equal runs, a workgroup walks its run and pays one epilogue per tile it touches (at most
-// ceil(run / nstages) + 1).  Every CU gets the same number of MFMAs whatever ntri is (55 tiles x split-K 4 leaves 36 of
-// 256 CUs idle in the lock-step launch).
-// The body is a device function wrapped by the kernel below it, which is held to 224 VGPRs per wave (the compiler takes all
-// 256 a 2-waves-per-SIMD kernel may have when left alone, and needs 196): two contraction waves then leave a SIMD 64 of its
-// 512 registers -- room for the waves of the persistent ring pre-pass (pack_kbits_ring_kernel), which shares the CU with
-// this kernel in the fp32 pipeline (DESIGN_HISTORY.md 4.1, profiles/r03s .. r03u_coreside.txt).
-#define PCOA_KBITS_CONTRACTION __device__ __forceinline__ void gram_kbits_body
-template <int NST, int LEFT, int ENC>
-PCOA_KBITS_CONTRACTION(const int8_t* __restrict__ p, int npad, int64_t nstages, int n,
-                                                            int ntile, int ntri, int splitk, int64_t stages_per,
-                                                            int32_t* __restrict__ s32, int xcd_map,
-                                                            const int32_t* __restrict__ skip, GramStrip strip) {
-  __shared__ __attribute__((aligned(16))) StageBits lds[NST];
-  if (skip != nullptr && *skip != 0) return;  // auto mode's device-side predicate (gram_packed_kernel)
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int wm = wave >> 2, wn = wave & 3;
-  const int b = blockIdx.x;
-
-  // the run of (tile, stage) units of this workgroup: [u, u_end) in tile-major order
-  int64_t u, u_end;
-  if (xcd_map == 4) {
-    const int64_t nwork = (int64_t)ntri * nstages;
-    const int64_t nwg = gridDim.x;
-    // consecutive runs go to consecutive workgroups of ONE XCD (block b runs on XCD b % 8), so that the workgroups
-    // which share a tile's operand panels at about the same k also share an L2
-    const int64_t slot = (nwg % kNumXcd == 0) ? (int64_t)(b & 7) * (nwg / kNumXcd) + (b >> 3) : (int64_t)b;
-    u = nwork * slot / nwg;
-    u_end = nwork * (slot + 1) / nwg;
-  } else {
-    int tile, ks;
-    if (xcd_map == 2) {
-      const int g = kNumXcd / splitk;
-      const int per = (ntri + g - 1) / g;
-      const int xcd = b & 7, slot = b >> 3;
-      tile = (xcd % g) * per + slot;
-      ks = xcd / g;
-      if (slot >= per || tile >= ntri) return;
-    } else if (xcd_map) {
-      const int q = b >> 3;
-      ks = (b & 7) + kNumXcd * (q / ntri);
-      tile = q % ntri;
-    } else {
-      tile = b % ntri;
-      ks = b / ntri;
-    }
-    const int64_t st_begin = (int64_t)ks * stages_per;
-    const int64_t st_end = (st_begin + stages_per < nstages) ? (st_begin + stages_per) : nstages;
-    if (st_begin >= st_end) return;
-    u = (int64_t)tile * nstages + st_begin;
-    u_end = (int64_t)tile * nstages + st_end;
-  }
-
-  while (u < u_end) {  // workgroup-uniform
-    const int tile = (int)(u / nstages);
-    const int64_t st_begin = u - (int64_t)tile * nstages;
-    const int64_t left = u_end - u;
-    const int ns = (int)((nstages - st_begin < left) ? (nstages - st_begin) : left);
-    u += ns;
-
-    int row_blk, col_blk;
-    if (strip.cols > 0) {  // strip owner: all (row block, column block of the strip) tiles, banded (gram_packed_kernel)
-      const int ctiles = ntri / ntile;
-      const int per_band = BAND * ctiles;
-      const int band = tile / per_band;
-      const int r0 = band * BAND;
-      const int h = (ntile - r0 < BAND) ? (ntile - r0) : BAND;
-      const int rem = tile - band * per_band;
-      row_blk = r0 + rem % h;
-      col_blk = strip.cb0 + rem / h;
-    } else {
-      tile_coords<2>(tile, ntile, row_blk, col_blk);
-    }
-    const int col_i = row_blk * 256, col_j = col_blk * TJ;
-    const bool idle = strip.cols == 0 && (col_i + wm * 128) > (col_j + wn * 64 + 63);
-
-    f32x16 acc[4][2];
-#pragma unroll
-    for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-      for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[mi][ni][r] = 0;
-
-    if (row_blk == col_blk && strip.cols == 0) {  // diagonal tile: one panel (workgroup-uniform branch)
-      if (wm == 0) ppb_loop<NST, 0, false, LEFT, true, ENC>(lds, p, npad, st_begin, ns, col_i, col_j, wave, lane, wm, wn, acc);
-      else if (idle) ppb_loop<NST, 1, true, LEFT, true, ENC>(lds, p, npad, st_begin, ns, col_i, col_j, wave, lane, wm, wn, acc);
-      else ppb_loop<NST, 1, false, LEFT, true, ENC>(lds, p, npad, st_begin, ns, col_i, col_j, wave, lane, wm, wn, acc);
-    } else if (wm == 0) {
-      ppb_loop<NST, 0, false, LEFT, false, ENC>(lds, p, npad, st_begin, ns, col_i, col_j, wave, lane, wm, wn, acc);
-    } else {
-      ppb_loop<NST, 1, false, LEFT, false, ENC>(lds, p, npad, st_begin, ns, col_i, col_j, wave, lane, wm, wn, acc);
-    }
-
-    asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");  // last asm MFMA -> VALU read of D
-    if (!idle) {
-#pragma unroll
-      for (int mi = 0; mi < 4; ++mi) {
-#pragma unroll
-        for (int ni = 0; ni < 2; ++ni) {
-          const int j = col_j + wn * 64 + ni * 32 + (lane & 31);
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const int i = col_i + wm * 128 + mi * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-            const int v = (int)acc[mi][ni][r];  // exact integers below 2^24
-            if (strip.cols > 0) {
-              if (i < n && j >= strip.col0 && j < strip.col0 + strip.cols && v != 0)
-                atomicAdd(&s32[(int64_t)i * strip.cols + (j - strip.col0)], v);
-            } else if (j >= i && j < n && v != 0) {
-              atomicAdd(&s32[(int64_t)i * n + j], v);
-            }
-          }
-          __builtin_amdgcn_sched_barrier(0);
-        }
-      }
-    }
-    // the next tile of this run reuses the LDS ring: every wave must be out of this tile's last stage first (the loops
-    // end with a barrier after the last reads; the epilogue touches no LDS)
-  }
-}
-#undef PCOA_KBITS_CONTRACTION
-// amdgpu_num_vgpr counts halves of the unified register file on gfx90a+: 112 -> at most 224 registers per wave
-template <int NST, int LEFT, int ENC>
-__global__ __launch_bounds__(512, 2) __attribute__((amdgpu_num_vgpr(112))) void gram_kbits_kernel(
-    const int8_t* __restrict__ p, int npad, int64_t nstages, int n, int ntile, int ntri, int splitk, int64_t stages_per,
-    int32_t* __restrict__ s32, int xcd_map, const int32_t* __restrict__ skip, GramStrip strip) {
-  gram_kbits_body<NST, LEFT, ENC>(p, npad, nstages, n, ntile, ntri, splitk, stages_per, s32, xcd_map, skip, strip);
-}
-#ifdef PCOA_EXPERIMENTS
-template <int NST, int LEFT, int ENC>
-__global__ __launch_bounds__(512, 2) void gram_kbits_uncapped_kernel(
-    const int8_t* __restrict__ p, int npad, int64_t nstages, int n, int ntile, int ntri, int splitk, int64_t stages_per,
-    int32_t* __restrict__ s32, int xcd_map, const int32_t* __restrict__ skip, GramStrip strip) {
-  gram_kbits_body<NST, LEFT, ENC>(p, npad, nstages, n, ntile, ntri, splitk, stages_per, s32, xcd_map, skip, strip);
-}
-#endif
-
-#endif  // PCOA_KBITS_KERNELS
-
-#ifdef PCOA_KBITS_LAUNCHERS
-
-#ifdef PCOA_EXPERIMENTS
-int g_kbits_variant = 0;  // harness knob: which instantiation launch_gram_kbits uses
-#endif
+}  // namespace
 
 // k-bits pre-passes.  nblk_out: blocks of 128 variants to write (the tail beyond nv is zero-filled); p = first block.
 hipError_t launch_pack_kbits(const void* x, int is_u8, int64_t ld, int64_t nv, int32_t n, int8_t* p, int32_t* flag,
@@ -1184,81 +771,4 @@ hipError_t launch_densify_csr_kbits(const int32_t* idx_dev, const int64_t* offs_
   return hipGetLastError();
 }
 
-// Contraction of a k-bits operand.  mode: 0 = legacy split-K launch, 2 = lock-step (splitk k-streams on 8 / splitk XCDs,
-// fails with hipErrorInvalidValue where the shape does not fit `num_cu`), 4 = even split over `num_cu` workgroups.
-hipError_t launch_gram_kbits(const int8_t* p, int64_t nv, int32_t n, int32_t* s32, int num_cu, hipStream_t stream, int mode,
-                             const int32_t* skip, GramStrip strip) {
-  if (mode == 5) mode = 4;   // (the XCD k-segment split exists in the one-wave-per-SIMD kernel only)
-  if (nv <= 0) return hipSuccess;
-  const int cus = num_cu > 0 ? num_cu : 256;
-  const int npad = (int)gram_packed_npad(n);
-  const int ntile = npad / TJ;
-  int64_t ntri64 = (int64_t)ntile * (ntile + 1) / 2;
-  if (strip.cols > 0) {
-    strip.cb0 = strip.col0 / TJ;
-    const int cb1 = (strip.col0 + strip.cols + TJ - 1) / TJ;
-    ntri64 = (int64_t)ntile * (cb1 - strip.cb0);
-  }
-  if (ntri64 > (1 << 28)) return hipErrorInvalidValue;
-  const int ntri = (int)ntri64;
-  const int64_t nstages = gram_kb_pad(nv, 2) / 4;  // blocks of 128 variants (the operand is padded to whole blocks)
-  int64_t splitk = 1, stages_per = nstages, nblocks = 0;
-  int xcd_map = 0;
-  if (mode == 2) {
-    if (strip.cols > 0) return hipErrorInvalidValue;
-    splitk = gram_lockstep_splitk(n, cus);
-    if (splitk == 0) return hipErrorInvalidValue;
-    const int g = kNumXcd / (int)splitk;
-    const int per = (ntri + g - 1) / g;
-    stages_per = (nstages + splitk - 1) / splitk;
-    nblocks = (int64_t)per * kNumXcd;
-    xcd_map = 2;
-  } else if (mode == 4) {
-    // one workgroup per CU, but never runs shorter than 8 stages (1,024 variants): an epilogue costs about as much
-    const int64_t nwork = (int64_t)ntri * nstages;
-    nblocks = std::max<int64_t>(1, std::min<int64_t>(cus, nwork / 8));
-    if (nblocks >= kNumXcd) nblocks = nblocks / kNumXcd * kNumXcd;  // the kernel's XCD-aware run order needs a multiple of 8
-    xcd_map = 4;
-  } else {
-    const int64_t target = (int64_t)cus * 7;
-    splitk = (target + ntri - 1) / ntri;
-    if (debug_knobs().gram_splitk > 0) splitk = debug_knobs().gram_splitk;
-    const int64_t max_by_work = nstages * 4 / 64;
-    if (splitk > max_by_work) splitk = max_by_work;
-    if (splitk < 1) splitk = 1;
-    if (splitk >= kNumXcd) {
-      splitk = (splitk / kNumXcd) * kNumXcd;
-      xcd_map = 1;
-    }
-    stages_per = (nstages + splitk - 1) / splitk;
-    nblocks = (int64_t)ntri * splitk;
-  }
-  if (nblocks > 0x7fffffffLL) return hipErrorInvalidValue;
-  const dim3 grid((unsigned)nblocks), block(512);
-#define PCOA_LAUNCH_KBITS(NST_, LEFT_, ENC_)                                                                              \
-  hipLaunchKernelGGL((gram_kbits_kernel<NST_, LEFT_, ENC_>), grid, block, 0, stream, p, npad, nstages, n, ntile, ntri,      \
-                     (int)splitk, stages_per, s32, xcd_map, skip, strip)
-#ifdef PCOA_EXPERIMENTS
-#define PCOA_LAUNCH_KBITS_UNCAPPED(NST_, LEFT_, ENC_)                                                                     \
-  hipLaunchKernelGGL((gram_kbits_uncapped_kernel<NST_, LEFT_, ENC_>), grid, block, 0, stream, p, npad, nstages, n, ntile,   \
-                     ntri, (int)splitk, stages_per, s32, xcd_map, skip, strip)
-  switch (g_kbits_variant) {  // harness knob (tools/exp_bits.hip)
-    case 1: PCOA_LAUNCH_KBITS(4, 2, 0); break;   // plain encoding (7 + 7 operations per word pair), whole expansion in the read phase
-    case 2: PCOA_LAUNCH_KBITS(3, 2, 1); break;   // conjugate weights, whole expansion in the read phase
-    case 3: PCOA_LAUNCH_KBITS(4, 2, 2); break;   // shipped schedule on a 4-stage ring
-    case 4: PCOA_LAUNCH_KBITS(3, 0, 2); break;   // no MFMAs behind the phase barrier
-    case 5: PCOA_LAUNCH_KBITS(3, 2, 2); break;          // = default (kept for the r03s .. r03u harness numbering)
-    case 6: PCOA_LAUNCH_KBITS(4, 2, 2); break;          // 4-stage ring (3 stages in flight)
-    case 7: PCOA_LAUNCH_KBITS(6, 2, 2); break;          // 6-stage ring (5 stages = 40 KiB in flight per workgroup)
-    case 8: PCOA_LAUNCH_KBITS_UNCAPPED(6, 2, 2); break; // 6-stage ring, no register cap
-    case 9: PCOA_LAUNCH_KBITS_UNCAPPED(3, 2, 2); break; // shipped schedule, no register cap
-    default: PCOA_LAUNCH_KBITS(3, 2, 2); break;
-  }
-#else
-  PCOA_LAUNCH_KBITS(3, 2, 2);  // conjugate weights, expansion split over the phases, 3-stage ring, two MFMAs behind the barrier
-#endif
-#undef PCOA_LAUNCH_KBITS
-  return hipGetLastError();
-}
-
-#endif  // PCOA_KBITS_LAUNCHERS
+}  // namespace pcoa

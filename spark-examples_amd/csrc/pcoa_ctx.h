@@ -123,7 +123,7 @@ struct pcoa_ctx {
   bool use_i8 = true;              // packed-operand Gram (FP4 / int8) or fp32-MFMA Gram
   int packed_mode = 0;             // 0 auto (FP4 for binary tiles, int8 otherwise), 2 int8 only, 3 FP4 only
   // Form of the binary-tile operand in HBM: 2 = k-bits (1 bit per genotype, expanded to MX-FP4 in registers by the
-  // contraction: gram_kbits.inl; default), 1 = MX-FP4 (4 bits per genotype, PCOA_FLAG_OPERAND_FP4).  The buffer logic
+  // contraction: gram_kbits.hip; default), 1 = MX-FP4 (4 bits per genotype, PCOA_FLAG_OPERAND_FP4).  The buffer logic
   // below counts in k-blocks of 32 variants either way; a k-bits chunk is padded to whole blocks of 128 variants.
   int op_fmt = 2;
   int64_t fp4_fallbacks = 0;

@@ -38,7 +38,7 @@ struct DebugKnobs {
   int kbits_pipe_wgs = 0;          // PCOA_KBITS_PIPE_WGS: workgroups of the k-bits contraction beside the fp32 pre-pass
   int symv_sym_min_n = 0;          // PCOA_SYMV_SYM_MIN_N: smallest N whose Lanczos mat-vec reads only the upper triangle of S (default 16384)
   int csr_legacy = 0;              // PCOA_CSR_LEGACY = 1: pcoa_accumulate_calls through the host-validated r03 path
-  int kbits_w4 = -1;               // PCOA_KBITS_W4 = 0 | 1 | 2: one-wave-per-SIMD contraction (gram_kbits_w4.inl): 0 never, 1 wherever the kernel has its CUs to itself (default), 2 also beside the ring pre-pass
+  int kbits_w4 = -1;               // PCOA_KBITS_W4 = 0 | 1 | 2: one-wave-per-SIMD contraction (gram_kbits_w4.hip): 0 never, 1 wherever the kernel has its CUs to itself (default), 2 also beside the ring pre-pass
   int kbits_w4_diag = -1;          // PCOA_KBITS_W4_DIAG: 0 = diagonal tiles as in r04a (one wave idles), 1..16 = wave roles on diagonal tiles with this cost (of 16) in the even split; default 11
   int kbits_coreside = -1;         // PCOA_KBITS_CORESIDE = 0 | 1: fp32 pipeline with pre-pass and contraction on the SAME CUs (ring pre-pass)
   int kbits_ring_prio = 0;         // PCOA_KBITS_RING_PRIO = 1: the ring pre-pass's waves at s_setprio 3 (harness knob)
@@ -55,7 +55,7 @@ struct DebugKnobs {
 };
 const DebugKnobs& debug_knobs();
 
-// ---- Gram kernels (gram_f32.hip / gram_packed.hip) ------------------------------------------------
+// ---- Gram kernels, fp32 operand (gram_f32.hip) -------------------------------------------------
 struct GramLaunch {
   const float* x;        // device, [nv][ld] carrier multiplicities (0/1)
   int64_t ld;
@@ -69,11 +69,26 @@ struct GramLaunch {
 };
 // Returns hipSuccess or the launch error.  *splitk_out (optional) receives the split-K factor used.
 hipError_t launch_gram_f32(const GramLaunch& g, int* splitk_out);
-// packed-operand path (gram_packed.hip): re-layout pre-pass into the k-blocked FP4 / int8 workspace, then the
-// matrix-core contraction.
+
+// ---- packed operands: a re-layout pre-pass into a k-blocked workspace, then the matrix-core contraction --------------
+// Strip owner (SURVEY 8e, N beyond one HBM): the launch computes S[:, col0 .. col0 + cols) -- every row block against the
+// column blocks of the strip, BOTH triangles -- into a row-major [n][cols] matrix.  cols == 0: the ordinary symmetric job.
+struct GramStrip {
+  int col0 = 0, cols = 0;
+  int cb0 = 0;  // first column block (filled in by the launcher)
+};
+
+// shapes (gram_shape.hip).  gram_kb_pad: fmt 0 = int8 (16 variants per 16-byte lane slice), 1 = FP4 (32), 2 = k-bits
 int64_t gram_packed_npad(int32_t n);
 int64_t gram_packed_kb_pad_i8(int64_t nv);
 size_t gram_packed_workspace_bytes(int32_t n, int64_t nv);
+int64_t gram_kb_pad(int64_t nv, int fmt);
+// Lock-step launch: all tiles of `splitk` k-streams resident at once, one workgroup per CU for the whole launch.
+// gram_lockstep_splitk: the k-stream count that fits `cus` CUs (8 XCDs), 0 if the shape does not fit.
+int gram_lockstep_splitk(int32_t n, int cus);
+int gram_lockstep_workgroups(int32_t n, int splitk);
+
+// pre-passes -> FP4 / int8 operand (pack_packed.hip)
 // flag[0]: bit 2 = a value that is not an integer in [0, 127]; flag[1] = max value seen (atomicMax): the carrier
 // multiplicity bound the host sizes its int32 launches and folds by
 hipError_t launch_pack_f32_i8(const float* x, int64_t ld, int64_t nv, int32_t n, int8_t* p, int32_t* flag,
@@ -83,57 +98,55 @@ hipError_t launch_pack_u8_i8(const uint8_t* x, int64_t ld, int64_t nv, int32_t n
 hipError_t launch_densify_csr_i8(const int32_t* idx_dev, const int64_t* offs_dev, int64_t nv, int64_t offs_base,
                                  int8_t* p, int32_t n, int32_t* flag, hipStream_t stream);
 // FP4 (MX E2M1) variant: fmt 1 = 32 variants per 16-byte lane slice, values must be exactly 0 / 1
-int64_t gram_kb_pad(int64_t nv, int fmt);
 hipError_t launch_densify_csr_fp4(const int32_t* idx_dev, const int64_t* offs_dev, int64_t nv, int64_t offs_base,
                                   int8_t* p, int32_t n, int32_t* flag, hipStream_t stream, int64_t nkb_out);
 hipError_t launch_expand_bits_fp4(const uint32_t* bits, int64_t ld_words, int64_t nv, int32_t n, int8_t* p,
                                   hipStream_t stream, int64_t nkb_out = 0);
 hipError_t launch_pack_fp4(const void* x, int is_u8, int64_t ld, int64_t nv, int32_t n, int8_t* p, int32_t* flag,
                            hipStream_t stream, int64_t nkb_out = 0);
-// k-bits operand (gram_kbits.inl): K1[V/128][Npad][4 words], one BIT per genotype, expanded to FP4 in registers by the
-// contraction.  nblk_out = blocks of 128 variants to write (the tail beyond nv is zero-filled).
+// fp32 tiles the LDS-DMA-ring pre-passes take: ld % 4 == 0 and a 16-byte aligned base
+bool pack_fp4_ring_ok(const void* x, int64_t ld);
+#ifdef PCOA_EXPERIMENTS
+hipError_t launch_pack_fp4_ring(const float* x, int64_t ld, int64_t nv, int32_t n, int8_t* p, int32_t* flag,
+                                hipStream_t stream, int64_t nkb_out, int wgs, int nt);
+#endif
+
+// contraction of an FP4 (fmt 1) / int8 (fmt 0) operand (gram_packed.hip)
+// skip (optional, device): the launch does nothing when *skip != 0 -- the auto mode's device-side predicate (a pre-pass
+// found a value other than 0 / 1 in the buffered tiles; the host learns it later and redoes them on the int8 kernel)
+hipError_t launch_gram_packed(const int8_t* p, int fmt, int64_t nv, int32_t n, int32_t* s32, int num_cu,
+                              hipStream_t stream, int* splitk_out, const int32_t* skip = nullptr,
+                              GramStrip strip = GramStrip{});
+hipError_t launch_gram_packed_lockstep(const int8_t* p, int fmt, int64_t nv, int32_t n, int32_t* s32, int num_cu,
+                                       hipStream_t stream, const int32_t* skip = nullptr);
+#ifdef PCOA_EXPERIMENTS
+extern int g_lockstep_map;  // harness knob (tools/exp_overlap.hip): 3 selects the balanced deal where it applies
+#endif
+
+// pre-passes -> k-bits operand (pack_kbits.hip): K1[V/128][Npad][4 words], one BIT per genotype, expanded to FP4 in
+// registers by the contraction.  nblk_out = blocks of 128 variants to write (the tail beyond nv is zero-filled).
 hipError_t launch_pack_kbits(const void* x, int is_u8, int64_t ld, int64_t nv, int32_t n, int8_t* p, int32_t* flag,
                              hipStream_t stream, int64_t nblk_out);
 hipError_t launch_transpose_bits_kbits(const uint32_t* bits, int64_t ld_words, int64_t nv, int32_t n, int8_t* p,
                                        hipStream_t stream, int64_t nblk_out);
 hipError_t launch_densify_csr_kbits(const int32_t* idx_dev, const int64_t* offs_dev, int64_t nv, int64_t offs_base,
                                     int8_t* p, int32_t n, int32_t* flag, hipStream_t stream, int64_t nblk_out);
-bool pack_fp4_ring_ok(const void* x, int64_t ld);
 // persistent LDS-DMA-ring form of the fp32 -> k-bits pre-pass (needs pack_fp4_ring_ok): <= wgs workgroups; ring: 8 = 8 rows
 // in flight per wave, default cache policy (what the library uses), 108 = nontemporal loads
 hipError_t launch_pack_kbits_ring(const float* x, int64_t ld, int64_t nv, int32_t n, int8_t* p, int32_t* flag,
                                   hipStream_t stream, int64_t nblk_out, int wgs, int ring);
-hipError_t launch_pack_fp4_ring(const float* x, int64_t ld, int64_t nv, int32_t n, int8_t* p, int32_t* flag,
-                                hipStream_t stream, int64_t nkb_out, int wgs, int nt);
 // the uint8 form: units of 128 variants x 1,024 samples, one wave per SIMD (ld % 8 == 0, 8-byte aligned base)
 bool pack_u8_ring_ok(const void* x, int64_t ld);
 hipError_t launch_pack_kbits_ring_u8(const uint8_t* x, int64_t ld, int64_t nv, int32_t n, int8_t* p, int32_t* flag,
                                      hipStream_t stream, int64_t nblk_out, int wgs, int ring);
-// Strip owner (SURVEY 8e, N beyond one HBM): the launch computes S[:, col0 .. col0 + cols) -- every row block against the
-// column blocks of the strip, BOTH triangles -- into a row-major [n][cols] matrix.  cols == 0: the ordinary symmetric job.
-struct GramStrip {
-  int col0 = 0, cols = 0;
-  int cb0 = 0;  // first column block (filled in by the launcher)
-};
-// skip (optional, device): the launch does nothing when *skip != 0 -- the auto mode's device-side predicate (a pre-pass
-// found a value other than 0 / 1 in the buffered tiles; the host learns it later and redoes them on the int8 kernel)
-hipError_t launch_gram_packed(const int8_t* p, int fmt, int64_t nv, int32_t n, int32_t* s32, int num_cu,
-                              hipStream_t stream, int* splitk_out, const int32_t* skip = nullptr,
-                              GramStrip strip = GramStrip{});
-// Lock-step launch: all tiles of `splitk` k-streams resident at once, one workgroup per CU for the whole launch.
-// gram_lockstep_splitk: the k-stream count that fits `cus` CUs (8 XCDs), 0 if the shape does not fit.
-// k-bits contraction; mode 0 = split-K launch, 2 = lock-step, 4 = even split of the (tile, stage) units over num_cu workgroups
+
+// contraction of a k-bits operand, two waves per SIMD (gram_kbits.hip); mode 0 = split-K launch, 2 = lock-step, 4 = even split
+// of the (tile, stage) units over num_cu workgroups
 hipError_t launch_gram_kbits(const int8_t* p, int64_t nv, int32_t n, int32_t* s32, int num_cu, hipStream_t stream, int mode,
                              const int32_t* skip = nullptr, GramStrip strip = GramStrip{});
-// the same contraction with one wave per SIMD and 128 x 128 wave tiles (gram_kbits_w4.inl); same modes
+// the same contraction with one wave per SIMD and 128 x 128 wave tiles (gram_kbits_w4.hip); same modes
 hipError_t launch_gram_kbits_w4(const int8_t* p, int64_t nv, int32_t n, int32_t* s32, int num_cu, hipStream_t stream, int mode,
                                 const int32_t* skip = nullptr, GramStrip strip = GramStrip{}, int wdiag = -1);
-int gram_lockstep_splitk(int32_t n, int cus);
-int gram_lockstep_workgroups(int32_t n, int splitk);
-hipError_t launch_gram_packed_lockstep(const int8_t* p, int fmt, int64_t nv, int32_t n, int32_t* s32, int num_cu,
-                                       hipStream_t stream, const int32_t* skip = nullptr);
-hipError_t launch_gram_i8_packed(const int8_t* p, int64_t nv, int32_t n, int32_t* s32, int num_cu,
-                                 hipStream_t stream, int* splitk_out);
 
 // ---- auxiliary Gram kernels (gram_aux.hip) ----------------------------------------------------
 hipError_t launch_densify_csr(const int32_t* idx_dev, const int64_t* offs_dev, int64_t v0, int64_t nv,

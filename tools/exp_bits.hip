@@ -1,6 +1,6 @@
-// exp_bits.hip -- correctness + A/B harness of the k-bits operand (spark-examples_amd/csrc/gram_kbits.inl).
+// exp_bits.hip -- correctness + A/B harness of the k-bits operand (spark-examples_amd/csrc/pack_kbits.hip, gram_kbits.hip).
 //
-// On one MI355X, with the library's own kernels (gram_packed.hip is included, so the anonymous-namespace kernels are visible):
+// On one MI355X, with the library's own kernels (their translation units are included, so the harness knobs reach them):
 //   1. small ragged shapes: every k-bits pre-pass (fp32 / uint8 / carrier bitsets / CSR) against a host-built operand, and the
 //      k-bits contraction (split-K, lock-step, even-split launches) against a host popcount Gram;
 //   2. BASELINE configs[1] size (2,504 samples x 2^20 variants): S of the k-bits path == S of the shipped FP4 path, bit for bit;
@@ -15,7 +15,11 @@
 #include <string>
 #include <vector>
 
+#include "../spark-examples_amd/csrc/gram_kbits.hip"
 #include "../spark-examples_amd/csrc/gram_packed.hip"
+#include "../spark-examples_amd/csrc/gram_shape.hip"
+#include "../spark-examples_amd/csrc/pack_kbits.hip"
+#include "../spark-examples_amd/csrc/pack_packed.hip"
 
 namespace pcoa {
 const DebugKnobs& debug_knobs() {

@@ -1,7 +1,7 @@
 // exp_overlap.hip -- A/B harness for the fp32 boundary of the Gram path (DESIGN_HISTORY.md 4.1).
 //
-// Measures, on one MI355X and on the kernels of spark-examples_amd/csrc/gram_packed.hip themselves (the file is
-// included, so the anonymous-namespace kernels are visible):
+// Measures, on one MI355X and on the kernels of spark-examples_amd/csrc/pack_packed.hip and gram_packed.hip themselves
+// (the files are included, so the experiment-only ring pre-pass and the harness knobs are visible):
 //   1. pack_fp4_kernel (shipped pre-pass) vs pack_fp4_ring_kernel (persistent, LDS-DMA ring, <= 64 VGPRs, 64 KiB LDS):
 //      bit-identical operand? time per 10^6 variants at several grid sizes, nt / default cache policy;
 //   2. the contraction alone;
@@ -18,6 +18,8 @@
 #include <vector>
 
 #include "../spark-examples_amd/csrc/gram_packed.hip"
+#include "../spark-examples_amd/csrc/gram_shape.hip"
+#include "../spark-examples_amd/csrc/pack_packed.hip"
 
 // the library reads its environment knobs through this accessor (devmem.hip); the harness has none
 namespace pcoa {

@@ -1,5 +1,5 @@
-// exp_w4.hip -- correctness + A/B harness of the one-wave-per-SIMD k-bits contraction (spark-examples_amd/csrc/gram_kbits_w4.inl,
-// VERDICT r03 item 1).  On one MI355X, with the library's own kernels (gram_packed.hip is included):
+// exp_w4.hip -- correctness + A/B harness of the one-wave-per-SIMD k-bits contraction (spark-examples_amd/csrc/gram_kbits_w4.hip,
+// VERDICT r03 item 1).  On one MI355X, with the library's own kernels (the two contractions' translation units are included):
 //   1. a random k-bits operand (density as the synthetic cohort, ~8 %) of N samples x V variants, built on the device;
 //   2. S of every w4 variant / launch mode == S of the shipped gram_kbits_kernel<3,2,2> (itself oracle-checked in tests/), bit for
 //      bit, on ragged shapes and at BASELINE configs[1] size;
@@ -11,7 +11,9 @@
 #include <functional>
 #include <vector>
 
-#include "../spark-examples_amd/csrc/gram_packed.hip"
+#include "../spark-examples_amd/csrc/gram_kbits.hip"
+#include "../spark-examples_amd/csrc/gram_kbits_w4.hip"
+#include "../spark-examples_amd/csrc/gram_shape.hip"
 
 namespace pcoa {
 const DebugKnobs& debug_knobs() {
