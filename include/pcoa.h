@@ -526,6 +526,32 @@ int pcoa_debug_centred_matvec(pcoa_ctx* ctx, const double* x, double* y, int upp
 int pcoa_debug_free(void* p);
 int pcoa_debug_guard_mode(void);
 
+/* ---- environment knobs ---------------------------------------------------------------------------------------------------
+ * For tests and measurements, not for users: nothing here is needed to use the library, and none is a stable interface.
+ * Each selects a path or a threshold that a test, bench.py or a tool under tools/ runs on purpose.  All of them are read
+ * once, at first use, in one place (debug_knobs(), csrc/devmem.hip).  One line per knob:
+ *   PCOA_GRAM_KERNEL            auto | fp4 | i8 | f32: the Gram kernel, overriding the create flags
+ *   PCOA_DEBUG_PACK_CHUNK       variants per pre-pass launch (forces the multi-chunk paths at test sizes)
+ *   PCOA_DEBUG_MAX_LAUNCH       variants per contraction launch (forces the multi-launch / two-buffer paths)
+ *   PCOA_DEBUG_FOLD_THRESHOLD   variants an int32 partial may hold before it is folded into int64
+ *   PCOA_DEBUG_GUARD            1 | 2: every device buffer ends | starts at an unmapped page (see the test hooks above)
+ *   PCOA_PIPELINE               0 | 1: the two-stream fp32 pipeline off | on wherever it fits
+ *   PCOA_BITS_PIPELINE          1: bitset tiles through the co-resident pipeline instead of transpose and contraction in series
+ *   PCOA_GRAM_LOCKSTEP          0 | 1: the lock-step contraction launch off | on wherever it fits
+ *   PCOA_EXPLICIT_CENTER        set: the Lanczos path materialises the centred matrix B
+ *   PCOA_SYMV_SYM_MIN_N         smallest N whose Lanczos mat-vec reads only the upper triangle of S (default 16,384)
+ *   PCOA_LANCZOS_BAND           0: no band-Lanczos fallback; 2: only the band iteration
+ *   PCOA_LANCZOS_BAND_MMAX      basis size of the band iteration (forces thick restarts)
+ *   PCOA_SYNTH_TILE             1: pcoa_accumulate_synthetic through the fp32 staging tile and the pre-pass
+ *   PCOA_NO_NARROW              1: an int64 S that fits int32 stays int64
+ *   PCOA_KBITS_MODE             0 | 2 | 4 | 5: launch form of the k-bits contraction (split-K, lock-step, even split, even split
+ *                               per XCD k-segment)
+ *   PCOA_KBITS_W4               0 | 1: the one-wave-per-SIMD k-bits contraction never | wherever it has its CUs to itself (default)
+ *   PCOA_KBITS_W4_DIAG          0: one wave of a diagonal tile idles; 1..16: wave roles, cost of a diagonal stage in the even split
+ *   PCOA_KBITS_CORESIDE         0 | 1: fp32 pipeline with pre-pass and contraction on disjoint | the same CUs
+ *   PCOA_CSR_LEGACY             1: pcoa_accumulate_calls through the host-validated path
+ */
+
 /* Name of the GPU the ctx runs on, its CU count and the library version string. */
 int pcoa_device_info(pcoa_ctx* ctx, char* name_out, int32_t name_cap, int32_t* cu_count_out);
 const char* pcoa_version(void);

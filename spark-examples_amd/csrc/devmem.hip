@@ -134,31 +134,16 @@ const DebugKnobs& debug_knobs() {
     k.max_launch = num("PCOA_DEBUG_MAX_LAUNCH");
     k.fold_threshold = num("PCOA_DEBUG_FOLD_THRESHOLD");
     if (const char* v = std::getenv("PCOA_PIPELINE")) k.pipeline = std::atoi(v) != 0;
-    if (const char* v = std::getenv("PCOA_FORK_LAZY")) k.fork_lazy = std::atoi(v);
-    if (const char* v = std::getenv("PCOA_HEADSTART_US")) k.headstart_us = std::atoi(v);
     if (const char* v = std::getenv("PCOA_BITS_PIPELINE")) k.bits_pipeline = std::atoi(v);
     if (const char* v = std::getenv("PCOA_KBITS_W4_DIAG")) k.kbits_w4_diag = std::atoi(v);
     if (const char* v = std::getenv("PCOA_GRAM_LOCKSTEP")) k.lockstep = std::atoi(v) != 0;
     k.explicit_center = std::getenv("PCOA_EXPLICIT_CENTER") != nullptr;
-    k.lanczos_first_check = (int)num("PCOA_LANCZOS_FIRST_CHECK");
-    k.lanczos_trace = std::getenv("PCOA_DEBUG_LANCZOS") != nullptr;
     k.guard = (int)num("PCOA_DEBUG_GUARD");
-    if (const char* v = std::getenv("PCOA_OPERAND")) {
-      if (!std::strcmp(v, "fp4")) k.operand = 1;
-      if (!std::strcmp(v, "bits")) k.operand = 2;
-    }
     if (const char* v = std::getenv("PCOA_KBITS_MODE")) k.kbits_mode = std::atoi(v);
     if (const char* v = std::getenv("PCOA_KBITS_W4")) k.kbits_w4 = std::atoi(v);
     if (const char* v = std::getenv("PCOA_CSR_LEGACY")) k.csr_legacy = std::atoi(v) != 0;
     if (const char* v = std::getenv("PCOA_SYMV_SYM_MIN_N")) k.symv_sym_min_n = std::atoi(v);
-    k.kbits_pipe_wgs = (int)num("PCOA_KBITS_PIPE_WGS");
     if (const char* v = std::getenv("PCOA_KBITS_CORESIDE")) k.kbits_coreside = std::atoi(v) != 0;
-    k.kbits_ring_wgs = (int)num("PCOA_KBITS_RING_WGS");
-    k.u8_ring_wgs = (int)num("PCOA_U8_RING_WGS");
-    k.kbits_ring_prio = (int)num("PCOA_KBITS_RING_PRIO");
-    k.kbits_coreside_max_npad = (int)num("PCOA_KBITS_CORESIDE_MAX_NPAD");
-    k.gram_cfg = (int)num("PCOA_GRAM_I8_CFG");
-    k.gram_splitk = (int)num("PCOA_GRAM_I8_SPLITK");
     k.no_narrow = (int)num("PCOA_NO_NARROW");
     k.synth_tile = (int)num("PCOA_SYNTH_TILE");
     if (const char* v = std::getenv("PCOA_LANCZOS_BAND")) k.lanczos_band = std::atoi(v);

@@ -844,7 +844,6 @@ hipError_t lanczos_single(const EigWorkspace& ws, double* lz, int32_t n, int32_t
   // three steps, and population structure converges early (configs[1] stand-in: estimate 1e-14 at m = 12, true
   // relative residual 3.7e-9)
   int next_check = 12;
-  if (debug_knobs().lanczos_first_check > 0) next_check = std::max(4, debug_knobs().lanczos_first_check);
   // a check needs the k wanted Ritz values and one more for their gaps: T_m must have at least k + 2 rows (mmax does)
   if (next_check < k + 2) next_check = k + 2;
   if (next_check > mmax) next_check = mmax;
@@ -940,13 +939,6 @@ hipError_t lanczos_single(const EigWorkspace& ws, double* lz, int32_t n, int32_t
     const bool breakdown = beta_m <= 1e-14 * scale;  // invariant subspace: T_m holds exact eigenvalues
     bool verified = true;
     for (int t = 0; t < k; ++t) verified = verified && std::isfinite(hres[t]) && accept(hres[t] * 0.125, t);
-    if (debug_knobs().lanczos_trace != 0) {
-      std::fprintf(stderr, "[lanczos] m=%d beta_m=%.3e scale=%.6e", m, beta_m, scale);
-      for (int t = 0; t < k; ++t)
-        std::fprintf(stderr, "  theta%d=%.10e est=%.3e gap=%.3e true=%.3e", t, lam_sel_host[t], fabs(beta_m * ylast[t]),
-                     gap[(size_t)t], hres[t]);
-      std::fprintf(stderr, "  ok=%d verified=%d\n", (int)ok, (int)verified);
-    }
     if (!ok && !breakdown) {   // the estimate says not yet: the speculative residual is not consulted
       if (m == mmax) return hipSuccess;
       // Stagnation: from m = 128 on a check comes every m / 2 steps; an estimate that has not improved fourfold since the
@@ -1059,7 +1051,6 @@ hipError_t lanczos_band(const EigWorkspace& ws, double* lz, int32_t n, int32_t k
   const int cap = mmax - pk;          // basis vectors in use at most: pk slots stay free for the Ritz vectors of a restart
   const int64_t budget = 40LL * mmax; // columns (= mat-vecs) in all
   int64_t columns = 0;
-  int restarts = 0;
   int j = 0;                          // next column to process
   for (;;) {
     // column j: w = B v_j, orthogonalised against the whole basis; what is left becomes v_cnt
@@ -1146,11 +1137,6 @@ hipError_t lanczos_band(const EigWorkspace& ws, double* lz, int32_t n, int32_t k
       loose = loose && fin && r * 0.125 <= tol * scale;
       tight = tight && fin && r * 0.125 <= tol * scale && (r * 0.125 <= 1e-8 * g || r <= 1e-13 * scale);
     }
-    if (debug_knobs().lanczos_trace != 0) {
-      std::fprintf(stderr, "[lanczos band] J=%d basis=%d restarts=%d columns=%lld scale=%.6e", J, cnt, restarts, (long long)columns, scale);
-      for (int t = 0; t < k; ++t) std::fprintf(stderr, "  theta%d=%.12e true=%.3e", t, lam_sel_host[t], hres[t]);
-      std::fprintf(stderr, "  tight=%d loose=%d last=%d full=%d\n", (int)tight, (int)loose, (int)last, (int)full);
-    }
     if (tight || (last && loose)) {
       *converged = 1;
       return hipGetLastError();
@@ -1169,7 +1155,6 @@ hipError_t lanczos_band(const EigWorkspace& ws, double* lz, int32_t n, int32_t k
     hipLaunchKernelGGL(band_restart_h_kernel, dim3(1), dim3(64), 0, stream, hfull, mcap, pw, hlam);
     cnt = pw + carry;
     j = pw;
-    restarts += 1;
     next_check = j + std::max(8, 2 * bw0);
   }
 }

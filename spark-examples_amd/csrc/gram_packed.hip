@@ -22,9 +22,7 @@
 //   One stage = 4 k-blocks x 2 panels x 256 samples x 16 B = 32 KiB, brought in by 32 global_load_lds_dwordx4 (1 KiB
 //   each), 3-stage LDS ring (96 KiB), counted vmcnt (two stages stay in flight), raw s_barrier (never
 //   __syncthreads, which would drain the DMA queue).  Operand reads are ds_read_b128 of 32 consecutive 16-B slots per
-//   half-wave: conflict-free.  Default schedule: ping-pong (two wave groups half a stage apart, see below);
-//   PCOA_GRAM_I8_CFG=43 selects the in-phase ring, 143 the
-//   ping-pong schedule without the two MFMAs issued behind the phase barrier.
+//   half-wave: conflict-free.  Schedule: ping-pong (two wave groups half a stage apart, see below).
 //
 // Measured at N = 2504 per 10^6 variants: FP4 1.13-1.16 ms (6 PFLOP/s issued), int8 2.14 ms; DESIGN_HISTORY.md 4.1 / 4.2.
 #include <utility>
@@ -34,13 +32,6 @@
 
 namespace pcoa {
 namespace {
-
-// barrier of the in-phase ring: this wave's LDS reads have returned, then s_barrier (the ping-pong schedule uses raw_barrier)
-__device__ __forceinline__ void wg_barrier() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
 
 // ---------------------------------------------------------------------------------------------- gemm
 // Template parameters
@@ -146,77 +137,8 @@ __device__ __forceinline__ void mfma_step_i8(const FragsI8<NNI>& f, typename Acc
     }
 }
 
-// One stage of the ring.  Prefetch distance D = NST - 1: when stage s is consumed, stages s+1 .. s+D-1
-// may still be in flight (counted vmcnt), and stage s+D is issued into the buffer stage s-1 used.
-// Inside the stage the fragment reads are software-pipelined one k32-step ahead of the MFMAs
-// (two register sets of 24 VGPRs), so the stage depth SKB does not cost registers.
-template <int FMT, int NWM, int NNI, int SKB, int NST, int BUF, bool IDLE>
-__device__ __forceinline__ void ring_step(StageI8<NWM, SKB>* lds, const int8_t* __restrict__ p, int npad,
-                                          int64_t kb_begin, int s, int ns, int col_i, int col_j, int wave, int lane,
-                                          int wm, int wn, typename AccType<FMT>::type (&acc)[4][NNI]) {
-  constexpr int NWAVES = NWM * (8 / NNI);
-  constexpr int PER_WAVE = SKB * (2 * NWM + 4) / NWAVES;
-  constexpr int D = NST - 1;
-  static_assert(D >= 1 && D <= 5 && D * PER_WAVE < 64, "prefetch distance 1..5, vmcnt is a 6-bit counter");
-  {
-    // stages s+1 .. s+min(D-1, ns-1-s) may stay in flight
-    const int rem = ns - 1 - s;
-    const int keep = rem < D - 1 ? rem : D - 1;
-    if (keep >= 4) wait_vmcnt<(D >= 5 ? 4 * PER_WAVE : 0)>();
-    else if (keep == 3) wait_vmcnt<(D >= 4 ? 3 * PER_WAVE : 0)>();
-    else if (keep == 2) wait_vmcnt<(D >= 3 ? 2 * PER_WAVE : 0)>();
-    else if (keep == 1) wait_vmcnt<(D >= 2 ? PER_WAVE : 0)>();
-    else wait_vmcnt<0>();
-  }
-  wg_barrier();  // all waves' stage-s DMA landed, and all waves are done reading the buffer of stage s-1
-  if constexpr (IDLE) {  // this wave's sub-tile lies below the diagonal: it only helps with the DMA
-    if (s + D < ns)
-      issue_stage_i8<NWM, SKB, NWAVES>(&lds[(BUF + D) % NST], p, npad, kb_begin + (int64_t)(s + D) * SKB, col_i,
-                                       col_j, wave, lane);
-    return;
-  }
-  FragsI8<NNI> f0, f1;
-  load_frags_i8<NWM, NNI, SKB>(&lds[BUF], 0, wm, wn, lane, f0);
-  __builtin_amdgcn_sched_barrier(0);
-  // the DMA of stage s+D is issued under the LDS latency of the first fragment reads
-  if (s + D < ns)
-    issue_stage_i8<NWM, SKB, NWAVES>(&lds[(BUF + D) % NST], p, npad, kb_begin + (int64_t)(s + D) * SKB, col_i, col_j,
-                                     wave, lane);
-  __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-  for (int k2 = 0; k2 < SKB / 2; k2 += 2) {
-    if (k2 + 1 < SKB / 2) load_frags_i8<NWM, NNI, SKB>(&lds[BUF], k2 + 1, wm, wn, lane, f1);
-    mfma_step_i8<FMT, NNI>(f0, acc);
-    if (k2 + 2 < SKB / 2) load_frags_i8<NWM, NNI, SKB>(&lds[BUF], k2 + 2, wm, wn, lane, f0);
-    if (k2 + 1 < SKB / 2) mfma_step_i8<FMT, NNI>(f1, acc);
-  }
-}
-
-template <int NWM, int SKB, int NST, int NWAVES, int... Is>
-__device__ __forceinline__ void ring_prologue(StageI8<NWM, SKB>* lds, const int8_t* __restrict__ p, int npad,
-                                              int64_t kb_begin, int ns, int col_i, int col_j, int wave, int lane,
-                                              std::integer_sequence<int, Is...>) {
-  ((Is < ns ? issue_stage_i8<NWM, SKB, NWAVES>(&lds[Is], p, npad, kb_begin + (int64_t)Is * SKB, col_i, col_j, wave,
-                                               lane)
-            : (void)0),
-   ...);
-}
-
-// `count` consecutive stages starting at s (s is a multiple of NST, so stage s+i lives in buffer i)
-template <int FMT, int NWM, int NNI, int SKB, int NST, bool IDLE, int... Is>
-__device__ __forceinline__ void ring_round(StageI8<NWM, SKB>* lds, const int8_t* __restrict__ p, int npad,
-                                           int64_t kb_begin, int s, int ns, int count, int col_i, int col_j,
-                                           int wave, int lane, int wm, int wn,
-                                           typename AccType<FMT>::type (&acc)[4][NNI],
-                                           std::integer_sequence<int, Is...>) {
-  ((Is < count ? ring_step<FMT, NWM, NNI, SKB, NST, Is, IDLE>(lds, p, npad, kb_begin, s + Is, ns, col_i, col_j, wave, lane,
-                                                          wm, wn, acc)
-               : (void)0),
-   ...);
-}
-
-// ---- ping-pong schedule (PP = true) -------------------------------------------------------------------------
-// The plain ring above keeps all eight waves in phase: after every barrier they all read fragments, then all
+// ---- ping-pong schedule --------------------------------------------------------------------------------------
+// A plain ring keeps all eight waves in phase: after every barrier they all read fragments, then all
 // issue MFMAs, and the matrix pipe idles during the read burst (53-64 % MFMA-busy measured).  Here the waves
 // form two groups, one wave of each group per SIMD (waves w and w+4 share a SIMD), half a stage apart:
 //
@@ -367,21 +289,12 @@ __device__ __forceinline__ void pp_loop(StageI8<NWM, SKB>* lds, const int8_t* __
   }
 }
 
-#ifdef PCOA_EXPERIMENTS
-// Experiment (xcd_map = 3; 10 x 10 tile triangle, two k-streams): the 55 tiles dealt to the 4 XCDs of a k-stream so
-// that every XCD touches exactly 6 of the 10 operand panels (a covering design on the panel pairs {0,1} .. {8,9}:
-// ABC, ADE, BDE, CDE) instead of 10 / 9 / 7 / 5 with the row-major cut.  Entries are 10 * row_blk + col_blk, -1 = idle.
-__device__ const signed char kBalancedTiles[4][14] = {
-    {2, 3, 12, 13, 4, 5, 14, 15, 24, 25, 34, 35, 0, 11},
-    {6, 7, 16, 17, 8, 9, 18, 19, 1, 66, 67, 77, 68, 69},
-    {26, 27, 36, 37, 28, 29, 38, 39, 22, 23, 33, 78, 79, 88},
-    {46, 47, 56, 57, 48, 49, 58, 59, 44, 45, 55, 89, 99, -1}};
-#endif
-
 template <int FMT, int NWM, int NNI, int SKB, int NST, bool PP, int LEFT = 0>
 __global__ __launch_bounds__(64 * NWM * (8 / NNI), (NNI == 2) ? 2 : 1) void gram_packed_kernel(
     const int8_t* __restrict__ p, int npad, int64_t nstages, int n, int ntile, int ntri, int splitk,
     int64_t stages_per, int32_t* __restrict__ s32, int xcd_map, const int32_t* __restrict__ skip, GramStrip strip) {
+  // the one schedule there is (DESIGN_HISTORY.md 4.1 / 4.2 has the others' numbers); the parameter list is the kernel's name
+  static_assert(NWM == 2 && NNI == 2 && SKB == 4 && NST == 3 && PP && LEFT == 2, "ping-pong: 8 waves, group = wave / 4 = wm");
   __shared__ __attribute__((aligned(16))) StageI8<NWM, SKB> lds[NST];
   // device-side predicate of the auto mode: a pre-pass met a value other than 0 / 1 in the buffered tiles, so this
   // launch must not add anything to S (the host redoes those tiles on the int8 kernel once it reads the same word)
@@ -390,24 +303,11 @@ __global__ __launch_bounds__(64 * NWM * (8 / NNI), (NNI == 2) ? 2 : 1) void gram
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   constexpr int NWN = 8 / NNI;  // waves along N
-  constexpr int NWAVES = NWM * NWN;
   const int wm = wave / NWN, wn = wave % NWN;
 
   int tile, ks;
   int row_blk = -1, col_blk = -1;
   const int b = blockIdx.x;
-#ifdef PCOA_EXPERIMENTS
-  if (xcd_map == 3) {
-    const int xcd = b & 7, slot = b >> 3;
-    if (slot >= 14) return;
-    const int code = kBalancedTiles[xcd & 3][slot];
-    if (code < 0) return;
-    row_blk = code / 10;
-    col_blk = code % 10;
-    ks = xcd >> 2;
-    tile = 0;
-  } else
-#endif
   if (xcd_map == 2) {
     // lock-step layout: the chip holds ALL tiles of `splitk` k-streams at once, one workgroup per CU for the whole
     // launch.  A k-stream's tiles live on a group of 8 / splitk XCDs, so every operand row is fetched into those L2s
@@ -426,9 +326,7 @@ __global__ __launch_bounds__(64 * NWM * (8 / NNI), (NNI == 2) ? 2 : 1) void gram
     tile = b % ntri;
     ks = b / ntri;
   }
-  if (row_blk >= 0) {
-    // coordinates already set (experiment deal)
-  } else if (strip.cols > 0) {
+  if (strip.cols > 0) {
     // strip owner: ALL tiles (row block, column block of the strip), in BANDS of 16 tile rows, column by column inside a
     // band -- workgroups that run together then cover ~16 x 16 tiles and share 16 + 16 operand panels (the ordering
     // that keeps the symmetric job MFMA-bound at N = 100,000, tile_coords)
@@ -463,42 +361,19 @@ __global__ __launch_bounds__(64 * NWM * (8 / NNI), (NNI == 2) ? 2 : 1) void gram
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[mi][ni][r] = 0;
 
-  if constexpr (PP) {
-    static_assert(!PP || (NWM == 2 && NNI == 2), "ping-pong: 8 waves, group = wave / 4 = wm");
-    if (row_blk == col_blk) {  // diagonal tile: one panel, below-diagonal waves idle (workgroup-uniform branch)
-      if (wm == 0) {
-        pp_loop<FMT, NWM, NNI, SKB, NST, 0, false, LEFT, true>(lds, p, npad, kb_begin, ns, col_i, col_j, wave, lane, wm, wn, acc);
-      } else if (idle) {
-        pp_loop<FMT, NWM, NNI, SKB, NST, 1, true, LEFT, true>(lds, p, npad, kb_begin, ns, col_i, col_j, wave, lane, wm, wn, acc);
-        return;
-      } else {
-        pp_loop<FMT, NWM, NNI, SKB, NST, 1, false, LEFT, true>(lds, p, npad, kb_begin, ns, col_i, col_j, wave, lane, wm, wn, acc);
-      }
-    } else if (wm == 0) {
-      pp_loop<FMT, NWM, NNI, SKB, NST, 0, false, LEFT, false>(lds, p, npad, kb_begin, ns, col_i, col_j, wave, lane, wm, wn, acc);
+  if (row_blk == col_blk) {  // diagonal tile: one panel, below-diagonal waves idle (workgroup-uniform branch)
+    if (wm == 0) {
+      pp_loop<FMT, NWM, NNI, SKB, NST, 0, false, LEFT, true>(lds, p, npad, kb_begin, ns, col_i, col_j, wave, lane, wm, wn, acc);
+    } else if (idle) {
+      pp_loop<FMT, NWM, NNI, SKB, NST, 1, true, LEFT, true>(lds, p, npad, kb_begin, ns, col_i, col_j, wave, lane, wm, wn, acc);
+      return;
     } else {
-      pp_loop<FMT, NWM, NNI, SKB, NST, 1, false, LEFT, false>(lds, p, npad, kb_begin, ns, col_i, col_j, wave, lane, wm, wn, acc);
+      pp_loop<FMT, NWM, NNI, SKB, NST, 1, false, LEFT, true>(lds, p, npad, kb_begin, ns, col_i, col_j, wave, lane, wm, wn, acc);
     }
+  } else if (wm == 0) {
+    pp_loop<FMT, NWM, NNI, SKB, NST, 0, false, LEFT, false>(lds, p, npad, kb_begin, ns, col_i, col_j, wave, lane, wm, wn, acc);
   } else {
-  // prologue: stages 0 .. D-1 go in flight
-  ring_prologue<NWM, SKB, NST, NWAVES>(lds, p, npad, kb_begin, ns, col_i, col_j, wave, lane,
-                                      std::make_integer_sequence<int, NST - 1>{});
-  int s = 0;
-  if (idle) {  // wave-uniform: a separate loop with no accumulator traffic at all, then nothing to store
-    for (; s + NST - 1 < ns; s += NST)
-      ring_round<FMT, NWM, NNI, SKB, NST, true>(lds, p, npad, kb_begin, s, ns, NST, col_i, col_j, wave, lane, wm, wn, acc,
-                                           std::make_integer_sequence<int, NST>{});
-    if (s < ns)
-      ring_round<FMT, NWM, NNI, SKB, NST, true>(lds, p, npad, kb_begin, s, ns, ns - s, col_i, col_j, wave, lane, wm, wn,
-                                           acc, std::make_integer_sequence<int, NST - 1>{});
-    return;
-  }
-  for (; s + NST - 1 < ns; s += NST)
-    ring_round<FMT, NWM, NNI, SKB, NST, false>(lds, p, npad, kb_begin, s, ns, NST, col_i, col_j, wave, lane, wm, wn, acc,
-                                          std::make_integer_sequence<int, NST>{});
-  if (s < ns)
-    ring_round<FMT, NWM, NNI, SKB, NST, false>(lds, p, npad, kb_begin, s, ns, ns - s, col_i, col_j, wave, lane, wm, wn,
-                                          acc, std::make_integer_sequence<int, NST - 1>{});
+    pp_loop<FMT, NWM, NNI, SKB, NST, 1, false, LEFT, false>(lds, p, npad, kb_begin, ns, col_i, col_j, wave, lane, wm, wn, acc);
   }
 
   if constexpr (FMT >= 1) asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");  // last asm MFMA -> VALU read of D
@@ -529,10 +404,6 @@ __global__ __launch_bounds__(64 * NWM * (8 / NNI), (NNI == 2) ? 2 : 1) void gram
 
 }  // namespace
 
-#ifdef PCOA_EXPERIMENTS
-int g_lockstep_map = 2;   // harness knob: 3 selects the balanced deal where it applies
-#endif
-
 // Lock-step launch of the FP4 / int8 contraction (gram_packed_kernel with xcd_map = 2): ntri * splitk <= #CUs
 // persistent workgroups, splitk in {1, 2, 4, 8} k-streams, each on 8 / splitk XCDs (DESIGN_HISTORY.md 4.1).
 hipError_t launch_gram_packed_lockstep(const int8_t* p, int fmt, int64_t nv, int32_t n, int32_t* s32, int num_cu,
@@ -549,33 +420,21 @@ hipError_t launch_gram_packed_lockstep(const int8_t* p, int fmt, int64_t nv, int
   const int g = kNumXcd / splitk;
   const int per = (ntri + g - 1) / g;
   const dim3 grid((unsigned)(per * kNumXcd)), block(512);
-  int map = 2;
-#ifdef PCOA_EXPERIMENTS
-  if (g_lockstep_map == 3 && ntile == 10 && splitk == 2) map = 3;
-#endif
   if (fmt == 1)
     hipLaunchKernelGGL((gram_packed_kernel<1, 2, 2, 4, 3, true, 2>), grid, block, 0, stream, p, npad, nstages, n, ntile, ntri,
-                       splitk, stages_per, s32, map, skip, GramStrip{});
+                       splitk, stages_per, s32, 2, skip, GramStrip{});
   else
     hipLaunchKernelGGL((gram_packed_kernel<0, 2, 2, 4, 3, true, 2>), grid, block, 0, stream, p, npad, nstages, n, ntile, ntri,
-                       splitk, stages_per, s32, map, skip, GramStrip{});
+                       splitk, stages_per, s32, 2, skip, GramStrip{});
   return hipGetLastError();
 }
 
 hipError_t launch_gram_packed(const int8_t* p, int fmt, int64_t nv, int32_t n, int32_t* s32, int num_cu,
                               hipStream_t stream, int* splitk_out, const int32_t* skip, GramStrip strip) {
   if (nv <= 0) return hipSuccess;
-  // Shipped schedule: ping-pong, 4 k-blocks per stage, 3-stage ring, two MFMAs behind the phase barrier ("243").  The
-  // other schedules of DESIGN_HISTORY.md 4.1 / 4.2 (PCOA_GRAM_I8_CFG = 43 | 44 | 143 | 144 | 443) only exist in a library built
-  // with -DPCOA_EXPERIMENTS.
-  int cfg = 243;
-#ifdef PCOA_EXPERIMENTS
-  {
-    const int t = debug_knobs().gram_cfg;
-    if (t == 43 || t == 44 || t == 143 || t == 144 || t == 443) cfg = t;
-  }
-#endif
-  const int skb = (cfg % 100) / 10;
+  // The schedule: ping-pong, 4 k-blocks per stage, 3-stage ring, two MFMAs behind the phase barrier ("243" in
+  // DESIGN_HISTORY.md 4.1 / 4.2, measured 1.218 (LEFT 2) / 1.218 (4) / 1.236 (0) ms per 10^6 variants).
+  const int skb = 4;
   const int npad = (int)gram_packed_npad(n);
   const int ntile = npad / TJ;
   int64_t ntri64 = (int64_t)ntile * (ntile + 1) / 2;
@@ -590,7 +449,6 @@ hipError_t launch_gram_packed(const int8_t* p, int fmt, int64_t nv, int32_t n, i
   // one 512-thread workgroup per CU is resident; aim at ~7 work units per CU, >= 1024 variants each
   const int64_t target = (int64_t)(num_cu > 0 ? num_cu : 256) * 7;
   int64_t splitk = (target + ntri - 1) / ntri;
-  if (debug_knobs().gram_splitk > 0) splitk = debug_knobs().gram_splitk;  // experiment hook
   const int64_t max_by_work = nstages * skb / 64;
   if (splitk > max_by_work) splitk = max_by_work;
   if (splitk < 1) splitk = 1;
@@ -604,26 +462,12 @@ hipError_t launch_gram_packed(const int8_t* p, int fmt, int64_t nv, int32_t n, i
   if (nblocks > 0x7fffffffLL) return hipErrorInvalidValue;
   if (splitk_out) *splitk_out = (int)splitk;
   const dim3 grid((unsigned)nblocks), block(512);
-#define PCOA_LAUNCH_I8(SKB_, NST_, PP_, LEFT_)                                                                            \
-  do {                                                                                                          \
-    if (fmt == 1)                                                                                               \
-      hipLaunchKernelGGL((gram_packed_kernel<1, 2, 2, SKB_, NST_, PP_, LEFT_>), grid, block, 0, stream, p, npad, nstages, n, ntile, \
-                         ntri, (int)splitk, stages_per, s32, xcd_map, skip, strip);                             \
-    else                                                                                                        \
-      hipLaunchKernelGGL((gram_packed_kernel<0, 2, 2, SKB_, NST_, PP_, LEFT_>), grid, block, 0, stream, p, npad, nstages, n, ntile, \
-                         ntri, (int)splitk, stages_per, s32, xcd_map, skip, strip);                             \
-  } while (0)
-  switch (cfg) {
-#ifdef PCOA_EXPERIMENTS
-    case 44: PCOA_LAUNCH_I8(4, 4, false, 0); break;
-    case 144: PCOA_LAUNCH_I8(4, 4, true, 0); break;
-    case 43: PCOA_LAUNCH_I8(4, 3, false, 0); break;
-    case 143: PCOA_LAUNCH_I8(4, 3, true, 0); break;
-    case 443: PCOA_LAUNCH_I8(4, 3, true, 4); break;
-#endif
-    default: PCOA_LAUNCH_I8(4, 3, true, 2); break;  // measured: 1.218 (LEFT 2) / 1.218 (4) / 1.236 (0) ms per 10^6 variants
-  }
-#undef PCOA_LAUNCH_I8
+  if (fmt == 1)
+    hipLaunchKernelGGL((gram_packed_kernel<1, 2, 2, 4, 3, true, 2>), grid, block, 0, stream, p, npad, nstages, n, ntile, ntri,
+                       (int)splitk, stages_per, s32, xcd_map, skip, strip);
+  else
+    hipLaunchKernelGGL((gram_packed_kernel<0, 2, 2, 4, 3, true, 2>), grid, block, 0, stream, p, npad, nstages, n, ntile, ntri,
+                       (int)splitk, stages_per, s32, xcd_map, skip, strip);
   return hipGetLastError();
 }
 

@@ -103,10 +103,9 @@ static hipError_t launch_pack_operand(const pcoa_ctx* c, const void* x, int is_u
                                hipStream_t s, int64_t kb, int ring_wgs = 0) {
   // ring_wgs > 0: the persistent ring pre-pass of the co-resident fp32 pipeline (fp32 tile, k-bits operand, ring_ok checked)
   if (ring_wgs > 0 && c->op_fmt == 2 && !is_u8)
-    return launch_pack_kbits_ring(static_cast<const float*>(x), ld, nv, c->n, dst, flag, s, kb / 4, ring_wgs,
-                                  8 + 1000 * std::max(0, debug_knobs().kbits_ring_prio));
+    return launch_pack_kbits_ring(static_cast<const float*>(x), ld, nv, c->n, dst, flag, s, kb / 4, ring_wgs);
   if (ring_wgs > 0 && c->op_fmt == 2 && is_u8)
-    return launch_pack_kbits_ring_u8(static_cast<const uint8_t*>(x), ld, nv, c->n, dst, flag, s, kb / 4, ring_wgs, 8);
+    return launch_pack_kbits_ring_u8(static_cast<const uint8_t*>(x), ld, nv, c->n, dst, flag, s, kb / 4, ring_wgs);
   return c->op_fmt == 2 ? launch_pack_kbits(x, is_u8, ld, nv, c->n, dst, flag, s, kb / 4)
                         : launch_pack_fp4(x, is_u8, ld, nv, c->n, dst, flag, s, kb);
 }
@@ -134,10 +133,8 @@ static int fork_to(pcoa_ctx* c, hipStream_t side) {
   if (side == c->stream) return PCOA_OK;
   // an idle ctx stream has nothing to wait for: no marker + barrier packet in front of every pre-pass and contraction of the
   // steady state (they cost 7 % of the fp32 step, profiles/r04w)
-  if (debug_knobs().fork_lazy != 0) {
-    if (hipStreamQuery(c->stream) == hipSuccess) return PCOA_OK;
-    (void)hipGetLastError();
-  }
+  if (hipStreamQuery(c->stream) == hipSuccess) return PCOA_OK;
+  (void)hipGetLastError();
   HIP_TRY(c, hipEventRecord(c->ev_fork, c->stream));
   HIP_TRY(c, hipStreamWaitEvent(side, c->ev_fork, 0));
   return PCOA_OK;
@@ -237,9 +234,8 @@ int fp4_setup(pcoa_ctx* c) {
   // is a real share of the step, up to kCoresideMaxNpad: +25 % at N = 3,072, +30 % at 4,096, +23 % at 8,192 over the serial
   // order, which is what these N had before, +8 .. 9 % at N = 10,240 .. 16,384 where the contraction dominates
   // (profiles/r03zi_coreside_large_n.txt, r03zn_coreside_n10k_16k.txt)
-  const int64_t cores_max = k.kbits_coreside_max_npad > 0 ? k.kbits_coreside_max_npad : kCoresideMaxNpad;
   const bool cores_shape = !c->is_strip && c->num_cu >= 64 && c->op_fmt == 2 && k.kbits_coreside != 0 &&
-                           gram_packed_npad(c->n) >= 5 * 256 && gram_packed_npad(c->n) <= cores_max;
+                           gram_packed_npad(c->n) >= 5 * 256 && gram_packed_npad(c->n) <= kCoresideMaxNpad;
   want = want || cores_shape;
   if (k.pipeline == 0) want = false;
   if (k.pipeline == 1) want = !c->is_strip && (lsh > 0 || cores_shape);
@@ -250,7 +246,6 @@ int fp4_setup(pcoa_ctx* c) {
     if (e1 == hipSuccess && e2 == hipSuccess) {
       c->pipe_ok = true;
       c->pipe_gram_cus = half;
-      if (c->op_fmt == 2 && k.kbits_pipe_wgs >= 8 && k.kbits_pipe_wgs <= c->num_cu) c->pipe_gram_cus = k.kbits_pipe_wgs / 8 * 8;
       c->fb_count = 2;
       // k-bits operand: the two kernels SHARE every CU instead (r03s .. r03u): the contraction (224 VGPRs per wave, 24 KiB
       // of LDS) takes the whole chip -- lock-step where the shape fits, so that the 36 CUs it leaves at N = 2504 run
@@ -263,13 +258,7 @@ int fp4_setup(pcoa_ctx* c) {
         c->coreside_mode = (ls > 0 && gram_lockstep_workgroups(c->n, ls) * 5 >= c->num_cu * 4 && k.kbits_mode != 4) ? 2 : c->kbits_mode;
         if (k.kbits_mode == 2 && ls > 0) c->coreside_mode = 2;
         c->pipe_gram_cus = c->num_cu;
-        // (harness knob: the co-resident contraction as an even split over fewer workgroups -- the CUs it leaves run
-        // pre-pass waves only)
-        if (k.kbits_pipe_wgs >= 8 && k.kbits_pipe_wgs <= c->num_cu) {
-          c->pipe_gram_cus = k.kbits_pipe_wgs / 8 * 8;
-          c->coreside_mode = 4;
-        }
-        c->ring_wgs = (k.kbits_ring_wgs > 0) ? k.kbits_ring_wgs : 2 * c->num_cu;
+        c->ring_wgs = 2 * c->num_cu;
       }
     } else {
       (void)hipGetLastError();
@@ -318,8 +307,7 @@ static int fp4_launch(pcoa_ctx* c, int bi, bool overlapped, int side_kind = 1) {
       const int mode = !side ? c->kbits_mode : !c->coreside ? 4 : (side_kind == 3 ? c->kbits_mode : c->coreside_mode);
       // The one-wave-per-SIMD kernel (512 registers per wave, gram_kbits_w4.hip) wherever the contraction has its CUs to
       // itself; beside the ring pre-pass the two-waves-per-SIMD kernel held to 224 registers, which leaves room for it.
-      const int w4 = debug_knobs().kbits_w4;
-      const bool use_w4 = w4 != 0 && (!(side && c->coreside) || w4 == 2);
+      const bool use_w4 = debug_knobs().kbits_w4 != 0 && !(side && c->coreside);
       auto launch = [&](int m) {
         return use_w4 ? launch_gram_kbits_w4(b.p, b.kb * 32, c->n, c->s32, cus, gs, m, skip, strip_of(c), debug_knobs().kbits_w4_diag)
                       : launch_gram_kbits(b.p, b.kb * 32, c->n, c->s32, cus, gs, m, skip, strip_of(c));
@@ -520,8 +508,8 @@ int fp4_reserve(pcoa_ctx* c, int64_t kb, int64_t chunk_variants, int side_kind, 
         // head start for the contraction that becomes runnable when the pre-pass queued in front of this one ends: its
         // workgroups must find the CUs empty, the pre-pass then takes the CUs that are left (fp4_setup)
         if ((rc = fork_to(c, c->pack_stream)) != PCOA_OK) return rc;
-        const int hs = debug_knobs().headstart_us;
-        if (hs != 0) HIP_TRY(c, launch_delay_us(c->pack_stream, hs > 0 ? hs : 10));
+        constexpr int kHeadstartUs = 10;
+        HIP_TRY(c, launch_delay_us(c->pack_stream, kHeadstartUs));
       }
       (void)hipGetLastError();
     }
@@ -591,8 +579,7 @@ static int packed_chunk(pcoa_ctx* c, const void* x_chunk, int is_u8, int64_t cur
       // of 128 variants x 1,024 samples
       if (c->coreside && deferrable_u8 && ps == c->pack_stream) {
         const int64_t units = (kb / 4) * ((gram_packed_npad(c->n) + 1023) / 1024);
-        const int cap = debug_knobs().u8_ring_wgs > 0 ? debug_knobs().u8_ring_wgs : c->num_cu;   // (PCOA_U8_RING_WGS: harness knob)
-        if (units >= 64) ring_wgs = (int)std::max<int64_t>(1, std::min<int64_t>(cap, units / 16));
+        if (units >= 64) ring_wgs = (int)std::max<int64_t>(1, std::min<int64_t>(c->num_cu, units / 16));
       }
       hipError_t e = launch_pack_operand(c, x_chunk, is_u8, ld, cur, dst, flag, ps, kb, ring_wgs);
       if (e != hipSuccess) return hip_fail(c, e, "operand pre-pass launch");

@@ -1,7 +1,6 @@
 // pack_kbits.hip -- every pre-pass into the k-bits operand K1 (kbits_layout.h: one BIT per genotype): fp32 / uint8 tiles
 // (plain, small-call, the two persistent LDS-DMA-ring forms, 8-byte loads), carrier bitsets (32 x 32 bit transposes) and
 // CSR carrier lists (global atomics, or through the LDS).  The contractions are gram_kbits.hip and gram_kbits_w4.hip.
-#include <cstdlib>
 #include <type_traits>
 
 #include "gram_common.h"
@@ -636,11 +635,10 @@ hipError_t launch_pack_kbits(const void* x, int is_u8, int64_t ld, int64_t nv, i
 }
 
 // Persistent LDS-DMA-ring pre-pass (fp32 tile, pack_fp4_ring_ok(x, ld)): at most `wgs` workgroups of 4 waves.
-// ring = R + 100 * nontemporal + 1000 * (waves at s_setprio 3); the product uses 8 (R = 8 rows in flight per wave, default
-// cache policy: beside the contraction, with two workgroups per CU, 2.19 vs 2.25 ms per step for nontemporal loads --
-// which win when the kernel has the chip to itself or one workgroup per CU, profiles/r03zl), the rest are harness knobs.
+// R = 8 rows in flight per wave, default cache policy: beside the contraction, with two workgroups per CU, 2.19 vs 2.25 ms
+// per step for nontemporal loads -- which win when the kernel has the chip to itself or one workgroup per CU (profiles/r03zl).
 hipError_t launch_pack_kbits_ring(const float* x, int64_t ld, int64_t nv, int32_t n, int8_t* p, int32_t* flag,
-                                  hipStream_t stream, int64_t nblk_out, int wgs, int ring) {
+                                  hipStream_t stream, int64_t nblk_out, int wgs) {
   if (nv <= 0) return hipSuccess;
   if (!pack_fp4_ring_ok(x, ld) || nv > 0x3fffffffLL) return hipErrorInvalidValue;
   const int npad = (int)gram_packed_npad(n);
@@ -650,40 +648,8 @@ hipError_t launch_pack_kbits_ring(const float* x, int64_t ld, int64_t nv, int32_
   uint32_t* pw = reinterpret_cast<uint32_t*>(p);
   const int64_t most = (units + 3) / 4;
   const dim3 grid((unsigned)(wgs > 0 && wgs < most ? wgs : most)), block(256);
-#define PCOA_RINGK(R_, AUX_, PRIO_)                                                                                        \
-  hipLaunchKernelGGL((pack_kbits_ring_kernel<R_, AUX_, PRIO_>), grid, block, 4 * R_ * 1024, stream, x, ld, (int)nv, n, npad, \
-                     (int)units, pw, flag)
-  ring %= 10000;  // (+ 10000 selected the natural bit order while a permuted form existed, r03w)
-#ifdef PCOA_EXPERIMENTS
-  if (ring >= 5000) {  // 5000 + aux: R = 8, the cache-policy bits of the LDS-DMA given directly (sc0 = 1, nt = 2, sc1 = 16)
-    switch (ring - 5000) {
-      case 1: PCOA_RINGK(8, 1, 0); break;
-      case 3: PCOA_RINGK(8, 3, 0); break;
-      case 16: PCOA_RINGK(8, 16, 0); break;
-      case 17: PCOA_RINGK(8, 17, 0); break;
-      case 18: PCOA_RINGK(8, 18, 0); break;
-      default: PCOA_RINGK(8, 0, 0); break;
-    }
-    return hipGetLastError();
-  }
-  const int R = ring % 100, nt = (ring / 100) % 10, prio = ring / 1000;
-#define PCOA_RINGK2(R_)                                                       \
-  do {                                                                        \
-    if (nt && prio) PCOA_RINGK(R_, 2, 3);                                     \
-    else if (nt) PCOA_RINGK(R_, 2, 0);                                        \
-    else if (prio) PCOA_RINGK(R_, 0, 3);                                      \
-    else PCOA_RINGK(R_, 0, 0);                                                \
-  } while (0)
-  if (R == 8) PCOA_RINGK2(8);
-  else if (R == 32) PCOA_RINGK2(32);
-  else PCOA_RINGK2(16);
-#undef PCOA_RINGK2
-#else
-  if ((ring / 100) % 10) PCOA_RINGK(8, 2, 0);
-  else if (ring / 1000) PCOA_RINGK(8, 0, 3);
-  else PCOA_RINGK(8, 0, 0);
-#endif
-#undef PCOA_RINGK
+  hipLaunchKernelGGL((pack_kbits_ring_kernel<8, 0, 0>), grid, block, 4 * 8 * 1024, stream, x, ld, (int)nv, n, npad, (int)units, pw,
+                     flag);
   return hipGetLastError();
 }
 
@@ -692,7 +658,7 @@ bool pack_u8_ring_ok(const void* x, int64_t ld) {
   return ((ld & 7) == 0) && ld >= 16 && ((reinterpret_cast<uintptr_t>(x) & 7) == 0);
 }
 hipError_t launch_pack_kbits_ring_u8(const uint8_t* x, int64_t ld, int64_t nv, int32_t n, int8_t* p, int32_t* flag,
-                                     hipStream_t stream, int64_t nblk_out, int wgs, int ring) {
+                                     hipStream_t stream, int64_t nblk_out, int wgs) {
   if (nv <= 0) return hipSuccess;
   if (!pack_u8_ring_ok(x, ld) || nv > 0x3fffffffLL || ld > 0x3fffffffLL) return hipErrorInvalidValue;
   const int npad = (int)gram_packed_npad(n);
@@ -702,11 +668,8 @@ hipError_t launch_pack_kbits_ring_u8(const uint8_t* x, int64_t ld, int64_t nv, i
   uint32_t* pw = reinterpret_cast<uint32_t*>(p);
   const int64_t most = (units + 3) / 4;
   const dim3 grid((unsigned)(wgs > 0 && wgs < most ? wgs : most)), block(256);
-  // 8 rows in flight per wave; ring / 100 odd = nontemporal loads
-  if ((ring / 100) % 10)
-    hipLaunchKernelGGL((pack_u8_kbits_ring_kernel<8, 2>), grid, block, 32 << 10, stream, x, ld, (int)nv, n, npad, (int)units, pw, flag);
-  else
-    hipLaunchKernelGGL((pack_u8_kbits_ring_kernel<8, 0>), grid, block, 32 << 10, stream, x, ld, (int)nv, n, npad, (int)units, pw, flag);
+  // 8 rows in flight per wave, default cache policy
+  hipLaunchKernelGGL((pack_u8_kbits_ring_kernel<8, 0>), grid, block, 32 << 10, stream, x, ld, (int)nv, n, npad, (int)units, pw, flag);
   return hipGetLastError();
 }
 
@@ -733,11 +696,7 @@ hipError_t launch_densify_csr_kbits(const int32_t* idx_dev, const int64_t* offs_
   if (nv <= 0) return hipSuccess;
   const int npad = (int)gram_packed_npad(n);
   // the LDS form while a block of 128 variants x npad samples (16 B per sample) + its offsets fit 128 KiB of LDS
-  // (npad <= 8,160); PCOA_CSR_GLOBAL_ATOMICS=1 gives the r04 form back (one wave per row, global atomic OR)
-  static const bool force_global = [] {
-    const char* v = std::getenv("PCOA_CSR_GLOBAL_ATOMICS");
-    return v && std::atoi(v) != 0;
-  }();
+  // (npad <= 8,160); beyond that the r04 form (one wave per row, global atomic OR)
   const size_t lds = (size_t)npad * 16 + 132 * sizeof(int32_t);
   // what the device lets ONE workgroup have (sharedMemPerBlockOptin; 160 KiB on gfx950): asked once per device
   static thread_local int lds_dev = -1;
@@ -749,7 +708,7 @@ hipError_t launch_densify_csr_kbits(const int32_t* idx_dev, const int64_t* offs_
     lds_dev = dev;
     (void)hipGetLastError();
   }
-  bool use_lds = !force_global && lds <= 128 * 1024 && lds <= lds_optin && nblk_out > 0 && nblk_out <= 0x7fffffffLL;
+  bool use_lds = lds <= 128 * 1024 && lds <= lds_optin && nblk_out > 0 && nblk_out <= 0x7fffffffLL;
   constexpr int T = 512;
   if (use_lds && lds > 64 * 1024) {  // opt in to more than 64 KiB of dynamic LDS (per device: cheap enough to repeat)
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(densify_csr_kbits_lds_kernel<T>),

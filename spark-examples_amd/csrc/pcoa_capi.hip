@@ -108,7 +108,6 @@ static int create_impl(pcoa_ctx** out, int32_t n_samples, int32_t device_ordinal
   c->packed_mode = (flags & PCOA_FLAG_GRAM_I8_MFMA) ? 2 : (flags & PCOA_FLAG_GRAM_FP4_MFMA) ? 3 : 0;
   c->op_fmt = (flags & PCOA_FLAG_OPERAND_FP4) ? 1 : 2;
   const DebugKnobs& knobs = debug_knobs();
-  if (knobs.operand == 1 || knobs.operand == 2) c->op_fmt = knobs.operand;
   if (knobs.gram_kernel == 1) c->use_i8 = false;
   if (knobs.gram_kernel == 2) { c->use_i8 = true; c->packed_mode = 2; }
   if (knobs.gram_kernel == 3) { c->use_i8 = true; c->packed_mode = 3; }

@@ -19,7 +19,7 @@ constexpr int kNumXcd = 8;    // MI355X: block b is dispatched to XCD b % 8 (spe
 
 // ---- debug / experiment knobs -------------------------------------------------------------------
 // Every environment variable the library looks at, read ONCE (first use) into this struct; nothing else calls getenv.
-// None is needed for normal use; DESIGN_HISTORY.md "Environment hooks" documents them.
+// None is needed for normal use: they exist for tests and measurements; include/pcoa.h lists them.
 struct DebugKnobs {
   int gram_kernel = -1;            // PCOA_GRAM_KERNEL = auto | fp4 | i8 | f32  -> 0 | 3 | 2 | 1 (overrides the create flags)
   int64_t pack_chunk = 0;          // PCOA_DEBUG_PACK_CHUNK: variants per pre-pass launch (tests: multi-chunk paths)
@@ -27,27 +27,15 @@ struct DebugKnobs {
   int64_t fold_threshold = 0;      // PCOA_DEBUG_FOLD_THRESHOLD: int32 -> int64 fold (tests: the fold / int64 all-reduce)
   int pipeline = -1;               // PCOA_PIPELINE = 0 | 1: force the two-stream fp32 pipeline off / on where it fits
   int explicit_center = 0;         // PCOA_EXPLICIT_CENTER: materialise B for the Lanczos path
-  int lanczos_first_check = 0;     // PCOA_LANCZOS_FIRST_CHECK: Krylov dimension of the first Ritz check
-  int lanczos_trace = 0;           // PCOA_DEBUG_LANCZOS: print the Ritz estimates
-  int gram_cfg = 0;                // PCOA_GRAM_I8_CFG: contraction schedule (library built with -DPCOA_EXPERIMENTS only)
-  int gram_splitk = 0;             // PCOA_GRAM_I8_SPLITK: split-K of the legacy launch
   int lockstep = -1;               // PCOA_GRAM_LOCKSTEP = 0 | 1: lock-step contraction launch off / on where it fits
   int guard = 0;                   // PCOA_DEBUG_GUARD = 1 | 2: every device buffer ends (1) / starts (2) at an unmapped page
-  int operand = 0;                 // PCOA_OPERAND = fp4 | bits -> 1 | 2: operand of the binary-tile contraction (0 = default)
-  int kbits_mode = -1;             // PCOA_KBITS_MODE = 0 | 2 | 4: launch form of the k-bits contraction (whole chip)
-  int kbits_pipe_wgs = 0;          // PCOA_KBITS_PIPE_WGS: workgroups of the k-bits contraction beside the fp32 pre-pass
+  int kbits_mode = -1;             // PCOA_KBITS_MODE = 0 | 2 | 4 | 5: launch form of the k-bits contraction (whole chip)
   int symv_sym_min_n = 0;          // PCOA_SYMV_SYM_MIN_N: smallest N whose Lanczos mat-vec reads only the upper triangle of S (default 16384)
   int csr_legacy = 0;              // PCOA_CSR_LEGACY = 1: pcoa_accumulate_calls through the host-validated r03 path
-  int kbits_w4 = -1;               // PCOA_KBITS_W4 = 0 | 1 | 2: one-wave-per-SIMD contraction (gram_kbits_w4.hip): 0 never, 1 wherever the kernel has its CUs to itself (default), 2 also beside the ring pre-pass
+  int kbits_w4 = -1;               // PCOA_KBITS_W4 = 0 | 1: one-wave-per-SIMD contraction (gram_kbits_w4.hip): 0 never, 1 wherever the kernel has its CUs to itself (default)
   int kbits_w4_diag = -1;          // PCOA_KBITS_W4_DIAG: 0 = diagonal tiles as in r04a (one wave idles), 1..16 = wave roles on diagonal tiles with this cost (of 16) in the even split; default 11
   int kbits_coreside = -1;         // PCOA_KBITS_CORESIDE = 0 | 1: fp32 pipeline with pre-pass and contraction on the SAME CUs (ring pre-pass)
-  int kbits_ring_prio = 0;         // PCOA_KBITS_RING_PRIO = 1: the ring pre-pass's waves at s_setprio 3 (harness knob)
-  int kbits_ring_wgs = 0;          // PCOA_KBITS_RING_WGS: workgroups of the ring pre-pass beside a contraction (default 2 per CU)
-  int u8_ring_wgs = 0;             // PCOA_U8_RING_WGS: workgroups of the uint8 ring pre-pass beside a contraction (default one per CU)
-  int fork_lazy = 1;               // PCOA_FORK_LAZY = 0: a side stream waits on the ctx stream even when that is idle (r03 behaviour: a barrier packet in front of every pre-pass and contraction -- 2.26 vs 2.11 ms per fp32 step, profiles/r04w)
   int bits_pipeline = 0;           // PCOA_BITS_PIPELINE = 1: bitset tiles through the co-resident pipeline as in r03 / r04 (default: transpose and contraction in series, the contraction as the one-wave-per-SIMD kernel)
-  int headstart_us = -1;           // PCOA_HEADSTART_US: the contraction's head start over the next pre-pass (default 10; 0 = none)
-  int kbits_coreside_max_npad = 0; // PCOA_KBITS_CORESIDE_MAX_NPAD: largest padded sample count the co-resident pipeline is used for
   int lanczos_band_mmax = 0;       // PCOA_LANCZOS_BAND_MMAX: basis size of the band iteration (tests: forces thick restarts)
   int lanczos_band = 1;            // PCOA_LANCZOS_BAND = 0: no band-Lanczos fallback (r05 behaviour); 2: ONLY the band iteration (tests)
   int synth_tile = 0;              // PCOA_SYNTH_TILE = 1: pcoa_accumulate_synthetic through the fp32 staging tile + pre-pass (r05 path) instead of generating the k-bits operand directly
@@ -106,10 +94,6 @@ hipError_t launch_pack_fp4(const void* x, int is_u8, int64_t ld, int64_t nv, int
                            hipStream_t stream, int64_t nkb_out = 0);
 // fp32 tiles the LDS-DMA-ring pre-passes take: ld % 4 == 0 and a 16-byte aligned base
 bool pack_fp4_ring_ok(const void* x, int64_t ld);
-#ifdef PCOA_EXPERIMENTS
-hipError_t launch_pack_fp4_ring(const float* x, int64_t ld, int64_t nv, int32_t n, int8_t* p, int32_t* flag,
-                                hipStream_t stream, int64_t nkb_out, int wgs, int nt);
-#endif
 
 // contraction of an FP4 (fmt 1) / int8 (fmt 0) operand (gram_packed.hip)
 // skip (optional, device): the launch does nothing when *skip != 0 -- the auto mode's device-side predicate (a pre-pass
@@ -119,9 +103,6 @@ hipError_t launch_gram_packed(const int8_t* p, int fmt, int64_t nv, int32_t n, i
                               GramStrip strip = GramStrip{});
 hipError_t launch_gram_packed_lockstep(const int8_t* p, int fmt, int64_t nv, int32_t n, int32_t* s32, int num_cu,
                                        hipStream_t stream, const int32_t* skip = nullptr);
-#ifdef PCOA_EXPERIMENTS
-extern int g_lockstep_map;  // harness knob (tools/exp_overlap.hip): 3 selects the balanced deal where it applies
-#endif
 
 // pre-passes -> k-bits operand (pack_kbits.hip): K1[V/128][Npad][4 words], one BIT per genotype, expanded to FP4 in
 // registers by the contraction.  nblk_out = blocks of 128 variants to write (the tail beyond nv is zero-filled).
@@ -131,14 +112,14 @@ hipError_t launch_transpose_bits_kbits(const uint32_t* bits, int64_t ld_words, i
                                        hipStream_t stream, int64_t nblk_out);
 hipError_t launch_densify_csr_kbits(const int32_t* idx_dev, const int64_t* offs_dev, int64_t nv, int64_t offs_base,
                                     int8_t* p, int32_t n, int32_t* flag, hipStream_t stream, int64_t nblk_out);
-// persistent LDS-DMA-ring form of the fp32 -> k-bits pre-pass (needs pack_fp4_ring_ok): <= wgs workgroups; ring: 8 = 8 rows
-// in flight per wave, default cache policy (what the library uses), 108 = nontemporal loads
+// persistent LDS-DMA-ring form of the fp32 -> k-bits pre-pass (needs pack_fp4_ring_ok): <= wgs workgroups, 8 rows in flight
+// per wave, default cache policy
 hipError_t launch_pack_kbits_ring(const float* x, int64_t ld, int64_t nv, int32_t n, int8_t* p, int32_t* flag,
-                                  hipStream_t stream, int64_t nblk_out, int wgs, int ring);
+                                  hipStream_t stream, int64_t nblk_out, int wgs);
 // the uint8 form: units of 128 variants x 1,024 samples, one wave per SIMD (ld % 8 == 0, 8-byte aligned base)
 bool pack_u8_ring_ok(const void* x, int64_t ld);
 hipError_t launch_pack_kbits_ring_u8(const uint8_t* x, int64_t ld, int64_t nv, int32_t n, int8_t* p, int32_t* flag,
-                                     hipStream_t stream, int64_t nblk_out, int wgs, int ring);
+                                     hipStream_t stream, int64_t nblk_out, int wgs);
 
 // contraction of a k-bits operand, two waves per SIMD (gram_kbits.hip); mode 0 = split-K launch, 2 = lock-step, 4 = even split
 // of the (tile, stage) units over num_cu workgroups

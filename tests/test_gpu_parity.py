@@ -1355,6 +1355,32 @@ np.savez(sys.argv[1], same=np.array_equal(got, int_gram(x)), even=t["evensplit_l
     assert bool(r["same"]) and int(r["even"]) >= 1
 
 
+@pytest.mark.parametrize("knob", ["PCOA_KBITS_W4_DIAG", "PCOA_KBITS_W4"])
+def test_idle_wave_form_and_two_wave_kernel_of_the_even_split_stay_exact(knob, tmp_path):
+    """Two launch forms that stay in the library behind a knob and that nothing else runs on a bitset tile: PCOA_KBITS_W4_DIAG=0
+    (diagonal tiles of the one-wave-per-SIMD kernel with the wave below the diagonal idle, role 4: what bench.py's roofline
+    share is measured with) and PCOA_KBITS_W4=0 (the two-waves-per-SIMD kernel alone on the chip).  N = 301 gives two tile rows
+    (diagonal and off-diagonal workgroup tiles, N no multiple of 4), 1,153 variants nine full blocks of 128 and a ragged tail."""
+    code = r"""
+import sys, numpy as np, importlib
+sys.path.insert(0, %r); sys.path.insert(0, %r)
+from conftest import int_gram
+P = importlib.import_module("spark-examples_amd"); ingest = importlib.import_module("spark-examples_amd.ingest")
+rng = np.random.default_rng(7)
+n, v = 301, 1153
+x = (rng.random((v, n)) < 0.12).astype(np.uint8)
+with P.PcoaEngine(n) as eng:
+    eng.accumulate_bits(ingest.pack_bits(x))
+    got = eng.gram()
+    t = eng.timings()
+np.savez(sys.argv[1], same=np.array_equal(got, int_gram(x)), even=t["evensplit_launches"])
+""" % (ROOT, os.path.join(ROOT, "tests"))
+    out = str(tmp_path / "w4.npz")
+    subprocess.check_call([sys.executable, "-c", code, out], env=dict(os.environ, **{knob: "0"}))
+    r = np.load(out)
+    assert bool(r["same"]) and int(r["even"]) >= 1
+
+
 def test_bench_with_two_ranks_runs_its_multi_rank_path_end_to_end(tmp_path):
     """bench.py --gpus 2 has never met a node: its multi-rank branch -- the self-spawn under torch.distributed.run, the sharded
     cohort, finalize -> reduction -> max-over-ranks timing, the telemetry the line must carry (VERDICT r05 Next 5) -- is run here

@@ -282,6 +282,37 @@ def test_similarity_matrix_stream_form_keeps_only_nonzero_keys():
     assert all(3 not in k for k in got) and (0, 0) in got and got[(0, 0)] == 6
 
 
+def test_environment_knobs_are_read_in_one_place_documented_and_exercised():
+    """Every environment variable of the library is read in csrc/devmem.hip (debug_knobs) and nowhere else, the set of names is
+    the set include/pcoa.h documents, and each name is set or named by a test, bench.py or a tool: a knob nobody exercises
+    selects a configuration nothing runs."""
+    csrc = os.path.join(ROOT, "spark-examples_amd", "csrc")
+    literal = re.compile(r'(?:getenv|\bnum)\("(PCOA_[A-Z0-9_]+)"\)')
+    read = set()
+    for f in sorted(os.listdir(csrc)):
+        if not f.endswith((".hip", ".h")):
+            continue
+        text = open(os.path.join(csrc, f)).read()
+        hits = len(re.findall(r"getenv\(", text)) + len(re.findall(r'\bnum\("PCOA_', text))
+        assert hits == 0 or f == "devmem.hip", "%s reads the environment (%d places)" % (f, hits)
+        if hits:
+            names = literal.findall(text)
+            assert len(names) == hits - 1, "one getenv inside the num() helper, a literal PCOA_ name everywhere else"
+            read.update(names)
+    header = open(os.path.join(ROOT, "include", "pcoa.h")).read()
+    block = re.search(r"/\* ---- environment knobs -+\n(.*?)\*/", header, re.S)
+    assert block and "for tests and measurements, not for users" in block.group(1).lower()
+    documented = re.findall(r"^ \*   (PCOA_[A-Z0-9_]+) ", block.group(1), re.M)
+    assert len(documented) == len(set(documented)) and set(documented) == read, sorted(read.symmetric_difference(documented))
+    users = [os.path.join(ROOT, "bench.py")]
+    for d in ("tests", "tools"):
+        for base, _, files in os.walk(os.path.join(ROOT, d)):
+            users += [os.path.join(base, f) for f in files if f.endswith((".py", ".sh", ".hip", ".cpp", ".h", ".md", ".txt"))]
+    corpus = "\n".join(open(u, errors="replace").read() for u in users)
+    unused = [k for k in sorted(read) if not re.search(r"\b%s\b" % k, corpus)]
+    assert not unused, "knobs no test, tool or bench.py names: %s" % unused
+
+
 def test_pack_bits_layout_is_the_one_pcoa_accumulate_bits_documents():
     """include/pcoa.h: sample i of variant v is bit (i & 31) of word bits[v * ld_words + (i >> 5)]."""
     ingest = load_pkg("ingest")

@@ -1,6 +1,6 @@
 // exp_bits.hip -- correctness + A/B harness of the k-bits operand (spark-examples_amd/csrc/pack_kbits.hip, gram_kbits.hip).
 //
-// On one MI355X, with the library's own kernels (their translation units are included, so the harness knobs reach them):
+// On one MI355X, with the library's own kernels (their translation units are included):
 //   1. small ragged shapes: every k-bits pre-pass (fp32 / uint8 / carrier bitsets / CSR) against a host-built operand, and the
 //      k-bits contraction (split-K, lock-step, even-split launches) against a host popcount Gram;
 //   2. BASELINE configs[1] size (2,504 samples x 2^20 variants): S of the k-bits path == S of the shipped FP4 path, bit for bit;
@@ -78,6 +78,27 @@ __global__ void diff_kernel(const uint32_t* a, const uint32_t* b, int64_t words,
 __global__ void delay_kernel(long long ticks) {
   const long long t0 = wall_clock64();
   while (wall_clock64() - t0 < ticks) __builtin_amdgcn_s_sleep(8);
+}
+
+// The ring pre-passes with nontemporal loads (AUX = 2): instantiations the library does not launch (it uses the default cache
+// policy beside the contraction, profiles/r03zl); same grid and LDS as launch_pack_kbits_ring / launch_pack_kbits_ring_u8.
+static hipError_t launch_ring(const float* x, int64_t ld, int64_t nv, int32_t n, int8_t* p, int32_t* flag, hipStream_t stream,
+                              int64_t nblk, int wgs, bool nt) {
+  if (!nt) return launch_pack_kbits_ring(x, ld, nv, n, p, flag, stream, nblk, wgs);
+  const int npad = (int)gram_packed_npad(n);
+  const int64_t units = nblk * (npad >> 8), most = (units + 3) / 4;
+  hipLaunchKernelGGL((pack_kbits_ring_kernel<8, 2, 0>), dim3((unsigned)(wgs > 0 && wgs < most ? wgs : most)), dim3(256), 32 << 10, stream,
+                     x, ld, (int)nv, n, npad, (int)units, reinterpret_cast<uint32_t*>(p), flag);
+  return hipGetLastError();
+}
+static hipError_t launch_ring_u8(const uint8_t* x, int64_t ld, int64_t nv, int32_t n, int8_t* p, int32_t* flag, hipStream_t stream,
+                                 int64_t nblk, int wgs, bool nt) {
+  if (!nt) return launch_pack_kbits_ring_u8(x, ld, nv, n, p, flag, stream, nblk, wgs);
+  const int npad = (int)gram_packed_npad(n);
+  const int64_t units = nblk * ((npad + 1023) >> 10), most = (units + 3) / 4;
+  hipLaunchKernelGGL((pack_u8_kbits_ring_kernel<8, 2>), dim3((unsigned)(wgs > 0 && wgs < most ? wgs : most)), dim3(256), 32 << 10, stream,
+                     x, ld, (int)nv, n, npad, (int)units, reinterpret_cast<uint32_t*>(p), flag);
+  return hipGetLastError();
 }
 
 static double now_ms() {
@@ -382,12 +403,12 @@ static int coreside_main(int n, int64_t v, int reps, int num_cu, unsigned long l
   CK(launch_pack_kbits(x, 0, ld, v, n, k1[0], flag, 0, nblk));
   CK(hipDeviceSynchronize());
   int bad = 0;
-  for (int ring : {108, 116, 8, 5016, 5018, 5001}) {
+  for (bool nt : {true, false}) {
     CK(hipMemset(k1[1], 0xa5, kbytes));
-    CK(launch_pack_kbits_ring(x, ld, v, n, k1[1], flag, 0, nblk, num_cu, ring));
+    CK(launch_ring(x, ld, v, n, k1[1], flag, 0, nblk, num_cu, nt));
     CK(hipDeviceSynchronize());
     const unsigned long long d = count_diff(k1[0], k1[1], (int64_t)kbytes, cnt);
-    std::printf("ring pre-pass (ring %d) operand vs pack_kbits operand: %s (%llu words differ)\n", ring, d ? "MISMATCH" : "identical", d);
+    std::printf("ring pre-pass (%s) operand vs pack_kbits operand: %s (%llu words differ)\n", nt ? "nontemporal" : "default policy", d ? "MISMATCH" : "identical", d);
     bad += d != 0;
   }
   {  // ragged small shape through the ring kernel
@@ -403,18 +424,17 @@ static int coreside_main(int n, int64_t v, int reps, int num_cu, unsigned long l
     hipLaunchKernelGGL(fill_kernel, dim3(1024), dim3(256), 0, 0, x2, v2, (int64_t)n2, ld2, 99u, 0x30000000u);
     CK(launch_pack_kbits(x2, 0, ld2, v2, n2, ka, flag, 0, nblk2));
     CK(hipMemset(kb, 0x5a, (size_t)nblk2 * npad2 * 16));
-    CK(launch_pack_kbits_ring(x2, ld2, v2, n2, kb, flag, 0, nblk2, 7, 108));
+    CK(launch_ring(x2, ld2, v2, n2, kb, flag, 0, nblk2, 7, true));
     CK(hipDeviceSynchronize());
     const unsigned long long d = count_diff(ka, kb, nblk2 * npad2 * 16, cnt);
     std::printf("ring pre-pass, n=1000 v=4100, 7 workgroups: %s (%llu words differ)\n", d ? "MISMATCH" : "identical", d);
     bad += d != 0;
     CK(hipFree(x2)); CK(hipFree(ka)); CK(hipFree(kb));
   }
-  g_kbits_variant = 0;
   CK(hipMemset(sa, 0, (size_t)n * n * 4));
   CK(launch_gram_kbits(k1[0], v, n, sa, num_cu, 0, 4));
   {
-    CK(launch_pack_kbits_ring(x, ld, v, n, k1[1], flag, 0, nblk, 2 * num_cu, 108));
+    CK(launch_ring(x, ld, v, n, k1[1], flag, 0, nblk, 2 * num_cu, true));
     CK(hipMemset(sb, 0, (size_t)n * n * 4));
     CK(launch_gram_kbits(k1[1], v, n, sb, num_cu, 0, 2));
     CK(hipDeviceSynchronize());
@@ -423,30 +443,14 @@ static int coreside_main(int n, int64_t v, int reps, int num_cu, unsigned long l
     bad += d != 0;
   }
   CK(launch_pack_kbits(x, 0, ld, v, n, k1[1], flag, 0, nblk));
-  const char* vname[9] = {"shipped (256 VGPRs, ring 3)", "", "", "ring 4", "", "capped 224, ring 3", "capped 224, ring 4", "capped 224, ring 6", "ring 6"};
-  for (int var : {5, 6, 7, 8}) {
-    g_kbits_variant = var;
-    CK(hipMemset(sb, 0, (size_t)n * n * 4));
-    CK(launch_gram_kbits(k1[0], v, n, sb, num_cu, 0, 4));
-    CK(hipDeviceSynchronize());
-    const unsigned long long d = count_diff(sa, sb, (int64_t)n * n * 4, cnt);
-    std::printf("S(%s) vs S(shipped): %s (%llu entries differ)\n", vname[var], d ? "MISMATCH" : "bit-identical", d);
-    bad += d != 0;
-  }
-  g_kbits_variant = 0;
   const double mv = (double)v / 1e6;
   auto line = [&](const char* what, float ms) { std::printf("time  %-66s %8.3f ms  (%.3f ms per 10^6 variants)\n", what, ms, ms / mv); };
   line("pack_kbits<float> (shipped) alone", time_ms(0, reps, [&] { CK(launch_pack_kbits(x, 0, ld, v, n, k1[1], flag, 0, nblk)); }));
-  for (int ring : {108, 5000, 5016, 5001})
-    line(("ring pre-pass alone, 256 workgroups, ring " + std::to_string(ring)).c_str(),
-         time_ms(0, reps, [&] { CK(launch_pack_kbits_ring(x, ld, v, n, k1[1], flag, 0, nblk, num_cu, ring)); }));
-  line("ring pre-pass alone, 512 workgroups, ring 108", time_ms(0, reps, [&] { CK(launch_pack_kbits_ring(x, ld, v, n, k1[1], flag, 0, nblk, 2 * num_cu, 108)); }));
-  line("ring pre-pass alone, 512 workgroups, ring 116", time_ms(0, reps, [&] { CK(launch_pack_kbits_ring(x, ld, v, n, k1[1], flag, 0, nblk, 2 * num_cu, 116)); }));
-  for (int var : {0, 3, 5, 6, 7, 8}) {
-    g_kbits_variant = var;
-    line((std::string("contraction alone, even split 256: ") + vname[var]).c_str(), time_ms(0, reps, [&] { CK(launch_gram_kbits(k1[0], v, n, sb, num_cu, 0, 4)); }));
-  }
-  g_kbits_variant = 0;
+  for (int wgs : {num_cu, 2 * num_cu})
+    for (bool nt : {true, false})
+      line(("ring pre-pass alone, " + std::to_string(wgs) + " workgroups, " + (nt ? "nontemporal" : "default policy")).c_str(),
+           time_ms(0, reps, [&] { CK(launch_ring(x, ld, v, n, k1[1], flag, 0, nblk, wgs, nt)); }));
+  line("contraction alone, even split 256", time_ms(0, reps, [&] { CK(launch_gram_kbits(k1[0], v, n, sb, num_cu, 0, 4)); }));
 
   hipStream_t ps, gs;
   CK(hipStreamCreateWithFlags(&ps, hipStreamNonBlocking));
@@ -459,7 +463,7 @@ static int coreside_main(int n, int64_t v, int reps, int num_cu, unsigned long l
   }
   for (int k = 0; k < K; ++k)
     for (int j = 0; j < 2; ++j) { CK(hipEventCreate(&pe[k][j])); CK(hipEventCreate(&ge[k][j])); }
-  // ring < 0: the shipped pre-pass; gram_cus workgroups of contraction variant `var`
+  // ring < 0: the ordinary pre-pass, 0 / 1: the ring pre-pass with default policy / nontemporal loads
   int8_t* ka = nullptr;
   {
     hipMemAllocationProp prop = {};
@@ -482,7 +486,7 @@ static int coreside_main(int n, int64_t v, int reps, int num_cu, unsigned long l
   }
   int gram_mode = 4;
   bool aliased = false;
-  auto pipeline = [&](const char* what, int var, int gram_cus, int ring, int ring_wgs, int delay_us) {
+  auto pipeline = [&](const char* what, int gram_cus, int ring, int ring_wgs, int delay_us) {
     double best = 1e30, bp = 0, bg = 0;
     for (int round = 0; round < 3; ++round) {
       CK(hipDeviceSynchronize());
@@ -493,14 +497,12 @@ static int coreside_main(int n, int64_t v, int reps, int num_cu, unsigned long l
         if (k >= 1 && delay_us > 0) hipLaunchKernelGGL(delay_kernel, dim3(1), dim3(64), 0, ps, (long long)delay_us * 100);
         CK(hipEventRecord(pe[k][0], ps));
         if (ring < 0) CK(launch_pack_kbits(x, 0, ld, v, n, k1[b], flag, ps, nblk));
-        else CK(launch_pack_kbits_ring(x, ld, v, n, k1[b], flag, ps, nblk, ring_wgs, ring));
+        else CK(launch_ring(x, ld, v, n, k1[b], flag, ps, nblk, ring_wgs, ring == 1));
         CK(hipEventRecord(pe[k][1], ps));
         CK(hipEventRecord(packed[b], ps));
         CK(hipStreamWaitEvent(gs, packed[b], 0));
         CK(hipEventRecord(ge[k][0], gs));
-        g_kbits_variant = var;
         CK(launch_gram_kbits(aliased ? ka : k1[b], v, n, sb, gram_cus, gs, gram_mode));
-        g_kbits_variant = 0;
         CK(hipEventRecord(ge[k][1], gs));
         CK(hipEventRecord(consumed[b], gs));
       }
@@ -518,23 +520,18 @@ static int coreside_main(int n, int64_t v, int reps, int num_cu, unsigned long l
     std::printf("pipe  %-74s %8.3f ms per step (%.0f M variants/s); inside: pre-pass %.3f ms, contraction %.3f ms\n", what, best,
                 v / best / 1e3, bp, bg);
   };
-  pipeline("shipped: pack_kbits || even split 128 (disjoint CUs)", 0, 128, -1, 0, 10);
-  struct Cfg { const char* what; int var, mode, cus, ring, wgs; };
+  pipeline("pack_kbits || even split 128 (disjoint CUs)", 128, -1, 0, 10);
+  struct Cfg { const char* what; int mode, cus, ring, wgs; };
   const Cfg cfgs[] = {
-      {"CO-RESIDENT: ring R8 aux 0 (default policy), 512 wgs || lock-step 220", 5, 2, 256, 5000, 512},
-      {"CO-RESIDENT: ring R8 aux 2 (nt), 512 wgs || lock-step 220", 5, 2, 256, 108, 512},
-      {"CO-RESIDENT: ring R8 aux 1 (sc0), 512 wgs || lock-step 220", 5, 2, 256, 5001, 512},
-      {"CO-RESIDENT: ring R8 aux 3 (sc0 nt), 512 wgs || lock-step 220", 5, 2, 256, 5003, 512},
-      {"CO-RESIDENT: ring R8 aux 16 (sc1), 512 wgs || lock-step 220", 5, 2, 256, 5016, 512},
-      {"CO-RESIDENT: ring R8 aux 17 (sc0 sc1), 512 wgs || lock-step 220", 5, 2, 256, 5017, 512},
-      {"CO-RESIDENT: ring R8 aux 18 (sc1 nt), 512 wgs || lock-step 220", 5, 2, 256, 5018, 512},
-      {"CO-RESIDENT: ring R8 aux 0 (default policy), 512 wgs || lock-step 220 (again)", 5, 2, 256, 5000, 512},
-      {"CO-RESIDENT: ring R8 aux 0, 512 wgs || even split 256", 5, 4, 256, 5000, 512},
-      {"CO-RESIDENT: ring R8 aux 0, 768 wgs || lock-step 220", 5, 2, 256, 5000, 768},
+      {"CO-RESIDENT: ring default policy, 512 wgs || lock-step 220", 2, 256, 0, 512},
+      {"CO-RESIDENT: ring nontemporal, 512 wgs || lock-step 220", 2, 256, 1, 512},
+      {"CO-RESIDENT: ring default policy, 512 wgs || lock-step 220 (again)", 2, 256, 0, 512},
+      {"CO-RESIDENT: ring default policy, 512 wgs || even split 256", 4, 256, 0, 512},
+      {"CO-RESIDENT: ring default policy, 768 wgs || lock-step 220", 2, 256, 0, 768},
   };
   for (const Cfg& c : cfgs) {
     gram_mode = c.mode;
-    pipeline(c.what, c.var, c.cus, c.ring, c.wgs, 10);
+    pipeline(c.what, c.cus, c.ring, c.wgs, 10);
   }
   gram_mode = 4;
   std::printf("%s\n", bad ? "RESULT: FAILED" : "RESULT: ok");
@@ -583,7 +580,7 @@ static int aln_main(int n, int64_t v, int reps, int num_cu, unsigned long long* 
                 (ld * 4) % 128 ? "rows OFF the 128-byte lines" : "rows on 128-byte lines");
     // S through both forms
     for (int form = 0; form < 2; ++form) {
-      CK(launch_pack_kbits_ring(x, ld, v, n, k1[form], flag, 0, nblk, 2 * num_cu, 8));
+      CK(launch_pack_kbits_ring(x, ld, v, n, k1[form], flag, 0, nblk, 2 * num_cu));
       CK(hipMemset(form ? sb : sa, 0, (size_t)n * n * 4));
       CK(launch_gram_kbits(k1[form], v, n, form ? sb : sa, num_cu, 0, 4));
     }
@@ -593,10 +590,10 @@ static int aln_main(int n, int64_t v, int reps, int num_cu, unsigned long long* 
     bad += d != 0;
     auto line = [&](const char* what, float ms) { std::printf("time  %-66s %8.3f ms  (%.3f ms per 10^6 variants)\n", what, ms, ms / mv); };
     for (int wgs : {num_cu, 2 * num_cu})
-      for (int ring : {8, 8})
+      for (int again = 0; again < 2; ++again)
         line((std::string("ring alone, ") + std::to_string(wgs) + " workgroups").c_str(),
-             time_ms(0, reps, [&] { CK(launch_pack_kbits_ring(x, ld, v, n, k1[1], flag, 0, nblk, wgs, ring)); }));
-    for (int ring : {8, 8}) {
+             time_ms(0, reps, [&] { CK(launch_pack_kbits_ring(x, ld, v, n, k1[1], flag, 0, nblk, wgs)); }));
+    for (int again = 0; again < 2; ++again) {
       if (g_aln_alone) break;
       double best = 1e30, bp = 0, bg = 0;
       for (int round = 0; round < 3; ++round) {
@@ -607,14 +604,12 @@ static int aln_main(int n, int64_t v, int reps, int num_cu, unsigned long long* 
           if (k >= 2) CK(hipStreamWaitEvent(ps, consumed[b], 0));
           if (k >= 1) hipLaunchKernelGGL(delay_kernel, dim3(1), dim3(64), 0, ps, (long long)10 * 100);
           CK(hipEventRecord(pe[k][0], ps));
-          CK(launch_pack_kbits_ring(x, ld, v, n, k1[b], flag, ps, nblk, 2 * num_cu, ring));
+          CK(launch_pack_kbits_ring(x, ld, v, n, k1[b], flag, ps, nblk, 2 * num_cu));
           CK(hipEventRecord(pe[k][1], ps));
           CK(hipEventRecord(packed[b], ps));
           CK(hipStreamWaitEvent(gs, packed[b], 0));
           CK(hipEventRecord(ge[k][0], gs));
-          g_kbits_variant = 5;
           CK(launch_gram_kbits(k1[b], v, n, sb, num_cu, gs, 2));
-          g_kbits_variant = 0;
           CK(hipEventRecord(ge[k][1], gs));
           CK(hipEventRecord(consumed[b], gs));
         }
@@ -654,7 +649,7 @@ static int u8_ring_case(int n, int64_t v, int64_t ld8, uint32_t thr, int wgs, un
   hipLaunchKernelGGL(to_u8_kernel, dim3(1024), dim3(256), 0, 0, xf, x8, v, (int64_t)n, (int64_t)n, ld8);
   CK(launch_pack_kbits(x8, 1, ld8, v, n, ka, flag, 0, nblk));
   CK(hipMemset(kb, 0x5a, kbytes));
-  CK(launch_pack_kbits_ring_u8(x8, ld8, v, n, kb, flag, 0, nblk, wgs, (n & 1) ? 8 : 108));
+  CK(launch_ring_u8(x8, ld8, v, n, kb, flag, 0, nblk, wgs, (n & 1) == 0));
   CK(hipDeviceSynchronize());
   const unsigned long long d = count_diff(ka, kb, (int64_t)kbytes, cnt);
   std::printf("u8 ring pre-pass n=%d v=%lld ld=%lld (%d workgroups) vs pack_kbits<uint8>: %s (%llu words differ)\n", n, (long long)v,
@@ -697,7 +692,7 @@ static int coreside_alt_main(int n, int64_t v, int reps, int num_cu, unsigned lo
   hipLaunchKernelGGL(to_bits_kernel, dim3(8192), dim3(256), 0, 0, x, bits, v, (int64_t)n, ld, ldw);
   CK(launch_pack_kbits(x8, 1, ld8, v, n, k1[0], flag, 0, nblk));
   CK(hipMemset(k1[1], 0x33, kbytes));
-  CK(launch_pack_kbits_ring_u8(x8, ld8, v, n, k1[1], flag, 0, nblk, num_cu, 8));
+  CK(launch_pack_kbits_ring_u8(x8, ld8, v, n, k1[1], flag, 0, nblk, num_cu));
   CK(hipDeviceSynchronize());
   {
     const unsigned long long d = count_diff(k1[0], k1[1], (int64_t)kbytes, cnt);
@@ -708,7 +703,7 @@ static int coreside_alt_main(int n, int64_t v, int reps, int num_cu, unsigned lo
     uint8_t two = 2;
     CK(hipMemcpy(x8 + 12345 * ld8 + 77, &two, 1, hipMemcpyHostToDevice));
     CK(hipMemset(flag, 0, 64));
-    CK(launch_pack_kbits_ring_u8(x8, ld8, v, n, k1[1], flag, 0, nblk, num_cu, 8));
+    CK(launch_pack_kbits_ring_u8(x8, ld8, v, n, k1[1], flag, 0, nblk, num_cu));
     CK(hipMemcpy(&hflag, flag, 4, hipMemcpyDeviceToHost));
     std::printf("a byte of value 2 in the tile: flag word %d (%s)\n", hflag, (hflag & 8) ? "raised" : "NOT RAISED");
     bad += (hflag & 8) == 0;
@@ -722,15 +717,15 @@ static int coreside_alt_main(int n, int64_t v, int reps, int num_cu, unsigned lo
   const double mv = (double)v / 1e6;
   auto line = [&](const char* what, float ms) { std::printf("time  %-66s %8.3f ms  (%.3f ms per 10^6 variants)\n", what, ms, ms / mv); };
   line("pack_u8x8_kbits (shipped) alone", time_ms(0, reps, [&] { CK(launch_pack_kbits(x8, 1, ld8, v, n, k1[1], flag, 0, nblk)); }));
-  line("u8 ring pre-pass alone, 256 workgroups", time_ms(0, reps, [&] { CK(launch_pack_kbits_ring_u8(x8, ld8, v, n, k1[1], flag, 0, nblk, num_cu, 8)); }));
-  line("u8 ring pre-pass alone, 512 workgroups", time_ms(0, reps, [&] { CK(launch_pack_kbits_ring_u8(x8, ld8, v, n, k1[1], flag, 0, nblk, 2 * num_cu, 8)); }));
+  line("u8 ring pre-pass alone, 256 workgroups", time_ms(0, reps, [&] { CK(launch_pack_kbits_ring_u8(x8, ld8, v, n, k1[1], flag, 0, nblk, num_cu)); }));
+  line("u8 ring pre-pass alone, 512 workgroups", time_ms(0, reps, [&] { CK(launch_pack_kbits_ring_u8(x8, ld8, v, n, k1[1], flag, 0, nblk, 2 * num_cu)); }));
   {  // the same tile with rows padded to a multiple of 16 bytes: is it the alignment of the 16-byte lane accesses?
     const int64_t ld16 = (n + 15) / 16 * 16;
     uint8_t* x16;
     CK(hipMalloc(&x16, (size_t)(v * ld16)));
     hipLaunchKernelGGL(to_u8_kernel, dim3(8192), dim3(256), 0, 0, x, x16, v, (int64_t)n, ld, ld16);
-    line("u8 ring pre-pass alone, 256 workgroups, ld % 16 == 0", time_ms(0, reps, [&] { CK(launch_pack_kbits_ring_u8(x16, ld16, v, n, k1[1], flag, 0, nblk, num_cu, 8)); }));
-    line("u8 ring pre-pass alone, 512 workgroups, ld % 16 == 0", time_ms(0, reps, [&] { CK(launch_pack_kbits_ring_u8(x16, ld16, v, n, k1[1], flag, 0, nblk, 2 * num_cu, 8)); }));
+    line("u8 ring pre-pass alone, 256 workgroups, ld % 16 == 0", time_ms(0, reps, [&] { CK(launch_pack_kbits_ring_u8(x16, ld16, v, n, k1[1], flag, 0, nblk, num_cu)); }));
+    line("u8 ring pre-pass alone, 512 workgroups, ld % 16 == 0", time_ms(0, reps, [&] { CK(launch_pack_kbits_ring_u8(x16, ld16, v, n, k1[1], flag, 0, nblk, 2 * num_cu)); }));
     line("pack_u8x8_kbits alone, ld % 16 == 0", time_ms(0, reps, [&] { CK(launch_pack_kbits(x16, 1, ld16, v, n, k1[1], flag, 0, nblk)); }));
     CK(hipFree(x16));
   }
@@ -756,7 +751,7 @@ static int coreside_alt_main(int n, int64_t v, int reps, int num_cu, unsigned lo
   }
   for (int k = 0; k < K; ++k)
     for (int j = 0; j < 2; ++j) { CK(hipEventCreate(&pe[k][j])); CK(hipEventCreate(&ge[k][j])); }
-  // kind: 2 = pack_u8x8 (shipped), 3 = u8 ring with `wgs` workgroups, 4 = bitset transpose
+  // kind: 2 = pack_u8x8, 3 / 5 = u8 ring with `wgs` workgroups, nontemporal / default policy, 4 = bitset transpose
   auto pipeline = [&](const char* what, int kind, int wgs, int gram_mode, int gram_cus, int delay_us) {
     double best = 1e30, bp = 0, bg = 0;
     for (int round = 0; round < 3; ++round) {
@@ -768,8 +763,8 @@ static int coreside_alt_main(int n, int64_t v, int reps, int num_cu, unsigned lo
         if (k >= 1 && delay_us > 0) hipLaunchKernelGGL(delay_kernel, dim3(1), dim3(64), 0, ps, (long long)delay_us * 100);
         CK(hipEventRecord(pe[k][0], ps));
         if (kind == 2) CK(launch_pack_kbits(x8, 1, ld8, v, n, k1[b], flag, ps, nblk));
-        else if (kind == 3) CK(launch_pack_kbits_ring_u8(x8, ld8, v, n, k1[b], flag, ps, nblk, wgs, 108));
-        else if (kind == 5) CK(launch_pack_kbits_ring_u8(x8, ld8, v, n, k1[b], flag, ps, nblk, wgs, 8));
+        else if (kind == 3) CK(launch_ring_u8(x8, ld8, v, n, k1[b], flag, ps, nblk, wgs, true));
+        else if (kind == 5) CK(launch_pack_kbits_ring_u8(x8, ld8, v, n, k1[b], flag, ps, nblk, wgs));
         else CK(launch_transpose_bits_kbits(bits, ldw, v, n, k1[b], ps, nblk));
         CK(hipEventRecord(pe[k][1], ps));
         CK(hipEventRecord(packed[b], ps));
@@ -810,7 +805,7 @@ static int coreside_alt_main(int n, int64_t v, int reps, int num_cu, unsigned lo
   CK(launch_pack_kbits(x8, 1, ld8, v, n, k1[0], flag, 0, nblk));
   CK(launch_gram_kbits(k1[0], v, n, sa, num_cu, 0, 4));
   CK(hipMemset(sb, 0, (size_t)n * n * 4));
-  CK(launch_pack_kbits_ring_u8(x8, ld8, v, n, k1[1], flag, 0, nblk, num_cu, 8));
+  CK(launch_pack_kbits_ring_u8(x8, ld8, v, n, k1[1], flag, 0, nblk, num_cu));
   CK(launch_gram_kbits(k1[1], v, n, sb, num_cu, 0, 2));
   CK(hipDeviceSynchronize());
   {
@@ -885,19 +880,14 @@ int main(int argc, char** argv) {
     CK(launch_gram_packed(p4[0], 1, nkb * 32, n, sa, num_cu, 0, nullptr));
   }
   CK(launch_pack_kbits(x, 0, ld, v, n, k1[0], flag, 0, nblk));
-  const char* vname[5] = {"enc1-split ring3 (shipped)", "enc0 ring4", "enc1 ring3", "enc1-split ring4", "enc1-split ring3 left0"};
-  const int nvar = 5;
-  for (int var = 0; var < nvar; ++var)
   for (int mode : {0, 2, 4}) {
-    g_kbits_variant = var;
-    if (var > 0 && mode == 0) continue;
     CK(hipMemset(sb, 0, (size_t)n * n * 4));
     hipError_t e = launch_gram_kbits(k1[0], v, n, sb, num_cu, 0, mode);
     if (e != hipSuccess) { (void)hipGetLastError(); std::printf("full size: k-bits mode %d does not fit\n", mode); continue; }
     CK(hipDeviceSynchronize());
     const unsigned long long d = count_diff(sa, sb, (int64_t)n * n * 4, cnt);
-    std::printf("full size n=%d v=%lld: S(k-bits %s, mode %d) vs S(FP4 path): %s (%llu entries differ)\n", n, (long long)v,
-                vname[var], mode, d ? "MISMATCH" : "bit-identical", d);
+    std::printf("full size n=%d v=%lld: S(k-bits, mode %d) vs S(FP4 path): %s (%llu entries differ)\n", n, (long long)v,
+                mode, d ? "MISMATCH" : "bit-identical", d);
     bad += d != 0;
     if (d) {  // where: by tile, by wave sub-tile (128 x 64), by MFMA tile, first few entries
       std::vector<int32_t> ha((size_t)n * n), hb((size_t)n * n);
@@ -930,7 +920,6 @@ int main(int argc, char** argv) {
       std::printf("\n");
     }
   }
-  g_kbits_variant = 0;
   int32_t hflag = 0;
   CK(hipMemcpy(&hflag, flag, 4, hipMemcpyDeviceToHost));
   std::printf("flag word after the pre-passes: %d\n", hflag);
@@ -964,12 +953,8 @@ int main(int argc, char** argv) {
   for (int cus : {num_cu, num_cu / 2}) {
     std::string tag = cus == num_cu ? " [whole chip]" : " [sized for half the chip]";
     line(("FP4 lock-step" + tag).c_str(), time_ms(0, reps, [&] { CK(launch_gram_packed_lockstep(p4[0], 1, nkb * 32, n, sa, cus, 0)); }));
-    for (int var = 0; var < nvar; ++var) {
-      g_kbits_variant = var;
-      line((std::string("k-bits ") + vname[var] + " lock-step (mode 2)" + tag).c_str(), time_ms(0, reps, [&] { CK(launch_gram_kbits(k1[0], v, n, sb, cus, 0, 2)); }));
-      line((std::string("k-bits ") + vname[var] + " even split (mode 4)" + tag).c_str(), time_ms(0, reps, [&] { CK(launch_gram_kbits(k1[0], v, n, sb, cus, 0, 4)); }));
-    }
-    g_kbits_variant = 0;
+    line(("k-bits lock-step (mode 2)" + tag).c_str(), time_ms(0, reps, [&] { CK(launch_gram_kbits(k1[0], v, n, sb, cus, 0, 2)); }));
+    line(("k-bits even split (mode 4)" + tag).c_str(), time_ms(0, reps, [&] { CK(launch_gram_kbits(k1[0], v, n, sb, cus, 0, 4)); }));
   }
   for (int cus : {192, 160, 144}) {
     std::string tag = " [" + std::to_string(cus) + " workgroups]";

@@ -1,13 +1,13 @@
 // exp_overlap.hip -- A/B harness for the fp32 boundary of the Gram path (DESIGN_HISTORY.md 4.1).
 //
 // Measures, on one MI355X and on the kernels of spark-examples_amd/csrc/pack_packed.hip and gram_packed.hip themselves
-// (the files are included, so the experiment-only ring pre-pass and the harness knobs are visible):
-//   1. pack_fp4_kernel (shipped pre-pass) vs pack_fp4_ring_kernel (persistent, LDS-DMA ring, <= 64 VGPRs, 64 KiB LDS):
-//      bit-identical operand? time per 10^6 variants at several grid sizes, nt / default cache policy;
-//   2. the contraction alone;
-//   3. a step = pre-pass + contraction, serial on one stream (what ships) vs pipelined on two streams with ping-pong
-//      operand buffers: pre-pass of chunk k+1 beside the contraction of chunk k, for both pre-pass kernels, with and
-//      without stream priorities, and on disjoint CU masks.
+// (the files are included):
+//   1. pack_fp4_kernel (the pre-pass): a non-binary value raises its flag; time per 10^6 variants;
+//   2. the contraction alone, split-K and lock-step launch (same S?);
+//   3. a step = pre-pass + contraction, serial on one stream vs pipelined on two streams with ping-pong operand
+//      buffers: pre-pass of chunk k+1 beside the contraction of chunk k, with a head start for the contraction, and on
+//      disjoint CU masks.
+// (The LDS-ring FP4 pre-pass and the balanced tile deal this harness once compared against: profiles/r02*.)
 // Not part of the product; build: make -C tools exp_overlap (hipcc, gfx950).  Prints one line per measurement.
 #include <chrono>
 #include <cstdio>
@@ -90,29 +90,17 @@ struct Ctx {
   unsigned long long* cnt = nullptr;
 };
 
-enum PackKind { PACK_OLD = 0, PACK_RING = 1 };
-struct PackCfg {
-  PackKind kind;
-  int wgs;  // ring: grid size
-  int nt;
-  std::string name() const {
-    if (kind == PACK_OLD) return "old";
-    return "ring" + std::string((nt & 2) ? "8" : "16") + "(wgs=" + std::to_string(wgs) + ((nt & 1) ? ",nt)" : ",dflt)");
-  }
-};
-
-static void pack(const Ctx& c, const PackCfg& k, int buf, hipStream_t s, int64_t nv = -1) {
+static void pack(const Ctx& c, int buf, hipStream_t s, int64_t nv = -1) {
   if (nv < 0) nv = c.v;
   if (g_delay_us > 0) hipLaunchKernelGGL(delay_kernel, dim3(1), dim3(64), 0, s, (long long)g_delay_us * 100);  // wall_clock64: 100 MHz
-  if (k.kind == PACK_OLD) CK(launch_pack_fp4(c.x, 0, c.ld, nv, c.n, c.p[buf], c.flag, s, c.nkb));
-  else CK(launch_pack_fp4_ring(c.x, c.ld, nv, c.n, c.p[buf], c.flag, s, c.nkb, k.wgs, k.nt));
+  CK(launch_pack_fp4(c.x, 0, c.ld, nv, c.n, c.p[buf], c.flag, s, c.nkb));
 }
 static int g_lockstep = 0;  // 1: lock-step contraction launch (all tiles of 4 k-streams resident, one workgroup per CU)
 static void contract(const Ctx& c, int buf, hipStream_t s, int num_cu = 0) {
   if (g_lockstep) {
     if (launch_gram_packed_lockstep(c.p[buf], 1, c.nkb * 32, c.n, c.s32, g_gram_cus_hint ? g_gram_cus_hint : c.num_cu, s) != hipSuccess) {
       (void)hipGetLastError();
-      CK(launch_gram_packed(c.p[buf], 1, c.nkb * 32, c.n, c.s32, c.num_cu, s, nullptr));  // shape does not fit: shipped launch
+      CK(launch_gram_packed(c.p[buf], 1, c.nkb * 32, c.n, c.s32, c.num_cu, s, nullptr));  // shape does not fit: split-K launch
     }
   } else {
     CK(launch_gram_packed(c.p[buf], 1, c.nkb * 32, c.n, c.s32, num_cu ? num_cu : c.num_cu, s, nullptr));
@@ -137,7 +125,7 @@ static float time_events(hipStream_t s, int reps, const std::function<void()>& b
 }
 
 // pipelined job: K chunks, pre-pass on sp, contraction on sg, ping-pong operand buffers
-static double pipelined(const Ctx& c, const PackCfg& k, hipStream_t sp, hipStream_t sg, int K, int gram_cus = 0) {
+static double pipelined(const Ctx& c, hipStream_t sp, hipStream_t sg, int K, int gram_cus = 0) {
   hipEvent_t ev_p[2], ev_g[2];
   for (int b = 0; b < 2; ++b) {
     CK(hipEventCreateWithFlags(&ev_p[b], hipEventDisableTiming));
@@ -147,7 +135,7 @@ static double pipelined(const Ctx& c, const PackCfg& k, hipStream_t sp, hipStrea
     for (int i = 0; i < chunks; ++i) {
       const int b = i & 1;
       if (i >= 2) CK(hipStreamWaitEvent(sp, ev_g[b], 0));  // the contraction that read this buffer has finished
-      pack(c, k, b, sp);
+      pack(c, b, sp);
       CK(hipEventRecord(ev_p[b], sp));
       CK(hipStreamWaitEvent(sg, ev_p[b], 0));
       contract(c, b, sg, gram_cus);
@@ -168,7 +156,7 @@ static double pipelined(const Ctx& c, const PackCfg& k, hipStream_t sp, hipStrea
 }
 
 // the same pipelined job with an event pair around every kernel: prints when each kernel ran (ms since the first one)
-static double timeline(const Ctx& c, const PackCfg& k, hipStream_t sp, hipStream_t sg, int K, bool verbose = true) {
+static double timeline(const Ctx& c, hipStream_t sp, hipStream_t sg, int K, bool verbose = true) {
   std::vector<hipEvent_t> pa(K), pb(K), ga(K), gb(K);
   for (int i = 0; i < K; ++i) {
     CK(hipEventCreate(&pa[i])); CK(hipEventCreate(&pb[i])); CK(hipEventCreate(&ga[i])); CK(hipEventCreate(&gb[i]));
@@ -177,7 +165,7 @@ static double timeline(const Ctx& c, const PackCfg& k, hipStream_t sp, hipStream
     const int b = i & 1;
     if (i >= 2) CK(hipStreamWaitEvent(sp, gb[i - 2], 0));
     CK(hipEventRecord(pa[i], sp));
-    pack(c, k, b, sp);
+    pack(c, b, sp);
     CK(hipEventRecord(pb[i], sp));
     CK(hipStreamWaitEvent(sg, pb[i], 0));
     CK(hipEventRecord(ga[i], sg));
@@ -194,8 +182,8 @@ static double timeline(const Ctx& c, const PackCfg& k, hipStream_t sp, hipStream
     CK(hipEventElapsedTime(&t, ga[i], gb[i])); gsum += t;
   }
   const double step = span / (K - 2);
-  std::printf("pipelined %-24s + %-9s contraction: steady state %.3f ms/step (pre-pass kernel %.3f ms, contraction %.3f ms from queue entry)\n",
-              k.name().c_str(), g_lockstep ? "lock-step" : "shipped", step, psum / (K - 2), gsum / (K - 2));
+  std::printf("pipelined pre-pass + %-9s contraction: steady state %.3f ms/step (pre-pass kernel %.3f ms, contraction %.3f ms from queue entry)\n",
+              g_lockstep ? "lock-step" : "split-K", step, psum / (K - 2), gsum / (K - 2));
   if (verbose) {
     for (int i = 0; i < K; ++i) {
       float a0, a1, b0, b1;
@@ -245,9 +233,8 @@ int main(int argc, char** argv) {
     CK(hipStreamCreateWithFlags(&sc, hipStreamNonBlocking));
     long long* probe = nullptr;
     CK(hipMalloc((void**)&probe, 64));
-    const PackCfg old_pack{PACK_OLD, 0, 0};
-    pack(c, old_pack, 0, s0);
-    pack(c, old_pack, 1, s0);
+    pack(c, 0, s0);
+    pack(c, 1, s0);
     CK(hipStreamSynchronize(s0));
     g_lockstep = 1;
     g_gram_cus_hint = 128;
@@ -257,7 +244,7 @@ int main(int argc, char** argv) {
         g_gram_cus_hint = (mode == 4) ? 0 : 128;
         const int reps = 6;
         // load first (a few launches deep), then the probe for 4 ms in the middle of it
-        if (mode == 1 || mode == 3) for (int i = 0; i < reps; ++i) pack(c, old_pack, 0, sp);
+        if (mode == 1 || mode == 3) for (int i = 0; i < reps; ++i) pack(c, 0, sp);
         if (mode == 2 || mode == 3) for (int i = 0; i < reps; ++i) contract(c, 1, sg);
         if (mode == 4) for (int i = 0; i < 2 * reps; ++i) contract(c, 1, sg);
         hipLaunchKernelGGL(delay_kernel, dim3(1), dim3(64), 0, sc, 150000LL);        // 1.5 ms: let the load ramp up
@@ -275,72 +262,15 @@ int main(int argc, char** argv) {
     std::printf("done\n");
     return 0;
   }
-  if (argc > 3 && std::string(argv[3]) == "balanced") {
-    // ---- focused A/B: tile deal of the half-chip lock-step contraction (row-major cut vs 6 panels per XCD), alone and in
-    // the shipped pipeline (no masks, 10-us head start), interleaved rounds
-    hipStream_t sp, sg;
-    CK(hipStreamCreateWithFlags(&sp, hipStreamNonBlocking));
-    CK(hipStreamCreateWithFlags(&sg, hipStreamNonBlocking));
-    const PackCfg old_pack{PACK_OLD, 0, 0};
-    pack(c, old_pack, 0, s0);
-    pack(c, old_pack, 1, s0);
-    g_lockstep = 1;
-    g_gram_cus_hint = 128;
-    const size_t nn = (size_t)c.n * c.n;
-    std::vector<int32_t> a(nn), b(nn);
-    for (int map : {2, 3}) {
-      g_lockstep_map = map;
-      CK(hipMemsetAsync(c.s32, 0, nn * 4, s0));
-      contract(c, 0, s0);
-      CK(hipMemcpyAsync(map == 2 ? a.data() : b.data(), c.s32, nn * 4, hipMemcpyDeviceToHost, s0));
-      CK(hipStreamSynchronize(s0));
-    }
-    size_t diff = 0; long long sum = 0;
-    for (size_t i = 0; i < nn; ++i) { diff += a[i] != b[i]; sum += a[i]; }
-    std::printf("balanced deal vs row-major cut: %zu differing entries of %zu (sum %lld)  %s\n", diff, nn, sum,
-                diff == 0 && sum > 0 ? "OK" : "MISMATCH");
-    for (int round = 0; round < 3; ++round)
-      for (int map : {2, 3}) {
-        g_lockstep_map = map;
-        g_delay_us = 0;
-        const float alone = time_events(s0, 4, [&] { contract(c, 0, s0); });
-        g_delay_us = 10;
-        std::printf("[deal %s] contraction alone (sized for 128 CUs) %.3f ms | ", map == 3 ? "balanced " : "row-major", alone);
-        timeline(c, old_pack, sp, sg, K, false);
-        std::fflush(stdout);
-      }
-    std::printf("done\n");
-    return 0;
-  }
-
-  // ---- 1. bit-identity of the two pre-passes (full tile, and a ragged variant count: rows beyond nv in the last k-block)
-  for (int64_t nv : {c.v, c.v - 13}) {
-    CK(hipMemsetAsync(c.p[0], 0xAB, pbytes, s0));
-    CK(hipMemsetAsync(c.p[1], 0xCD, pbytes, s0));
-    pack(c, PackCfg{PACK_OLD, 0, 0}, 0, s0, nv);
-    pack(c, PackCfg{PACK_RING, c.num_cu, 1}, 1, s0, nv);
-    CK(hipMemsetAsync(c.cnt, 0, 8, s0));
-    hipLaunchKernelGGL(diff_kernel, dim3(2048), dim3(256), 0, s0, (const uint32_t*)c.p[0], (const uint32_t*)c.p[1],
-                       (int64_t)c.nkb * c.npad * 4, c.cnt);
-    unsigned long long d = 0;
-    int32_t fl = 0;
-    CK(hipMemcpyAsync(&d, c.cnt, 8, hipMemcpyDeviceToHost, s0));
-    CK(hipMemcpyAsync(&fl, c.flag, 4, hipMemcpyDeviceToHost, s0));
-    CK(hipStreamSynchronize(s0));
-    std::printf("identity nv=%lld: %llu differing words of %lld, flag=%d  %s\n", (long long)nv, d,
-                (long long)c.nkb * c.npad * 4, fl, (d == 0 && fl == 0) ? "OK" : "MISMATCH");
-  }
-  {  // a non-binary value must raise flag bit 3 in both kernels
+  {  // ---- 1. a non-binary value must raise flag bit 3
     const float two = 2.0f;
     CK(hipMemcpy(c.x + (size_t)77777 * c.ld + 1234, &two, 4, hipMemcpyHostToDevice));
-    for (int kind = 0; kind < 2; ++kind) {
-      CK(hipMemsetAsync(c.flag, 0, 64, s0));
-      pack(c, kind ? PackCfg{PACK_RING, c.num_cu, 1} : PackCfg{PACK_OLD, 0, 0}, 0, s0);
-      int32_t fl = 0;
-      CK(hipMemcpyAsync(&fl, c.flag, 4, hipMemcpyDeviceToHost, s0));
-      CK(hipStreamSynchronize(s0));
-      std::printf("non-binary value, %s: flag=%d %s\n", kind ? "ring" : "old", fl, fl == 8 ? "OK" : "MISSED");
-    }
+    CK(hipMemsetAsync(c.flag, 0, 64, s0));
+    pack(c, 0, s0);
+    int32_t fl = 0;
+    CK(hipMemcpyAsync(&fl, c.flag, 4, hipMemcpyDeviceToHost, s0));
+    CK(hipStreamSynchronize(s0));
+    std::printf("non-binary value: flag=%d %s\n", fl, fl == 8 ? "OK" : "MISSED");
     const float one = 1.0f;
     CK(hipMemcpy(c.x + (size_t)77777 * c.ld + 1234, &one, 4, hipMemcpyHostToDevice));
     CK(hipMemset(c.flag, 0, 64));
@@ -348,15 +278,12 @@ int main(int argc, char** argv) {
 
   // ---- 2. kernels alone
   const double gb = (4.0 * c.v * c.n + (double)c.nkb * c.npad * 16) / 1e9;
-  std::vector<PackCfg> packs = {{PACK_OLD, 0, 0}};
-  for (int nt : {1, 0})
-    for (int mult : {1, 2, 3, 4}) packs.push_back({PACK_RING, c.num_cu * mult, nt});
-  for (const auto& k : packs) {
-    const float ms = time_events(s0, 6, [&] { pack(c, k, 0, s0); });
-    std::printf("alone  pack %-22s %.3f ms  %.0f GB/s (read+write, algorithmic)\n", k.name().c_str(), ms, gb / ms * 1e3);
+  {
+    const float ms = time_events(s0, 6, [&] { pack(c, 0, s0); });
+    std::printf("alone  pack %.3f ms  %.0f GB/s (read+write, algorithmic)\n", ms, gb / ms * 1e3);
   }
-  pack(c, packs[0], 0, s0);
-  pack(c, packs[0], 1, s0);
+  pack(c, 0, s0);
+  pack(c, 1, s0);
   int least = 0, greatest = 0;
   CK(hipDeviceGetStreamPriorityRange(&least, &greatest));
   hipStream_t sp, sg, sp_lo, sg_hi;
@@ -364,7 +291,7 @@ int main(int argc, char** argv) {
   CK(hipStreamCreateWithFlags(&sg, hipStreamNonBlocking));
   CK(hipStreamCreateWithPriority(&sp_lo, hipStreamNonBlocking, least));
   CK(hipStreamCreateWithPriority(&sg_hi, hipStreamNonBlocking, greatest));
-  // the lock-step launch must give the same S as the shipped one
+  // the lock-step launch must give the same S as the split-K one
   {
     const size_t nn = (size_t)c.n * c.n;
     std::vector<int32_t> a(nn), b(nn);
@@ -377,18 +304,18 @@ int main(int argc, char** argv) {
     CK(hipStreamSynchronize(s0));
     size_t diff = 0; long long sum = 0;
     for (size_t i = 0; i < nn; ++i) { diff += a[i] != b[i]; sum += a[i]; }
-    std::printf("lock-step contraction vs shipped: %zu differing entries of %zu (sum %lld)  %s\n", diff, nn, sum,
+    std::printf("lock-step contraction vs split-K: %zu differing entries of %zu (sum %lld)  %s\n", diff, nn, sum,
                 diff == 0 && sum > 0 ? "OK" : "MISMATCH");
   }
   std::printf("LDS per CU reported: sharedMemPerMultiprocessor %zu, maxSharedMemoryPerMultiProcessor %zu, sharedMemPerBlock %zu\n",
               (size_t)prop.sharedMemPerMultiprocessor, (size_t)prop.maxSharedMemoryPerMultiProcessor, (size_t)prop.sharedMemPerBlock);
   for (int ls : {0, 1}) {
     g_lockstep = ls;
-    const char* gname = ls ? "lock-step(220 WGs, split-K 4)" : "shipped(1760 WGs, split-K 32)";
+    const char* gname = ls ? "lock-step(220 WGs, split-K 4)" : "split-K(1760 WGs, split-K 32)";
     const float gram_ms = time_events(s0, 6, [&] { contract(c, 0, s0); });
     std::printf("alone  contraction %-32s %.3f ms per launch of %lld variants\n", gname, gram_ms, (long long)c.v);
-    const float ms = time_events(s0, K, [&] { pack(c, packs[0], 0, s0); contract(c, 0, s0); });
-    std::printf("serial step    [%s], pack old  %.3f ms/step\n", gname, ms);
+    const float ms = time_events(s0, K, [&] { pack(c, 0, s0); contract(c, 0, s0); });
+    std::printf("serial step    [%s]  %.3f ms/step\n", gname, ms);
   }
   // ---- no masks: the contraction (lock-step, 112 workgroups = one per CU on 110 CUs) gets a head start of a few us, the
   // pre-pass then fills every CU the contraction left (its 96-VGPR waves do not fit beside 2 x 224 on a SIMD)
@@ -398,12 +325,12 @@ int main(int argc, char** argv) {
     for (int dl : {0, 5, 20, 50, 200}) {
       g_delay_us = dl;
       std::printf("[no masks, contraction sized for %d CUs, pre-pass delayed %3d us] ", hint, dl);
-      timeline(c, packs[0], sp, sg, K, false);
+      timeline(c, sp, sg, K, false);
       std::fflush(stdout);
     }
   }
   g_delay_us = 20; g_gram_cus_hint = 128;
-  timeline(c, packs[0], sp, sg, 6, true);
+  timeline(c, sp, sg, 6, true);
   g_delay_us = 0; g_gram_cus_hint = 0; g_lockstep = 0;
   // ---- disjoint CU sets.  Mask bit g = (XCD g % 8, CU g / 8 of that XCD) -- decoded from r02a (12 bits per word gave
   // 16 CUs on XCDs 0-3 and 8 on XCDs 4-7).  Pre-pass on CUs [0, pc) of every XCD, contraction on CUs [pc, 32).
@@ -428,17 +355,14 @@ int main(int argc, char** argv) {
       g_lockstep = ls;
       c.num_cu = gcus;  // the contraction sizes its grid for the CUs it owns
       const float galone = time_events(smg, 4, [&] { contract(c, 0, smg); });
-      std::printf("[%2d + %2d CUs per XCD] contraction %-9s alone on %3d CUs: %.3f ms\n", pc, gc, ls ? "lock-step" : "shipped",
+      std::printf("[%2d + %2d CUs per XCD] contraction %-9s alone on %3d CUs: %.3f ms\n", pc, gc, ls ? "lock-step" : "split-K",
                   gcus, galone);
-      std::vector<PackCfg> cand = {{PACK_OLD, 0, 0}, {PACK_RING, 16 * pc, 0}};
-      for (const auto& k : cand) {
-        c.num_cu = saved;
-        const float alone = time_events(smp, 3, [&] { pack(c, k, 0, smp); });
-        c.num_cu = gcus;
-        std::printf("   pre-pass alone on %3d CUs %.3f ms (%.1f GB/s per CU) | ", 8 * pc, alone, gb / alone * 1e3 / (8 * pc));
-        timeline(c, k, smp, smg, K, false);
-        std::fflush(stdout);
-      }
+      c.num_cu = saved;
+      const float alone = time_events(smp, 3, [&] { pack(c, 0, smp); });
+      c.num_cu = gcus;
+      std::printf("   pre-pass alone on %3d CUs %.3f ms (%.1f GB/s per CU) | ", 8 * pc, alone, gb / alone * 1e3 / (8 * pc));
+      timeline(c, smp, smg, K, false);
+      std::fflush(stdout);
     }
     c.num_cu = saved;
     g_lockstep = 0;
@@ -461,13 +385,11 @@ int main(int argc, char** argv) {
         (void)hipGetLastError();
         break;
       }
-      for (const auto& k : {packs[0], PackCfg{PACK_RING, 8 * m, 1}, PackCfg{PACK_RING, 16 * m, 1}, PackCfg{PACK_RING, 32 * m, 1}}) {
-        const float alone = time_events(smp, 3, [&] { pack(c, k, 0, smp); });
-        const double step = pipelined(c, k, smp, smg, K, 256 - 8 * m);
-        std::printf("CU masks %3d + %3d CUs, pack %-22s alone %.3f ms (%.0f GB/s, %.1f GB/s per CU)   pipelined %.3f ms/step\n",
-                    8 * m, 256 - 8 * m, k.name().c_str(), alone, gb / alone * 1e3, gb / alone * 1e3 / (8 * m), step);
-        std::fflush(stdout);
-      }
+      const float alone = time_events(smp, 3, [&] { pack(c, 0, smp); });
+      const double step = pipelined(c, smp, smg, K, 256 - 8 * m);
+      std::printf("CU masks %3d + %3d CUs, pack alone %.3f ms (%.0f GB/s, %.1f GB/s per CU)   pipelined %.3f ms/step\n",
+                  8 * m, 256 - 8 * m, alone, gb / alone * 1e3, gb / alone * 1e3 / (8 * m), step);
+      std::fflush(stdout);
       CK(hipStreamDestroy(smp));
       CK(hipStreamDestroy(smg));
     }

@@ -1,8 +1,8 @@
 // exp_w4.hip -- correctness + A/B harness of the one-wave-per-SIMD k-bits contraction (spark-examples_amd/csrc/gram_kbits_w4.hip,
 // VERDICT r03 item 1).  On one MI355X, with the library's own kernels (the two contractions' translation units are included):
 //   1. a random k-bits operand (density as the synthetic cohort, ~8 %) of N samples x V variants, built on the device;
-//   2. S of every w4 variant / launch mode == S of the shipped gram_kbits_kernel<3,2,2> (itself oracle-checked in tests/), bit for
-//      bit, on ragged shapes and at BASELINE configs[1] size;
+//   2. S of gram_kbits_w4_kernel in every launch mode / diagonal form == S of gram_kbits_kernel<3,2,2> (itself oracle-checked in
+//      tests/), bit for bit, on ragged shapes and at BASELINE configs[1] size;
 //   3. ms per launch for each.
 // Not part of the product.  Build: make -C tools exp_w4.  Prints one line per measurement.
 #include <cstdio>
@@ -92,10 +92,8 @@ int main(int argc, char** argv) {
   int64_t v = 1 << 20;
   bool small = true, big = true, two_streams = false, hot = false;
   uint32_t thr = 0x14000000u;  // ~7.8 %
-  std::vector<int> variants = {0, 1, 2, 3};
   std::vector<int> modes = {4, 2, 0};
   std::vector<int> diags = {-1};
-  std::vector<int> epis = {0};
   for (int i = 1; i < argc; ++i) {
     if (!std::strcmp(argv[i], "--n") && i + 1 < argc) n = std::atoi(argv[++i]);
     if (!std::strcmp(argv[i], "--v") && i + 1 < argc) v = std::atoll(argv[++i]);
@@ -110,17 +108,9 @@ int main(int argc, char** argv) {
       modes.clear();
       for (char* t = std::strtok(argv[++i], ","); t; t = std::strtok(nullptr, ",")) modes.push_back(std::atoi(t));
     }
-    if (!std::strcmp(argv[i], "--epi") && i + 1 < argc) {
-      epis.clear();
-      for (char* t = std::strtok(argv[++i], ","); t; t = std::strtok(nullptr, ",")) epis.push_back(std::atoi(t));
-    }
     if (!std::strcmp(argv[i], "--diag") && i + 1 < argc) {
       diags.clear();
       for (char* t = std::strtok(argv[++i], ","); t; t = std::strtok(nullptr, ",")) diags.push_back(std::atoi(t));
-    }
-    if (!std::strcmp(argv[i], "--variants") && i + 1 < argc) {
-      variants.clear();
-      for (char* t = std::strtok(argv[++i], ","); t; t = std::strtok(nullptr, ",")) variants.push_back(std::atoi(t));
     }
   }
   hipDeviceProp_t prop;
@@ -159,9 +149,7 @@ int main(int argc, char** argv) {
       CK(launch_gram_kbits(k1, cv, cn, s_ref, num_cu, 0, ref_mode));
       CK(hipDeviceSynchronize());
     }
-    for (int var : variants) for (int wd : diags) for (int ep : epis) {
-      g_w4_variant = var;
-      g_w4_epilogue_cost = ep;
+    for (int wd : diags) {
       for (int mode : modes) {
         if (mode == 2 && gram_lockstep_splitk(cn, num_cu) == 0) continue;
         if ((mode == 4 || mode == 5) && ntri > 4 * num_cu) continue;
@@ -170,13 +158,9 @@ int main(int argc, char** argv) {
         CK(launch_gram_kbits_w4(k1, cv, cn, s_new, num_cu, 0, mode, nullptr, GramStrip{}, wd));
         CK(hipDeviceSynchronize());
         const unsigned long long d = count_diff(s_ref, s_new, sbytes, cnt);
-        if (d && var < 100) ++fails;
+        if (d) ++fails;
         if (timeit) {
-          unsigned long long zero4[4] = {0, 0, 0, 0};
-          CK(hipMemcpyToSymbol(HIP_SYMBOL(g_w4_clk), zero4, sizeof(zero4)));
           const float t = time_ms(reps, [&] { CK(launch_gram_kbits_w4(k1, cv, cn, s_new, num_cu, 0, mode, nullptr, GramStrip{}, wd)); });
-          unsigned long long clk[4] = {0, 0, 0, 0};
-          CK(hipMemcpyFromSymbol(clk, HIP_SYMBOL(g_w4_clk), sizeof(clk)));
           if (hot) {  // each launch behind 8 GB of HBM traffic, timed alone: the state the library's serial order leaves the chip in
             char* junk;
             CK(hipMalloc(&junk, (size_t)4 << 30));
@@ -194,7 +178,7 @@ int main(int argc, char** argv) {
               CK(hipEventElapsedTime(&ms1, ea, eb));
               tot += ms1;
             }
-            std::printf("n %d v %lld  w4 variant %d mode %d behind 8 GB of memset, one launch per event pair: %.4f ms\n", cn, (long long)cv, var, mode, tot / reps);
+            std::printf("n %d v %lld  w4 mode %d behind 8 GB of memset, one launch per event pair: %.4f ms\n", cn, (long long)cv, mode, tot / reps);
             CK(hipFree(junk));
           }
           if (two_streams) {  // consecutive launches on alternating streams: the tail of one overlaps the head of the next
@@ -213,14 +197,12 @@ int main(int argc, char** argv) {
             CK(hipEventSynchronize(e1));
             float ms2 = 0;
             CK(hipEventElapsedTime(&ms2, e0, e1));
-            std::printf("n %d v %lld  w4 variant %d mode %d on two streams: %.4f ms per launch\n", cn, (long long)cv, var, mode, ms2 / (2 * reps));
+            std::printf("n %d v %lld  w4 mode %d on two streams: %.4f ms per launch\n", cn, (long long)cv, mode, ms2 / (2 * reps));
             CK(hipStreamDestroy(st[0])); CK(hipStreamDestroy(st[1]));
           }
-          std::printf("n %d v %lld  w4 variant %d diag %d epi %d mode %d: %.4f ms   diff %llu %s   block 8: %llu shader cycles in %.1f us = %.3f GHz; slowest block %llu cycles, %.1f us\n", cn,
-                      (long long)cv, var, wd, ep, mode, t, d, var >= 100 ? "(timing-only build)" : d ? "MISMATCH" : "ok", clk[0], clk[1] / 100.0,
-                      clk[1] ? clk[0] / (clk[1] * 10.0) : 0.0, clk[2], clk[3] / 100.0);
+          std::printf("n %d v %lld  w4 diag %d mode %d: %.4f ms   diff %llu %s\n", cn, (long long)cv, wd, mode, t, d, d ? "MISMATCH" : "ok");
         } else {
-          std::printf("n %d v %lld  w4 variant %d diag %d mode %d: diff %llu %s\n", cn, (long long)cv, var, wd, mode, d, d ? "MISMATCH" : "ok");
+          std::printf("n %d v %lld  w4 diag %d mode %d: diff %llu %s\n", cn, (long long)cv, wd, mode, d, d ? "MISMATCH" : "ok");
         }
       }
     }
