@@ -35,7 +35,7 @@ extern "C" {
 #endif
 
 #define PCOA_VERSION_MAJOR 0
-#define PCOA_VERSION_MINOR 6
+#define PCOA_VERSION_MINOR 7
 
 typedef struct pcoa_ctx pcoa_ctx;
 
@@ -146,6 +146,10 @@ typedef struct pcoa_timings {
                                    N >= 6,785), 8 bisection from LDS (N <= 4,080), 16 inverse iteration from LDS
                                    (N <= 3,490), 32 inverse iteration with one workgroup per vector, 64 blocked compact-WY
                                    back-transform (N >= 130).  0 when eig_method != 2                                        */
+  /* ---- 0.7: the implicit similarity operator (pcoa_create_operator) ---- */
+  int64_t operator_products;      /* products y = S v / y = B v applied since pcoa_create_operator / pcoa_reset_timings       */
+  double operator_matvec_seconds; /* HIP-event time of those products (both passes, the combine stages, the centring terms)   */
+  int64_t operator_store_bytes;   /* HBM the bit store holds now (whole segments); 0 on every other kind of ctx               */
 } pcoa_timings;
 #define PCOA_TIMINGS_R03_BYTES 192  /* offsetof(pcoa_timings, csr_stage_seconds): what pcoa_get_timings writes */
 
@@ -211,6 +215,58 @@ int pcoa_strip_matvec(pcoa_ctx* ctx, const double* v, const double* means, doubl
  * Nothing crosses PCIe per Lanczos step. */
 int pcoa_strip_set_centering(pcoa_ctx* ctx, const double* means, double matrix_mean);
 int pcoa_strip_matvec_device(pcoa_ctx* ctx, const double* v_dev, double* y_dev);
+
+/* ---- the implicit similarity operator: principal coordinates without forming S ---------------------------------------
+ * With X the V x N carrier bit matrix (row v = the bitset of variant v, what pcoa_accumulate_bits and
+ * pcoa_accumulate_plink_bed bring to the device), S = X^T X and S v = X^T (X v): two passes over a 1-bit operand of V N / 8
+ * bytes instead of N^2 V matrix-core work and 4 N^2 bytes of S.  computePca's Lanczos iteration touches S only through such
+ * products, and the row sums its centring needs are S 1 = X^T (X 1), exact integers.
+ *
+ * pcoa_create_operator: a ctx that holds the carrier bitsets of every variant it has been fed and NO N x N matrix of any kind;
+ * its HBM use is the bit store, the Lanczos workspace, O(N) + O(V) vectors and the partial sums of the two passes
+ * (ceil(N / 8192) V + ceil(V / 512) N doubles), so the sample count of one GPU is bounded by "the bitsets fit", not by "S fits".
+ *   input:  pcoa_accumulate_bits (host or device pointer) and pcoa_accumulate_plink_bed (host, device, PCOA_BED_HOST_ASYNC;
+ *           the same lifetime rules) append to the store.  The dense fp32 / uint8 tiles, the carrier lists (a list can repeat a
+ *           callset, a bitset cannot) and pcoa_accumulate_synthetic (it writes the contraction operand, not variant-major
+ *           bitsets) return PCOA_ERR_STATE.
+ *   store:  segments of a fixed number of rows (about 256 MiB each; whole multiples of 2,048 rows where a segment holds that
+ *           many), allocated as the store grows and never reallocated or copied; rows at a fixed pitch of ceil(N / 32) words
+ *           rounded up to 4; bits of samples >= N are cleared on append.  An append that cannot get its segments leaves the
+ *           store as it was and returns PCOA_ERR_OUT_OF_MEMORY.  pcoa_reset empties the store.
+ *   pcoa_compute: the outputs of a full engine ([num_pc][N] unit sign-normalised columns, eigenvalues, non-zero rows): row
+ *           sums -> means, matrix mean, non-zero rows -> the Lanczos iteration with the centred product; PCOA_ERR_NOT_CONVERGED
+ *           if no verified pair is reached (no dense fallback: there is no matrix).  PCOA_FLAG_EIG_BAND is honoured;
+ *           PCOA_FLAG_EIG_HOUSEHOLDER with N >= 32 and the PCOA_FLAG_GRAM_* / PCOA_FLAG_OPERAND_FP4 flags are
+ *           PCOA_ERR_INVALID_ARG at create.  N < 32 (below the Lanczos path): the resident segments are fed, as device
+ *           bitsets, to a temporary full engine on the same device and its pcoa_compute is returned.
+ *   not available (PCOA_ERR_STATE, the ctx stays usable): everything that reads or moves S -- pcoa_gram_read_i64 /
+ *           _read_block_i64 / _load_i64 / _export_device_i64 / _import_device_i64, pcoa_gram_reduce_from (either side),
+ *           pcoa_gram_allreduce_rccl, pcoa_center_read_f64, pcoa_project (either side), pcoa_compute_strips, the pcoa_strip_*
+ *           calls.  pcoa_gram_finalize and pcoa_sync drain the appends; pcoa_reserve reserves the Lanczos workspace and the
+ *           first segment.
+ *   results are reproducible: the same store and the same v give bit-identical y, run to run and whatever the sizes of the
+ *           accumulate calls that filled the store were (no floating-point atomics; the order of every addition is fixed by N,
+ *           the segment size and a row's index in the store).
+ * Replaces: getSimilarityMatrix's per-partition matrix and its reduceByKey (VariantsPca.scala:183-190) by the rows they are
+ * built from (getCallsRdd, :153-168), and computePca (:198-231) over them. */
+int pcoa_create_operator(pcoa_ctx** out, int32_t n_samples, int32_t device_ordinal, uint32_t flags);
+
+/* Returns 1 for an operator ctx, 0 otherwise (like pcoa_strip_info).  *variants_out: rows in the store; *store_bytes_out:
+ * the HBM its segments hold (whole segments).  Either pointer may be NULL. */
+int pcoa_operator_info(const pcoa_ctx* ctx, int64_t* variants_out, int64_t* store_bytes_out);
+
+/* out_n[i] = sum_j S(i, j), exact: one integer pass for the per-variant carrier counts c_v, one for
+ * r_i = sum_v bit(v, i) c_v in int64.  Replaces: rowSums (VariantsPca.scala:206). */
+int pcoa_operator_row_sums(pcoa_ctx* ctx, int64_t* out_n);
+
+/* One product on DEVICE vectors of N doubles on the ctx's GPU.  centred = 0: y = S v.  centred = 1: y = B v with
+ * B(j, i) = ((S(j, i) - m_j) - m_i) + mm (VariantsPca.scala:216-221), applied around the product as
+ * y = S v - m (1^T v) - 1 (m^T v) + mm (1^T v) 1; m = rowSums / N and mm come from the exact row sums, computed once and
+ * resident until the store changes.  Returns when y is complete (synchronous on the ctx stream, like
+ * pcoa_strip_matvec_device); v must be complete when it is called.  Public so that variant-sharded operator engines can be
+ * combined by one all-reduce of an N-vector per product.  Replaces: the products inside MLlib's computePrincipalComponents
+ * (VariantsPca.scala:224-227). */
+int pcoa_operator_matvec_device(pcoa_ctx* ctx, const double* v_dev, double* y_dev, int centred);
 
 /* ---- layout of S over the engines of one job ------------------------------------------------------------------------
  * FULL: every engine holds a whole N x N partial S (4 N^2 bytes) for its share of the variants; the partials are reduced
@@ -544,6 +600,7 @@ int pcoa_debug_guard_mode(void);
  *   PCOA_LANCZOS_BAND_MMAX      basis size of the band iteration (forces thick restarts)
  *   PCOA_SYNTH_TILE             1: pcoa_accumulate_synthetic through the fp32 staging tile and the pre-pass
  *   PCOA_NO_NARROW              1: an int64 S that fits int32 stays int64
+ *   PCOA_OPERATOR_SEGMENT_ROWS  rows per segment of an operator ctx's bit store (crosses segment boundaries with a few hundred rows)
  *   PCOA_KBITS_MODE             0 | 2 | 4 | 5: launch form of the k-bits contraction (split-K, lock-step, even split, even split
  *                               per XCD k-segment)
  *   PCOA_KBITS_W4               0 | 1: the one-wave-per-SIMD k-bits contraction never | wherever it has its CUs to itself (default)

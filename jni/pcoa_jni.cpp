@@ -8,7 +8,7 @@
 // mapping"); only create() throws by itself, because it has no handle to return a message through.
 //
 // Replaces, together with NativePcoa.scala / VariantsPcaNative.scala:
-//   VariantsPcaDriver.getSimilarityMatrix  (VariantsPca.scala:182-191)  create, accumulateCalls | accumulateBits,
+//   VariantsPcaDriver.getSimilarityMatrix  (VariantsPca.scala:182-191)  create | createOperator, accumulateCalls | accumulateBits,
 //                                                                        gramFinalize, comm*, gramAllreduce
 //   VariantsPcaDriver.computePca           (VariantsPca.scala:198-231)  compute
 //   VariantsPcaDriver.stop                 (VariantsPca.scala:283-285)  destroy
@@ -42,6 +42,18 @@ extern "C" {
 JNIEXPORT jlong JNICALL FN(create)(JNIEnv* env, jobject, jint n_samples, jint device, jint flags) {
   pcoa_ctx* c = nullptr;
   if (pcoa_create(&c, n_samples, device, static_cast<uint32_t>(flags)) != PCOA_OK) {
+    jclass ex = env->FindClass("java/lang/IllegalStateException");
+    if (ex) env->ThrowNew(ex, pcoa_last_error(nullptr));
+    return 0;
+  }
+  return static_cast<jlong>(reinterpret_cast<intptr_t>(c));
+}
+
+// pcoa_create_operator: the implicit similarity operator -- the engine keeps the carrier bitsets accumulateBits feeds it and no
+// N x N matrix; compute runs over the products S v = X^T (X v).  Throws like create.
+JNIEXPORT jlong JNICALL FN(createOperator)(JNIEnv* env, jobject, jint n_samples, jint device, jint flags) {
+  pcoa_ctx* c = nullptr;
+  if (pcoa_create_operator(&c, n_samples, device, static_cast<uint32_t>(flags)) != PCOA_OK) {
     jclass ex = env->FindClass("java/lang/IllegalStateException");
     if (ex) env->ThrowNew(ex, pcoa_last_error(nullptr));
     return 0;

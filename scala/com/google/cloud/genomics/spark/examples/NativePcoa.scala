@@ -34,6 +34,7 @@ object NativePcoa {
   val BedHostAsync = 2 // PCOA_BED_HOST_ASYNC: page-locked .bed rows are only queued (untouched until the second later call returned, or sync)
 
   @native def create(nSamples: Int, device: Int, flags: Int): Long // pcoa_create; throws IllegalStateException
+  @native def createOperator(nSamples: Int, device: Int, flags: Int): Long // pcoa_create_operator: keeps the carrier bitsets (accumulateBits), no N x N matrix; compute runs over S v = X^T (X v)
   @native def destroy(ctx: Long): Unit // pcoa_destroy
   @native def lastError(ctx: Long): String // pcoa_last_error
   @native def reset(ctx: Long): Int // pcoa_reset

@@ -85,6 +85,9 @@ class PcoaTimings(ctypes.Structure):
         ("narrowed_to_int32", ctypes.c_int64),
         ("lanczos_block_steps", ctypes.c_int32),
         ("eig_dense_form", ctypes.c_int32),
+        ("operator_products", ctypes.c_int64),
+        ("operator_matvec_seconds", ctypes.c_double),
+        ("operator_store_bytes", ctypes.c_int64),
     ]
 
 
@@ -106,6 +109,10 @@ _SIGNATURES = [
     ("pcoa_version", ctypes.c_char_p, []),
     ("pcoa_create", ctypes.c_int, [ctypes.POINTER(_vp), _i32, _i32, ctypes.c_uint32]),
     ("pcoa_create_strip", ctypes.c_int, [ctypes.POINTER(_vp), _i32, _i32, _i32, _i32, ctypes.c_uint32]),
+    ("pcoa_create_operator", ctypes.c_int, [ctypes.POINTER(_vp), _i32, _i32, ctypes.c_uint32]),
+    ("pcoa_operator_info", ctypes.c_int, [_vp, ctypes.POINTER(_i64), ctypes.POINTER(_i64)]),
+    ("pcoa_operator_row_sums", ctypes.c_int, [_vp, _vp]),
+    ("pcoa_operator_matvec_device", ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int]),
     ("pcoa_strip_info", ctypes.c_int, [_vp, ctypes.POINTER(_i32), ctypes.POINTER(_i32)]),
     ("pcoa_strip_col_sums", ctypes.c_int, [_vp, _vp]),
     ("pcoa_strip_matvec", ctypes.c_int, [_vp, _vp, _vp, ctypes.c_double, _vp]),

@@ -21,6 +21,12 @@ static int64_t staging_rows(int64_t n_variants, int64_t ld4) {
   return std::max<int64_t>(1, std::min(n_variants, rows));
 }
 
+// an operator ctx (pcoa_create_operator) stores carrier bitsets: every other boundary names the two that feed it
+static int not_a_bitset_boundary(pcoa_ctx* c, const char* call, const char* why = "") {
+  return fail(c, PCOA_ERR_STATE, std::string(call) + ": an operator ctx (pcoa_create_operator) stores carrier BITSETS: feed it "
+                                 "through pcoa_accumulate_bits or pcoa_accumulate_plink_bed" + why);
+}
+
 // ---- the staging ring (protocol: StagingRing, pcoa_ctx.h) ---------------------------------------------------------------
 // buffer i of a slot whose last reader is done: regrown to grow_to bytes unless it holds `need` already
 static int staging_fit(pcoa_ctx* c, StagingRing::Slot& sl, int i, size_t need, size_t grow_to) {
@@ -496,6 +502,7 @@ extern "C" {
 
 int pcoa_accumulate_dense_f32(pcoa_ctx* c, const float* x, int64_t n_variants, int64_t ld, int is_device_ptr) {
   CHECK_CTX(c);
+  if (c->is_operator) return not_a_bitset_boundary(c, "pcoa_accumulate_dense_f32");
   if (n_variants < 0 || (n_variants > 0 && !x)) return fail(c, PCOA_ERR_INVALID_ARG, "x is NULL or n_variants < 0");
   if (ld < c->n) return fail(c, PCOA_ERR_INVALID_ARG, "ld must be >= n_samples");
   if (n_variants == 0) return PCOA_OK;
@@ -504,6 +511,7 @@ int pcoa_accumulate_dense_f32(pcoa_ctx* c, const float* x, int64_t n_variants, i
 
 int pcoa_accumulate_dense_u8(pcoa_ctx* c, const uint8_t* x, int64_t n_variants, int64_t ld, int is_device_ptr) {
   CHECK_CTX(c);
+  if (c->is_operator) return not_a_bitset_boundary(c, "pcoa_accumulate_dense_u8");
   if (n_variants < 0 || (n_variants > 0 && !x)) return fail(c, PCOA_ERR_INVALID_ARG, "x is NULL or n_variants < 0");
   if (ld < c->n) return fail(c, PCOA_ERR_INVALID_ARG, "ld must be >= n_samples");
   if (n_variants == 0) return PCOA_OK;
@@ -614,6 +622,8 @@ int pcoa_accumulate_plink_bed(pcoa_ctx* c, const uint8_t* bed_rows, int64_t n_va
 int pcoa_accumulate_calls_ex(pcoa_ctx* c, const int32_t* sample_idx, const int64_t* row_offsets, int64_t n_variants,
                              uint32_t flags) {
   CHECK_CTX(c);
+  if (c->is_operator) return not_a_bitset_boundary(c, "pcoa_accumulate_calls",
+                                                        " (a carrier list can repeat a callset, a bitset cannot)");
   if (n_variants < 0 || !row_offsets) return fail(c, PCOA_ERR_INVALID_ARG, "row_offsets is NULL or n_variants < 0");
   if (flags & ~(uint32_t)(PCOA_CALLS_DEVICE_PTR | PCOA_CALLS_HOST_PINNED | PCOA_CALLS_ASYNC))
     return fail(c, PCOA_ERR_INVALID_ARG, "unknown PCOA_CALLS_* flag");
@@ -666,6 +676,8 @@ int pcoa_synth_fill_f32(pcoa_ctx* c, const pcoa_synth_params* p, int64_t first_v
 
 int pcoa_accumulate_synthetic(pcoa_ctx* c, const pcoa_synth_params* p, int64_t first_variant, int64_t n_variants) {
   CHECK_CTX(c);
+  if (c->is_operator) return not_a_bitset_boundary(c, "pcoa_accumulate_synthetic",
+                                                        " (the generator writes the contraction operand, not variant-major bitsets)");
   if (n_variants < 0 || first_variant < 0) return fail(c, PCOA_ERR_INVALID_ARG, "synthetic: negative range");
   if (n_variants == 0) return PCOA_OK;
   if (!p || !p->thresholds) return fail(c, PCOA_ERR_INVALID_ARG, "synthetic params: null");

@@ -64,10 +64,6 @@ int ensure_b(pcoa_ctx* c) {
   return PCOA_OK;
 }
 
-}  // namespace pcoa
-
-namespace {
-
 // the body of pcoa_lanczos_with_matvec / pcoa_compute_strips: c's Lanczos over the operator mv (c's device is current)
 int lanczos_over(pcoa_ctx* c, int32_t num_pc, const LanczosMatvec& mv, double* out_components, double* out_eigenvalues,
                  int32_t* steps_out) {
@@ -106,6 +102,10 @@ int lanczos_over(pcoa_ctx* c, int32_t num_pc, const LanczosMatvec& mv, double* o
     for (int32_t t = 0; t < num_pc; ++t) out_eigenvalues[t] = sel[(size_t)t];
   return PCOA_OK;
 }
+
+}  // namespace pcoa
+
+namespace {
 
 // a failed input check of either engine: the engine cannot serve a projection (its S is invalid until pcoa_reset)
 int project_engine_state(pcoa_ctx* report, pcoa_ctx* c, const char* who, int rc) {
@@ -146,6 +146,7 @@ extern "C" {
 int pcoa_center_read_f64(pcoa_ctx* c, double* out_b, double* out_row_sums, int32_t* out_nonzero_rows,
                          double* out_matrix_mean) {
   CHECK_CTX(c);
+  NOT_ON_OPERATOR(c, "pcoa_center_read_f64");
   if (c->is_strip) return fail(c, PCOA_ERR_STATE, "a strip owner holds N x cols of S: use pcoa_strip_col_sums / pcoa_strip_matvec");
   int rc = finalize_impl(c);
   if (rc != PCOA_OK) return rc;
@@ -180,6 +181,7 @@ int pcoa_compute(pcoa_ctx* c, int32_t num_pc, double* out_components, double* ou
     return fail(c, PCOA_ERR_INVALID_ARG, buf);
   }
   if (!out_components) return fail(c, PCOA_ERR_INVALID_ARG, "out_components is NULL");
+  if (c->is_operator) return operator_compute(c, num_pc, out_components, out_eigenvalues, out_nonzero_rows);
   if (c->is_strip)
     return fail(c, PCOA_ERR_STATE, "a strip owner holds N x cols of S: the eigensolve over strips is driven by the host "
                                    "(pcoa_strip_col_sums / pcoa_strip_matvec; spark-examples_amd/strips.py)");
@@ -434,6 +436,8 @@ int pcoa_project(pcoa_ctx* ref, pcoa_ctx* cross, int32_t num_pc, const double* c
                  double* out_coords) {
   if (!cross) return fail(ref, PCOA_ERR_INVALID_ARG, "project: cross is NULL");
   CHECK_CTX(ref);
+  NOT_ON_OPERATOR(ref, "pcoa_project (ref)");
+  if (cross->is_operator) return fail(ref, PCOA_ERR_STATE, "pcoa_project: cross is an operator ctx (pcoa_create_operator), which holds no S");
   if (!components || !eigenvalues || !out_coords)
     return fail(ref, PCOA_ERR_INVALID_ARG, "project: components, eigenvalues or out_coords is NULL");
   if (ref->is_strip)
@@ -592,6 +596,7 @@ int pcoa_compute_strips(pcoa_ctx* const* owners, int32_t n_owners, int32_t num_p
     const pcoa_ctx* o = owners[i];
     const std::string who = "compute_strips: owner " + std::to_string(i);
     if (!o) return fail(lead, PCOA_ERR_INVALID_ARG, who + " is NULL");
+    if (o->is_operator) return fail(lead, PCOA_ERR_STATE, who + " is an operator ctx (pcoa_create_operator), which holds no S: pcoa_compute solves it");
     if (!o->is_strip) return fail(lead, PCOA_ERR_INVALID_ARG, who + " is not a strip owner (pcoa_create_strip)");
     if (o->n != n) return fail(lead, PCOA_ERR_INVALID_ARG, who + " has a different N");
     if (o->strip_col0 != next)
@@ -749,6 +754,7 @@ int pcoa_compute_strips(pcoa_ctx* const* owners, int32_t n_owners, int32_t num_p
 int pcoa_debug_centred_matvec(pcoa_ctx* c, const double* x, double* y, int upper_triangle_form) {
   CHECK_CTX(c);
   if (!x || !y) return fail(c, PCOA_ERR_INVALID_ARG, "x or y is NULL");
+  NOT_ON_OPERATOR(c, "pcoa_debug_centred_matvec");
   if (c->is_strip) return fail(c, PCOA_ERR_STATE, "not available on a strip owner");
   int rc = finalize_impl(c);
   if (rc != PCOA_OK) return rc;

@@ -111,6 +111,7 @@ int pcoa_gram_finalize(pcoa_ctx* c) {
 
 int pcoa_gram_export_device_i64(pcoa_ctx* c, int64_t* dst_dev) {
   CHECK_CTX(c);
+  NOT_ON_OPERATOR(c, "pcoa_gram_export_device_i64");
   if (!dst_dev) return fail(c, PCOA_ERR_INVALID_ARG, "dst_dev is NULL");
   int rc = finalize_impl(c);
   if (rc != PCOA_OK) return rc;
@@ -127,6 +128,8 @@ int pcoa_gram_reduce_from(pcoa_ctx* dst, pcoa_ctx* src) {
   CHECK_CTX(dst);
   if (!src) return fail(dst, PCOA_ERR_INVALID_ARG, "src ctx is NULL");
   if (src == dst) return fail(dst, PCOA_ERR_INVALID_ARG, "src and dst are the same ctx");
+  NOT_ON_OPERATOR(dst, "pcoa_gram_reduce_from (dst)");
+  if (src->is_operator) return fail(dst, PCOA_ERR_STATE, "pcoa_gram_reduce_from: src is an operator ctx (pcoa_create_operator), which holds no S");
   if (src->n != dst->n || src->s_cols != dst->s_cols || src->strip_col0 != dst->strip_col0 || src->is_strip != dst->is_strip)
     return fail(dst, PCOA_ERR_INVALID_ARG, "reduce_from: the two engines hold different matrices (n / strip)");
   const size_t nn = s_count(dst);
@@ -204,6 +207,7 @@ int pcoa_gram_reduce_from(pcoa_ctx* dst, pcoa_ctx* src) {
 
 int pcoa_gram_import_device_i64(pcoa_ctx* c, const int64_t* src_dev) {
   CHECK_CTX(c);
+  NOT_ON_OPERATOR(c, "pcoa_gram_import_device_i64");
   if (!src_dev) return fail(c, PCOA_ERR_INVALID_ARG, "src_dev is NULL");
   const size_t nn = s_count(c);
   int rc = fp4_discard(c);  // S is replaced: what was buffered or in flight for the old S goes with it
@@ -219,6 +223,7 @@ int pcoa_gram_import_device_i64(pcoa_ctx* c, const int64_t* src_dev) {
 
 int pcoa_gram_read_i64(pcoa_ctx* c, int64_t* out_nxn) {
   CHECK_CTX(c);
+  NOT_ON_OPERATOR(c, "pcoa_gram_read_i64");
   if (!out_nxn) return fail(c, PCOA_ERR_INVALID_ARG, "out is NULL");
   const size_t nn = s_count(c);
   int rc = ensure_xfer(c, sizeof(int64_t) * nn);
@@ -230,6 +235,7 @@ int pcoa_gram_read_i64(pcoa_ctx* c, int64_t* out_nxn) {
 
 int pcoa_gram_read_block_i64(pcoa_ctx* c, int32_t row0, int32_t col0, int32_t rows, int32_t cols, int64_t* out) {
   CHECK_CTX(c);
+  NOT_ON_OPERATOR(c, "pcoa_gram_read_block_i64");
   if (!out || rows < 0 || cols < 0 || row0 < 0 || col0 < 0 || (int64_t)row0 + rows > c->n || (int64_t)col0 + cols > c->s_cols)
     return fail(c, PCOA_ERR_INVALID_ARG, "block outside the matrix the ctx holds (N x N, or N x cols of a strip) or out is NULL");
   if (rows == 0 || cols == 0) return PCOA_OK;
@@ -256,6 +262,7 @@ int pcoa_gram_read_block_i64(pcoa_ctx* c, int32_t row0, int32_t col0, int32_t ro
 
 int pcoa_gram_load_i64(pcoa_ctx* c, const int64_t* in_nxn) {
   CHECK_CTX(c);
+  NOT_ON_OPERATOR(c, "pcoa_gram_load_i64");
   if (!in_nxn) return fail(c, PCOA_ERR_INVALID_ARG, "in is NULL");
   const size_t nn = s_count(c);
   int rc = ensure_xfer(c, sizeof(int64_t) * nn);
@@ -332,6 +339,7 @@ int pcoa_comm_count(void* nccl_comm, int32_t* count_out) {
 int pcoa_gram_allreduce_rccl(pcoa_ctx* c, void* nccl_comm) {
   CHECK_CTX(c);
   if (!nccl_comm) return fail(c, PCOA_ERR_INVALID_ARG, "nccl_comm is NULL");
+  NOT_ON_OPERATOR(c, "pcoa_gram_allreduce_rccl");
   if (c->is_strip)
     return fail(c, PCOA_ERR_STATE, "a strip owner holds N x cols of S: the owners' strips tile S and are never summed "
                                    "(the exchange step of that layout is the all-gather of pcoa_strip_matvec's results)");

@@ -651,6 +651,7 @@ int gram_device(pcoa_ctx* c, const void* x_dev, int is_u8, int64_t nv, int64_t l
 // can_defer: a caller's device pointer (valid until the next synchronising call): in the co-resident pipeline its transpose
 // (68 VGPRs: one wave per SIMD fits beside the contraction) runs while the previous buffer is contracted
 int gram_device_bits(pcoa_ctx* c, const uint32_t* bits_dev, int64_t nv, int64_t ld_words, bool can_defer) {
+  if (c->is_operator) return operator_append(c, bits_dev, nv, ld_words);   // the rows join the bit store as they are
   int64_t done = 0;
   const int64_t max_cur = std::min(c->max_launch, c->pack_chunk);
   while (done < nv) {

@@ -76,12 +76,18 @@ void drain_events(pcoa_ctx* c, bool wait) {
 // ================================================================================================
 extern "C" {
 
-const char* pcoa_version(void) { return "pcoa_hip 0.6 (gfx950)"; }
+const char* pcoa_version(void) { return "pcoa_hip 0.7 (gfx950)"; }
 
-static int create_impl(pcoa_ctx** out, int32_t n_samples, int32_t device_ordinal, uint32_t flags, int32_t col0, int32_t cols) {
+static int create_impl(pcoa_ctx** out, int32_t n_samples, int32_t device_ordinal, uint32_t flags, int32_t col0, int32_t cols,
+                       bool op = false) {
   if (!out) return fail(nullptr, PCOA_ERR_INVALID_ARG, "out is NULL");
   *out = nullptr;
   if (n_samples <= 0) return fail(nullptr, PCOA_ERR_INVALID_ARG, "n_samples must be positive");
+  if (op && n_samples >= 32 && (flags & PCOA_FLAG_EIG_HOUSEHOLDER))
+    return fail(nullptr, PCOA_ERR_INVALID_ARG, "an operator ctx has no N x N matrix for the dense Householder solver "
+                                               "(PCOA_FLAG_EIG_HOUSEHOLDER); its computePca is the Lanczos iteration");
+  if (op && (flags & (PCOA_FLAG_GRAM_F32_MFMA | PCOA_FLAG_GRAM_I8_MFMA | PCOA_FLAG_GRAM_FP4_MFMA | PCOA_FLAG_OPERAND_FP4)))
+    return fail(nullptr, PCOA_ERR_INVALID_ARG, "an operator ctx runs no Gram kernel: the PCOA_FLAG_GRAM_* / PCOA_FLAG_OPERAND_FP4 flags do not apply");
   const bool strip = cols >= 0;
   if (strip && (col0 < 0 || cols <= 0 || (int64_t)col0 + cols > n_samples))
     return fail(nullptr, PCOA_ERR_INVALID_ARG, "strip [col0, col0 + cols) must lie inside [0, n_samples) and be non-empty");
@@ -100,6 +106,7 @@ static int create_impl(pcoa_ctx** out, int32_t n_samples, int32_t device_ordinal
   if (!c) return fail(nullptr, PCOA_ERR_OUT_OF_MEMORY, "host allocation failed");
   c->n = n_samples;
   c->is_strip = strip;
+  c->is_operator = op;
   c->s_cols = strip ? cols : n_samples;
   c->strip_col0 = strip ? col0 : 0;
   c->device = device_ordinal;
@@ -113,6 +120,17 @@ static int create_impl(pcoa_ctx** out, int32_t n_samples, int32_t device_ordinal
   if (knobs.gram_kernel == 3) { c->use_i8 = true; c->packed_mode = 3; }
   if (knobs.gram_kernel == 0) { c->use_i8 = true; c->packed_mode = 0; }
   c->gram_kind = c->use_i8 ? (c->packed_mode == 2 ? 2 : 3) : 1;
+  if (op) {   // no Gram kernel of any kind; the bitset boundaries only ask for "not the fp32 engine"
+    c->use_i8 = true;
+    c->packed_mode = 3;
+    c->gram_kind = 0;
+    // rows per segment: ~256 MiB, whole ranges of the second pass where a segment holds several
+    const int64_t row_bytes = (int64_t)operator_pitch_words(n_samples) * 4;
+    int64_t rows = std::max<int64_t>(1, ((int64_t)256 << 20) / row_bytes);
+    if (rows >= kOperatorSegmentAlign) rows -= rows % kOperatorSegmentAlign;
+    if (knobs.operator_segment_rows > 0) rows = std::min<int64_t>(knobs.operator_segment_rows, (int64_t)1 << 24);
+    c->op_seg_rows = rows;
+  }
   {
     // keep the int8 workspace at or below ~4 GiB whatever N is (one byte per genotype, Npad columns)
     const int64_t by_mem = (((int64_t)4 << 30) / gram_packed_npad(n_samples)) / 1536 * 1536;
@@ -140,8 +158,10 @@ static int create_impl(pcoa_ctx** out, int32_t n_samples, int32_t device_ordinal
     return fail(nullptr, PCOA_ERR_INVALID_ARG, "a strip owner needs a packed-operand engine (PCOA_GRAM_KERNEL=f32 is set)");
   }
   const size_t nn = s_count(c);
-  if ((e = dev_alloc((void**)&c->s32, sizeof(int32_t) * nn, c->device)) != hipSuccess) return bail(e, "allocation of S");
-  if ((e = hipMemsetAsync(c->s32, 0, sizeof(int32_t) * nn, c->stream)) != hipSuccess) return bail(e, "memset(S)");
+  if (!op) {
+    if ((e = dev_alloc((void**)&c->s32, sizeof(int32_t) * nn, c->device)) != hipSuccess) return bail(e, "allocation of S");
+    if ((e = hipMemsetAsync(c->s32, 0, sizeof(int32_t) * nn, c->stream)) != hipSuccess) return bail(e, "memset(S)");
+  }
   if ((e = dev_alloc((void**)&c->zeros, 4096, c->device)) != hipSuccess) return bail(e, "allocation of the zero page");
   if ((e = hipMemsetAsync(c->zeros, 0, 4096, c->stream)) != hipSuccess) return bail(e, "memset(zeros)");
   if ((e = dev_alloc((void**)&c->err_flag, 16, c->device)) != hipSuccess) return bail(e, "allocation of the flag words");
@@ -162,6 +182,10 @@ int pcoa_create_strip(pcoa_ctx** out, int32_t n_samples, int32_t col0, int32_t c
                       uint32_t flags) {
   if (cols < 0) return fail(nullptr, PCOA_ERR_INVALID_ARG, "cols must be positive");
   return create_impl(out, n_samples, device_ordinal, flags, col0, cols);
+}
+
+int pcoa_create_operator(pcoa_ctx** out, int32_t n_samples, int32_t device_ordinal, uint32_t flags) {
+  return create_impl(out, n_samples, device_ordinal, flags, 0, -1, true);
 }
 
 void pcoa_destroy(pcoa_ctx* c) {
@@ -192,6 +216,7 @@ void pcoa_destroy(pcoa_ctx* c) {
                   c->out_dev};
   for (void* b : bufs)
     if (b) dev_free(b);
+  operator_destroy(c);
   if (c->pack_stream) (void)hipStreamDestroy(c->pack_stream);
   if (c->gram_stream) (void)hipStreamDestroy(c->gram_stream);
   if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
@@ -224,6 +249,7 @@ int pcoa_reserve(pcoa_ctx* c, int64_t variants_per_call, int32_t num_pc) {
   CHECK_CTX(c);
   if (variants_per_call < 0 || num_pc < 0 || num_pc > c->n)
     return fail(c, PCOA_ERR_INVALID_ARG, "reserve: variants_per_call < 0 or num_pc outside [0, n]");
+  if (c->is_operator) return operator_reserve(c, num_pc);
   int rc = PCOA_OK;
   if (variants_per_call > 0 && c->use_i8 && c->packed_mode != 2) {
     // the operand buffer(s) of the binary-tile path, at the size fp4_grow would reach after the first large call
@@ -255,6 +281,7 @@ int pcoa_reset(pcoa_ctx* c) {
   CHECK_CTX(c);
   int rc = fp4_discard(c);  // buffered or in-flight operands belong to the old S
   if (rc != PCOA_OK) return rc;
+  if (c->is_operator) return operator_reset(c);
   const size_t nn = s_count(c);
   HIP_TRY(c, hipMemsetAsync(c->s32, 0, sizeof(int32_t) * nn, c->stream));
   if (c->s64) HIP_TRY(c, hipMemsetAsync(c->s64, 0, sizeof(int64_t) * nn, c->stream));
@@ -323,6 +350,9 @@ int pcoa_get_timings_sized(pcoa_ctx* c, pcoa_timings* out_user, size_t out_size)
   out->narrowed_to_int32 = c->narrowed;
   out->lanczos_block_steps = c->lanczos_block_steps;
   out->eig_dense_form = c->eig_dense_form;
+  out->operator_products = c->op_products;
+  out->operator_matvec_seconds = c->tsec[T_OPERATOR];
+  out->operator_store_bytes = operator_store_bytes(c);
   std::memcpy(out_user, out, std::min(out_size, sizeof(full)));
   return PCOA_OK;
 }
@@ -350,6 +380,7 @@ int pcoa_reset_timings(pcoa_ctx* c) {
   c->lockstep_launches = 0;
   c->pipeline_launches = 0;
   c->evensplit_launches = 0;
+  c->op_products = 0;
   return PCOA_OK;
 }
 

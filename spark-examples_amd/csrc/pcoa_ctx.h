@@ -7,6 +7,7 @@
 //   capi_accumulate.hip  the staging ring and the input boundaries
 //   capi_reduce.hip      RCCL, reductions, export / import / read / load
 //   capi_compute.hip     the eigensolver workspace, computePca, strips, projection
+//   capi_operator.hip    the implicit similarity operator: the bit store, its products, computePca over it
 //   pcoa_capi.hip        create / destroy, errors, timings
 #pragma once
 
@@ -15,7 +16,7 @@
 
 #include "pcoa_internal.h"
 
-enum TimeCat { T_GRAM = 0, T_DENSIFY, T_SYNTH, T_FINALIZE, T_CENTER, T_TRIDIAG, T_EIG, T_BACK, T_PACK, T_LANCZOS, T_ALLREDUCE, T_NCAT };
+enum TimeCat { T_GRAM = 0, T_DENSIFY, T_SYNTH, T_FINALIZE, T_CENTER, T_TRIDIAG, T_EIG, T_BACK, T_PACK, T_LANCZOS, T_ALLREDUCE, T_OPERATOR, T_NCAT };
 
 struct EventPair {
   hipEvent_t a, b;
@@ -60,6 +61,17 @@ struct pcoa_ctx {
   bool strip_centering_set = false;
   double* proj_ws = nullptr;       // pcoa_project on a strip owner: reference means, components, eigenvalues, partials, result (lazy)
   int64_t proj_ws_cap = 0;
+  // implicit similarity operator (pcoa_create_operator, capi_operator.hip): the ctx holds the carrier bitsets of every variant
+  // it was fed, in segments of op_seg_rows rows that are never reallocated or copied, and no N x N matrix of any kind
+  bool is_operator = false;
+  struct OpSegment { uint32_t* p; int64_t rows; };
+  std::vector<OpSegment> op_segs;
+  int64_t op_seg_rows = 0;         // rows a segment holds
+  int64_t op_variants = 0;         // rows in the store
+  bool op_centering_set = false;   // row_sums / stats / colmean / nz belong to the current store
+  double* op_ws = nullptr;         // t, the passes' partials, the two dots (sized by the store, lazy)
+  int64_t op_ws_cap = 0;
+  int64_t op_products = 0;
   int device = 0;
   uint32_t flags = 0;
   int num_cu = 256;
@@ -210,6 +222,14 @@ struct pcoa_ctx {
     if (_e != hipSuccess) return hip_fail((ctx), _e, "hipSetDevice");       \
   } while (0)
 
+// the calls that read or move S do not exist on an operator ctx
+#define NOT_ON_OPERATOR(ctx, what)                                                                                       \
+  do {                                                                                                                   \
+    if ((ctx)->is_operator)                                                                                              \
+      return fail((ctx), PCOA_ERR_STATE, what ": an operator ctx (pcoa_create_operator) holds the carrier bitsets, not " \
+                                         "S; use a full engine (pcoa_create) for this call");                         \
+  } while (0)
+
 namespace pcoa {
 
 constexpr int64_t KB_I8 = 16;                             // variants per int8 k-block
@@ -272,6 +292,16 @@ void staging_destroy(StagingRing& r);
 // ---- capi_compute.hip
 int ensure_workspace(pcoa_ctx* c, int32_t k);
 int ensure_b(pcoa_ctx* c);
+int lanczos_over(pcoa_ctx* c, int32_t num_pc, const LanczosMatvec& mv, double* out_components, double* out_eigenvalues,
+                 int32_t* steps_out);
+
+// ---- capi_operator.hip
+int operator_append(pcoa_ctx* c, const uint32_t* bits_dev, int64_t nv, int64_t ld_words);
+int operator_reset(pcoa_ctx* c);
+int operator_reserve(pcoa_ctx* c, int32_t num_pc);
+int operator_compute(pcoa_ctx* c, int32_t num_pc, double* out_components, double* out_eigenvalues, int32_t* out_nonzero_rows);
+void operator_destroy(pcoa_ctx* c);
+int64_t operator_store_bytes(const pcoa_ctx* c);
 
 struct ScopedTimer {
   pcoa_ctx* c;

@@ -39,6 +39,7 @@ struct DebugKnobs {
   int lanczos_band_mmax = 0;       // PCOA_LANCZOS_BAND_MMAX: basis size of the band iteration (tests: forces thick restarts)
   int lanczos_band = 1;            // PCOA_LANCZOS_BAND = 0: no band-Lanczos fallback (r05 behaviour); 2: ONLY the band iteration (tests)
   int synth_tile = 0;              // PCOA_SYNTH_TILE = 1: pcoa_accumulate_synthetic through the fp32 staging tile + pre-pass (r05 path) instead of generating the k-bits operand directly
+  int64_t operator_segment_rows = 0;  // PCOA_OPERATOR_SEGMENT_ROWS: rows per segment of an operator ctx's bit store (tests: segment boundaries with a few hundred rows)
   int no_narrow = 0;               // PCOA_NO_NARROW = 1: an int64 S that fits int32 stays int64 and pcoa_gram_reduce_from always widens (r05 behaviour; tests of the int64 kernels)
 };
 const DebugKnobs& debug_knobs();
@@ -154,6 +155,33 @@ hipError_t launch_synth_fill_f32(uint64_t seed, const uint32_t* thresholds_dev, 
 hipError_t launch_synth_kbits(uint64_t seed, const uint32_t* thresholds_dev, const int32_t* sample_pop_dev, int32_t n_pops,
                               int64_t first_variant, int64_t nv, int32_t n, int32_t npad, int8_t* p, int64_t nblk_out,
                               hipStream_t stream);
+
+// ---- implicit similarity operator (operator_bits.hip): y = X^T (X v) from the carrier bitsets, S never formed -------------
+// The store is a list of segments, each rows x operator_pitch_words(n) words; bits of samples >= n and the pitch's padding are
+// zero.  A product's additions are ordered by sample group (kOperatorGroupWords word columns), segment and range of
+// kOperatorRangeRows rows -- never by the grid.
+constexpr int32_t kOperatorRangeRows = 512;    // rows of a segment whose pass-2 partial vector one wave accumulates in order
+constexpr int32_t kOperatorSegmentAlign = 2048;   // a segment that holds this many rows holds a whole multiple of them (whole ranges)
+constexpr int32_t kOperatorGroupWords = 256;   // word columns (8,192 samples) a pass-1 workgroup reduces before it writes
+int32_t operator_pitch_words(int32_t n);
+int32_t operator_groups(int32_t n);
+hipError_t launch_operator_append(const uint32_t* src, int64_t ld_words, int64_t nv, int32_t n, uint32_t* dst, hipStream_t stream);
+// tpart[g * vstride + r] = the part of (X v)[r] from sample group g, r in [0, rows) of this segment
+hipError_t launch_operator_xv(const uint32_t* seg, int32_t rows, int32_t n, const double* v, double* tpart, int64_t vstride,
+                              hipStream_t stream);
+hipError_t launch_operator_combine_t(const double* tpart, int64_t vstride, int32_t n, int64_t rows, double* t, hipStream_t stream);
+// ypart[q * pitch * 32 + i] = sum over the rows r of range q of this segment of bit(r, i) t[r]; ceil(rows / range) ranges
+hipError_t launch_operator_xt_f64(const uint32_t* seg, int32_t rows, int32_t n, const double* t, double* ypart, hipStream_t stream);
+hipError_t launch_operator_xt_i64(const uint32_t* seg, int32_t rows, int32_t n, const int32_t* cnt, int64_t* ipart,
+                                  hipStream_t stream);
+hipError_t launch_operator_popcount(const uint32_t* seg, int32_t rows, int32_t n, int32_t* cnt, hipStream_t stream);
+// dots[0] = 1^T v, dots[1] = means^T v
+hipError_t launch_operator_dots(const double* v, const double* means, int32_t n, double* dots, hipStream_t stream);
+// y = the ranges' partials added in order; centred: ((y - means (1^T v)) - means^T v) + stats[1] (1^T v)
+hipError_t launch_operator_finish(const double* ypart, int32_t nranges, int32_t n, const double* means, const double* stats,
+                                  const double* dots, int centred, double* y, hipStream_t stream);
+hipError_t launch_operator_row_sums_finish(const int64_t* ipart, int32_t nranges, int32_t n, int64_t* rs_i64, double* rs_f64,
+                                           hipStream_t stream);
 
 // ---- centring (center.hip) --------------------------------------------------------------------
 // s = s32 + (s64 ? s64 : 0).  row_sums[n] (fp64), stats[0] = matrix sum, stats[1] = matrix mean,

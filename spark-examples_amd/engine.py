@@ -27,7 +27,7 @@ def _ptr(a):
 
 class PcoaEngine(object):
     def __init__(self, n_samples, device=0, flags=L.PCOA_FLAG_DEFAULT, gram_kernel=None, eig=None, strip=None,
-                 pipeline=True, operand=None):
+                 pipeline=True, operand=None, operator=False):
         """gram_kernel: None/"auto" (MX-FP4 MFMA for binary tiles, int8 MFMA for multiplicities; both exact),
         "fp4", "i8" (force one of them) or "f32" (fp32-MFMA path).
         eig: None/"auto" (Lanczos with verified residual -- single vector, then the band iteration --, Householder fallback),
@@ -35,7 +35,9 @@ class PcoaEngine(object):
         strip: None, or (col0, cols): a strip owner holding S[:, col0:col0+cols] (pcoa_create_strip; see strips.py).
         pipeline=False: PCOA_FLAG_NO_PIPELINE (fp32 pre-pass and contraction strictly serial; measurements).
         operand: None/"bits" (binary tiles are re-laid out to 1 bit per genotype and expanded to MX-FP4 inside the
-        contraction) or "fp4" (PCOA_FLAG_OPERAND_FP4: the operand is stored as MX-FP4, 4 bits per genotype)."""
+        contraction) or "fp4" (PCOA_FLAG_OPERAND_FP4: the operand is stored as MX-FP4, 4 bits per genotype).
+        operator=True: the implicit similarity operator (pcoa_create_operator): the engine keeps the carrier bitsets it is fed
+        (accumulate_bits / accumulate_plink_bed) and no N x N matrix; compute() runs over the products S v = X^T (X v)."""
         if not pipeline:
             flags |= L.PCOA_FLAG_NO_PIPELINE
         if operand == "fp4":
@@ -61,7 +63,12 @@ class PcoaEngine(object):
         self._lib = L.load()
         self._ctx = ctypes.c_void_p()
         self.strip = None if strip is None else (int(strip[0]), int(strip[1]))
-        if self.strip is None:
+        self.operator = bool(operator)
+        if self.operator and self.strip is not None:
+            raise ValueError("operator=True and strip= exclude each other")
+        if self.operator:
+            rc = self._lib.pcoa_create_operator(ctypes.byref(self._ctx), int(n_samples), int(device), int(flags))
+        elif self.strip is None:
             rc = self._lib.pcoa_create(ctypes.byref(self._ctx), int(n_samples), int(device), int(flags))
         else:
             rc = self._lib.pcoa_create_strip(ctypes.byref(self._ctx), int(n_samples), self.strip[0], self.strip[1],
@@ -425,6 +432,35 @@ class PcoaEngine(object):
         y = torch.empty(self.cols, dtype=torch.float64, device=v_dev.device)
         torch.cuda.current_stream(v_dev.device).synchronize()   # the engine runs on its own stream
         self._check(self._lib.pcoa_strip_matvec_device(self._ctx, ctypes.c_void_p(v_dev.data_ptr()), ctypes.c_void_p(y.data_ptr())))
+        return y
+
+    # ------------------------------------------------------------------ implicit similarity operator
+    def operator_info(self):
+        """(variants in the bit store, bytes of HBM its segments hold), or None on an engine that is not an operator."""
+        nv, nb = ctypes.c_int64(0), ctypes.c_int64(0)
+        rc = self._lib.pcoa_operator_info(self._ctx, ctypes.byref(nv), ctypes.byref(nb))
+        if rc < 0:
+            self._check(rc)
+        return (int(nv.value), int(nb.value)) if rc == 1 else None
+
+    def operator_row_sums(self):
+        """rowSums of S (VariantsPca.scala:206) as exact int64, from the bit store."""
+        out = np.zeros(self.n, dtype=np.int64)
+        self._check(self._lib.pcoa_operator_row_sums(self._ctx, _ptr(out)))
+        return out
+
+    def operator_matvec_device(self, v_dev, centred):
+        """y = S v (centred false) or y = B v (centred true) for a float64 torch tensor v of N entries on this engine's GPU;
+        returns a device tensor."""
+        import torch  # plumbing only: device memory handles
+        assert v_dev.is_cuda and v_dev.dtype == torch.float64 and v_dev.dim() == 1 and v_dev.shape[0] == self.n
+        if v_dev.device.index != self.device:
+            raise ValueError("v lives on cuda:%d, this engine on cuda:%d" % (v_dev.device.index, self.device))
+        v_dev = v_dev.contiguous()
+        y = torch.empty(self.n, dtype=torch.float64, device=v_dev.device)
+        torch.cuda.current_stream(v_dev.device).synchronize()   # the engine runs on its own stream
+        self._check(self._lib.pcoa_operator_matvec_device(self._ctx, ctypes.c_void_p(v_dev.data_ptr()),
+                                                          ctypes.c_void_p(y.data_ptr()), int(bool(centred))))
         return y
 
     # ------------------------------------------------------------------ computePca

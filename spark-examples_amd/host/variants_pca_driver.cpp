@@ -86,6 +86,10 @@ struct Conf {  // PcaConf / GenomicsConf (GenomicsConf.scala:31-101), same flag 
                                         // whose mean list is longer than N / 32 entries goes over as carrier bitsets (fewer bytes), else as lists
   std::vector<std::string> project_input_path;  // --project-input-path: VCFs whose samples are placed onto the PCA of --input-path
                                                 // (pcoa_project); their callsets follow the reference's, variants matched by join / merge
+  std::string gram = "stored";          // --gram stored|implicit: stored = S is accumulated and decomposed (every path above); implicit = one
+                                        // operator engine (pcoa_create_operator) keeps the carrier bitsets and computePca runs over the
+                                        // products S v = X^T (X v): no N x N matrix exists.  No auto: which form is faster at which N
+                                        // has not been measured
 };
 
 const char* kUsage =
@@ -93,7 +97,8 @@ const char* kUsage =
     "  reference flags: --output-path P --num-pc K --references R.. --all-references --min-allele-frequency F\n"
     "                   --debug-datasets --bases-per-partition B --num-reduce-partitions P --variant-set-id ..\n"
     "  engine flags:    --gpu D --gpus K --gpu-map a,b,.. --reduce auto|rccl|peer --layout auto|full|strips\n"
-    "                   --carrier-format auto|lists|bits --plink-decode device|host --plink-ref-allele a1|a2 --stream-rows R\n"
+    "                   --gram stored|implicit --carrier-format auto|lists|bits --plink-decode device|host\n"
+    "                   --plink-ref-allele a1|a2 --stream-rows R\n"
     "                   --no-stream --join-partitions P --spill-dir D --spark-output-layout --ingest-threads T\n"
     "                   --parse-only --dump-similarity FILE\n"
     "  --project-input-path <file.vcf[.gz]> [more]\n"
@@ -154,6 +159,10 @@ Conf parse(int argc, char** argv) {
       c.carrier_format = one(i);
       if (c.carrier_format != "auto" && c.carrier_format != "lists" && c.carrier_format != "bits") die("--carrier-format takes auto, lists or bits");
     }
+    else if (a == "--gram") {
+      c.gram = one(i);
+      if (c.gram != "stored" && c.gram != "implicit") die("--gram takes stored or implicit");
+    }
     else if (a == "--parse-only") c.parse_only = true;
     else if (a == "--dump-similarity") c.dump_similarity = one(i);
     else if (a == "--ingest-threads") c.ingest_threads = std::atoi(one(i).c_str());
@@ -172,6 +181,17 @@ Conf parse(int argc, char** argv) {
   if (c.layout == "strips" && c.reduce == "rccl") die("--layout strips has no reduction step: it cannot take --reduce rccl");
   if (c.plink_decode != "device" && c.plink_decode != "host") die("--plink-decode takes device or host");
   if (c.stream_rows < 1) die("--stream-rows must be >= 1");
+  if (c.gram == "implicit") {
+    // one operator engine holds the carrier bitsets of every variant: what needs S, or several engines, is refused here,
+    // before any file is read or any engine exists
+    if (c.gpus > 1) die("--gram implicit runs on one operator engine: it cannot take --gpus " + std::to_string(c.gpus));
+    if (c.layout == "strips") die("--gram implicit holds no similarity matrix to tile: it cannot take --layout strips");
+    if (!c.project_input_path.empty()) die("--gram implicit holds no similarity matrix to project against: it cannot take --project-input-path");
+    if (c.carrier_format == "lists") die("--gram implicit stores carrier bitsets: it cannot take --carrier-format lists");
+    if (!c.dump_similarity.empty()) die("--gram implicit never forms the similarity matrix: it cannot take --dump-similarity");
+    c.carrier_format = "bits";
+    c.layout = "full";
+  }
   return c;
 }
 
@@ -894,6 +914,9 @@ struct CarrierFeeder {
       std::thread packer;
       if (r1 < rows)
         packer = std::thread([&, r1, r2, k] { ok_next = pack(idx, offs, r1, r2, n, words, reinterpret_cast<uint32_t*>(pin[(k + 1) & 1]), threads > 1 ? threads - 1 : 1); });
+      if (!ok_cur && conf.gram == "implicit")
+        die("--gram implicit: a carrier list names a callset twice (a merge of sets with a repeated key); a carrier bitset cannot "
+            "carry that multiplicity -- use --gram stored");
       if (ok_cur) {
         check(ctx, pcoa_accumulate_bits(ctx, reinterpret_cast<const uint32_t*>(pin[k & 1]), r1 - r0, words, 0), "getSimilarityMatrix");
         rows_as_bits += r1 - r0;
@@ -1137,11 +1160,13 @@ std::vector<pcoa_ctx*> run_engines(const Conf& conf, int32_t n, const std::vecto
   const bool tiled = !strips.empty();
   std::vector<pcoa_ctx*> ctx((size_t)k, nullptr);
   for (int g = 0; g < k; ++g) {
+    const bool op = conf.gram == "implicit";
     const int rc = tiled ? pcoa_create_strip(&ctx[(size_t)g], n, strips[(size_t)g].first, strips[(size_t)g].second,
                                              conf.gpu_map[(size_t)g], PCOA_FLAG_DEFAULT)
+                   : op  ? pcoa_create_operator(&ctx[(size_t)g], n, conf.gpu_map[(size_t)g], PCOA_FLAG_DEFAULT)
                          : pcoa_create(&ctx[(size_t)g], n, conf.gpu_map[(size_t)g], PCOA_FLAG_DEFAULT);
     if (rc != PCOA_OK)
-      die(std::string(tiled ? "pcoa_create_strip" : "pcoa_create") + " on device " + std::to_string(conf.gpu_map[(size_t)g]) +
+      die(std::string(tiled ? "pcoa_create_strip" : op ? "pcoa_create_operator" : "pcoa_create") + " on device " + std::to_string(conf.gpu_map[(size_t)g]) +
           ": " + pcoa_last_error(nullptr));
   }
   // operand buffers and the computePca workspace now, not inside the first accumulate calls (pcoa_reserve: the warm-up a Spark
@@ -1187,7 +1212,7 @@ std::vector<pcoa_ctx*> run_engines(const Conf& conf, int32_t n, const std::vecto
     for (int g = 1; g < k; ++g) check(ctx[0], pcoa_gram_reduce_from(ctx[0], ctx[(size_t)g]), "reduce");
     *how = "peer reduction of " + std::to_string(k) + " engines into engine 0";
   } else {
-    *how = "one engine";
+    *how = conf.gram == "implicit" ? "one operator engine: the carrier bitsets kept, no similarity matrix" : "one engine";
   }
   for (int g = 0; g < (tiled ? k : 1); ++g) check(ctx[(size_t)g], pcoa_gram_finalize(ctx[(size_t)g]), "getSimilarityMatrix");
   *feed_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_feed).count();
@@ -1641,6 +1666,10 @@ int main(int argc, char** argv) {
     }
     std::fprintf(stderr, "Variants accumulated: %lld; Gram kernel %.3f ms; PCoA %.3f ms\n", (long long)t.gram_variants,
                  1e3 * gram_s, 1e3 * t.compute_total_seconds);
+    int64_t op_variants = 0, op_bytes = 0;
+    if (pcoa_operator_info(ctx, &op_variants, &op_bytes) == 1)
+      std::fprintf(stderr, "Implicit similarity operator: %lld variants in %.1f MB of carrier bitsets, %d Lanczos steps over S v = X^T (X v)\n",
+                   (long long)op_variants, op_bytes / 1e6, t.lanczos_steps);
     if (!strips.empty())
       std::fprintf(stderr, "computePca over %zu strip owners: %d Lanczos steps (each one product over every owner)\n", owners.size(),
                    t.lanczos_steps);

@@ -289,6 +289,11 @@ class PcaConf(object):
                        help="full: every rank a whole partial S over its share of the variants, then the all-reduce; strips: "
                             "rank r owns the columns strip_ranges(N, K)[r] of S and reads every variant, nothing is reduced; "
                             "auto: strips only when K > 1 and S does not fit (pcoa_plan_layout)")
+        p.add_argument("--gram", choices=["stored", "implicit"], default="stored",
+                       help="stored: the N x N similarity matrix is accumulated and decomposed; implicit: one operator engine "
+                            "(pcoa_create_operator) keeps the carrier bitsets and computePca runs over the products "
+                            "S v = X^T (X v), no N x N matrix exists.  One GPU, full layout; there is no auto: which form is "
+                            "faster at which N has not been measured")
         p.add_argument("--dump-similarity", type=str, default=None,
                        help="write S (N x N int64, little-endian, row-major) to this file (parity tests)")
         p.add_argument("--project-input-path", type=str, nargs="+", default=None,
@@ -513,6 +518,10 @@ class VariantsPcaDriver(object):
             t = self.engine.timings()
             out.write("Variants accumulated: %d; Gram kernel %.3f ms; PCoA %.3f ms\n" %
                       (t["gram_variants"], 1e3 * t["gram_kernel_seconds"], 1e3 * t["compute_total_seconds"]))
+            info = self.engine.operator_info()
+            if info is not None:
+                out.write("Implicit similarity operator: %d variants in %.1f MB of carrier bitsets, %d Lanczos steps over "
+                          "S v = X^T (X v)\n" % (info[0], info[1] / 1e6, t["lanczos_steps"]))
 
     def stop(self):
         if self.engine is not None:
@@ -614,6 +623,48 @@ def resolve_layout(conf, n, world, devices):
     return ranges if layout == "strips" else None
 
 
+def check_gram_conf(conf):
+    """--gram implicit: one operator engine holds the carrier bitsets of every variant.  What needs S, or several engines, is
+    refused before any file is read or any device is touched."""
+    if conf.gram != "implicit":
+        return
+    if conf.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise SystemExit("VariantsPcaDriver: --gram implicit runs on one operator engine: it cannot take --gpus %d"
+                         % max(conf.gpus, int(os.environ.get("WORLD_SIZE", "1"))))
+    if conf.layout == "strips":
+        raise SystemExit("VariantsPcaDriver: --gram implicit holds no similarity matrix to tile: it cannot take --layout strips")
+    if conf.project_input_path:
+        raise SystemExit("VariantsPcaDriver: --gram implicit holds no similarity matrix to project against: it cannot take "
+                         "--project-input-path")
+    if conf.dump_similarity:
+        raise SystemExit("VariantsPcaDriver: --gram implicit never forms the similarity matrix: it cannot take --dump-similarity")
+
+
+def calls_as_bits(call_rdd, n):
+    """--gram implicit: an RDD[Seq[Int]] in any of the forms getCallsRdd returns, as what an operator engine stores -- raw
+    PLINK rows and bitsets as they are, carrier lists packed into bitsets.  A list that names a callset twice (a merge of sets
+    with a repeated key; the reference counts it with multiplicity, VariantsPca.scala:187) cannot be a bitset: refused."""
+    if isinstance(call_rdd, tuple) and isinstance(call_rdd[0], str):
+        return call_rdd
+    if isinstance(call_rdd, tuple):
+        idx, offs = np.asarray(call_rdd[0], dtype=np.int64), np.asarray(call_rdd[1], dtype=np.int64)
+        idx = idx[offs[0]:offs[-1]]
+        rows = np.repeat(np.arange(offs.size - 1, dtype=np.int64), np.diff(offs))
+    else:
+        rows = np.repeat(np.arange(len(call_rdd), dtype=np.int64), [len(c) for c in call_rdd])
+        idx = np.fromiter((i for c in call_rdd for i in c), dtype=np.int64, count=int(rows.size))
+    n_rows = (len(call_rdd[1]) - 1) if isinstance(call_rdd, tuple) else len(call_rdd)
+    if idx.size and (idx.min() < 0 or idx.max() >= n):
+        raise IndexError("callset index outside [0, %d) in a carrier list" % n)   # mapping(call.callsetId) throws (:59)
+    key = rows * n + idx
+    if np.unique(key).size != key.size:
+        raise SystemExit("VariantsPcaDriver: --gram implicit: a carrier list names a callset twice; a carrier bitset cannot carry "
+                         "that multiplicity -- use --gram stored")
+    bits = np.zeros((n_rows, (n + 31) // 32), dtype=np.uint32)
+    np.bitwise_or.at(bits, (rows, idx >> 5), (np.uint32(1) << (idx & 31).astype(np.uint32)))
+    return ("bits", bits)
+
+
 def check_projection_conf(conf):
     """--project-input-path: what cannot be served is refused before any file is read or any device is touched."""
     from . import ingest
@@ -694,6 +745,7 @@ def main_projection(conf):
 def main(args):
     """VariantsPcaDriver.main (VariantsPca.scala:38-50)."""
     conf = PcaConf(args)
+    check_gram_conf(conf)
     if conf.project_input_path:
         check_projection_conf(conf)
         return main_projection(conf)
@@ -731,6 +783,14 @@ def main(args):
     filtered = [driver.filterDataset(d) for d in driver.data]
     calls_rdd = driver.getCallsRdd(filtered)
     n = len(driver.indexes)
+    if conf.gram == "implicit":
+        driver.engine = calculate_similarity_matrix(calls_as_bits(calls_rdd, n), n,
+                                                    engine=PcoaEngine(n, device=conf.gpu, operator=True))
+        result = driver.computePca(driver.engine)
+        driver.emitResult(result)
+        driver.reportIoStats(sys.stderr)
+        driver.stop()
+        return 0
     if world > 1:
         import torch.distributed as td
         devices = [int(t) for t in conf.rank_devices.split(",")] if conf.rank_devices else list(range(world))
