@@ -35,7 +35,7 @@ extern "C" {
 #endif
 
 #define PCOA_VERSION_MAJOR 0
-#define PCOA_VERSION_MINOR 7
+#define PCOA_VERSION_MINOR 8
 
 typedef struct pcoa_ctx pcoa_ctx;
 
@@ -150,6 +150,10 @@ typedef struct pcoa_timings {
   int64_t operator_products;      /* products y = S v / y = B v applied since pcoa_create_operator / pcoa_reset_timings       */
   double operator_matvec_seconds; /* HIP-event time of those products (both passes, the combine stages, the centring terms)   */
   int64_t operator_store_bytes;   /* HBM the bit store holds now (whole segments); 0 on every other kind of ctx               */
+  /* ---- 0.8: S of a sample subset (pcoa_create_subset); counted on the ctx that call returned ---- */
+  double subset_seconds;          /* HIP-event time of the gathers that filled this ctx's S                                   */
+  int64_t subset_bytes;           /* bytes those gathers read and wrote: 8 m^2 for the int32 matrix, 16 m^2 more for an int64
+                                     part                                                                                     */
 } pcoa_timings;
 #define PCOA_TIMINGS_R03_BYTES 192  /* offsetof(pcoa_timings, csr_stage_seconds): what pcoa_get_timings writes */
 
@@ -267,6 +271,35 @@ int pcoa_operator_row_sums(pcoa_ctx* ctx, int64_t* out_n);
  * combined by one all-reduce of an N-vector per product.  Replaces: the products inside MLlib's computePrincipalComponents
  * (VariantsPca.scala:224-227). */
 int pcoa_operator_matvec_device(pcoa_ctx* ctx, const double* v_dev, double* y_dev, int centred);
+
+/* ---- PCoA over a sample subset of a stored S ------------------------------------------------------------------------------
+ * For a kept index set I, S[I, I] is exactly the similarity matrix of the reduced cohort (an entry counts the variants two
+ * samples share; no other sample enters it), and the centring and the eigenpairs are functions of that sub-matrix alone.  A
+ * round of outlier removal -- computePca, drop the samples far out on a leading axis, computePca again -- therefore costs one
+ * gather of S (8 m^2 bytes of traffic) plus one pcoa_compute, not one more pass over every variant.
+ *
+ * pcoa_create_subset: a NEW full engine over n_keep samples, on src's device and with src's create flags, whose S is
+ *   S_new(a, b) = S_src(keep[a], keep[b]).
+ *   keep:   host array of n_keep >= 1 STRICTLY INCREASING indices in [0, pcoa_n_samples(src)); consumed when the call returns.
+ *           NULL, n_keep < 1, an index out of range, an unsorted or a repeated index: PCOA_ERR_INVALID_ARG, found on the host
+ *           before any device work.
+ *   src:    an ordinary full engine (pcoa_create, or the result of this call).  A strip owner or an operator ctx:
+ *           PCOA_ERR_STATE.  src is finalized and its input checks are read first (an S that a check has invalidated is never
+ *           subset; that error comes back as it would from pcoa_gram_finalize).  src is otherwise unchanged: it may be fed
+ *           further, read, subset again or destroyed afterwards.
+ *   result: an ordinary engine in every respect -- pcoa_compute, pcoa_gram_read*, pcoa_center_read_f64, pcoa_gram_reduce_from,
+ *           pcoa_create_subset again and further pcoa_accumulate_* calls over n_keep samples all work on it.  It carries src's
+ *           bound of the int32 entries (what the int64 fold and the int32 reductions go by) and src's gram_variants; where src
+ *           has an int64 part that is gathered too and then narrowed back into the int32 matrix if every kept entry fits
+ *           (pcoa_timings.narrowed_to_int32), as every other int64 hand-over is.  Timings: subset_seconds / subset_bytes.
+ *   memory: the peak is S of src PLUS S of the result (4 n^2 + 4 n_keep^2 bytes; 12 of each where src has an int64 part).
+ *           Allocation failure: PCOA_ERR_OUT_OF_MEMORY, *out = NULL, src usable.  An in-place or masked form for an S that
+ *           fills the HBM does not exist.
+ * Errors are reported on src (pcoa_last_error(src)); with src == NULL or out == NULL, on pcoa_last_error(NULL).  On any
+ * failure *out = NULL.  Synchronising on both engines.
+ * Extends: computePca (VariantsPca.scala:198-231) to a sub-cohort of the matrix getSimilarityMatrix built, the step a
+ * smartpca-style outlier loop repeats. */
+int pcoa_create_subset(pcoa_ctx** out, pcoa_ctx* src, const int32_t* keep, int32_t n_keep);
 
 /* ---- layout of S over the engines of one job ------------------------------------------------------------------------
  * FULL: every engine holds a whole N x N partial S (4 N^2 bytes) for its share of the variants; the partials are reduced

@@ -88,6 +88,8 @@ class PcoaTimings(ctypes.Structure):
         ("operator_products", ctypes.c_int64),
         ("operator_matvec_seconds", ctypes.c_double),
         ("operator_store_bytes", ctypes.c_int64),
+        ("subset_seconds", ctypes.c_double),
+        ("subset_bytes", ctypes.c_int64),
     ]
 
 
@@ -110,6 +112,7 @@ _SIGNATURES = [
     ("pcoa_create", ctypes.c_int, [ctypes.POINTER(_vp), _i32, _i32, ctypes.c_uint32]),
     ("pcoa_create_strip", ctypes.c_int, [ctypes.POINTER(_vp), _i32, _i32, _i32, _i32, ctypes.c_uint32]),
     ("pcoa_create_operator", ctypes.c_int, [ctypes.POINTER(_vp), _i32, _i32, ctypes.c_uint32]),
+    ("pcoa_create_subset", ctypes.c_int, [ctypes.POINTER(_vp), _vp, _vp, _i32]),
     ("pcoa_operator_info", ctypes.c_int, [_vp, ctypes.POINTER(_i64), ctypes.POINTER(_i64)]),
     ("pcoa_operator_row_sums", ctypes.c_int, [_vp, _vp]),
     ("pcoa_operator_matvec_device", ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int]),

@@ -1,6 +1,6 @@
 // pcoa_capi.hip -- the C ABI of include/pcoa.h on top of the HIP kernels: an engine's life (create / destroy / reset /
 // reserve / set_stream / sync), error reporting, and the timings.  The rest of the ABI lives in capi_accumulate.hip,
-// capi_reduce.hip, capi_compute.hip and devmem.hip (map: pcoa_ctx.h).  There is deliberately NO CPU fallback: without a HIP
+// capi_reduce.hip, capi_compute.hip, capi_operator.hip, capi_subset.hip and devmem.hip (map: pcoa_ctx.h).  There is deliberately NO CPU fallback: without a HIP
 // device pcoa_create fails with PCOA_ERR_NO_DEVICE.
 #include <cstdio>
 #include <cstring>
@@ -74,12 +74,9 @@ void drain_events(pcoa_ctx* c, bool wait) {
 }  // namespace pcoa
 
 // ================================================================================================
-extern "C" {
-
-const char* pcoa_version(void) { return "pcoa_hip 0.7 (gfx950)"; }
-
+// zero_s = false (pcoa_create_subset): S is allocated but not zeroed -- the caller overwrites every entry before anything reads it
 static int create_impl(pcoa_ctx** out, int32_t n_samples, int32_t device_ordinal, uint32_t flags, int32_t col0, int32_t cols,
-                       bool op = false) {
+                       bool op = false, bool zero_s = true) {
   if (!out) return fail(nullptr, PCOA_ERR_INVALID_ARG, "out is NULL");
   *out = nullptr;
   if (n_samples <= 0) return fail(nullptr, PCOA_ERR_INVALID_ARG, "n_samples must be positive");
@@ -160,7 +157,7 @@ static int create_impl(pcoa_ctx** out, int32_t n_samples, int32_t device_ordinal
   const size_t nn = s_count(c);
   if (!op) {
     if ((e = dev_alloc((void**)&c->s32, sizeof(int32_t) * nn, c->device)) != hipSuccess) return bail(e, "allocation of S");
-    if ((e = hipMemsetAsync(c->s32, 0, sizeof(int32_t) * nn, c->stream)) != hipSuccess) return bail(e, "memset(S)");
+    if (zero_s && (e = hipMemsetAsync(c->s32, 0, sizeof(int32_t) * nn, c->stream)) != hipSuccess) return bail(e, "memset(S)");
   }
   if ((e = dev_alloc((void**)&c->zeros, 4096, c->device)) != hipSuccess) return bail(e, "allocation of the zero page");
   if ((e = hipMemsetAsync(c->zeros, 0, 4096, c->stream)) != hipSuccess) return bail(e, "memset(zeros)");
@@ -173,6 +170,17 @@ static int create_impl(pcoa_ctx** out, int32_t n_samples, int32_t device_ordinal
   *out = c;
   return PCOA_OK;
 }
+
+namespace pcoa {
+// pcoa_create's path with S left as allocated: pcoa_create_subset's gather writes every entry (capi_subset.hip)
+int create_full_engine_unfilled(pcoa_ctx** out, int32_t n_samples, int32_t device_ordinal, uint32_t flags) {
+  return create_impl(out, n_samples, device_ordinal, flags, 0, -1, false, false);
+}
+}  // namespace pcoa
+
+extern "C" {
+
+const char* pcoa_version(void) { return "pcoa_hip 0.8 (gfx950)"; }
 
 int pcoa_create(pcoa_ctx** out, int32_t n_samples, int32_t device_ordinal, uint32_t flags) {
   return create_impl(out, n_samples, device_ordinal, flags, 0, -1);
@@ -353,6 +361,8 @@ int pcoa_get_timings_sized(pcoa_ctx* c, pcoa_timings* out_user, size_t out_size)
   out->operator_products = c->op_products;
   out->operator_matvec_seconds = c->tsec[T_OPERATOR];
   out->operator_store_bytes = operator_store_bytes(c);
+  out->subset_seconds = c->tsec[T_SUBSET];
+  out->subset_bytes = c->subset_bytes;
   std::memcpy(out_user, out, std::min(out_size, sizeof(full)));
   return PCOA_OK;
 }
@@ -381,6 +391,7 @@ int pcoa_reset_timings(pcoa_ctx* c) {
   c->pipeline_launches = 0;
   c->evensplit_launches = 0;
   c->op_products = 0;
+  c->subset_bytes = 0;
   return PCOA_OK;
 }
 

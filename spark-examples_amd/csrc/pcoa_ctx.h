@@ -8,6 +8,7 @@
 //   capi_reduce.hip      RCCL, reductions, export / import / read / load
 //   capi_compute.hip     the eigensolver workspace, computePca, strips, projection
 //   capi_operator.hip    the implicit similarity operator: the bit store, its products, computePca over it
+//   capi_subset.hip      pcoa_create_subset: a new engine whose S is S[I, I] of another
 //   pcoa_capi.hip        create / destroy, errors, timings
 #pragma once
 
@@ -16,7 +17,7 @@
 
 #include "pcoa_internal.h"
 
-enum TimeCat { T_GRAM = 0, T_DENSIFY, T_SYNTH, T_FINALIZE, T_CENTER, T_TRIDIAG, T_EIG, T_BACK, T_PACK, T_LANCZOS, T_ALLREDUCE, T_OPERATOR, T_NCAT };
+enum TimeCat { T_GRAM = 0, T_DENSIFY, T_SYNTH, T_FINALIZE, T_CENTER, T_TRIDIAG, T_EIG, T_BACK, T_PACK, T_LANCZOS, T_ALLREDUCE, T_OPERATOR, T_SUBSET, T_NCAT };
 
 struct EventPair {
   hipEvent_t a, b;
@@ -72,6 +73,7 @@ struct pcoa_ctx {
   double* op_ws = nullptr;         // t, the passes' partials, the two dots (sized by the store, lazy)
   int64_t op_ws_cap = 0;
   int64_t op_products = 0;
+  int64_t subset_bytes = 0;        // bytes the gathers of pcoa_create_subset moved into this ctx (read + written)
   int device = 0;
   uint32_t flags = 0;
   int num_cu = 256;
@@ -257,6 +259,7 @@ int regrow(pcoa_ctx* c, void** buf, size_t bytes, bool sync_ctx_stream);
 // ---- pcoa_capi.hip: errors (c == nullptr: the thread's create error) and the timing events
 int fail(pcoa_ctx* c, int code, const std::string& msg);
 int hip_fail(pcoa_ctx* c, hipError_t e, const char* what);
+int create_full_engine_unfilled(pcoa_ctx** out, int32_t n_samples, int32_t device_ordinal, uint32_t flags);   // pcoa_create, S not zeroed
 hipEvent_t get_event(pcoa_ctx* c);
 void drain_events(pcoa_ctx* c, bool wait);
 

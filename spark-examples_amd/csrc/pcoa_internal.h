@@ -156,6 +156,16 @@ hipError_t launch_synth_kbits(uint64_t seed, const uint32_t* thresholds_dev, con
                               int64_t first_variant, int64_t nv, int32_t n, int32_t npad, int8_t* p, int64_t nblk_out,
                               hipStream_t stream);
 
+// ---- S of a sample subset (subset.hip): dst[a][b] = src[keep[a]][keep[b]], dst [m][m], src [n][n], keep_dev m strictly
+// increasing indices in [0, n) on the device (the caller validates them).  A workgroup takes kSubsetBandRows dst rows x
+// kSubsetTileCols dst columns; every entry of dst is written exactly once
+constexpr int32_t kSubsetTileCols = 1024;
+constexpr int32_t kSubsetBandRows = 32;
+hipError_t launch_subset_gather_i32(const int32_t* src, int32_t n, const int32_t* keep_dev, int32_t m, int32_t* dst,
+                                    hipStream_t stream);
+hipError_t launch_subset_gather_i64(const int64_t* src, int32_t n, const int32_t* keep_dev, int32_t m, int64_t* dst,
+                                    hipStream_t stream);
+
 // ---- implicit similarity operator (operator_bits.hip): y = X^T (X v) from the carrier bitsets, S never formed -------------
 // The store is a list of segments, each rows x operator_pitch_words(n) words; bits of samples >= n and the pitch's padding are
 // zero.  A product's additions are ordered by sample group (kOperatorGroupWords word columns), segment and range of

@@ -361,6 +361,23 @@ class PcoaEngine(object):
         """self.S += other.S (two engines of this process; pcoa_gram_reduce_from: peer copy + int64 add, no collective)."""
         self._check(self._lib.pcoa_gram_reduce_from(self._ctx, other._ctx))
 
+    def subset(self, keep):
+        """A new PcoaEngine over the samples `keep` (strictly increasing indices into this engine's samples) whose S is
+        S[keep][:, keep] of this one, gathered on the device (pcoa_create_subset): the similarity matrix of the reduced cohort
+        without feeding a variant again.  This engine is unchanged; the peak is both matrices resident."""
+        idx = np.ascontiguousarray(keep, dtype=np.int32)
+        if idx.ndim != 1:
+            raise ValueError("keep must be one-dimensional")
+        ctx = ctypes.c_void_p()
+        self._check(self._lib.pcoa_create_subset(ctypes.byref(ctx), self._ctx, _ptr(idx) if idx.size else None, int(idx.size)))
+        sub = object.__new__(PcoaEngine)
+        sub._lib, sub._ctx = self._lib, ctx
+        sub.strip, sub.operator = None, False
+        sub.n = sub.cols = int(idx.size)
+        sub.device = self.device
+        sub._keepalive = []
+        return sub
+
     def export_device(self, dst_ptr):
         self._check(self._lib.pcoa_gram_export_device_i64(self._ctx, ctypes.c_void_p(int(dst_ptr))))
 

@@ -18,6 +18,7 @@
 #include <algorithm>
 #include <atomic>
 #include <charconv>
+#include <cerrno>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -90,6 +91,9 @@ struct Conf {  // PcaConf / GenomicsConf (GenomicsConf.scala:31-101), same flag 
                                         // operator engine (pcoa_create_operator) keeps the carrier bitsets and computePca runs over the
                                         // products S v = X^T (X v): no N x N matrix exists.  No auto: which form is faster at which N
                                         // has not been measured
+  int outlier_iterations = 0;           // --outlier-iterations K: up to K rounds of outlier removal around computePca; a round replaces the engine by
+                                        // its subset over the kept samples (pcoa_create_subset: one gather of S, no variant read twice).  0 = off
+  double outlier_sigma = 6.0;           // --outlier-sigma X: a sample further than X population standard deviations from the mean of an axis goes
 };
 
 const char* kUsage =
@@ -101,6 +105,8 @@ const char* kUsage =
     "                   --plink-ref-allele a1|a2 --stream-rows R\n"
     "                   --no-stream --join-partitions P --spill-dir D --spark-output-layout --ingest-threads T\n"
     "                   --parse-only --dump-similarity FILE\n"
+    "                   --outlier-iterations K --outlier-sigma X (K rounds: samples beyond X sd on a principal component are\n"
+    "                   removed and computePca runs again on S[kept, kept]; one engine, stored S, full layout)\n"
     "  --project-input-path <file.vcf[.gz]> [more]\n"
     "                   place these samples onto the principal coordinates of the --input-path cohort instead of\n"
     "                   decomposing the union (one GPU, VCF inputs, full layout)\n";
@@ -109,6 +115,8 @@ const char* kUsage =
   std::cerr << "VariantsPcaDriver: " << m << std::endl;
   std::exit(2);
 }
+
+const char* kStripsRefuseOutliers = "--outlier-iterations subsets one whole similarity matrix on one engine: it cannot take --layout strips";
 
 Conf parse(int argc, char** argv) {
   Conf c;
@@ -163,6 +171,20 @@ Conf parse(int argc, char** argv) {
       c.gram = one(i);
       if (c.gram != "stored" && c.gram != "implicit") die("--gram takes stored or implicit");
     }
+    else if (a == "--outlier-iterations") {   // a value that does not parse must not silently mean "off"
+      const std::string v = one(i);
+      char* end = nullptr;
+      errno = 0;
+      const long k = std::strtol(v.c_str(), &end, 10);
+      if (v.empty() || *end != 0 || errno != 0 || k > 1000000 || k < -1000000) die("--outlier-iterations takes an integer >= 0 (0 = off), not '" + v + "'");
+      c.outlier_iterations = (int)k;
+    }
+    else if (a == "--outlier-sigma") {
+      const std::string v = one(i);
+      char* end = nullptr;
+      c.outlier_sigma = std::strtod(v.c_str(), &end);
+      if (v.empty() || *end != 0) die("--outlier-sigma (the threshold of --outlier-iterations) takes a number, not '" + v + "'");
+    }
     else if (a == "--parse-only") c.parse_only = true;
     else if (a == "--dump-similarity") c.dump_similarity = one(i);
     else if (a == "--ingest-threads") c.ingest_threads = std::atoi(one(i).c_str());
@@ -181,6 +203,15 @@ Conf parse(int argc, char** argv) {
   if (c.layout == "strips" && c.reduce == "rccl") die("--layout strips has no reduction step: it cannot take --reduce rccl");
   if (c.plink_decode != "device" && c.plink_decode != "host") die("--plink-decode takes device or host");
   if (c.stream_rows < 1) die("--stream-rows must be >= 1");
+  // --outlier-iterations: what cannot be served is refused here, before any file is read or any engine exists
+  if (c.outlier_iterations < 0) die("--outlier-iterations must be >= 0 (0 = off)");
+  if (!(c.outlier_sigma > 0) || !std::isfinite(c.outlier_sigma))
+    die("--outlier-sigma must be a finite number > 0 (the threshold of --outlier-iterations)");
+  if (c.outlier_iterations > 0) {
+    if (c.gram == "implicit") die("--outlier-iterations subsets a stored similarity matrix: it cannot take --gram implicit");
+    if (c.layout == "strips") die(kStripsRefuseOutliers);
+    if (!c.project_input_path.empty()) die("--outlier-iterations decomposes the cohort it is given: it cannot take --project-input-path");
+  }
   if (c.gram == "implicit") {
     // one operator engine holds the carrier bitsets of every variant: what needs S, or several engines, is refused here,
     // before any file is read or any engine exists
@@ -1240,6 +1271,30 @@ void emit_result(const Conf& conf, std::vector<OutRow>& rows) {
   }
 }
 
+// The outlier rule of --outlier-iterations, as variants_pca.py's outlier_rule states it: comps is [num_pc][n].  Per axis:
+// mean = (sum of the n entries) / n, sd = sqrt((sum of the squared deviations from the mean) / n) -- the population standard
+// deviation --, both sums added left to right in double; sample i is removed if |u[i] - mean| > sigma * sd on any axis with
+// sd > 0.
+std::vector<char> outlier_rule(const double* comps, int num_pc, int32_t n, double sigma) {
+  std::vector<char> removed((size_t)n, 0);
+  for (int c = 0; c < num_pc; ++c) {
+    const double* u = comps + (size_t)c * (size_t)n;
+    double sum = 0.0;
+    for (int32_t i = 0; i < n; ++i) sum += u[i];
+    const double mean = sum / n;
+    double ss = 0.0;
+    for (int32_t i = 0; i < n; ++i) {
+      const double d = u[i] - mean;
+      ss += d * d;
+    }
+    const double sd = std::sqrt(ss / n);
+    if (!(sd > 0)) continue;
+    for (int32_t i = 0; i < n; ++i)
+      if (std::fabs(u[i] - mean) > sigma * sd) removed[(size_t)i] = 1;
+  }
+  return removed;
+}
+
 int main(int argc, char** argv) {
   const auto t_start = std::chrono::steady_clock::now();
   Conf conf = parse(argc, argv);
@@ -1430,6 +1485,7 @@ int main(int argc, char** argv) {
     if (pcoa_plan_layout(n, k, free_bytes.data(), request, &layout, col0.data(), cols.data()) != PCOA_OK)
       die(std::string("pcoa_plan_layout: ") + pcoa_last_error(nullptr));
     if (layout == PCOA_LAYOUT_STRIPS) {
+      if (conf.outlier_iterations > 0) die(kStripsRefuseOutliers);   // --layout auto resolved to strips
       if (conf.reduce == "rccl") die("the strip layout has no reduction step: it cannot take --reduce rccl");
       for (int g = 0; g < k; ++g) strips.emplace_back(col0[(size_t)g], cols[(size_t)g]);
     }
@@ -1595,8 +1651,8 @@ int main(int argc, char** argv) {
     pcoa_destroy(ref);
     return 0;
   }
-  const std::vector<pcoa_ctx*> owners = run_engines(conf, n, strips, feed, &how, &feed_s, prepare);
-  pcoa_ctx* const ctx = owners[0];
+  std::vector<pcoa_ctx*> owners = run_engines(conf, n, strips, feed, &how, &feed_s, prepare);
+  pcoa_ctx* ctx = owners[0];   // (--outlier-iterations replaces it by its subsets)
   if (stream_join) {
     std::fprintf(stderr, "%zu variant set(s) through %d key partitions: %lld records, %.1f MB of spill files in %s\n",
                  conf.input_path.size(), spill.parts, (long long)spilled_records, spill.bytes / 1e6, spill.dir.c_str());
@@ -1643,23 +1699,63 @@ int main(int argc, char** argv) {
     die("computePca emits exactly PC1 and PC2 (VariantsPca.scala:229-230); --num-pc must be >= 2");
   std::vector<double> comps((size_t)conf.num_pc * (size_t)n), lam((size_t)conf.num_pc);
   int32_t nonzero = 0;
-  if (strips.empty())
-    check(ctx, pcoa_compute(ctx, conf.num_pc, comps.data(), lam.data(), &nonzero), "computePca");
-  else
+  double gram_s_before = 0.0;             // Gram kernel seconds of engines that --outlier-iterations has replaced
+  std::vector<int32_t> kept((size_t)n);   // original index of every sample of the current cohort
+  for (int32_t i = 0; i < n; ++i) kept[(size_t)i] = i;
+  if (!strips.empty()) {
     check(ctx, pcoa_compute_strips(owners.data(), (int32_t)owners.size(), conf.num_pc, comps.data(), lam.data(), &nonzero), "computePca");
-  std::printf("Non zero rows in matrix: %d / %d.\n", nonzero, n);
+  } else {
+    // --outlier-iterations K: computePca, the rule, and while something is removed and fewer than K rounds have removed
+    // something, the engine is replaced by its subset over the kept samples and computePca runs again.  The final cohort
+    // always gets a computePca.  K = 0: the one computePca of the reference
+    for (int done = 0;;) {
+      const int32_t m = (int32_t)kept.size();
+      check(ctx, pcoa_compute(ctx, conf.num_pc, comps.data(), lam.data(), &nonzero), "computePca");
+      if (done == conf.outlier_iterations) break;
+      const std::vector<char> removed = outlier_rule(comps.data(), conf.num_pc, m, conf.outlier_sigma);
+      std::vector<int32_t> keep, kept_next;
+      std::string gone_names;
+      for (int32_t a = 0; a < m; ++a) {
+        if (removed[(size_t)a]) {
+          gone_names += (gone_names.empty() ? ": " : ", ") + names[(size_t)kept[(size_t)a]];
+        } else {
+          keep.push_back(a);
+          kept_next.push_back(kept[(size_t)a]);
+        }
+      }
+      const int32_t gone = m - (int32_t)keep.size();
+      std::fprintf(stderr, "Outlier round %d: removed %d sample(s)%s\n", done + 1, gone, gone_names.c_str());
+      if (gone == 0) break;
+      const int32_t least = std::max(3, conf.num_pc + 1);
+      if ((int32_t)keep.size() < least)
+        die("--outlier-iterations: round " + std::to_string(done + 1) + " would leave " + std::to_string(keep.size()) + " of " +
+            std::to_string(m) + " samples, fewer than the " + std::to_string(least) + " that " + std::to_string(conf.num_pc) +
+            " principal components need; raise --outlier-sigma");
+      pcoa_ctx* sub = nullptr;
+      check(ctx, pcoa_create_subset(&sub, ctx, keep.data(), (int32_t)keep.size()), "pcoa_create_subset");
+      pcoa_timings tp;   // the Gram kernels ran on the predecessor: its time goes into the closing line
+      if (pcoa_get_timings(ctx, &tp) == PCOA_OK) gram_s_before += tp.gram_kernel_seconds;
+      pcoa_destroy(ctx);
+      ctx = owners[0] = sub;
+      kept.swap(kept_next);
+      ++done;
+    }
+  }
+  const int32_t n_out = (int32_t)kept.size();
+  std::printf("Non zero rows in matrix: %d / %d.\n", nonzero, n_out);
 
-  // emitResult (:233-246)
+  // emitResult (:233-246): the kept samples, in the original order
   std::vector<OutRow> rows;
-  for (int32_t i = 0; i < n; ++i)
-    rows.push_back({names[(size_t)i], ids[(size_t)i].substr(0, ids[(size_t)i].find('-')), comps[(size_t)i],
-                    comps[(size_t)i + (size_t)n]});
+  for (int32_t a = 0; a < n_out; ++a) {
+    const size_t i = (size_t)kept[(size_t)a];
+    rows.push_back({names[i], ids[i].substr(0, ids[i].find('-')), comps[(size_t)a], comps[(size_t)a + (size_t)n_out]});
+  }
   emit_result(conf, rows);
 
   // reportIoStats (:48) / stop (:49)
   pcoa_timings t;
   if (pcoa_get_timings(ctx, &t) == PCOA_OK) {
-    double gram_s = t.gram_kernel_seconds;   // (strip layout: summed over the owners)
+    double gram_s = t.gram_kernel_seconds + gram_s_before;   // (strip layout: summed over the owners)
     for (size_t g = 1; g < owners.size(); ++g) {
       pcoa_timings tg;
       if (pcoa_get_timings(owners[g], &tg) == PCOA_OK) gram_s += tg.gram_kernel_seconds;

@@ -240,6 +240,32 @@ def _as_engine(obj, row_count):
     return eng
 
 
+# --------------------------------------------------------------------------------------------- outlier rounds
+def outlier_rule(components, sigma):
+    """The outlier rule of --outlier-iterations (the compiled host restates it): `components` is [num_pc][n], the principal
+    components of the current cohort.  Per axis c: mean_c = (sum of the n entries) / n and sd_c = sqrt((sum of the squared
+    deviations from mean_c) / n), the POPULATION standard deviation, both sums added left to right in double (cumsum adds in
+    order; numpy's sum adds pairwise).  Sample i is removed if |u_c[i] - mean_c| > sigma * sd_c on any axis with sd_c > 0.
+    Returns a bool array of n entries, True = removed."""
+    u = np.asarray(components, dtype=np.float64)
+    if u.ndim != 2:
+        raise ValueError("components must be [num_pc][n]")
+    n = u.shape[1]
+    removed = np.zeros(n, dtype=bool)
+    for c in range(u.shape[0]):
+        mean = np.cumsum(u[c])[-1] / n
+        dev = u[c] - mean
+        sd = np.sqrt(np.cumsum(dev * dev)[-1] / n)
+        if sd > 0:
+            removed |= np.abs(dev) > sigma * sd
+    return removed
+
+
+def min_cohort(num_pc):
+    """The smallest cohort an outlier round may leave behind."""
+    return max(3, int(num_pc) + 1)
+
+
 # --------------------------------------------------------------------------------------------- conf
 class PcaConf(object):
     """Flags of PcaConf / GenomicsConf (GenomicsConf.scala:31-101), same names and defaults.
@@ -300,6 +326,13 @@ class PcaConf(object):
                        help="VCFs whose samples are placed onto the principal coordinates of the --input-path cohort "
                             "(pcoa_project) instead of decomposing the union: their callsets follow the reference's, variants "
                             "are matched by the join / merge of all sets; one GPU, VCF inputs, full layout")
+        p.add_argument("--outlier-iterations", type=int, default=0,
+                       help="K > 0: up to K rounds of outlier removal around computePca (smartpca's loop): samples further than "
+                            "--outlier-sigma standard deviations from the mean of a principal component are removed and "
+                            "computePca runs again on S[kept, kept], gathered on the device (pcoa_create_subset) -- no variant "
+                            "is read twice.  Rows go out for the kept samples only.  One full engine: stored S, full layout")
+        p.add_argument("--outlier-sigma", type=float, default=6.0,
+                       help="--outlier-iterations: the threshold, in population standard deviations of an axis")
         a = p.parse_args(list(arguments))
         self.__dict__.update(vars(a))
         self.numPc = a.num_pc
@@ -370,6 +403,7 @@ class VariantsPcaDriver(object):
         self.data = data  # list of datasets, each a list of variant dicts (or ('csr', idx, offs))
         print("Matrix size: %d." % (len(self.indexes) if matrix_size is None else matrix_size))  # VariantsCommon.scala:48
         self.engine = None
+        self.gram_seconds_before = 0.0   # Gram kernel seconds of engines that --outlier-iterations has replaced
 
     # filterDataset, VariantsPca.scala:96-108
     def filterDataset(self, data):
@@ -490,6 +524,41 @@ class VariantsPcaDriver(object):
         reverse = dict((v, k) for (k, v) in self.indexes.items())
         return [(reverse[i], float(comps[i, 0]), float(comps[i, 1])) for i in range(n)]
 
+    # computePca inside --outlier-iterations K: computePca, outlier_rule, and while something is removed and fewer than K
+    # rounds have removed something, the engine is replaced by its subset over the kept samples (pcoa_create_subset: one
+    # gather of S, no variant fed again) and computePca runs again.  The final cohort always gets a computePca; rows come back
+    # for the kept samples only, in the original order.  sim_matrix is closed when it is replaced (self.engine follows).
+    def computePcaOutlierRounds(self, sim_matrix, err=None):
+        err = err or sys.stderr
+        iterations, sigma = self.conf.outlier_iterations, self.conf.outlier_sigma
+        if self.conf.numPc < 2:
+            raise IndexError("computePca emits exactly PC1 and PC2 (VariantsPca.scala:229-230); --num-pc must be >= 2")
+        reverse = dict((v, k) for (k, v) in self.indexes.items())
+        kept = np.arange(len(self.indexes))
+        eng, done = sim_matrix, 0
+        while True:
+            comps, _, nonzero = eng.compute(self.conf.numPc)
+            if done == iterations:
+                break
+            removed = outlier_rule(comps.T, sigma)
+            gone = kept[removed]
+            err.write("Outlier round %d: removed %d sample(s)%s\n"
+                      % (done + 1, gone.size, (": " + ", ".join(self.names[reverse[int(i)]] for i in gone)) if gone.size else ""))
+            if gone.size == 0:
+                break
+            if kept.size - gone.size < min_cohort(self.conf.numPc):
+                raise SystemExit("VariantsPcaDriver: --outlier-iterations: round %d would leave %d of %d samples, fewer than the "
+                                 "%d that %d principal components need; raise --outlier-sigma"
+                                 % (done + 1, kept.size - gone.size, kept.size, min_cohort(self.conf.numPc), self.conf.numPc))
+            sub = eng.subset(np.nonzero(~removed)[0])
+            self.gram_seconds_before += eng.timings()["gram_kernel_seconds"]
+            eng.close()
+            eng = self.engine = sub
+            kept = kept[~removed]
+            done += 1
+        print("Non zero rows in matrix: %d / %d." % (nonzero, kept.size))  # :208, once, for the final cohort
+        return [(reverse[int(i)], float(comps[a, 0]), float(comps[a, 1])) for a, i in enumerate(kept)]
+
     # emitResult, VariantsPca.scala:233-246.  stdout: name, dataset, pc1, pc2 sorted by name, as the reference prints.
     # File: the reference hands the rows to Spark's saveAsTextFile, i.e. a DIRECTORY <output-path>-pca.tsv/ of unsorted
     # part-* files (name, pc1, pc2, dataset per line); here the same lines go, sorted by name, into ONE file of that name.
@@ -517,7 +586,8 @@ class VariantsPcaDriver(object):
         if self.engine is not None:
             t = self.engine.timings()
             out.write("Variants accumulated: %d; Gram kernel %.3f ms; PCoA %.3f ms\n" %
-                      (t["gram_variants"], 1e3 * t["gram_kernel_seconds"], 1e3 * t["compute_total_seconds"]))
+                      (t["gram_variants"], 1e3 * (t["gram_kernel_seconds"] + self.gram_seconds_before),
+                       1e3 * t["compute_total_seconds"]))
             info = self.engine.operator_info()
             if info is not None:
                 out.write("Implicit similarity operator: %d variants in %.1f MB of carrier bitsets, %d Lanczos steps over "
@@ -640,6 +710,28 @@ def check_gram_conf(conf):
         raise SystemExit("VariantsPcaDriver: --gram implicit never forms the similarity matrix: it cannot take --dump-similarity")
 
 
+STRIPS_REFUSE_OUTLIERS = ("--outlier-iterations subsets one whole similarity matrix on one engine: it cannot take --layout "
+                          "strips")
+
+
+def check_outlier_conf(conf):
+    """--outlier-iterations / --outlier-sigma: what cannot be served is refused before any file is read or any engine exists."""
+    k, x = conf.outlier_iterations, conf.outlier_sigma
+    if k < 0:
+        raise SystemExit("VariantsPcaDriver: --outlier-iterations must be >= 0 (0 = off)")
+    if not (x > 0 and x != float("inf")):
+        raise SystemExit("VariantsPcaDriver: --outlier-sigma must be a finite number > 0 (the threshold of --outlier-iterations)")
+    if k == 0:
+        return
+    if conf.gram == "implicit":
+        raise SystemExit("VariantsPcaDriver: --outlier-iterations subsets a stored similarity matrix: it cannot take --gram implicit")
+    if conf.layout == "strips":
+        raise SystemExit("VariantsPcaDriver: " + STRIPS_REFUSE_OUTLIERS)
+    if conf.project_input_path:
+        raise SystemExit("VariantsPcaDriver: --outlier-iterations decomposes the cohort it is given: it cannot take "
+                         "--project-input-path")
+
+
 def calls_as_bits(call_rdd, n):
     """--gram implicit: an RDD[Seq[Int]] in any of the forms getCallsRdd returns, as what an operator engine stores -- raw
     PLINK rows and bitsets as they are, carrier lists packed into bitsets.  A list that names a callset twice (a merge of sets
@@ -745,6 +837,7 @@ def main_projection(conf):
 def main(args):
     """VariantsPcaDriver.main (VariantsPca.scala:38-50)."""
     conf = PcaConf(args)
+    check_outlier_conf(conf)
     check_gram_conf(conf)
     if conf.project_input_path:
         check_projection_conf(conf)
@@ -799,6 +892,8 @@ def main(args):
         ranges = decided[0]
     else:
         ranges = resolve_layout(conf, n, 1, [conf.gpu])
+    if ranges is not None and conf.outlier_iterations > 0:   # --layout auto resolved to strips
+        raise SystemExit("VariantsPcaDriver: " + STRIPS_REFUSE_OUTLIERS)
     if ranges is not None:
         owner = driver.getSimilarityMatrixStrip(calls_rdd, ranges[rank], local_rank if world > 1 else conf.gpu)
         if rank == 0:
@@ -829,7 +924,7 @@ def main(args):
     if rank == 0:
         if conf.dump_similarity:
             sim_matrix.gram().astype("<i8").tofile(conf.dump_similarity)
-        result = driver.computePca(sim_matrix)
+        result = driver.computePcaOutlierRounds(sim_matrix) if conf.outlier_iterations > 0 else driver.computePca(sim_matrix)
         driver.emitResult(result)
         driver.reportIoStats(sys.stderr)
     if world > 1:
