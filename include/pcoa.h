@@ -35,7 +35,7 @@ extern "C" {
 #endif
 
 #define PCOA_VERSION_MAJOR 0
-#define PCOA_VERSION_MINOR 8
+#define PCOA_VERSION_MINOR 9
 
 typedef struct pcoa_ctx pcoa_ctx;
 
@@ -522,6 +522,46 @@ int pcoa_host_free_pinned(void* p);
  * Replaces: reduceByKey(_ + _, conf.numReducePartitions()) (VariantsPca.scala:190, GenomicsConf.scala:42-45) inside one JVM. */
 int pcoa_gram_reduce_from(pcoa_ctx* dst, pcoa_ctx* src);
 
+/* S of every engine := the sum over the k engines of their finalized S: the reduction of ALL engines of one process at once
+ * (called from one host thread after the feeding threads have joined), as a reduce-scatter and an all-gather over the engines'
+ * own matrices.  The flat element range [0, N^2) of S is cut into k chunks of whole 16-byte quads -- with Q = ceil(N^2 / 4),
+ * owner g takes the quads [g Q / k, (g + 1) Q / k); the last owner's chunk ends with the N^2 % 4 tail elements; a chunk is empty
+ * when Q < k leaves it none.  Phase 1: owner g's kernel, on its own stream, reads chunk g of all k matrices and writes the sums
+ * into its OWN matrix.  Phase 2: every engine copies chunk h from owner h behind that kernel's event.  Every link carries 1 / k
+ * of the matrix at a time, every engine takes part, and nothing is staged: no exchange buffer of any size beside S (the chain
+ * of pcoa_gram_reduce_from calls sends k - 1 whole matrices into engine 0, one after the other, through an N^2 staging buffer).
+ *   root_only == 0: on return every engine holds the total (what pcoa_gram_allreduce_rccl leaves behind).
+ *   root_only != 0: ctxs[0] holds the total; every other engine comes back as after pcoa_reset -- S zero, books zero, usable.
+ *   k == 1: pcoa_gram_finalize.
+ *   The sums are integers: the result is, entry for entry, what the pcoa_gram_reduce_from chain gives.  When no engine has an
+ *   int64 part and the summed variant weights stay below 2^31 - 1 the int32 matrices are summed in place
+ *   (pcoa_timings.reduce_int32_calls counts it on every engine that holds the total); otherwise every engine gets an int64 matrix
+ *   for the totals (PCOA_ERR_OUT_OF_MEMORY before any kernel leaves the engines unchanged) and each total is narrowed back into
+ *   the int32 matrix where it fits, as after every int64 import.
+ * Refusals, all before any device work; afterwards every engine is as it was and still computes:
+ *   PCOA_ERR_INVALID_ARG  ctxs NULL, k < 1, k > PCOA_REDUCE_MAX_ENGINES, a NULL entry, the same ctx twice, differing N
+ *   PCOA_ERR_STATE        a strip owner or an operator ctx among them (the message names the kind and the index); engines on
+ *                         different devices without mutual peer access (the message names the two devices): phase 1 reads the
+ *                         peers' matrices from a kernel, and there is no staged fallback in this call -- reduce such engines with
+ *                         pcoa_gram_reduce_from.
+ * Every engine is then finalized and its input checks are read; a failure on engine g comes back with its code, the message on
+ * ctxs[0] prefixed with the index.  A HIP failure once phase 1 has started leaves EVERY S undefined: the engines must be reset
+ * (pcoa_reset) before they are used again.  Errors are reported on ctxs[0] (on pcoa_last_error(NULL) where that is no ctx).
+ * Synchronising on every engine.
+ * Replaces: reduceByKey(_ + _) (VariantsPca.scala:190) for the k engines of one JVM. */
+#define PCOA_REDUCE_MAX_ENGINES 16
+int pcoa_gram_reduce_peers(pcoa_ctx* const* ctxs, int32_t k, int32_t root_only);
+
+/* What pcoa_gram_reduce_peers did on THIS engine, cumulative since pcoa_create / pcoa_reset_timings.  (A struct of its own:
+ * the layout and the size of pcoa_timings are held fixed by its readers.)  It grows at its end; out_size = sizeof of the
+ * struct the caller compiled against.  Synchronising, like pcoa_get_timings. */
+typedef struct pcoa_reduce_peers_stats {
+  int64_t reduce_peers_calls;     /* calls this engine took part in                                                       */
+  double reduce_peers_seconds;    /* HIP-event time of this engine's chunk kernel plus its gather copies                  */
+  int64_t reduce_peers_bytes_in;  /* bytes this engine read (phase 1) or copied (phase 2) from OTHER engines' matrices    */
+} pcoa_reduce_peers_stats;
+int pcoa_get_reduce_peers_stats(pcoa_ctx* ctx, pcoa_reduce_peers_stats* out, size_t out_size);
+
 /* Host-driven reduction alternative (bench.py uses torch.distributed, whose "nccl" backend is RCCL):
  * export copies the finalized S as int64 [N][N] into a DEVICE buffer; import replaces S with the
  * (reduced) contents of a DEVICE buffer. */
@@ -612,6 +652,9 @@ int pcoa_debug_alloc(int32_t device_ordinal, size_t bytes, void** out);
  * 0 = one wave per row over all N^2 entries, 1 = upper-triangular 1024 x 1024 tiles, each entry read once and used for y_i and
  * y_j (the form pcoa_compute takes from N = 16,384; needs N % 4 == 0). */
 int pcoa_debug_centred_matvec(pcoa_ctx* ctx, const double* x, double* y, int upper_triangle_form);
+/* The partition pcoa_gram_reduce_peers cuts S by: chunk g of k over N samples as [*first_out, *first_out + *count_out) of the flat
+ * element range [0, N^2).  Pure function (no GPU): the one the library's launches and copies go by. */
+int pcoa_debug_reduce_chunk(int32_t g, int32_t k, int32_t n_samples, int64_t* first_out, int64_t* count_out);
 int pcoa_debug_free(void* p);
 int pcoa_debug_guard_mode(void);
 

@@ -93,6 +93,18 @@ class PcoaTimings(ctypes.Structure):
     ]
 
 
+class PcoaReducePeersStats(ctypes.Structure):
+    """pcoa_reduce_peers_stats: a struct of its own beside pcoa_timings, whose layout and size are held fixed."""
+    _fields_ = [
+        ("reduce_peers_calls", ctypes.c_int64),
+        ("reduce_peers_seconds", ctypes.c_double),
+        ("reduce_peers_bytes_in", ctypes.c_int64),
+    ]
+
+
+PCOA_REDUCE_MAX_ENGINES = 16
+
+
 class PcoaSynthParams(ctypes.Structure):
     _fields_ = [
         ("seed", ctypes.c_uint64),
@@ -135,9 +147,12 @@ _SIGNATURES = [
     ("pcoa_comm_runtime", ctypes.c_int, [ctypes.c_char_p, _i32, ctypes.POINTER(_i32)]),
     ("pcoa_debug_alloc", ctypes.c_int, [_i32, ctypes.c_size_t, ctypes.POINTER(_vp)]),
     ("pcoa_debug_free", ctypes.c_int, [_vp]),
+    ("pcoa_debug_reduce_chunk", ctypes.c_int, [_i32, _i32, _i32, ctypes.POINTER(_i64), ctypes.POINTER(_i64)]),
     ("pcoa_debug_guard_mode", ctypes.c_int, []),
     ("pcoa_accumulate_calls", ctypes.c_int, [_vp, _vp, _vp, _i64]),
     ("pcoa_gram_reduce_from", ctypes.c_int, [_vp, _vp]),
+    ("pcoa_gram_reduce_peers", ctypes.c_int, [_vp, _i32, _i32]),
+    ("pcoa_get_reduce_peers_stats", ctypes.c_int, [_vp, ctypes.POINTER(PcoaReducePeersStats), ctypes.c_size_t]),
     ("pcoa_lanczos_with_matvec", ctypes.c_int, [_vp, ctypes.c_int32, _vp, _vp, _vp, _vp, ctypes.POINTER(ctypes.c_int32)]),
     ("pcoa_debug_centred_matvec", ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int]),
     ("pcoa_host_alloc_pinned", ctypes.c_int, [ctypes.c_size_t, ctypes.POINTER(ctypes.c_void_p)]),

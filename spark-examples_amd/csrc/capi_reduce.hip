@@ -1,5 +1,6 @@
-// capi_reduce.hip -- S leaves or enters an engine: finalize / export / import / read / load, the peer reduction of two
-// engines of one process, and the RCCL all-reduce (RCCL is bound at run time).
+// capi_reduce.hip -- S leaves or enters an engine: finalize / export / import / read / load, the peer reductions of the
+// engines of one process (pair-wise: pcoa_gram_reduce_from; all k at once: pcoa_gram_reduce_peers), and the RCCL all-reduce
+// (RCCL is bound at run time).
 #include <dlfcn.h>
 #include <link.h>
 #include <rccl/rccl.h>   // types and prototypes only: the library is bound at run time (rccl_api below), not linked
@@ -205,6 +206,195 @@ int pcoa_gram_reduce_from(pcoa_ctx* dst, pcoa_ctx* src) {
   return narrow_s64(c);   // the total may fit int32 although the books could not promise it
 }
 
+// S of every engine := the sum over the k engines (root_only: of ctxs[0] alone, the others reset), as a reduce-scatter and
+// an all-gather over the engines' own matrices.  Phase 1: owner g sums chunk g (reduce_chunk) of all k matrices into its own,
+// on its stream.  Phase 2: every receiver copies chunk h from owner h behind owner h's event.  Every link carries 1 / k of the
+// matrix at a time, nothing is staged (xfer is not touched) and every engine takes part.
+int pcoa_gram_reduce_peers(pcoa_ctx* const* ctxs, int32_t k, int32_t root_only) {
+  const char* const me = "pcoa_gram_reduce_peers";
+  if (!ctxs) return fail(nullptr, PCOA_ERR_INVALID_ARG, std::string(me) + ": ctxs is NULL");
+  if (k < 1 || k > PCOA_REDUCE_MAX_ENGINES)
+    return fail(nullptr, PCOA_ERR_INVALID_ARG, std::string(me) + ": k must be in [1, " + std::to_string(PCOA_REDUCE_MAX_ENGINES) + "]");
+  pcoa_ctx* const c0 = ctxs[0];   // where errors are reported (NULL: the thread's create error, as pcoa_create_subset does)
+  // ---- validation: nothing below touches a device until all of it has passed
+  for (int g = 0; g < k; ++g) {
+    if (!ctxs[g]) return fail(c0, PCOA_ERR_INVALID_ARG, std::string(me) + ": ctxs[" + std::to_string(g) + "] is NULL");
+    for (int h = 0; h < g; ++h)
+      if (ctxs[h] == ctxs[g])
+        return fail(c0, PCOA_ERR_INVALID_ARG, std::string(me) + ": ctxs[" + std::to_string(g) + "] is the same ctx as ctxs[" + std::to_string(h) + "]");
+  }
+  for (int g = 0; g < k; ++g) {
+    if (ctxs[g]->is_strip)
+      return fail(c0, PCOA_ERR_STATE, std::string(me) + ": ctxs[" + std::to_string(g) + "] is a strip owner (pcoa_create_strip): the "
+                                      "owners' strips tile S and are never summed");
+    if (ctxs[g]->is_operator)
+      return fail(c0, PCOA_ERR_STATE, std::string(me) + ": ctxs[" + std::to_string(g) + "] is an operator ctx (pcoa_create_operator), "
+                                      "which holds no S");
+  }
+  for (int g = 1; g < k; ++g)
+    if (ctxs[g]->n != c0->n)
+      return fail(c0, PCOA_ERR_INVALID_ARG, std::string(me) + ": ctxs[" + std::to_string(g) + "] holds " + std::to_string(ctxs[g]->n) +
+                                            " samples, ctxs[0] " + std::to_string(c0->n));
+  // engines on different devices: kernels of each must be able to read the other's memory.  Every pair is asked first, then
+  // enabled; a pair that cannot be made addressable is the caller's to reduce pair-wise (no staged fallback in here)
+  for (int pass = 0; pass < 2; ++pass)
+    for (int g = 0; g < k; ++g)
+      for (int h = 0; h < k; ++h) {
+        const int dg = ctxs[g]->device, dh = ctxs[h]->device;
+        if (dg == dh) continue;
+        hipError_t e = hipSuccess;
+        int can = 0;
+        if (pass == 0) {
+          e = hipDeviceCanAccessPeer(&can, dg, dh);
+        } else {
+          can = 1;
+          if ((e = hipSetDevice(dg)) == hipSuccess) e = hipDeviceEnablePeerAccess(dh, 0);
+          if (e == hipErrorPeerAccessAlreadyEnabled) e = hipSuccess;
+        }
+        (void)hipGetLastError();
+        if (e != hipSuccess || !can)
+          return fail(c0, PCOA_ERR_STATE, std::string(me) + ": device " + std::to_string(dg) + " cannot address the memory of device " +
+                                          std::to_string(dh) + " (no peer access): reduce these engines pair-wise with "
+                                          "pcoa_gram_reduce_from, which stages through a copy");
+      }
+  // ---- preparation: every engine finalized and its input checks read (synchronises it) before any kernel of the reduction
+  for (int g = 0; g < k; ++g) {
+    pcoa_ctx* c = ctxs[g];
+    CHECK_CTX(c);
+    int rc = finalize_impl(c);
+    if (rc == PCOA_OK) rc = check_device_flags(c);   // never reduce an S that an input check has invalidated
+    if (rc != PCOA_OK) {
+      if (g > 0) c0->last_error = std::string(me) + ": ctxs[" + std::to_string(g) + "]: " + c->last_error;
+      return rc;
+    }
+  }
+  if (k == 1) return PCOA_OK;
+  const int32_t n = c0->n;
+  bool any64 = false;
+  int64_t sum_bound = 0, sum_variants = 0;
+  for (int g = 0; g < k; ++g) {
+    any64 = any64 || ctxs[g]->s64 != nullptr;
+    sum_bound += ctxs[g]->variants_in_s32;
+    sum_variants += ctxs[g]->gram_variants;
+  }
+  // the test pcoa_gram_reduce_from and the native all-reduce apply: no sum can leave int32
+  const bool narrow = !any64 && sum_bound < (((int64_t)1 << 31) - 1) && !debug_knobs().no_narrow;
+  ReduceSources src = {};
+  src.k = k;
+  for (int g = 0; g < k; ++g) {
+    src.s32[g] = ctxs[g]->s32;
+    src.s64[g] = ctxs[g]->s64;   // as the engine came in: an int64 matrix it is only given below holds nothing yet
+  }
+  if (!narrow) {   // int64 branch: every engine gets an int64 matrix for the totals; a failure leaves all of them as they were
+    bool fresh[PCOA_REDUCE_MAX_ENGINES] = {false};
+    for (int g = 0; g < k; ++g) {
+      pcoa_ctx* c = ctxs[g];
+      if (c->s64) continue;
+      int rc = PCOA_OK;
+      if (hipSetDevice(c->device) != hipSuccess || (rc = take_s64(c)) != PCOA_OK) {
+        if (rc == PCOA_OK) rc = fail(c, PCOA_ERR_HIP, "hipSetDevice");
+        if (g > 0) c0->last_error = std::string(me) + ": ctxs[" + std::to_string(g) + "]: " + c->last_error;
+        for (int h = 0; h < g; ++h)
+          if (fresh[h]) retire_s64(ctxs[h]);
+        return rc;
+      }
+      fresh[g] = true;
+    }
+  }
+  // guard-page mappings name the devices that may touch them (plain allocations are covered by the peer access above)
+  for (int g = 0; g < k; ++g)
+    for (int h = 0; h < k; ++h) {
+      pcoa_ctx* c = ctxs[g];
+      if (c->device == ctxs[h]->device) continue;
+      HIP_TRY(c0, dev_grant_peer(c->s32, c->device, ctxs[h]->device));
+      HIP_TRY(c0, dev_grant_peer(c->s64, c->device, ctxs[h]->device));
+    }
+  // ---- phase 1: owner g sums chunk g of every matrix into its own, on its stream.  From here on a failure leaves every S
+  // undefined (pcoa.h): the error comes back on ctxs[0] and the engines are the caller's to reset.
+  const size_t esize = narrow ? sizeof(int32_t) : sizeof(int64_t);
+  int64_t first[PCOA_REDUCE_MAX_ENGINES], count[PCOA_REDUCE_MAX_ENGINES];
+  hipEvent_t done[PCOA_REDUCE_MAX_ENGINES] = {nullptr};
+  for (int g = 0; g < k; ++g) reduce_chunk(g, k, n, &first[g], &count[g]);
+  for (int g = 0; g < k; ++g) {
+    pcoa_ctx* c = ctxs[g];
+    HIP_TRY(c0, hipSetDevice(c->device));
+    if (!(done[g] = get_event(c))) return fail(c0, PCOA_ERR_HIP, std::string(me) + ": hipEventCreate failed");
+    {
+      ScopedTimer t(c, T_REDUCE_PEERS);
+      HIP_TRY(c0, narrow ? launch_reduce_chunk_i32(src, c->s32, first[g], count[g], c->stream)
+                         : launch_reduce_chunk_i64(src, any64, c->s64, first[g], count[g], c->stream));
+    }
+    HIP_TRY(c0, hipEventRecord(done[g], c->stream));
+    for (int h = 0; h < k; ++h) {   // what the kernel read from OTHER engines
+      if (h == g) continue;
+      c->reduce_peers_bytes_in += (int64_t)sizeof(int32_t) * count[g];
+      if (!narrow && src.s64[h]) c->reduce_peers_bytes_in += (int64_t)sizeof(int64_t) * count[g];
+    }
+  }
+  // ---- phase 2: the all-gather (root_only: the gather to engine 0).  Receiver g copies chunk h from owner h's matrix into its
+  // own behind owner h's event; owner h's kernel was the only reader of g's chunk h
+  for (int g = 0; g < (root_only ? 1 : k); ++g) {
+    pcoa_ctx* c = ctxs[g];
+    HIP_TRY(c0, hipSetDevice(c->device));
+    ScopedTimer t(c, T_REDUCE_PEERS);
+    for (int h = 0; h < k; ++h) {
+      if (h == g || count[h] == 0) continue;
+      pcoa_ctx* o = ctxs[h];
+      HIP_TRY(c0, hipStreamWaitEvent(c->stream, done[h], 0));
+      const size_t off = (size_t)first[h] * esize, bytes = (size_t)count[h] * esize;
+      char* to = (narrow ? reinterpret_cast<char*>(c->s32) : reinterpret_cast<char*>(c->s64)) + off;
+      const char* from = (narrow ? reinterpret_cast<const char*>(o->s32) : reinterpret_cast<const char*>(o->s64)) + off;
+      if (o->device == c->device) HIP_TRY(c0, hipMemcpyAsync(to, from, bytes, hipMemcpyDeviceToDevice, c->stream));
+      else HIP_TRY(c0, hipMemcpyPeerAsync(to, c->device, from, o->device, bytes, c->stream));
+      c->reduce_peers_bytes_in += (int64_t)bytes;
+    }
+  }
+  for (int g = 0; g < k; ++g) {
+    HIP_TRY(c0, hipSetDevice(ctxs[g]->device));
+    HIP_TRY(c0, hipStreamSynchronize(ctxs[g]->stream));
+  }
+  for (int g = 0; g < k; ++g) ctxs[g]->pool.push_back(done[g]);
+  // ---- books.  An engine that holds the total: as after a reduction into it; with root_only every other one: as after pcoa_reset
+  for (int g = 0; g < k; ++g) {
+    pcoa_ctx* c = ctxs[g];
+    HIP_TRY(c0, hipSetDevice(c->device));
+    c->reduce_peers_calls += 1;
+    c->dirty = false;
+    c->strip_centering_set = false;
+    if (root_only && g > 0) {
+      HIP_TRY(c0, hipMemsetAsync(c->s32, 0, sizeof(int32_t) * s_count(c), c->stream));
+      HIP_TRY(c0, hipStreamSynchronize(c->stream));
+      retire_s64(c);   // S = 0 needs no int64 part
+      c->variants_in_s32 = 0;
+      c->gram_variants = 0;
+      continue;
+    }
+    c->gram_variants = sum_variants;
+    if (narrow) {
+      c->variants_in_s32 = sum_bound;
+      c->reduce_i32_calls += 1;
+      continue;
+    }
+    // the hand-over every int64 import makes: the total is in s64, the int32 partial is zero, and a total that fits goes back
+    HIP_TRY(c0, hipMemsetAsync(c->s32, 0, sizeof(int32_t) * s_count(c), c->stream));
+    c->variants_in_s32 = 0;
+    const int rc = narrow_s64(c);
+    if (rc != PCOA_OK) {
+      if (g > 0) c0->last_error = std::string(me) + ": ctxs[" + std::to_string(g) + "]: " + c->last_error;
+      return rc;
+    }
+  }
+  return PCOA_OK;
+}
+
+// test hook: the partition pcoa_gram_reduce_peers cuts S by (reduce_chunk, reduce_peers.hip); no GPU
+int pcoa_debug_reduce_chunk(int32_t g, int32_t k, int32_t n_samples, int64_t* first_out, int64_t* count_out) {
+  if (!first_out || !count_out || k < 1 || k > PCOA_REDUCE_MAX_ENGINES || g < 0 || g >= k || n_samples < 1)
+    return fail(nullptr, PCOA_ERR_INVALID_ARG, "pcoa_debug_reduce_chunk: need 0 <= g < k <= PCOA_REDUCE_MAX_ENGINES, n_samples >= 1 and both outputs");
+  reduce_chunk(g, k, n_samples, first_out, count_out);
+  return PCOA_OK;
+}
+
 int pcoa_gram_import_device_i64(pcoa_ctx* c, const int64_t* src_dev) {
   CHECK_CTX(c);
   NOT_ON_OPERATOR(c, "pcoa_gram_import_device_i64");
@@ -212,7 +402,7 @@ int pcoa_gram_import_device_i64(pcoa_ctx* c, const int64_t* src_dev) {
   const size_t nn = s_count(c);
   int rc = fp4_discard(c);  // S is replaced: what was buffered or in flight for the old S goes with it
   if (rc != PCOA_OK) return rc;
-  if (!c->s64) HIP_TRY(c, dev_alloc((void**)&c->s64, sizeof(int64_t) * nn, c->device));
+  if ((rc = take_s64(c)) != PCOA_OK) return rc;   // the matrix narrow_s64 retired last time, else a fresh one
   HIP_TRY(c, hipMemcpyAsync(c->s64, src_dev, sizeof(int64_t) * nn, hipMemcpyDeviceToDevice, c->stream));
   HIP_TRY(c, hipMemsetAsync(c->s32, 0, sizeof(int32_t) * nn, c->stream));
   c->variants_in_s32 = 0;

@@ -105,6 +105,22 @@ void dev_free(void* p) {
   (void)hipFree(p);
 }
 
+hipError_t dev_grant_peer(void* p, int owner_device, int peer_device) {
+  if (!p || owner_device == peer_device || debug_knobs().guard == 0) return hipSuccess;
+  GuardRec r;
+  {
+    std::lock_guard<std::mutex> lock(g_guard_mu);
+    auto it = g_guard_recs.find(p);
+    if (it == g_guard_recs.end()) return hipSuccess;   // a plain allocation
+    r = it->second;
+  }
+  hipMemAccessDesc acc = {};
+  acc.location.type = hipMemLocationTypeDevice;
+  acc.location.id = peer_device;
+  acc.flags = hipMemAccessFlagsProtReadWrite;
+  return hipMemSetAccess(r.map, r.map_size, &acc, 1);
+}
+
 // The one way a device buffer of the library is regrown: *buf is freed and replaced by `bytes` fresh bytes; its old contents
 // are not kept, and *buf is null if the allocation fails.  sync_ctx_stream: kernels queued on the ctx stream may still read
 // the old buffer (a staging slot's owner has waited for the slot's last reader instead).  Capacities and their growth

@@ -10,15 +10,35 @@ using namespace pcoa;
 
 namespace pcoa {
 
+// an int64 matrix for a ctx that has none: the one narrow_s64 retired, else a fresh one (contents undefined either way)
+int take_s64(pcoa_ctx* c) {
+  if (c->s64) return PCOA_OK;
+  if (c->s64_spare) {
+    c->s64 = c->s64_spare;
+    c->s64_spare = nullptr;
+    return PCOA_OK;
+  }
+  HIP_TRY(c, dev_alloc((void**)&c->s64, sizeof(int64_t) * s_count(c), c->device));
+  return PCOA_OK;
+}
+
+// the int64 matrix is no longer part of S (nothing queued may still touch it): kept as the spare a later fold or import
+// takes, or freed -- and a spare the ctx already holds is freed, never overwritten
+void retire_s64(pcoa_ctx* c) {
+  if (!c->s64) return;
+  if (s_count(c) * sizeof(int64_t) <= ((size_t)1 << 30) && !c->s64_spare) {
+    c->s64_spare = c->s64;   // kept: a later fold needs one again
+  } else {
+    dev_free(c->s64);        // large N: 8 N^2 bytes are worth more than the allocation they would save
+  }
+  c->s64 = nullptr;
+}
+
 int fold_now(pcoa_ctx* c) {
   const int64_t count = (int64_t)s_count(c);
   if (!c->s64) {
-    if (c->s64_spare) {
-      c->s64 = c->s64_spare;
-      c->s64_spare = nullptr;
-    } else {
-      HIP_TRY(c, dev_alloc((void**)&c->s64, sizeof(int64_t) * (size_t)count, c->device));
-    }
+    const int rc = take_s64(c);
+    if (rc != PCOA_OK) return rc;
     HIP_TRY(c, hipMemsetAsync(c->s64, 0, sizeof(int64_t) * (size_t)count, c->stream));
   }
   // s64 is kept symmetric: mirror the partial before it is folded in (a strip holds both triangles already)
@@ -58,12 +78,7 @@ int narrow_s64(pcoa_ctx* c) {
     HIP_TRY(c, hipMemsetAsync(c->s32, 0, sizeof(int32_t) * (size_t)count, c->stream));
     return PCOA_OK;
   }
-  if ((size_t)count * sizeof(int64_t) <= ((size_t)1 << 30)) {
-    c->s64_spare = c->s64;   // kept: a later fold needs one again
-  } else {
-    dev_free(c->s64);        // large N: 8 N^2 bytes are worth more than the allocation they would save
-  }
-  c->s64 = nullptr;
+  retire_s64(c);
   c->variants_in_s32 = maxabs;   // an upper bound of every |entry|, which is what the fold and the int32 reductions go by
   c->narrowed += 1;
   return PCOA_OK;

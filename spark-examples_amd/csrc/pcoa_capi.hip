@@ -180,7 +180,7 @@ int create_full_engine_unfilled(pcoa_ctx** out, int32_t n_samples, int32_t devic
 
 extern "C" {
 
-const char* pcoa_version(void) { return "pcoa_hip 0.8 (gfx950)"; }
+const char* pcoa_version(void) { return "pcoa_hip 0.9 (gfx950)"; }
 
 int pcoa_create(pcoa_ctx** out, int32_t n_samples, int32_t device_ordinal, uint32_t flags) {
   return create_impl(out, n_samples, device_ordinal, flags, 0, -1);
@@ -367,6 +367,21 @@ int pcoa_get_timings_sized(pcoa_ctx* c, pcoa_timings* out_user, size_t out_size)
   return PCOA_OK;
 }
 
+int pcoa_get_reduce_peers_stats(pcoa_ctx* c, pcoa_reduce_peers_stats* out_user, size_t out_size) {
+  CHECK_CTX(c);
+  if (!out_user || out_size < sizeof(int64_t)) return fail(c, PCOA_ERR_INVALID_ARG, "out is NULL or out_size too small");
+  int rc0 = fp4_sync_point(c);
+  if (rc0 != PCOA_OK) return rc0;
+  drain_events(c, true);
+  pcoa_reduce_peers_stats full;
+  std::memset(&full, 0, sizeof(full));
+  full.reduce_peers_calls = c->reduce_peers_calls;
+  full.reduce_peers_seconds = c->tsec[T_REDUCE_PEERS];
+  full.reduce_peers_bytes_in = c->reduce_peers_bytes_in;
+  std::memcpy(out_user, &full, std::min(out_size, sizeof(full)));
+  return PCOA_OK;
+}
+
 static_assert(offsetof(pcoa_timings, csr_stage_seconds) == PCOA_TIMINGS_R03_BYTES, "the r03 prefix of pcoa_timings is frozen");
 // the r03 layout (ends behind evensplit_launches), whatever the struct has grown to since
 int pcoa_get_timings(pcoa_ctx* c, pcoa_timings* out) { return pcoa_get_timings_sized(c, out, PCOA_TIMINGS_R03_BYTES); }
@@ -392,6 +407,7 @@ int pcoa_reset_timings(pcoa_ctx* c) {
   c->evensplit_launches = 0;
   c->op_products = 0;
   c->subset_bytes = 0;
+  c->reduce_peers_calls = c->reduce_peers_bytes_in = 0;
   return PCOA_OK;
 }
 

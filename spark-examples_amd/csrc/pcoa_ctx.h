@@ -6,6 +6,7 @@
 //   operand.hip          S and its int64 fold, the operand buffers, the contractions, finalize
 //   capi_accumulate.hip  the staging ring and the input boundaries
 //   capi_reduce.hip      RCCL, reductions, export / import / read / load
+//   reduce_peers.hip     the partition and the chunk kernel of pcoa_gram_reduce_peers
 //   capi_compute.hip     the eigensolver workspace, computePca, strips, projection
 //   capi_operator.hip    the implicit similarity operator: the bit store, its products, computePca over it
 //   capi_subset.hip      pcoa_create_subset: a new engine whose S is S[I, I] of another
@@ -17,7 +18,7 @@
 
 #include "pcoa_internal.h"
 
-enum TimeCat { T_GRAM = 0, T_DENSIFY, T_SYNTH, T_FINALIZE, T_CENTER, T_TRIDIAG, T_EIG, T_BACK, T_PACK, T_LANCZOS, T_ALLREDUCE, T_OPERATOR, T_SUBSET, T_NCAT };
+enum TimeCat { T_GRAM = 0, T_DENSIFY, T_SYNTH, T_FINALIZE, T_CENTER, T_TRIDIAG, T_EIG, T_BACK, T_PACK, T_LANCZOS, T_ALLREDUCE, T_OPERATOR, T_SUBSET, T_REDUCE_PEERS, T_NCAT };
 
 struct EventPair {
   hipEvent_t a, b;
@@ -130,6 +131,7 @@ struct pcoa_ctx {
   size_t xfer_bytes = 0;
   int32_t* narrow_flag = nullptr;  // device: narrow_s64's {overflow, -, max |entry| (64 bit)}
   int64_t reduce_i32_calls = 0, narrowed = 0, allreduce_calls = 0;
+  int64_t reduce_peers_calls = 0, reduce_peers_bytes_in = 0;   // pcoa_gram_reduce_peers: calls, bytes read or copied from OTHER engines
   int32_t comm_ranks = 0, allreduce_int32 = 0, matvec_form = 0, lanczos_block_steps = 0;
   int64_t* coll = nullptr;         // 2 int64: {variants in S32, has-S64 flag} agreed across ranks
   int8_t* pack_buf = nullptr;      // k-blocked int8 workspace of the i8 path (lazy)
@@ -255,6 +257,9 @@ inline GramStrip strip_of(const pcoa_ctx* c) {
 hipError_t dev_alloc(void** out, size_t bytes, int device);
 void dev_free(void* p);
 int regrow(pcoa_ctx* c, void** buf, size_t bytes, bool sync_ctx_stream);
+// kernels on `peer_device` may read and write the buffer p (a dev_alloc result on another device).  A plain allocation is
+// covered by hipDeviceEnablePeerAccess (the caller's); a guard-page mapping needs its own hipMemSetAccess naming the peer
+hipError_t dev_grant_peer(void* p, int owner_device, int peer_device);
 
 // ---- pcoa_capi.hip: errors (c == nullptr: the thread's create error) and the timing events
 int fail(pcoa_ctx* c, int code, const std::string& msg);
@@ -267,6 +272,8 @@ void drain_events(pcoa_ctx* c, bool wait);
 int fold_now(pcoa_ctx* c);
 int ensure_xfer(pcoa_ctx* c, size_t bytes);
 int narrow_s64(pcoa_ctx* c);
+int take_s64(pcoa_ctx* c);      // c->s64 := the spare, else a fresh allocation; contents undefined
+void retire_s64(pcoa_ctx* c);   // c->s64 becomes the spare (small N) or is freed; c->s64 = nullptr
 void account_gram(pcoa_ctx* c, int64_t cur, int64_t weight = 1);
 int fold_if_needed(pcoa_ctx* c, int64_t cur);
 int64_t kb_of(const pcoa_ctx* c, int64_t nv);
@@ -286,6 +293,23 @@ int gram_device(pcoa_ctx* c, const void* x_dev, int is_u8, int64_t nv, int64_t l
 int gram_device_bits(pcoa_ctx* c, const uint32_t* bits_dev, int64_t nv, int64_t ld_words, bool can_defer);
 int check_device_flags(pcoa_ctx* c);
 int finalize_impl(pcoa_ctx* c);
+
+// ---- reduce_peers.hip
+// The partition of pcoa_gram_reduce_peers, stated once: with Q = ceil(N^2 / 4) quads of 16 bytes, owner g of k takes the quads
+// [g Q / k, (g + 1) Q / k) (64-bit arithmetic) of the flat element range [0, N^2); *first / *count are in ELEMENTS, *first is a
+// multiple of 4, and the last owner's count ends with the N^2 % 4 tail elements.  A chunk is empty when Q < k leaves it none.
+void reduce_chunk(int32_t g, int32_t k, int32_t n, int64_t* first, int64_t* count);
+// the matrices one chunk kernel sums, by value in the kernel's arguments: s32 of every engine, s64 where the engine has one
+struct ReduceSources {
+  const int32_t* s32[PCOA_REDUCE_MAX_ENGINES];
+  const int64_t* s64[PCOA_REDUCE_MAX_ENGINES];
+  int32_t k;
+};
+// dst[e] = sum over the sources of their element e, e in [first, first + count); dst may be one of the sources (the owner's own
+// matrix: a lane reads an element before it writes it).  has64: some s64 entry is set
+hipError_t launch_reduce_chunk_i32(const ReduceSources& src, int32_t* dst, int64_t first, int64_t count, hipStream_t stream);
+hipError_t launch_reduce_chunk_i64(const ReduceSources& src, bool has64, int64_t* dst, int64_t first, int64_t count,
+                                   hipStream_t stream);
 
 // ---- capi_accumulate.hip
 int csr_validate(pcoa_ctx* c);

@@ -520,7 +520,11 @@ class PcoaEngine(object):
     def timings(self):
         t = L.PcoaTimings()
         self._check(self._lib.pcoa_get_timings_sized(self._ctx, ctypes.byref(t), ctypes.sizeof(t)))
-        return dict((f[0], getattr(t, f[0])) for f in L.PcoaTimings._fields_ if not f[0].startswith("reserved"))
+        out = dict((f[0], getattr(t, f[0])) for f in L.PcoaTimings._fields_ if not f[0].startswith("reserved"))
+        r = L.PcoaReducePeersStats()   # reduce_peers_calls / _seconds / _bytes_in: a struct of their own in pcoa.h
+        self._check(self._lib.pcoa_get_reduce_peers_stats(self._ctx, ctypes.byref(r), ctypes.sizeof(r)))
+        out.update((f[0], getattr(r, f[0])) for f in L.PcoaReducePeersStats._fields_)
+        return out
 
     def reset_timings(self):
         self._check(self._lib.pcoa_reset_timings(self._ctx))
@@ -584,3 +588,19 @@ def compute_strips(owners, num_pc=2):
     nz = ctypes.c_int32(0)
     lead._check(lead._lib.pcoa_compute_strips(arr, len(owners), k, _ptr(comps), _ptr(lam), ctypes.byref(nz)))
     return np.ascontiguousarray(comps[:k].T), lam[:k].copy(), int(nz.value)
+
+
+def reduce_peers(engines, root_only=False):
+    """S of every engine := the sum over `engines` (pcoa_gram_reduce_peers): a reduce-scatter + all-gather over the engines'
+    own matrices, nothing staged.  The engines are full engines of this process over the same samples; they may share a device.
+    root_only: engines[0] holds the total and every other engine comes back reset.  Errors are raised from engines[0]."""
+    lib = L.load()
+    engines = list(engines)
+    if not engines:
+        raise ValueError("no engines")
+    arr = (ctypes.c_void_p * len(engines))(*[e._ctx.value if e._ctx else None for e in engines])
+    rc = lib.pcoa_gram_reduce_peers(arr, len(engines), int(bool(root_only)))
+    if rc != L.PCOA_OK:
+        lead = engines[0]
+        msg = lib.pcoa_last_error(lead._ctx if lead._ctx else None)
+        raise PcoaError(rc, msg.decode(errors="replace") if msg else "")

@@ -72,7 +72,8 @@ struct Conf {  // PcaConf / GenomicsConf (GenomicsConf.scala:31-101), same flag 
   // r04: the variant-sharded job of BASELINE configs[2] from the command line (VariantsPca.scala:190: partitions + reduceByKey)
   int gpus = 1;                       // --gpus k: k host threads, one engine per device, variants dealt by contiguous ranges
   std::vector<int> gpu_map;           // --gpu-map a,b,..: device ordinal of each engine (default: --gpu, --gpu + 1, ..)
-  std::string reduce = "auto";        // --reduce auto|rccl|peer: all-reduce over RCCL / peer copies + int64 adds
+  std::string reduce = "auto";        // --reduce auto|rccl|peer|scatter: all-reduce over RCCL / peer copies + adds into engine 0, one
+                                      // engine after the other / reduce-scatter over all k engines at once (pcoa_gram_reduce_peers)
   std::string layout = "auto";        // --layout auto|full|strips: S whole on every engine (variants dealt, then reduced) or
                                       // tiled by columns (every engine fed every variant, no reduction); auto: pcoa_plan_layout
   std::string plink_decode = "device";  // --plink-decode device|host: where the 2-bit codes become carrier bits
@@ -100,7 +101,7 @@ const char* kUsage =
     "usage: variants_pca_driver --input-path <file.vcf[.gz]> [more] | <prefix>.bed [options]\n"
     "  reference flags: --output-path P --num-pc K --references R.. --all-references --min-allele-frequency F\n"
     "                   --debug-datasets --bases-per-partition B --num-reduce-partitions P --variant-set-id ..\n"
-    "  engine flags:    --gpu D --gpus K --gpu-map a,b,.. --reduce auto|rccl|peer --layout auto|full|strips\n"
+    "  engine flags:    --gpu D --gpus K --gpu-map a,b,.. --reduce auto|rccl|peer|scatter --layout auto|full|strips\n"
     "                   --gram stored|implicit --carrier-format auto|lists|bits --plink-decode device|host\n"
     "                   --plink-ref-allele a1|a2 --stream-rows R\n"
     "                   --no-stream --join-partitions P --spill-dir D --spark-output-layout --ingest-threads T\n"
@@ -198,7 +199,8 @@ Conf parse(int argc, char** argv) {
   if (c.gpu_map.empty())
     for (int g = 0; g < c.gpus; ++g) c.gpu_map.push_back(c.gpu + g);
   if ((int)c.gpu_map.size() != c.gpus) die("--gpu-map must name exactly --gpus devices");
-  if (c.reduce != "auto" && c.reduce != "rccl" && c.reduce != "peer") die("--reduce takes auto, rccl or peer");
+  if (c.reduce != "auto" && c.reduce != "rccl" && c.reduce != "peer" && c.reduce != "scatter")
+    die("--reduce takes auto, rccl, peer or scatter");
   if (c.layout != "auto" && c.layout != "full" && c.layout != "strips") die("--layout takes auto, full or strips");
   if (c.layout == "strips" && c.reduce == "rccl") die("--layout strips has no reduction step: it cannot take --reduce rccl");
   if (c.plink_decode != "device" && c.plink_decode != "host") die("--plink-decode takes device or host");
@@ -1240,8 +1242,21 @@ std::vector<pcoa_ctx*> run_engines(const Conf& conf, int32_t n, const std::vecto
               std::to_string(strips[(size_t)g].first + strips[(size_t)g].second) + ") on device " +
               std::to_string(conf.gpu_map[(size_t)g]);
   } else if (k > 1) {
-    for (int g = 1; g < k; ++g) check(ctx[0], pcoa_gram_reduce_from(ctx[0], ctx[(size_t)g]), "reduce");
-    *how = "peer reduction of " + std::to_string(k) + " engines into engine 0";
+    // --reduce scatter: all k engines at once, 1 / k of S per link, nothing staged.  Engines that cannot address each other's
+    // memory are the one case the library hands back (PCOA_ERR_STATE): the chain below then does the job
+    bool scattered = false;
+    if (conf.reduce == "scatter") {
+      const int rc = pcoa_gram_reduce_peers(ctx.data(), k, 1);
+      if (rc == PCOA_ERR_STATE) std::fprintf(stderr, "%s; falling back to the peer reduction into engine 0\n", pcoa_last_error(ctx[0]));
+      else check(ctx[0], rc, "reduce");
+      scattered = rc == PCOA_OK;
+    }
+    if (scattered) {
+      *how = "reduce-scatter over " + std::to_string(k) + " engines, total gathered on engine 0";
+    } else {
+      for (int g = 1; g < k; ++g) check(ctx[0], pcoa_gram_reduce_from(ctx[0], ctx[(size_t)g]), "reduce");
+      *how = "peer reduction of " + std::to_string(k) + " engines into engine 0";
+    }
   } else {
     *how = conf.gram == "implicit" ? "one operator engine: the carrier bitsets kept, no similarity matrix" : "one engine";
   }
