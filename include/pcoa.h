@@ -648,10 +648,13 @@ int pcoa_reset_timings(pcoa_ctx* ctx);
  * of touching a neighbouring allocation.  The GPU test suite runs its fuzz and parity sweeps in that mode with the
  * input tiles allocated here (tests/test_gpu_guard.py).  pcoa_debug_guard_mode returns the mode in effect (0 = off). */
 int pcoa_debug_alloc(int32_t device_ordinal, size_t bytes, void** out);
-/* One y = B x of the centred matrix of the current S (host vectors of N doubles) with either form of the eigensolver's mat-vec:
- * 0 = one wave per row over all N^2 entries, 1 = upper-triangular 1024 x 1024 tiles, each entry read once and used for y_i and
- * y_j (the form pcoa_compute takes from N = 16,384; needs N % 4 == 0). */
-int pcoa_debug_centred_matvec(pcoa_ctx* ctx, const double* x, double* y, int upper_triangle_form);
+/* One y = B x of the centred matrix of the current S (host vectors of N doubles) with one form of the eigensolver's mat-vec
+ * (the numbers of pcoa_timings.matvec_form):
+ * 0 = one wave per row over all N^2 entries of S, centred on the fly, 1 = upper-triangular 1024 x 1024 tiles, each entry read
+ * once and used for y_i and y_j (the form pcoa_compute takes from N = 16,384; needs N % 4 == 0 and no int64 part, else
+ * PCOA_ERR_STATE), 2 = one wave per row over the materialised B (the form of PCOA_EXPLICIT_CENTER; allocates the N x N fp64
+ * matrix).  Any other form: PCOA_ERR_INVALID_ARG. */
+int pcoa_debug_centred_matvec(pcoa_ctx* ctx, const double* x, double* y, int form);
 /* The partition pcoa_gram_reduce_peers cuts S by: chunk g of k over N samples as [*first_out, *first_out + *count_out) of the flat
  * element range [0, N^2).  Pure function (no GPU): the one the library's launches and copies go by. */
 int pcoa_debug_reduce_chunk(int32_t g, int32_t k, int32_t n_samples, int64_t* first_out, int64_t* count_out);

@@ -749,11 +749,14 @@ int pcoa_compute_strips(pcoa_ctx* const* owners, int32_t n_owners, int32_t num_p
   return PCOA_OK;
 }
 
-// Test hook: one y = B x of the centred matrix of the CURRENT S with either form of the mat-vec (0 = one wave per row over all
-// N^2 entries, 1 = upper-triangular tiles); x, y host arrays of N doubles.  N % 4 == 0 and no int64 part for form 1.
-int pcoa_debug_centred_matvec(pcoa_ctx* c, const double* x, double* y, int upper_triangle_form) {
+// Test hook: one y = B x of the centred matrix of the CURRENT S with one form of the mat-vec (0 = one wave per row over all
+// N^2 entries of S, centred on the fly; 1 = upper-triangular tiles; 2 = one wave per row over the materialised B: ensure_b,
+// center_kernel, symv_kernel); x, y host arrays of N doubles.  N % 4 == 0 and no int64 part for form 1.
+int pcoa_debug_centred_matvec(pcoa_ctx* c, const double* x, double* y, int form) {
   CHECK_CTX(c);
   if (!x || !y) return fail(c, PCOA_ERR_INVALID_ARG, "x or y is NULL");
+  if (form < 0 || form > 2) return fail(c, PCOA_ERR_INVALID_ARG, "form must be 0, 1 or 2");
+  const bool upper_triangle_form = form == 1;
   NOT_ON_OPERATOR(c, "pcoa_debug_centred_matvec");
   if (c->is_strip) return fail(c, PCOA_ERR_STATE, "not available on a strip owner");
   int rc = finalize_impl(c);
@@ -775,7 +778,11 @@ int pcoa_debug_centred_matvec(pcoa_ctx* c, const double* x, double* y, int upper
     // the large-N form of computePca's first pass as well: row sums from the upper-triangular tiles
     HIP_TRY(c, launch_row_sums_sym(c->s32, n, c->sym_part, c->row_sums, reinterpret_cast<int64_t*>(c->stats + 2), c->stream));
   }
-  HIP_TRY(c, launch_center(c->s32, c->s64, n, c->row_sums, c->stats, c->nz, nullptr, c->stream, upper_triangle_form != 0));
+  if (form == 2) {
+    if ((rc = ensure_b(c)) != PCOA_OK) return rc;
+    wl.a = c->ws.a;
+  }
+  HIP_TRY(c, launch_center(c->s32, c->s64, n, c->row_sums, c->stats, c->nz, wl.a, c->stream, upper_triangle_form));
   HIP_TRY(c, launch_col_means(c->row_sums, n, c->colmean, c->stream));
   double* xd = c->ws.q;   // two N-vectors of the eigensolver workspace
   double* yd = c->ws.w;

@@ -350,11 +350,13 @@ class PcoaEngine(object):
         self._check(rc)
         return np.ascontiguousarray(comps.T), lam
 
-    def debug_centred_matvec(self, x, upper_triangle_form):
-        """One y = B x of the centred matrix of the current S (test hook of the two mat-vec forms of the eigensolver)."""
+    def debug_centred_matvec(self, x, form):
+        """One y = B x of the centred matrix of the current S (test hook of the mat-vec forms of the eigensolver, numbered as
+        timings()["matvec_form"]): 0 = one wave per row, S centred on the fly; 1 = upper-triangular tiles (N % 4 == 0, no
+        int64 part); 2 = one wave per row over the materialised B."""
         x = np.ascontiguousarray(x, dtype=np.float64)
         y = np.zeros(self.n, dtype=np.float64)
-        self._check(self._lib.pcoa_debug_centred_matvec(self._ctx, _ptr(x), _ptr(y), int(upper_triangle_form)))
+        self._check(self._lib.pcoa_debug_centred_matvec(self._ctx, _ptr(x), _ptr(y), int(form)))
         return y
 
     def reduce_from(self, other):

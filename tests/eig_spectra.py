@@ -1,5 +1,7 @@
 """Integer similarity matrices S whose centred matrix B = J S J has a known spectrum, a high-precision reference for it, and
-the checks that hold the dense eigensolver (csrc/eig.hip) to that reference.  Test infrastructure: imported by tests only.
+the checks that hold the dense eigensolver (csrc/eig.hip) and, with bars of its own (`lanczos_bars`), the Lanczos path
+(csrc/eig_lanczos.hip) to that reference; and `integer_centred`, an S whose centred matrix is an integer matrix, the exact
+reference of the centred mat-vec.  Test infrastructure: imported by tests only.
 
 Every builder returns a Spectrum for the top k pairs of B, ranked by |lambda| with ties to the larger value (the order of
 pcoa_compute and of MLlib).  Most families have the form
@@ -31,10 +33,12 @@ class Spectrum(object):
     NaN where only the eigenvalue is known (the bulk c, the null space); the columns of a cluster span its eigenspace.
     groups: (indices into the top k, whole) per cluster of the whole spectrum that the top k touch; whole = every
     eigenvalue of the cluster is among the top k.  norm: ||B||_2.  lam_tol: extra eigenvalue bar (Weyl bound; 0 = exact).
-    vec_tol: [k] extra vector bars (Davis-Kahan; 0 = exact).  levels: [(value, multiplicity)] of the whole spectrum."""
+    vec_tol: [k] extra vector bars (Davis-Kahan; 0 = exact).  levels: [(value, multiplicity)] of the whole spectrum.
+    gap: [k] distance of every selected eigenvalue to the nearest level outside its cluster (inf if there is none)."""
 
-    def __init__(self, s, lam, vecs, groups, norm, levels, lam_tol=0.0, vec_tol=None, family=""):
+    def __init__(self, s, lam, vecs, groups, norm, levels, lam_tol=0.0, vec_tol=None, family="", gap=None):
         self.s, self.lam, self.vecs, self.groups, self.norm, self.levels = s, lam, vecs, groups, norm, levels
+        self.gap = np.full(len(lam), np.inf) if gap is None else gap
         self.lam_tol = lam_tol
         self.vec_tol = np.zeros(len(lam)) if vec_tol is None else vec_tol
         self.family = family
@@ -136,7 +140,8 @@ def _low_rank_levels(y, cmat, c):
 def _spectrum(s, levels, k, family, weyl=0.0):
     lam, vecs, groups, norm, gap = _select(levels, k)
     vec_tol = 2.0 * weyl / gap if weyl > 0 else None
-    sp = Spectrum(s, lam, vecs, groups, norm, [(v, m) for v, m, _ in levels], lam_tol=weyl, vec_tol=vec_tol, family=family)
+    sp = Spectrum(s, lam, vecs, groups, norm, [(v, m) for v, m, _ in levels], lam_tol=weyl, vec_tol=vec_tol, family=family,
+                  gap=gap)
     sp._levels = levels
     return sp
 
@@ -246,6 +251,42 @@ def near_tie(n, k, c=1000, within=1000000100, across=100, bump=1):
     return _spectrum(s, levels, k, "near tie")
 
 
+# ------------------------------------------------------------------------------------------------- exactly integer B
+INT_X_MAX = 8        # integer_vectors draws from [-INT_X_MAX, INT_X_MAX]
+
+
+def integer_centred(n, seed, hi=1000, scale=1, zero_row=None):
+    """A symmetric int64 S whose centred matrix is an INTEGER matrix, and that matrix: (S, B).  A random symmetric matrix
+    with entries in [0, hi); row and column `zero_row` zeroed (a sample that carries nothing); every diagonal entry raised by
+    (-rowsum) % n, so that every row sum is divisible by n; S[0, 0] raised by n ((-(total // n)) % n), so that the total is
+    divisible by n^2; everything times `scale`.  rowMean, colMean and the matrix mean are then integers, B = S - r_i / n -
+    r_j / n + m is an integer matrix, and for an integer x every partial sum of B x, in any order of addition, is an integer:
+    asserted to stay below 2^53 for |x| <= INT_X_MAX, so every correct mat-vec equals the int64 product bit for bit."""
+    rng = np.random.default_rng(seed)
+    a = rng.integers(0, hi, size=(n, n), dtype=np.int64)
+    s = np.triu(a) + np.triu(a, 1).T
+    if zero_row is not None:
+        s[zero_row, :] = 0
+        s[:, zero_row] = 0
+    s[np.diag_indices_from(s)] += (-s.sum(axis=1)) % n
+    s[0, 0] += n * ((-(int(s.sum()) // n)) % n)
+    s *= scale
+    r = s.sum(axis=1)
+    total = int(r.sum())
+    assert np.all(r % n == 0) and total % (n * n) == 0 and np.array_equal(s, s.T)
+    rm = r // n
+    b = s - rm[:, None] - rm[None, :] + total // (n * n)
+    assert n * int(np.abs(b).max()) * INT_X_MAX < 2 ** 53 and int(np.abs(r).max()) < 2 ** 53 and abs(total) < 2 ** 53, (
+        "n = %d, seed = %d, scale = %d: a partial sum of B x may leave the integers of float64" % (n, seed, scale))
+    return s, b
+
+
+def integer_vectors(n, seed, count=3):
+    """[count, n] float64 vectors of integers drawn per position from [-INT_X_MAX, INT_X_MAX]."""
+    rng = np.random.default_rng([seed, n])
+    return rng.integers(-INT_X_MAX, INT_X_MAX + 1, size=(count, n)).astype(np.float64)
+
+
 # ------------------------------------------------------------------------------------------------- helpers
 def symmetric_noise(rng, n, rows=2048):
     """E + E^T as float32 [n, n], E uniform in {-1, 0, 1} (generated in row blocks)."""
@@ -310,19 +351,40 @@ def centred_matmul_host(sf):
 
 
 # ------------------------------------------------------------------------------------------------- checks
-def check_pairs(sp, comps, lam, bmul, what=""):
+def lanczos_bars(sp):
+    """The bars of the Lanczos path (csrc/eig_lanczos.hip), derived from its acceptance rule instead of the dense solver's
+    accuracy: a pair is returned once its TRUE residual r on the device satisfies 0.125 r <= 1e-11 scale (`accept`, tol =
+    1e-11, scale = the largest |Ritz value| <= ||B||), i.e. r <= 8e-11 ||B||.  The host's residual differs from the device's
+    by the rounding of one product, O(N 2^-53 ||B||) < 1e-12 ||B|| at the N of the tests, so
+        residual, eigenvalue:  1e-10 ||B||          (|lambda - lambda_ref| <= ||r|| for a symmetric B)
+        isolated vector:       VEC_BAR + 2e-10 ||B|| / gap
+        whole cluster:         SUB_BAR + 2e-10 ||B|| / gap_cluster
+    (Davis-Kahan with the residual bar: sin of the angle <= r / gap, and ||u - u_ref|| <= sqrt(2) sin, taken as 2), with
+    gap the distance to the nearest level outside the cluster (Spectrum.gap; a cluster takes its members' smallest).
+    Orthogonality keeps ORTH_BAR: the returned vectors are Ritz vectors of ONE orthonormal basis."""
+    scale = sp.norm if sp.norm > 0 else 1.0
+    extra = 2e-10 * scale / sp.gap
+    return {"eig": 1e-10, "res": 1e-10, "orth": ORTH_BAR, "vec": extra, "sub": extra}
+
+
+def check_pairs(sp, comps, lam, bmul, what="", bars=None):
     """Holds computed pairs (comps [N, k], lam [k]) to the Spectrum sp.  bmul(U) = B U on the host.  Returns the observed
-    maxima {eig, res, orth, vec, sub} relative to the bars' units (eigenvalue and residual as multiples of ||B||_2)."""
+    maxima {eig, res, orth, vec, sub} relative to the bars' units (eigenvalue and residual as multiples of ||B||_2).
+    bars: None = the dense solver's (EIG_BAR, RES_BAR, ORTH_BAR, VEC_BAR, SUB_BAR), or a dict {eig, res, orth: scalars in
+    the same units; vec, sub: [k] additions to VEC_BAR / SUB_BAR per selected eigenvalue} such as `lanczos_bars`."""
     scale = sp.norm if sp.norm > 0 else 1.0
     k = sp.k
+    if bars is None:
+        bars = {"eig": EIG_BAR, "res": RES_BAR, "orth": ORTH_BAR, "vec": np.zeros(k), "sub": np.zeros(k)}
+    eig_bar, res_bar, orth_bar = bars["eig"], bars["res"], bars["orth"]
     assert comps.shape == (sp.n, k) and lam.shape == (k,), what
     err = np.abs(lam - sp.lam)
-    assert np.all(err <= EIG_BAR * scale + sp.lam_tol), "%s eigenvalues: |lambda - ref| = %s > %.3g ||B|| + %.3g" % (
-        what, err.tolist(), EIG_BAR, sp.lam_tol)
+    assert np.all(err <= eig_bar * scale + sp.lam_tol), "%s eigenvalues: |lambda - ref| = %s > %.3g ||B|| + %.3g" % (
+        what, err.tolist(), eig_bar, sp.lam_tol)
     res = np.linalg.norm(bmul(comps) - comps * lam, axis=0)
-    assert np.all(res <= RES_BAR * scale), "%s residual ||Bu - lambda u|| / ||B|| = %s" % (what, (res / scale).tolist())
+    assert np.all(res <= res_bar * scale), "%s residual ||Bu - lambda u|| / ||B|| = %s" % (what, (res / scale).tolist())
     orth = float(np.abs(comps.T @ comps - np.eye(k)).max())
-    assert orth <= ORTH_BAR, "%s orthogonality |U^T U - I| = %.3g" % (what, orth)
+    assert orth <= orth_bar, "%s orthogonality |U^T U - I| = %.3g" % (what, orth)
     for t in range(k):
         u = comps[:, t]
         assert u.max() >= -u.min(), "%s sign rule: PC%d has its largest magnitude negative" % (what, t + 1)
@@ -337,14 +399,15 @@ def check_pairs(sp, comps, lam, bmul, what=""):
             ref = sp.vecs[:, t]
             u = comps[:, t] if comps[:, t] @ ref >= 0 else -comps[:, t]
             d = float(np.linalg.norm(u - ref))
-            assert d <= VEC_BAR + sp.vec_tol[t], "%s vector PC%d: ||u - u_ref|| = %.3g > %.3g" % (
-                what, t + 1, d, VEC_BAR + sp.vec_tol[t])
+            vec_bar = VEC_BAR + sp.vec_tol[t] + bars["vec"][t]
+            assert d <= vec_bar, "%s vector PC%d: ||u - u_ref|| = %.3g > %.3g" % (what, t + 1, d, vec_bar)
             vec = max(vec, d)
         else:
             u, ref = comps[:, members], sp.vecs[:, members]
             # ||U U^T - R R^T||_2 = sin of the largest principal angle = ||(I - R R^T) U||_2 for equal dimensions
             d = float(np.linalg.norm(u - ref @ (ref.T @ u), 2))
-            assert d <= SUB_BAR + max(sp.vec_tol[t] for t in members), "%s cluster PC%s: ||UU^T - U_ref U_ref^T|| = %.3g" % (
-                what, [t + 1 for t in members], d)
+            sub_bar = SUB_BAR + max(sp.vec_tol[t] for t in members) + max(bars["sub"][t] for t in members)
+            assert d <= sub_bar, "%s cluster PC%s: ||UU^T - U_ref U_ref^T|| = %.3g > %.3g" % (
+                what, [t + 1 for t in members], d, sub_bar)
             sub = max(sub, d)
     return {"eig": float((err / scale).max()), "res": float((res / scale).max()), "orth": orth, "vec": vec, "sub": sub}

@@ -103,3 +103,39 @@ def test_checker_rejects_what_each_bar_is_for(O):
         E.check_pairs(sp, swapped, lam, bmul)
     with pytest.raises(AssertionError, match="sign rule"):
         E.check_pairs(sp, u * np.array([1.0, -1.0, 1.0]), lam, bmul)
+
+
+def test_lanczos_bars_of_every_case_stay_below_the_parity_bar():
+    """The Lanczos bars (E.lanczos_bars) are derived from the path's acceptance rule, residual <= 8e-11 ||B||, and grow with
+    1 / gap.  Every case of tests/test_gpu_lanczos_bands.py keeps the solver's share of its vector and subspace bar,
+    VEC_BAR + 2e-10 ||B|| / gap, below the project's 1e-6 parity bar (REL_GAP = 1e-3 bounds it by 2.1e-7), and so the whole
+    bar wherever the reference is exact (vec_tol = 0; the Davis-Kahan term of the perturbed family is the reference's own
+    uncertainty).  The schedule helper is held to the constants of lanczos_single."""
+    import test_gpu_lanczos_bands as LB
+    for case in LB.CASES:
+        sp = LB.spectrum(case)
+        bars = E.lanczos_bars(sp)
+        assert bars["eig"] == bars["res"] == 1e-10 and bars["orth"] == E.ORTH_BAR
+        assert sp.gap.shape == (sp.k,) and np.all(sp.gap >= E.REL_GAP * sp.norm), (case, sp.gap / sp.norm)
+        for members, whole in sp.groups:
+            if not whole or np.isnan(sp.vecs[:, members]).any():
+                continue
+            share = max(E.VEC_BAR, E.SUB_BAR) + max(bars["vec"][t] for t in members)
+            assert share <= 2.1e-7, (case, members, share)
+            if not sp.lam_tol:
+                assert share + max(sp.vec_tol[t] for t in members) < 1e-6, (case, members)
+    assert sorted(LB.schedule(4100, 2)) == [12, 16, 20, 24, 32, 40, 48, 56, 64, 96, 144, 216, 324, 486, 512]
+    assert sorted(LB.schedule(33, 2)) == [12, 16, 20, 24, 32, 33] and min(LB.schedule(600, 15)) == 17
+
+
+def test_check_pairs_takes_other_bars(O):
+    """bars= replaces the dense bars: a residual of 5e-11 ||B|| fails the dense bar and passes the Lanczos one; one
+    of 2e-10 ||B|| fails both."""
+    sp = E.shifted_low_rank(300, 3, v=8)
+    b, _, u, lam = _lapack(O, sp)
+    off = lambda x: (1 + 5e-11 * sp.norm / np.abs(lam).min()) * (b @ x)   # noqa: E731
+    with pytest.raises(AssertionError, match="residual"):
+        E.check_pairs(sp, u, lam, off)
+    E.check_pairs(sp, u, lam, off, bars=E.lanczos_bars(sp))
+    with pytest.raises(AssertionError, match="residual"):
+        E.check_pairs(sp, u, lam, lambda x: (1 + 2e-10 * sp.norm / np.abs(lam).min()) * (b @ x), bars=E.lanczos_bars(sp))
