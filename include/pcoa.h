@@ -301,6 +301,50 @@ int pcoa_operator_matvec_device(pcoa_ctx* ctx, const double* v_dev, double* y_de
  * smartpca-style outlier loop repeats. */
 int pcoa_create_subset(pcoa_ctx** out, pcoa_ctx* src, const int32_t* keep, int32_t n_keep);
 
+/* ---- screening a stored S for duplicate and related sample pairs ------------------------------------------------------------
+ * S(i, i) = d_i is the number of variants sample i carries, S(i, j) the number two samples share, so
+ * S(i, j) / (d_i + d_j - S(i, j)) is the Jaccard index of their carrier sets: 1 for a duplicate, high for first-degree relatives.
+ * The rule, with S(i, j) the TOTAL entry (the int32 matrix plus the int64 part where the ctx has one) and U = d_i + d_j - S(i, j):
+ *   the pair (i, j), i < j, is REPORTED iff U > 0 and (double)S(i, j) >= min_jaccard * (double)U
+ * -- one IEEE fp64 multiplication and one comparison (nothing to contract), every integer below 2^53: the same expression in
+ * numpy (variants_pca.related_pairs_rule) reports the same pairs, bit for bit.
+ *
+ * pcoa_similar_pairs: one memory-bound screen of the upper triangle of S on the device (count, scan, write: csrc/pairs.hip).
+ *   ctx:     an ordinary full engine: from pcoa_create, a subset, or one with a loaded or reduced S.  A strip owner or an operator
+ *            ctx: PCOA_ERR_STATE, the message names the kind of ctx, the ctx stays usable.  ctx is finalized and its input checks
+ *            are read first (an S that a check has invalidated is never screened; that error comes back as it would from
+ *            pcoa_gram_finalize).
+ *   min_jaccard: finite, in (0, 1].
+ *   out_pairs / capacity: receives the first min(n_found, capacity) reported pairs in increasing (i, j) order; entries behind
+ *            them are not touched.  capacity == 0 is a count-only call (out_pairs may be NULL).  n_found > capacity is not an
+ *            error: the caller compares the two.
+ *   *n_found_out: the number of pairs the rule reports -- always the full count.
+ *   out_diag: N entries d_0 .. d_{N-1}, or NULL.
+ *   PCOA_ERR_INVALID_ARG, found on the host before any device work: ctx or n_found_out NULL, capacity < 0, capacity > 0 with
+ *            out_pairs NULL, min_jaccard not finite or outside (0, 1].
+ *   memory:  N ceil(N / 1024) int32 counts, 2 N + 2 int64 and min(capacity, N (N - 1) / 2) pairs on the device, all allocated
+ *            before the first launch and freed before the call returns; PCOA_ERR_OUT_OF_MEMORY leaves the ctx usable.
+ * Content and order are a function of S and min_jaccard alone: not of the grid, the CU count or how S was accumulated (no
+ * floating-point atomics; the list is not sorted, it is written in order).  S is unchanged and the ctx computes the same bits
+ * afterwards.  Synchronising.  Statistics: pcoa_get_pairs_stats.
+ * Extends: computePca (VariantsPca.scala:198-231) by the screen every genetics PCA pipeline runs before the decomposition, over
+ * the matrix getSimilarityMatrix built (:182-191); with pcoa_create_subset: screen, drop one of each pair, decompose
+ * S[kept, kept], no variant read twice. */
+typedef struct pcoa_pair { int32_t i, j; int64_t shared; } pcoa_pair;   /* i < j, shared = S(i, j) */
+int pcoa_similar_pairs(pcoa_ctx* ctx, double min_jaccard, pcoa_pair* out_pairs, int64_t capacity, int64_t* n_found_out,
+                       int64_t* out_diag /* N entries or NULL */);
+
+/* What pcoa_similar_pairs did on THIS engine, cumulative since pcoa_create / pcoa_reset_timings.  (A struct of its own, like
+ * pcoa_reduce_peers_stats: the layout and the size of pcoa_timings are held fixed by its readers.)  It grows at its end;
+ * out_size = sizeof of the struct the caller compiled against.  Synchronising, like pcoa_get_timings. */
+typedef struct pcoa_pairs_stats {
+  double pairs_seconds;   /* HIP-event time of the screens: diagonal, count, scans, write                                     */
+  int64_t pairs_bytes;    /* bytes of S the scan kernels read: the count pass's (band, tile) blocks above the diagonal plus the
+                             (row, tile) cells the write pass read again; 4 per entry, 12 where S has an int64 part           */
+  int64_t pairs_calls;
+} pcoa_pairs_stats;
+int pcoa_get_pairs_stats(pcoa_ctx* ctx, pcoa_pairs_stats* out, size_t out_size);
+
 /* ---- layout of S over the engines of one job ------------------------------------------------------------------------
  * FULL: every engine holds a whole N x N partial S (4 N^2 bytes) for its share of the variants; the partials are reduced
  * into engine 0 (peer copies: engine 0 stages one more 4 N^2 matrix when the engines sit on different devices, RCCL

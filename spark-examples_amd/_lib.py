@@ -105,6 +105,24 @@ class PcoaReducePeersStats(ctypes.Structure):
 PCOA_REDUCE_MAX_ENGINES = 16
 
 
+class PcoaPair(ctypes.Structure):
+    """pcoa_pair: one reported pair of pcoa_similar_pairs, i < j, shared = S(i, j); 16 bytes."""
+    _fields_ = [
+        ("i", ctypes.c_int32),
+        ("j", ctypes.c_int32),
+        ("shared", ctypes.c_int64),
+    ]
+
+
+class PcoaPairsStats(ctypes.Structure):
+    """pcoa_pairs_stats: a struct of its own beside pcoa_timings, like pcoa_reduce_peers_stats."""
+    _fields_ = [
+        ("pairs_seconds", ctypes.c_double),
+        ("pairs_bytes", ctypes.c_int64),
+        ("pairs_calls", ctypes.c_int64),
+    ]
+
+
 class PcoaSynthParams(ctypes.Structure):
     _fields_ = [
         ("seed", ctypes.c_uint64),
@@ -125,6 +143,8 @@ _SIGNATURES = [
     ("pcoa_create_strip", ctypes.c_int, [ctypes.POINTER(_vp), _i32, _i32, _i32, _i32, ctypes.c_uint32]),
     ("pcoa_create_operator", ctypes.c_int, [ctypes.POINTER(_vp), _i32, _i32, ctypes.c_uint32]),
     ("pcoa_create_subset", ctypes.c_int, [ctypes.POINTER(_vp), _vp, _vp, _i32]),
+    ("pcoa_similar_pairs", ctypes.c_int, [_vp, ctypes.c_double, _vp, _i64, ctypes.POINTER(_i64), _vp]),
+    ("pcoa_get_pairs_stats", ctypes.c_int, [_vp, ctypes.POINTER(PcoaPairsStats), ctypes.c_size_t]),
     ("pcoa_operator_info", ctypes.c_int, [_vp, ctypes.POINTER(_i64), ctypes.POINTER(_i64)]),
     ("pcoa_operator_row_sums", ctypes.c_int, [_vp, _vp]),
     ("pcoa_operator_matvec_device", ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int]),

@@ -1,6 +1,6 @@
 // pcoa_capi.hip -- the C ABI of include/pcoa.h on top of the HIP kernels: an engine's life (create / destroy / reset /
 // reserve / set_stream / sync), error reporting, and the timings.  The rest of the ABI lives in capi_accumulate.hip,
-// capi_reduce.hip, capi_compute.hip, capi_operator.hip, capi_subset.hip and devmem.hip (map: pcoa_ctx.h).  There is deliberately NO CPU fallback: without a HIP
+// capi_reduce.hip, capi_compute.hip, capi_operator.hip, capi_subset.hip, capi_pairs.hip and devmem.hip (map: pcoa_ctx.h).  There is deliberately NO CPU fallback: without a HIP
 // device pcoa_create fails with PCOA_ERR_NO_DEVICE.
 #include <cstdio>
 #include <cstring>
@@ -407,6 +407,7 @@ int pcoa_reset_timings(pcoa_ctx* c) {
   c->evensplit_launches = 0;
   c->op_products = 0;
   c->subset_bytes = 0;
+  c->pairs_bytes = c->pairs_calls = 0;
   c->reduce_peers_calls = c->reduce_peers_bytes_in = 0;
   return PCOA_OK;
 }

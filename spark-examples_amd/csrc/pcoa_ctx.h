@@ -10,6 +10,7 @@
 //   capi_compute.hip     the eigensolver workspace, computePca, strips, projection
 //   capi_operator.hip    the implicit similarity operator: the bit store, its products, computePca over it
 //   capi_subset.hip      pcoa_create_subset: a new engine whose S is S[I, I] of another
+//   capi_pairs.hip       pcoa_similar_pairs: the screen of S for duplicate and related sample pairs
 //   pcoa_capi.hip        create / destroy, errors, timings
 #pragma once
 
@@ -18,7 +19,7 @@
 
 #include "pcoa_internal.h"
 
-enum TimeCat { T_GRAM = 0, T_DENSIFY, T_SYNTH, T_FINALIZE, T_CENTER, T_TRIDIAG, T_EIG, T_BACK, T_PACK, T_LANCZOS, T_ALLREDUCE, T_OPERATOR, T_SUBSET, T_REDUCE_PEERS, T_NCAT };
+enum TimeCat { T_GRAM = 0, T_DENSIFY, T_SYNTH, T_FINALIZE, T_CENTER, T_TRIDIAG, T_EIG, T_BACK, T_PACK, T_LANCZOS, T_ALLREDUCE, T_OPERATOR, T_SUBSET, T_REDUCE_PEERS, T_PAIRS, T_NCAT };
 
 struct EventPair {
   hipEvent_t a, b;
@@ -75,6 +76,7 @@ struct pcoa_ctx {
   int64_t op_ws_cap = 0;
   int64_t op_products = 0;
   int64_t subset_bytes = 0;        // bytes the gathers of pcoa_create_subset moved into this ctx (read + written)
+  int64_t pairs_bytes = 0, pairs_calls = 0;   // pcoa_similar_pairs: bytes of S its scan kernels read, calls
   int device = 0;
   uint32_t flags = 0;
   int num_cu = 256;

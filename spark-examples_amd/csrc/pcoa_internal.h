@@ -166,6 +166,25 @@ hipError_t launch_subset_gather_i32(const int32_t* src, int32_t n, const int32_t
 hipError_t launch_subset_gather_i64(const int64_t* src, int32_t n, const int32_t* keep_dev, int32_t m, int64_t* dst,
                                     hipStream_t stream);
 
+// ---- the screen for duplicate and related pairs (pairs.hip): pair (i, j), i < j, is reported iff U = d_i + d_j - S(i, j) > 0 and
+// (double)S(i, j) >= x * (double)U, d = the diagonal of S.  A workgroup takes kPairsBandRows rows x kPairsTileCols columns.
+// All buffers are the caller's, on the device of s32: diag n int64; cnt n * pairs_tiles(n) int32 (the counts, then their
+// exclusive prefix within each row); rowoff n + 1 int64 (row totals, then their exclusive prefix; rowoff[n] = n_found)
+constexpr int32_t kPairsTileCols = 1024;
+constexpr int32_t kPairsBandRows = 32;
+constexpr int32_t kPairsMaxSamples = 1 << 30;   // column arithmetic stays inside int32 with a tile to spare
+int32_t pairs_tiles(int32_t n);
+int64_t pairs_count_pass_entries(int32_t n);   // entries of S the count pass loads (pure function of n)
+hipError_t launch_pairs_diag(const int32_t* s32, const int64_t* s64_or_null, int32_t n, int64_t* diag, hipStream_t stream);
+hipError_t launch_pairs_count(const int32_t* s32, const int64_t* s64_or_null, int32_t n, const int64_t* diag, double x,
+                              int32_t* cnt, hipStream_t stream);
+hipError_t launch_pairs_scan(int32_t* cnt, int32_t n, int64_t* rowoff, hipStream_t stream);   // both scans
+// out[p] for the list positions p < capacity (capacity >= 1 entries allocated), in increasing (i, j) order.  *entries_read
+// (optional, zeroed by the caller) grows by the entries of S the pass reads again: the widths of the (row, tile) cells it visits
+hipError_t launch_pairs_write(const int32_t* s32, const int64_t* s64_or_null, int32_t n, const int64_t* diag, double x,
+                              const int32_t* prefix, const int64_t* rowoff, int64_t capacity, pcoa_pair* out,
+                              unsigned long long* entries_read, hipStream_t stream);
+
 // ---- implicit similarity operator (operator_bits.hip): y = X^T (X v) from the carrier bitsets, S never formed -------------
 // The store is a list of segments, each rows x operator_pitch_words(n) words; bits of samples >= n and the pitch's padding are
 // zero.  A product's additions are ordered by sample group (kOperatorGroupWords word columns), segment and range of

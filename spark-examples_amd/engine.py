@@ -380,6 +380,22 @@ class PcoaEngine(object):
         sub._keepalive = []
         return sub
 
+    PAIR_DTYPE = np.dtype([("i", np.int32), ("j", np.int32), ("shared", np.int64)])   # pcoa_pair
+
+    def similar_pairs(self, min_jaccard, capacity=1 << 20):
+        """The screen for duplicate and related sample pairs (pcoa_similar_pairs): with d = diag(S), the pairs i < j with
+        U = d_i + d_j - S(i, j) > 0 and S(i, j) >= min_jaccard * U, found on the device in one pass over the upper triangle.
+        Returns (pairs, n_found, diag): `pairs` a structured array (fields i, j, shared) of the first min(n_found, capacity)
+        pairs in increasing (i, j) order, `n_found` the full count whatever the capacity, `diag` int64 [N]."""
+        cap = int(capacity)
+        pairs = np.zeros(max(cap, 0), dtype=self.PAIR_DTYPE)
+        diag = np.zeros(self.n, dtype=np.int64)
+        found = ctypes.c_int64(0)
+        self._check(self._lib.pcoa_similar_pairs(self._ctx, float(min_jaccard), _ptr(pairs) if cap > 0 else None, cap,
+                                                 ctypes.byref(found), _ptr(diag)))
+        n_found = int(found.value)
+        return pairs[:min(n_found, cap)], n_found, diag
+
     def export_device(self, dst_ptr):
         self._check(self._lib.pcoa_gram_export_device_i64(self._ctx, ctypes.c_void_p(int(dst_ptr))))
 
@@ -526,6 +542,9 @@ class PcoaEngine(object):
         r = L.PcoaReducePeersStats()   # reduce_peers_calls / _seconds / _bytes_in: a struct of their own in pcoa.h
         self._check(self._lib.pcoa_get_reduce_peers_stats(self._ctx, ctypes.byref(r), ctypes.sizeof(r)))
         out.update((f[0], getattr(r, f[0])) for f in L.PcoaReducePeersStats._fields_)
+        q = L.PcoaPairsStats()         # pairs_seconds / _bytes / _calls: likewise
+        self._check(self._lib.pcoa_get_pairs_stats(self._ctx, ctypes.byref(q), ctypes.sizeof(q)))
+        out.update((f[0], getattr(q, f[0])) for f in L.PcoaPairsStats._fields_)
         return out
 
     def reset_timings(self):

@@ -95,6 +95,12 @@ struct Conf {  // PcaConf / GenomicsConf (GenomicsConf.scala:31-101), same flag 
   int outlier_iterations = 0;           // --outlier-iterations K: up to K rounds of outlier removal around computePca; a round replaces the engine by
                                         // its subset over the kept samples (pcoa_create_subset: one gather of S, no variant read twice).  0 = off
   double outlier_sigma = 6.0;           // --outlier-sigma X: a sample further than X population standard deviations from the mean of an axis goes
+  bool related = false;                 // --related-min-jaccard X given: screen S for duplicate and related sample pairs before computePca
+  double related_min_jaccard = 0.0;     // (pcoa_similar_pairs): a pair is reported when S(i, j) >= X (S(i, i) + S(j, j) - S(i, j)); X in (0, 1]
+  std::string related_output_path;      // --related-output-path FILE: the reported pairs, one line each
+  int64_t related_max_pairs = 1048576;  // --related-max-pairs M: the capacity handed to the library; more reported pairs stop the job
+  bool related_max_pairs_given = false;
+  bool remove_related = false;          // --remove-related: drop one sample of every reported pair, go on with pcoa_create_subset over the rest
 };
 
 const char* kUsage =
@@ -108,6 +114,10 @@ const char* kUsage =
     "                   --parse-only --dump-similarity FILE\n"
     "                   --outlier-iterations K --outlier-sigma X (K rounds: samples beyond X sd on a principal component are\n"
     "                   removed and computePca runs again on S[kept, kept]; one engine, stored S, full layout)\n"
+    "                   --related-min-jaccard X [--related-output-path FILE] [--related-max-pairs M] [--remove-related]\n"
+    "                   (before computePca: report the sample pairs whose carrier sets have a Jaccard index >= X, X in (0, 1];\n"
+    "                   --remove-related drops one sample of each pair and decomposes S[kept, kept]; one engine, stored S,\n"
+    "                   full layout)\n"
     "  --project-input-path <file.vcf[.gz]> [more]\n"
     "                   place these samples onto the principal coordinates of the --input-path cohort instead of\n"
     "                   decomposing the union (one GPU, VCF inputs, full layout)\n";
@@ -118,6 +128,7 @@ const char* kUsage =
 }
 
 const char* kStripsRefuseOutliers = "--outlier-iterations subsets one whole similarity matrix on one engine: it cannot take --layout strips";
+const char* kStripsRefuseRelated = "--related-min-jaccard screens one whole similarity matrix on one engine: it cannot take --layout strips";
 
 Conf parse(int argc, char** argv) {
   Conf c;
@@ -186,6 +197,24 @@ Conf parse(int argc, char** argv) {
       c.outlier_sigma = std::strtod(v.c_str(), &end);
       if (v.empty() || *end != 0) die("--outlier-sigma (the threshold of --outlier-iterations) takes a number, not '" + v + "'");
     }
+    else if (a == "--related-min-jaccard") {   // a value that does not parse must not silently mean "off"
+      const std::string v = one(i);
+      char* end = nullptr;
+      c.related_min_jaccard = std::strtod(v.c_str(), &end);
+      if (v.empty() || *end != 0) die("--related-min-jaccard takes a number in (0, 1], not '" + v + "'");
+      c.related = true;
+    }
+    else if (a == "--related-output-path") c.related_output_path = one(i);
+    else if (a == "--related-max-pairs") {
+      const std::string v = one(i);
+      char* end = nullptr;
+      errno = 0;
+      const long long m = std::strtoll(v.c_str(), &end, 10);
+      if (v.empty() || *end != 0 || errno != 0) die("--related-max-pairs takes an integer >= 0, not '" + v + "'");
+      c.related_max_pairs = (int64_t)m;
+      c.related_max_pairs_given = true;
+    }
+    else if (a == "--remove-related") c.remove_related = true;
     else if (a == "--parse-only") c.parse_only = true;
     else if (a == "--dump-similarity") c.dump_similarity = one(i);
     else if (a == "--ingest-threads") c.ingest_threads = std::atoi(one(i).c_str());
@@ -213,6 +242,18 @@ Conf parse(int argc, char** argv) {
     if (c.gram == "implicit") die("--outlier-iterations subsets a stored similarity matrix: it cannot take --gram implicit");
     if (c.layout == "strips") die(kStripsRefuseOutliers);
     if (!c.project_input_path.empty()) die("--outlier-iterations decomposes the cohort it is given: it cannot take --project-input-path");
+  }
+  // --related-min-jaccard and its companions: likewise
+  if (!c.related) {
+    if (!c.related_output_path.empty()) die("--related-output-path needs --related-min-jaccard X (the screen is off without it)");
+    if (c.related_max_pairs_given) die("--related-max-pairs needs --related-min-jaccard X (the screen is off without it)");
+    if (c.remove_related) die("--remove-related needs --related-min-jaccard X (the screen is off without it)");
+  } else {
+    if (!(c.related_min_jaccard > 0 && c.related_min_jaccard <= 1)) die("--related-min-jaccard must be a finite number in (0, 1]");
+    if (c.related_max_pairs < 0) die("--related-max-pairs must be >= 0 (the pairs --related-min-jaccard may report)");
+    if (c.gram == "implicit") die("--related-min-jaccard screens a stored similarity matrix: it cannot take --gram implicit");
+    if (c.layout == "strips") die(kStripsRefuseRelated);
+    if (!c.project_input_path.empty()) die("--related-min-jaccard screens the cohort it decomposes: it cannot take --project-input-path");
   }
   if (c.gram == "implicit") {
     // one operator engine holds the carrier bitsets of every variant: what needs S, or several engines, is refused here,
@@ -1310,6 +1351,35 @@ std::vector<char> outlier_rule(const double* comps, int num_pc, int32_t n, doubl
   return removed;
 }
 
+// The removal rule of --remove-related, as variants_pca.py's related_removal states it: while any reported pair has both
+// samples still kept, the kept sample with the most kept partners is removed; a tie goes to the highest index; the partners'
+// counts are updated and the step repeats.  Returns the removed samples in increasing order.
+std::vector<int32_t> related_removal(const std::vector<pcoa_pair>& pairs, int32_t n) {
+  std::vector<std::vector<int32_t>> partners((size_t)n);
+  for (const pcoa_pair& p : pairs) {
+    partners[(size_t)p.i].push_back(p.j);
+    partners[(size_t)p.j].push_back(p.i);
+  }
+  std::vector<int64_t> degree((size_t)n);
+  for (int32_t i = 0; i < n; ++i) degree[(size_t)i] = (int64_t)partners[(size_t)i].size();   // (the library reports a pair once)
+  std::vector<char> gone((size_t)n, 0);
+  std::vector<int32_t> removed;
+  for (;;) {
+    int32_t v = -1;
+    int64_t most = 0;
+    for (int32_t i = 0; i < n; ++i)
+      if (degree[(size_t)i] > 0 && degree[(size_t)i] >= most) { most = degree[(size_t)i]; v = i; }
+    if (v < 0) break;
+    removed.push_back(v);
+    gone[(size_t)v] = 1;
+    for (int32_t w : partners[(size_t)v])
+      if (!gone[(size_t)w]) --degree[(size_t)w];
+    degree[(size_t)v] = 0;
+  }
+  std::sort(removed.begin(), removed.end());
+  return removed;
+}
+
 int main(int argc, char** argv) {
   const auto t_start = std::chrono::steady_clock::now();
   Conf conf = parse(argc, argv);
@@ -1501,6 +1571,7 @@ int main(int argc, char** argv) {
       die(std::string("pcoa_plan_layout: ") + pcoa_last_error(nullptr));
     if (layout == PCOA_LAYOUT_STRIPS) {
       if (conf.outlier_iterations > 0) die(kStripsRefuseOutliers);   // --layout auto resolved to strips
+      if (conf.related) die(kStripsRefuseRelated);
       if (conf.reduce == "rccl") die("the strip layout has no reduction step: it cannot take --reduce rccl");
       for (int g = 0; g < k; ++g) strips.emplace_back(col0[(size_t)g], cols[(size_t)g]);
     }
@@ -1717,6 +1788,56 @@ int main(int argc, char** argv) {
   double gram_s_before = 0.0;             // Gram kernel seconds of engines that --outlier-iterations has replaced
   std::vector<int32_t> kept((size_t)n);   // original index of every sample of the current cohort
   for (int32_t i = 0; i < n; ++i) kept[(size_t)i] = i;
+  if (conf.related) {
+    // --related-min-jaccard X, before the first computePca: the screen of S on the device.  The rule, as pcoa.h and
+    // variants_pca.py's related_pairs_rule state it: with d_i = S(i, i) and U = d_i + d_j - S(i, j), the pair (i, j), i < j, is
+    // reported iff U > 0 and (double)S(i, j) >= X * (double)U.  Then the pair file, one stderr line, and with --remove-related
+    // the engine replaced by its subset over the kept samples (one gather of S, no variant read twice)
+    std::vector<pcoa_pair> pairs((size_t)std::min<int64_t>(conf.related_max_pairs, (int64_t)n * (n - 1) / 2));
+    std::vector<int64_t> diag((size_t)n);
+    int64_t n_found = 0;
+    check(ctx, pcoa_similar_pairs(ctx, conf.related_min_jaccard, pairs.empty() ? nullptr : pairs.data(), (int64_t)pairs.size(), &n_found,
+                                  diag.data()), "pcoa_similar_pairs");
+    if (n_found > conf.related_max_pairs)
+      die("--related-min-jaccard " + java_double(conf.related_min_jaccard) + " reports " + std::to_string(n_found) +
+          " pairs, more than --related-max-pairs " + std::to_string(conf.related_max_pairs) + " takes; raise --related-max-pairs or the threshold");
+    pairs.resize((size_t)n_found);
+    if (!conf.related_output_path.empty()) {
+      std::ofstream out(conf.related_output_path);
+      out << "name_i\tname_j\tshared\td_i\td_j\tjaccard\n";
+      for (const pcoa_pair& p : pairs) {
+        const int64_t di = diag[(size_t)p.i], dj = diag[(size_t)p.j], u = di + dj - p.shared;
+        out << names[(size_t)p.i] << "\t" << names[(size_t)p.j] << "\t" << p.shared << "\t" << di << "\t" << dj << "\t"
+            << java_double((double)p.shared / (double)u) << "\n";
+      }
+      if (!out) die("cannot write " + conf.related_output_path);
+    }
+    const std::vector<int32_t> gone = conf.remove_related ? related_removal(pairs, n) : std::vector<int32_t>();
+    std::string gone_names;
+    for (int32_t i : gone) gone_names += (gone_names.empty() ? ": " : ", ") + names[(size_t)i];
+    std::fprintf(stderr, "Related pairs: %lld at jaccard >= %s; removed %zu sample(s)%s\n", (long long)n_found,
+                 java_double(conf.related_min_jaccard).c_str(), gone.size(), gone_names.c_str());
+    if (!gone.empty()) {
+      const int32_t least = std::max(3, conf.num_pc + 1);
+      if (n - (int32_t)gone.size() < least)
+        die("--remove-related would leave " + std::to_string(n - (int32_t)gone.size()) + " of " + std::to_string(n) +
+            " samples, fewer than the " + std::to_string(least) + " that " + std::to_string(conf.num_pc) +
+            " principal components need; raise --related-min-jaccard");
+      std::vector<int32_t> keep;
+      size_t g = 0;
+      for (int32_t i = 0; i < n; ++i) {
+        if (g < gone.size() && gone[g] == i) ++g;
+        else keep.push_back(i);
+      }
+      pcoa_ctx* sub = nullptr;
+      check(ctx, pcoa_create_subset(&sub, ctx, keep.data(), (int32_t)keep.size()), "pcoa_create_subset");
+      pcoa_timings tp;   // the Gram kernels ran on the predecessor: its time goes into the closing line
+      if (pcoa_get_timings(ctx, &tp) == PCOA_OK) gram_s_before += tp.gram_kernel_seconds;
+      pcoa_destroy(ctx);
+      ctx = owners[0] = sub;
+      kept.swap(keep);
+    }
+  }
   if (!strips.empty()) {
     check(ctx, pcoa_compute_strips(owners.data(), (int32_t)owners.size(), conf.num_pc, comps.data(), lam.data(), &nonzero), "computePca");
   } else {

@@ -266,6 +266,59 @@ def min_cohort(num_pc):
     return max(3, int(num_pc) + 1)
 
 
+# --------------------------------------------------------------------------------------------- related pairs
+PAIR_DTYPE = np.dtype([("i", np.int32), ("j", np.int32), ("shared", np.int64)])   # pcoa_pair (include/pcoa.h)
+
+
+def related_pairs_rule(s, x):
+    """The rule of --related-min-jaccard and of pcoa_similar_pairs (the library and the compiled host restate it): `s` is the
+    N x N similarity matrix, d_i = s[i, i] the number of variants sample i carries, s[i, j] the number two samples share and
+    U = d_i + d_j - s[i, j] the number either carries.  The pair (i, j), i < j, is reported iff U > 0 and
+    float64(s[i, j]) >= x * float64(U): one multiplication and one comparison in double, every integer below 2^53 -- the
+    Jaccard index of the carrier sets against the threshold x without a division.  Returns the reported pairs in increasing
+    (i, j) order as a structured array with the fields i, j, shared."""
+    s = np.asarray(s, dtype=np.int64)
+    if s.ndim != 2 or s.shape[0] != s.shape[1]:
+        raise ValueError("s must be N x N")
+    d = np.diagonal(s)
+    u = d[:, None] + d[None, :] - s
+    hit = (u > 0) & (s.astype(np.float64) >= np.float64(x) * u.astype(np.float64))
+    hit &= np.triu(np.ones(s.shape, dtype=bool), 1)
+    i, j = np.nonzero(hit)                      # row-major: increasing (i, j)
+    out = np.zeros(i.size, dtype=PAIR_DTYPE)
+    out["i"], out["j"], out["shared"] = i, j, s[i, j]
+    return out
+
+
+def related_removal(pairs, n):
+    """The removal rule of --remove-related (the compiled host restates it): `pairs` are the reported pairs (a structured
+    array with the fields i and j, or any sequence of (i, j)) among n samples.  While any pair has both samples still kept,
+    the kept sample with the most kept partners is removed; a tie goes to the highest index; the partners' counts are
+    updated and the step repeats.  Returns the removed samples as a sorted int64 array; it depends on the set of pairs only,
+    not on their order."""
+    if isinstance(pairs, np.ndarray) and pairs.dtype.names:
+        edges = zip(pairs["i"].tolist(), pairs["j"].tolist())
+    else:
+        edges = [(int(a), int(b)) for a, b in pairs]
+    partners = [set() for _ in range(n)]
+    for a, b in edges:
+        if not (0 <= a < n and 0 <= b < n) or a == b:
+            raise ValueError("a pair names a sample outside [0, %d) or the same sample twice" % n)
+        partners[a].add(b)
+        partners[b].add(a)
+    degree = np.array([len(p) for p in partners], dtype=np.int64)
+    removed = []
+    while n > 0 and degree.max() > 0:
+        v = int(np.nonzero(degree == degree.max())[0][-1])
+        removed.append(v)
+        for w in partners[v]:
+            partners[w].discard(v)
+            degree[w] -= 1
+        partners[v] = set()
+        degree[v] = 0
+    return np.array(sorted(removed), dtype=np.int64)
+
+
 # --------------------------------------------------------------------------------------------- conf
 class PcaConf(object):
     """Flags of PcaConf / GenomicsConf (GenomicsConf.scala:31-101), same names and defaults.
@@ -333,12 +386,33 @@ class PcaConf(object):
                             "is read twice.  Rows go out for the kept samples only.  One full engine: stored S, full layout")
         p.add_argument("--outlier-sigma", type=float, default=6.0,
                        help="--outlier-iterations: the threshold, in population standard deviations of an axis")
+        p.add_argument("--related-min-jaccard", type=float, default=None,
+                       help="X in (0, 1]: screen S for duplicate and related sample pairs before computePca "
+                            "(pcoa_similar_pairs): a pair is reported when the Jaccard index of the two carrier sets, "
+                            "S(i, j) / (S(i, i) + S(j, j) - S(i, j)), is at least X.  Off by default.  One full engine: stored S, "
+                            "full layout")
+        p.add_argument("--related-output-path", type=str, default=None,
+                       help="--related-min-jaccard: write the reported pairs to this file, one line per pair in (i, j) order: "
+                            "name_i, name_j, shared, d_i, d_j, jaccard (tab-separated, one header line)")
+        p.add_argument("--related-max-pairs", type=int, default=None,
+                       help="--related-min-jaccard: the most pairs the job takes from the library (default 1048576); if more "
+                            "are reported the job stops")
+        p.add_argument("--remove-related", action="store_true",
+                       help="--related-min-jaccard: drop one sample of every reported pair before computePca (the sample with "
+                            "the most reported partners first, ties to the highest index) and decompose S[kept, kept], "
+                            "gathered on the device (pcoa_create_subset) -- no variant is read twice")
         a = p.parse_args(list(arguments))
         self.__dict__.update(vars(a))
         self.numPc = a.num_pc
         self.outputPath = a.output_path
         self.inputPath = a.input_path
         self.minAlleleFrequency = a.min_allele_frequency
+        self.related_max_pairs_given = a.related_max_pairs is not None
+        if a.related_max_pairs is None:
+            self.related_max_pairs = RELATED_MAX_PAIRS
+
+
+RELATED_MAX_PAIRS = 1 << 20   # default of --related-max-pairs
 
 
 def java_float_to_string(f):
@@ -403,7 +477,8 @@ class VariantsPcaDriver(object):
         self.data = data  # list of datasets, each a list of variant dicts (or ('csr', idx, offs))
         print("Matrix size: %d." % (len(self.indexes) if matrix_size is None else matrix_size))  # VariantsCommon.scala:48
         self.engine = None
-        self.gram_seconds_before = 0.0   # Gram kernel seconds of engines that --outlier-iterations has replaced
+        self.gram_seconds_before = 0.0   # Gram kernel seconds of engines that --outlier-iterations / --remove-related have replaced
+        self.kept = None                 # original indices of the current cohort once --remove-related has dropped samples
 
     # filterDataset, VariantsPca.scala:96-108
     def filterDataset(self, data):
@@ -515,14 +590,53 @@ class VariantsPcaDriver(object):
 
     # computePca, VariantsPca.scala:198-231
     def computePca(self, sim_matrix):
-        n = len(self.indexes)
+        kept = self.kept if self.kept is not None else np.arange(len(self.indexes))   # (--remove-related: the kept samples)
         comps, _, nonzero = sim_matrix.compute(self.conf.numPc)
-        print("Non zero rows in matrix: %d / %d." % (nonzero, n))  # :208
+        print("Non zero rows in matrix: %d / %d." % (nonzero, kept.size))  # :208
         if comps.shape[1] < 2:
             # the reference indexes array(i + pca.numRows) unconditionally (:230) and fails for --num-pc 1
             raise IndexError("computePca emits exactly PC1 and PC2 (VariantsPca.scala:229-230); --num-pc must be >= 2")
         reverse = dict((v, k) for (k, v) in self.indexes.items())
-        return [(reverse[i], float(comps[i, 0]), float(comps[i, 1])) for i in range(n)]
+        return [(reverse[int(i)], float(comps[a, 0]), float(comps[a, 1])) for a, i in enumerate(kept)]
+
+    # --related-min-jaccard X, before the first computePca: the screen of S on the device (pcoa_similar_pairs), the pair file,
+    # one stderr line, and with --remove-related the engine replaced by its subset over the kept samples (pcoa_create_subset:
+    # one gather of S, no variant fed again); self.kept then names the cohort that computePca and the outlier rounds go on
+    # with.  Returns the engine to decompose; sim_matrix is closed when it is replaced (self.engine follows).
+    def screenRelated(self, sim_matrix, err=None):
+        err = err or sys.stderr
+        x, cap = self.conf.related_min_jaccard, self.conf.related_max_pairs
+        n = len(self.indexes)
+        reverse = dict((v, k) for (k, v) in self.indexes.items())
+        name = lambda i: self.names[reverse[int(i)]]
+        pairs, n_found, diag = sim_matrix.similar_pairs(x, capacity=cap)
+        if n_found > cap:
+            raise SystemExit("VariantsPcaDriver: --related-min-jaccard %s reports %d pairs, more than --related-max-pairs %d "
+                             "takes; raise --related-max-pairs or the threshold" % (java_double_to_string(x), n_found, cap))
+        if self.conf.related_output_path:
+            with open(self.conf.related_output_path, "w") as f:
+                f.write("name_i\tname_j\tshared\td_i\td_j\tjaccard\n")
+                for p in pairs:
+                    i, j, shared = int(p["i"]), int(p["j"]), int(p["shared"])
+                    union = int(diag[i]) + int(diag[j]) - shared
+                    f.write("%s\t%s\t%d\t%d\t%d\t%s\n" % (name(i), name(j), shared, diag[i], diag[j],
+                                                          java_double_to_string(float(shared) / float(union))))
+        gone = related_removal(pairs, n) if self.conf.remove_related else np.zeros(0, dtype=np.int64)
+        err.write("Related pairs: %d at jaccard >= %s; removed %d sample(s)%s\n"
+                  % (n_found, java_double_to_string(x), gone.size, (": " + ", ".join(name(i) for i in gone)) if gone.size else ""))
+        if gone.size == 0:
+            return sim_matrix
+        if n - gone.size < min_cohort(self.conf.numPc):
+            raise SystemExit("VariantsPcaDriver: --remove-related would leave %d of %d samples, fewer than the %d that %d "
+                             "principal components need; raise --related-min-jaccard"
+                             % (n - gone.size, n, min_cohort(self.conf.numPc), self.conf.numPc))
+        keep = np.setdiff1d(np.arange(n), gone)
+        sub = sim_matrix.subset(keep)
+        self.gram_seconds_before += sim_matrix.timings()["gram_kernel_seconds"]
+        sim_matrix.close()
+        self.engine = sub
+        self.kept = keep
+        return sub
 
     # computePca inside --outlier-iterations K: computePca, outlier_rule, and while something is removed and fewer than K
     # rounds have removed something, the engine is replaced by its subset over the kept samples (pcoa_create_subset: one
@@ -534,7 +648,7 @@ class VariantsPcaDriver(object):
         if self.conf.numPc < 2:
             raise IndexError("computePca emits exactly PC1 and PC2 (VariantsPca.scala:229-230); --num-pc must be >= 2")
         reverse = dict((v, k) for (k, v) in self.indexes.items())
-        kept = np.arange(len(self.indexes))
+        kept = self.kept.copy() if self.kept is not None else np.arange(len(self.indexes))   # (--remove-related went first)
         eng, done = sim_matrix, 0
         while True:
             comps, _, nonzero = eng.compute(self.conf.numPc)
@@ -732,6 +846,33 @@ def check_outlier_conf(conf):
                          "--project-input-path")
 
 
+STRIPS_REFUSE_RELATED = ("--related-min-jaccard screens one whole similarity matrix on one engine: it cannot take --layout "
+                         "strips")
+
+
+def check_related_conf(conf):
+    """--related-min-jaccard and its companions: what cannot be served is refused before any file is read or any engine
+    exists."""
+    x = conf.related_min_jaccard
+    if x is None:
+        for flag, given in (("--related-output-path", conf.related_output_path is not None),
+                            ("--related-max-pairs", conf.related_max_pairs_given), ("--remove-related", conf.remove_related)):
+            if given:
+                raise SystemExit("VariantsPcaDriver: %s needs --related-min-jaccard X (the screen is off without it)" % flag)
+        return
+    if not (x > 0 and x <= 1):   # (NaN fails both comparisons)
+        raise SystemExit("VariantsPcaDriver: --related-min-jaccard must be a finite number in (0, 1]")
+    if conf.related_max_pairs < 0:
+        raise SystemExit("VariantsPcaDriver: --related-max-pairs must be >= 0 (the pairs --related-min-jaccard may report)")
+    if conf.gram == "implicit":
+        raise SystemExit("VariantsPcaDriver: --related-min-jaccard screens a stored similarity matrix: it cannot take --gram implicit")
+    if conf.layout == "strips":
+        raise SystemExit("VariantsPcaDriver: " + STRIPS_REFUSE_RELATED)
+    if conf.project_input_path:
+        raise SystemExit("VariantsPcaDriver: --related-min-jaccard screens the cohort it decomposes: it cannot take "
+                         "--project-input-path")
+
+
 def calls_as_bits(call_rdd, n):
     """--gram implicit: an RDD[Seq[Int]] in any of the forms getCallsRdd returns, as what an operator engine stores -- raw
     PLINK rows and bitsets as they are, carrier lists packed into bitsets.  A list that names a callset twice (a merge of sets
@@ -838,6 +979,7 @@ def main(args):
     """VariantsPcaDriver.main (VariantsPca.scala:38-50)."""
     conf = PcaConf(args)
     check_outlier_conf(conf)
+    check_related_conf(conf)
     check_gram_conf(conf)
     if conf.project_input_path:
         check_projection_conf(conf)
@@ -894,6 +1036,8 @@ def main(args):
         ranges = resolve_layout(conf, n, 1, [conf.gpu])
     if ranges is not None and conf.outlier_iterations > 0:   # --layout auto resolved to strips
         raise SystemExit("VariantsPcaDriver: " + STRIPS_REFUSE_OUTLIERS)
+    if ranges is not None and conf.related_min_jaccard is not None:
+        raise SystemExit("VariantsPcaDriver: " + STRIPS_REFUSE_RELATED)
     if ranges is not None:
         owner = driver.getSimilarityMatrixStrip(calls_rdd, ranges[rank], local_rank if world > 1 else conf.gpu)
         if rank == 0:
@@ -924,6 +1068,8 @@ def main(args):
     if rank == 0:
         if conf.dump_similarity:
             sim_matrix.gram().astype("<i8").tofile(conf.dump_similarity)
+        if conf.related_min_jaccard is not None:   # the screen first, then the rounds on the reduced cohort
+            sim_matrix = driver.screenRelated(sim_matrix)
         result = driver.computePcaOutlierRounds(sim_matrix) if conf.outlier_iterations > 0 else driver.computePca(sim_matrix)
         driver.emitResult(result)
         driver.reportIoStats(sys.stderr)
