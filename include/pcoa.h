@@ -345,6 +345,45 @@ typedef struct pcoa_pairs_stats {
 } pcoa_pairs_stats;
 int pcoa_get_pairs_stats(pcoa_ctx* ctx, pcoa_pairs_stats* out, size_t out_size);
 
+/* ---- principal coordinates of a normalised similarity, evaluated on the fly from S -------------------------------------------
+ * S(i, j) scales with how many variants each of the two samples carries, d_i = S(i, i): samples with more non-reference calls
+ * (coverage, caller, array, ancestry) have uniformly larger rows, and after centring a leading axis tracks d_i.  The remedy is to
+ * decompose a normalised similarity K: classical PCoA on the distance sqrt(1 - Jaccard) is the eigenproblem of 1/2 J K J, the
+ * vectors of the centred K with the eigenvalues halved.  K is never in memory: the mat-vecs, the row sums and the centring
+ * evaluate it per entry from the integer S (csrc/measure.hip).  The rule, with s = S(i, j) the TOTAL entry (the int32 matrix plus
+ * the int64 part where the ctx has one), in IEEE fp64 with no contraction:
+ *   PCOA_SIMILARITY_SHARED   K = (double)s                                                 what the reference decomposes
+ *   PCOA_SIMILARITY_JACCARD  U = d_i + d_j - s (integer);  K = U > 0 ? (double)s / (double)U : 0.0        one division
+ *   PCOA_SIMILARITY_COSINE   q_i = d_i > 0 ? 1.0 / sqrt((double)d_i) : 0.0;  K = ((double)s * q_i) * q_j      (Ochiai)
+ *   centring (all three)     r_i = sum_j K(i, j);  mm = (sum_i r_i) / N / N;  B(i, j) = ((K(i, j) - r_i / N) - r_j / N) + mm
+ * -- variants_pca.similarity_measure / centred_measure are the numpy statement.  Jaccard's diagonal is 1 where d_i > 0; a sample
+ * that carries nothing has a zero row and column under both measures and is not counted in nonzero_rows.  Both are positive
+ * semi-definite (Tanimoto, cosine), so pcoa_compute's selection by |lambda| applies unchanged.  The upper-triangle mat-vec
+ * evaluates K(i, j) once, for i <= j, and uses it for both triangles.
+ *
+ * pcoa_set_similarity: what pcoa_compute decomposes from now on.  A property of how the ctx DECOMPOSES S, not of how it
+ *   accumulates it: it may be set at any time (before the first variant, after a reduction or a load), survives pcoa_reset as the
+ *   create flags do, and the result of pcoa_create_subset inherits it.  Nothing of a centring is kept between calls, so the next
+ *   pcoa_compute / pcoa_center_read_f64 starts from the row sums of the measure then set.
+ *   With JACCARD or COSINE set: pcoa_compute decomposes the measure's B (Lanczos, band Lanczos, the Householder fallback; the
+ *   timings, matvec_form, eig_method and lanczos_steps describe the path as before); pcoa_center_read_f64 returns the measure's B,
+ *   its fp64 row sums r_i, mm and nonzero_rows = #{r_i > 0}; pcoa_debug_centred_matvec multiplies by the measure's B, forms 0, 1,
+ *   2 with the preconditions it has.  pcoa_project with such a ref: PCOA_ERR_STATE (not built).  pcoa_similar_pairs, pcoa_gram_*,
+ *   pcoa_gram_reduce_* and pcoa_create_subset's gather never look at the measure.  With SHARED (the default) every call is what it
+ *   was, bit for bit.
+ *   kind:  an unknown kind: PCOA_ERR_INVALID_ARG.  ctx NULL: PCOA_ERR_INVALID_ARG on pcoa_last_error(NULL).
+ *   ctx:   a strip owner or an operator ctx takes SHARED only; any other kind: PCOA_ERR_STATE, the message names the kind of ctx,
+ *          the ctx stays usable (measures over strips or over the implicit operator are not built).
+ *   memory: N int64 (and N doubles for the cosine), allocated by the first centring under a measure.
+ * pcoa_get_similarity: *kind_out = the kind set (PCOA_SIMILARITY_SHARED after create).  No device work in either call.
+ * Extends: computePca (VariantsPca.scala:198-231), which centres and decomposes the shared counts only, by the normalised
+ * similarities a principal COORDINATES analysis is usually run on. */
+#define PCOA_SIMILARITY_SHARED  0   /* default: today's behaviour, bit for bit */
+#define PCOA_SIMILARITY_JACCARD 1
+#define PCOA_SIMILARITY_COSINE  2
+int pcoa_set_similarity(pcoa_ctx* ctx, int32_t kind);
+int pcoa_get_similarity(const pcoa_ctx* ctx, int32_t* kind_out);
+
 /* ---- layout of S over the engines of one job ------------------------------------------------------------------------
  * FULL: every engine holds a whole N x N partial S (4 N^2 bytes) for its share of the variants; the partials are reduced
  * into engine 0 (peer copies: engine 0 stages one more 4 N^2 matrix when the engines sit on different devices, RCCL

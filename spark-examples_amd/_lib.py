@@ -145,6 +145,8 @@ _SIGNATURES = [
     ("pcoa_create_subset", ctypes.c_int, [ctypes.POINTER(_vp), _vp, _vp, _i32]),
     ("pcoa_similar_pairs", ctypes.c_int, [_vp, ctypes.c_double, _vp, _i64, ctypes.POINTER(_i64), _vp]),
     ("pcoa_get_pairs_stats", ctypes.c_int, [_vp, ctypes.POINTER(PcoaPairsStats), ctypes.c_size_t]),
+    ("pcoa_set_similarity", ctypes.c_int, [_vp, _i32]),
+    ("pcoa_get_similarity", ctypes.c_int, [_vp, ctypes.POINTER(_i32)]),
     ("pcoa_operator_info", ctypes.c_int, [_vp, ctypes.POINTER(_i64), ctypes.POINTER(_i64)]),
     ("pcoa_operator_row_sums", ctypes.c_int, [_vp, _vp]),
     ("pcoa_operator_matvec_device", ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int]),

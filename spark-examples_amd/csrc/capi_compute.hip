@@ -157,8 +157,12 @@ int pcoa_center_read_f64(pcoa_ctx* c, double* out_b, double* out_row_sums, int32
   const size_t n = (size_t)c->n;
   {
     ScopedTimer t(c, T_CENTER);
-    HIP_TRY(c, launch_center(c->s32, c->s64, c->n, c->row_sums, c->stats, c->nz, out_b ? c->ws.a : nullptr,
-                             c->stream));
+    if (c->similarity != PCOA_SIMILARITY_SHARED) {   // the measure's row sums, mean, non-zero rows and B (capi_measure.hip)
+      if ((rc = measure_centre(c, false, out_b ? c->ws.a : nullptr)) != PCOA_OK) return rc;
+    } else {
+      HIP_TRY(c, launch_center(c->s32, c->s64, c->n, c->row_sums, c->stats, c->nz, out_b ? c->ws.a : nullptr,
+                               c->stream));
+    }
   }
   if (out_b) HIP_TRY(c, hipMemcpyAsync(out_b, c->ws.a, sizeof(double) * n * n, hipMemcpyDeviceToHost, c->stream));
   if (out_row_sums)
@@ -215,13 +219,18 @@ int pcoa_compute(pcoa_ctx* c, int32_t num_pc, double* out_components, double* ou
   const int sym_min = debug_knobs().symv_sym_min_n > 0 ? debug_knobs().symv_sym_min_n : 16384;
   const bool sym_form = !explicit_b && !c->s64 && n >= sym_min && (n & 3) == 0;
   if (sym_form && (rc = ensure(c, &c->sym_part, &c->sym_part_cap, (int64_t)symv_sym_workspace_doubles(n))) != PCOA_OK) return rc;
+  const bool measured = c->similarity != PCOA_SIMILARITY_SHARED;   // Jaccard / cosine: the centring and the mat-vecs of measure.hip
   {
     ScopedTimer t(c, T_CENTER);
-    if (sym_form)
-      HIP_TRY(c, launch_row_sums_sym(c->s32, n, c->sym_part, c->row_sums, reinterpret_cast<int64_t*>(c->stats + 2), c->stream));
-    HIP_TRY(c, launch_center(c->s32, c->s64, n, c->row_sums, c->stats, c->nz, explicit_b ? c->ws.a : nullptr,
-                             c->stream, sym_form));
-    HIP_TRY(c, launch_col_means(c->row_sums, n, c->colmean, c->stream));
+    if (measured) {
+      if ((rc = measure_centre(c, sym_form, explicit_b ? c->ws.a : nullptr)) != PCOA_OK) return rc;
+    } else {
+      if (sym_form)
+        HIP_TRY(c, launch_row_sums_sym(c->s32, n, c->sym_part, c->row_sums, reinterpret_cast<int64_t*>(c->stats + 2), c->stream));
+      HIP_TRY(c, launch_center(c->s32, c->s64, n, c->row_sums, c->stats, c->nz, explicit_b ? c->ws.a : nullptr,
+                               c->stream, sym_form));
+      HIP_TRY(c, launch_col_means(c->row_sums, n, c->colmean, c->stream));
+    }
   }
   c->ws.s32 = c->s32;
   c->ws.s64 = c->s64;
@@ -247,6 +256,7 @@ int pcoa_compute(pcoa_ctx* c, int32_t num_pc, double* out_components, double* ou
       wl.sym_part = (sym_form && !wl.a) ? c->sym_part : nullptr;
       c->matvec_form = wl.a ? 2 : wl.sym_part ? 1 : 0;
       wl.band_only = (c->flags & PCOA_FLAG_EIG_BAND) != 0;
+      if (measured) measure_bind(c, &wl);
       int band = 0;
       HIP_TRY(c, lanczos_topk(wl, c->lanczos_ws, n, num_pc, mmax, 1e-11, sel.data(), &conv, &steps, c->stream, nullptr, &band));
       c->lanczos_block_steps = band;
@@ -269,7 +279,11 @@ int pcoa_compute(pcoa_ctx* c, int32_t num_pc, double* out_components, double* ou
     if (!b_ready) {  // the dense solver needs B in memory
       if ((rc = ensure_b(c)) != PCOA_OK) return rc;
       ScopedTimer t(c, T_CENTER);
-      HIP_TRY(c, launch_center(c->s32, c->s64, n, c->row_sums, c->stats, c->nz, c->ws.a, c->stream));
+      if (measured) {
+        if ((rc = measure_b(c, c->ws.a)) != PCOA_OK) return rc;
+      } else {
+        HIP_TRY(c, launch_center(c->s32, c->s64, n, c->row_sums, c->stats, c->nz, c->ws.a, c->stream));
+      }
       b_ready = true;
     }
     {
@@ -444,6 +458,9 @@ int pcoa_project(pcoa_ctx* ref, pcoa_ctx* cross, int32_t num_pc, const double* c
     return fail(ref, PCOA_ERR_INVALID_ARG, "project: ref is a strip owner; the reference must be a full engine (pcoa_create) -- "
                                            "a reference solved over strips is not supported");
   if (!cross->is_strip) return fail(ref, PCOA_ERR_INVALID_ARG, "project: cross is not a strip owner (pcoa_create_strip)");
+  if (ref->similarity != PCOA_SIMILARITY_SHARED)
+    return fail(ref, PCOA_ERR_STATE, "project: ref decomposes a Jaccard / cosine measure (pcoa_set_similarity); projection under a "
+                                     "measure is not built");
   const int32_t n_ref = ref->n, cols = cross->s_cols;
   if (cross->n < n_ref)
     return fail(ref, PCOA_ERR_INVALID_ARG, "project: cross has N = " + std::to_string(cross->n) + " rows, fewer than ref's " +
@@ -776,14 +793,20 @@ int pcoa_debug_centred_matvec(pcoa_ctx* c, const double* x, double* y, int form)
     if ((rc = ensure(c, &c->sym_part, &c->sym_part_cap, (int64_t)symv_sym_workspace_doubles(n))) != PCOA_OK) return rc;
     wl.sym_part = c->sym_part;
     // the large-N form of computePca's first pass as well: row sums from the upper-triangular tiles
-    HIP_TRY(c, launch_row_sums_sym(c->s32, n, c->sym_part, c->row_sums, reinterpret_cast<int64_t*>(c->stats + 2), c->stream));
+    if (c->similarity == PCOA_SIMILARITY_SHARED)
+      HIP_TRY(c, launch_row_sums_sym(c->s32, n, c->sym_part, c->row_sums, reinterpret_cast<int64_t*>(c->stats + 2), c->stream));
   }
   if (form == 2) {
     if ((rc = ensure_b(c)) != PCOA_OK) return rc;
     wl.a = c->ws.a;
   }
-  HIP_TRY(c, launch_center(c->s32, c->s64, n, c->row_sums, c->stats, c->nz, wl.a, c->stream, upper_triangle_form));
-  HIP_TRY(c, launch_col_means(c->row_sums, n, c->colmean, c->stream));
+  if (c->similarity != PCOA_SIMILARITY_SHARED) {   // the measure's centring, by the same forms (capi_measure.hip)
+    if ((rc = measure_centre(c, upper_triangle_form, wl.a)) != PCOA_OK) return rc;
+    measure_bind(c, &wl);
+  } else {
+    HIP_TRY(c, launch_center(c->s32, c->s64, n, c->row_sums, c->stats, c->nz, wl.a, c->stream, upper_triangle_form));
+    HIP_TRY(c, launch_col_means(c->row_sums, n, c->colmean, c->stream));
+  }
   double* xd = c->ws.q;   // two N-vectors of the eigensolver workspace
   double* yd = c->ws.w;
   HIP_TRY(c, hipMemcpyAsync(xd, x, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, c->stream));

@@ -73,6 +73,7 @@ int pcoa_create_subset(pcoa_ctx** out, pcoa_ctx* src, const int32_t* keep, int32
   keep_dev = nullptr;
   sub->variants_in_s32 = src->variants_in_s32;   // the bound of every int32 entry holds for a sub-matrix as it stands
   sub->gram_variants = src->gram_variants;
+  sub->similarity = src->similarity;             // what computePca decomposes (pcoa_set_similarity) follows the cohort
   sub->dirty = false;                            // both triangles were gathered from a mirrored S
   if (sub->s64) {
     // the int64 hand-over every import makes: the total in the int64 matrix, the int32 partial zero, then back into the

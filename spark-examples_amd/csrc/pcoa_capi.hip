@@ -219,7 +219,7 @@ void pcoa_destroy(pcoa_ctx* c) {
   if (c->hw) (void)hipHostFree(c->hw);
   if (c->ws.host_rec) (void)hipHostFree(c->ws.host_rec);
   void* bufs[] = {c->s32, c->s64, c->s64_spare, c->narrow_flag, c->zeros, c->err_flag, c->tile, c->csr_idx, c->csr_offs, c->thr_dev,
-                  c->sample_pop, c->xfer, c->coll, c->fb_flags, c->strip_ws, c->strip_means, c->proj_ws, c->pack_buf, c->lanczos_ws, c->sym_part, c->ws.a, c->ws.d, c->ws.e, c->ws.tau, c->ws.q, c->ws.w, c->ws.lam,
+                  c->sample_pop, c->measure_diag, c->measure_q, c->xfer, c->coll, c->fb_flags, c->strip_ws, c->strip_means, c->proj_ws, c->pack_buf, c->lanczos_ws, c->sym_part, c->ws.a, c->ws.d, c->ws.e, c->ws.tau, c->ws.q, c->ws.w, c->ws.lam,
                   c->ws.z, c->ws.wy, c->ws.scratch, c->ws.iscratch, c->row_sums, c->colmean, c->stats, c->nz,
                   c->out_dev};
   for (void* b : bufs)

@@ -11,6 +11,7 @@
 //   capi_operator.hip    the implicit similarity operator: the bit store, its products, computePca over it
 //   capi_subset.hip      pcoa_create_subset: a new engine whose S is S[I, I] of another
 //   capi_pairs.hip       pcoa_similar_pairs: the screen of S for duplicate and related sample pairs
+//   capi_measure.hip     pcoa_set_similarity / pcoa_get_similarity and the centring of a Jaccard / cosine measure
 //   pcoa_capi.hip        create / destroy, errors, timings
 #pragma once
 
@@ -201,6 +202,13 @@ struct pcoa_ctx {
   int32_t eig_method = 0;          // of the last pcoa_compute: 1 = Lanczos, 2 = Householder
   int32_t eig_dense_form = 0;      // EIG_FORM_* bits of the last pcoa_compute's dense solve of B (0 unless eig_method == 2)
   int32_t lanczos_steps = 0;
+  // pcoa_set_similarity: what computePca decomposes (PCOA_SIMILARITY_*).  A property of the ctx like its create flags: it
+  // survives pcoa_reset and a subset inherits it.  Nothing of a centring is kept between calls (every pcoa_compute /
+  // pcoa_center_read_f64 starts from the row sums), so a change has nothing to invalidate beyond these two buffers' contents,
+  // which are rewritten from S by every centring.
+  int32_t similarity = 0;
+  int64_t* measure_diag = nullptr;   // [n] (lazy)
+  double* measure_q = nullptr;       // [n] (lazy)
 
   // timings
   std::vector<EventPair> pending;
@@ -323,6 +331,13 @@ int ensure_workspace(pcoa_ctx* c, int32_t k);
 int ensure_b(pcoa_ctx* c);
 int lanczos_over(pcoa_ctx* c, int32_t num_pc, const LanczosMatvec& mv, double* out_components, double* out_eigenvalues,
                  int32_t* steps_out);
+
+// ---- capi_measure.hip: the centring of c's measure (c->similarity != PCOA_SIMILARITY_SHARED) from the current S -- diagonal,
+// row sums of K (from the upper-triangular tiles when sym_form: c->sym_part sized by the caller), stats, c->colmean, and B
+// into b where b is not NULL.  measure_b: B alone, from the centring already there
+int measure_centre(pcoa_ctx* c, bool sym_form, double* b);
+int measure_b(pcoa_ctx* c, double* b);
+void measure_bind(const pcoa_ctx* c, EigWorkspace* ws);   // ws->measure / diag / q from c
 
 // ---- capi_operator.hip
 int operator_append(pcoa_ctx* c, const uint32_t* bits_dev, int64_t nv, int64_t ld_words);

@@ -284,6 +284,11 @@ struct EigWorkspace {
   // doubles: 1024 row sums + 1024 column sums per upper-triangular 1024 x 1024 tile), or nullptr: one wave per row
   double* sym_part = nullptr;
   bool band_only = false;   // PCOA_FLAG_EIG_BAND: skip the single-vector iteration (eigenvalues of multiplicity > 1)
+  // A similarity measure other than the shared count (pcoa_set_similarity, measure.hip): the implicit forms evaluate
+  // K(i, j) from S(i, j) and the two samples' diagonal entries before they centre it; colmean / stats are then K's.
+  int measure = 0;                 // PCOA_SIMILARITY_*
+  const int64_t* diag = nullptr;   // [n] d_i = S(i, i), the total entry
+  const double* qcos = nullptr;    // [n] cosine: q_i = d_i > 0 ? 1 / sqrt(d_i) : 0  (q is the tridiagonalisation's)
 };
 size_t symv_sym_workspace_doubles(int32_t n);
 // exact row sums of a finalized (symmetric) int32 S from its upper-triangular tiles: half the bytes of launch_center's row
@@ -291,6 +296,33 @@ size_t symv_sym_workspace_doubles(int32_t n);
 hipError_t launch_row_sums_sym(const int32_t* s32, int32_t n, double* sym_part, double* row_sums, int64_t* row_sums_i64,
                                hipStream_t stream);
 void launch_centred_matvec(const EigWorkspace& ws, int32_t n, const double* x, double* y, hipStream_t stream);  // one y = B x (test hook)
+// y_i = the partials of the upper-triangle form (symv_sym_workspace_doubles(n) doubles, the layout of symv_sym_tiles_kernel)
+// added in symv_sym_gather_kernel's fixed order
+hipError_t launch_symv_sym_gather(const double* sym_part, int32_t n, double* y, hipStream_t stream);
+
+// ---- similarity measures evaluated on the fly from S (measure.hip; pcoa_set_similarity) ---------------------------------
+// kind = PCOA_SIMILARITY_JACCARD | _COSINE.  With s = the total entry (s32 + s64 where there is one), d = its diagonal:
+//   Jaccard  U = d_i + d_j - s (int64);  K = U > 0 ? (double)s / (double)U : 0.0
+//   cosine   q_i = d_i > 0 ? 1.0 / sqrt((double)d_i) : 0.0;  K = ((double)s * q_i) * q_j
+//   centred  B = ((K - r_i / N) - r_j / N) + mm,  r = the row sums of K,  mm = (sum_i r_i) / N / N    (no contraction)
+// diag [n] (both kinds) and q [n] (cosine; may be NULL for Jaccard) from the current S
+hipError_t launch_measure_diag(const int32_t* s32, const int64_t* s64_or_null, int32_t n, int kind, int64_t* diag, double* q,
+                               hipStream_t stream);
+// row_sums[i] = sum_j K(i, j), one wave per row, added in row_dot's order (ones: n doubles the call fills with 1.0)
+hipError_t launch_measure_row_sums(const int32_t* s32, const int64_t* s64_or_null, int32_t n, int kind, const int64_t* diag,
+                                   const double* q, double* ones, double* row_sums, hipStream_t stream);
+// the same from the upper-triangular tiles of an int32 S, n % 4 == 0 (sym_part: symv_sym_workspace_doubles(n) doubles): the
+// tiles' partials in symv_sym_gather_kernel's order
+hipError_t launch_measure_row_sums_sym(const int32_t* s32, int32_t n, int kind, const int64_t* diag, const double* q,
+                                       double* ones, double* sym_part, double* row_sums, hipStream_t stream);
+// stats[0] = sum_i row_sums[i] (one workgroup: thread t adds i = t, t + 256, .. in order, then the 64 lanes of a wave by
+// halving strides, then the four waves left to right), stats[1] = stats[0] / N / N, nz[0] = #{i : row_sums[i] > 0}
+hipError_t launch_measure_stats(const double* row_sums, int32_t n, double* stats, int32_t* nz, hipStream_t stream);
+// b = B, [n][n] fp64 (cm = row_sums / N: launch_col_means)
+hipError_t launch_measure_center(const int32_t* s32, const int64_t* s64_or_null, int32_t n, int kind, const int64_t* diag,
+                                 const double* q, const double* cm, const double* stats, double* b, hipStream_t stream);
+// y = B x through the implicit forms: upper-triangular tiles when ws.sym_part is set (int32 S, n % 4 == 0), else one wave per row
+hipError_t launch_measure_symv(const EigWorkspace& ws, int32_t n, const double* x, double* y, hipStream_t stream);
 // form (optional): the launcher ORs in the EIG_FORM_* bits (pcoa.h, pcoa_timings.eig_dense_form) of the form it launched
 hipError_t launch_tridiagonalize(const EigWorkspace& ws, int32_t n, hipStream_t stream, int32_t* form = nullptr);
 // eigenvalues with ascending indices idx[0..count) of T -> lam_out[0..count) (device)

@@ -396,6 +396,25 @@ class PcoaEngine(object):
         n_found = int(found.value)
         return pairs[:min(n_found, cap)], n_found, diag
 
+    SIMILARITY_KINDS = {"shared": 0, "jaccard": 1, "cosine": 2}   # PCOA_SIMILARITY_*
+
+    def set_similarity(self, kind):
+        """What compute() decomposes from now on (pcoa_set_similarity): "shared" (the counts S, the default), "jaccard"
+        (S_ij / (d_i + d_j - S_ij)) or "cosine" (S_ij / sqrt(d_i d_j)), d = diag(S), evaluated on the fly from the integer S;
+        variants_pca.similarity_measure is the rule.  Survives reset(); subset() inherits it.  The number of a kind is
+        accepted as well (an unknown one is the library's error)."""
+        if isinstance(kind, str):
+            if kind not in self.SIMILARITY_KINDS:
+                raise ValueError("similarity kind must be one of shared, jaccard, cosine, not %r" % (kind,))
+            kind = self.SIMILARITY_KINDS[kind]
+        self._check(self._lib.pcoa_set_similarity(self._ctx, int(kind)))
+
+    def get_similarity(self):
+        """The name of the measure set (pcoa_get_similarity)."""
+        kind = ctypes.c_int32(-1)
+        self._check(self._lib.pcoa_get_similarity(self._ctx, ctypes.byref(kind)))
+        return dict((v, k) for k, v in self.SIMILARITY_KINDS.items())[int(kind.value)]
+
     def export_device(self, dst_ptr):
         self._check(self._lib.pcoa_gram_export_device_i64(self._ctx, ctypes.c_void_p(int(dst_ptr))))
 

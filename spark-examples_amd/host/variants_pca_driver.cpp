@@ -101,6 +101,11 @@ struct Conf {  // PcaConf / GenomicsConf (GenomicsConf.scala:31-101), same flag 
   int64_t related_max_pairs = 1048576;  // --related-max-pairs M: the capacity handed to the library; more reported pairs stop the job
   bool related_max_pairs_given = false;
   bool remove_related = false;          // --remove-related: drop one sample of every reported pair, go on with pcoa_create_subset over the rest
+  std::string similarity_measure = "shared";  // --similarity-measure shared|jaccard|cosine: what computePca decomposes (pcoa_set_similarity);
+                                              // jaccard / cosine are evaluated on the fly from S, set on the engine that runs computePca
+  int32_t similarity_kind() const {
+    return similarity_measure == "jaccard" ? PCOA_SIMILARITY_JACCARD : similarity_measure == "cosine" ? PCOA_SIMILARITY_COSINE : PCOA_SIMILARITY_SHARED;
+  }
 };
 
 const char* kUsage =
@@ -118,6 +123,9 @@ const char* kUsage =
     "                   (before computePca: report the sample pairs whose carrier sets have a Jaccard index >= X, X in (0, 1];\n"
     "                   --remove-related drops one sample of each pair and decomposes S[kept, kept]; one engine, stored S,\n"
     "                   full layout)\n"
+    "                   --similarity-measure shared|jaccard|cosine (what computePca decomposes: the counts S as the reference,\n"
+    "                   S(i,j) / (S(i,i) + S(j,j) - S(i,j)), or S(i,j) / sqrt(S(i,i) S(j,j)), evaluated on the fly from S; one\n"
+    "                   engine, stored S, full layout, no projection)\n"
     "  --project-input-path <file.vcf[.gz]> [more]\n"
     "                   place these samples onto the principal coordinates of the --input-path cohort instead of\n"
     "                   decomposing the union (one GPU, VCF inputs, full layout)\n";
@@ -128,6 +136,9 @@ const char* kUsage =
 }
 
 const char* kStripsRefuseOutliers = "--outlier-iterations subsets one whole similarity matrix on one engine: it cannot take --layout strips";
+std::string strips_refuse_measure(const std::string& m) {
+  return "--similarity-measure " + m + " needs the diagonal of one whole similarity matrix on one engine: it cannot take --layout strips";
+}
 const char* kStripsRefuseRelated = "--related-min-jaccard screens one whole similarity matrix on one engine: it cannot take --layout strips";
 
 Conf parse(int argc, char** argv) {
@@ -215,6 +226,11 @@ Conf parse(int argc, char** argv) {
       c.related_max_pairs_given = true;
     }
     else if (a == "--remove-related") c.remove_related = true;
+    else if (a == "--similarity-measure") {
+      c.similarity_measure = one(i);
+      if (c.similarity_measure != "shared" && c.similarity_measure != "jaccard" && c.similarity_measure != "cosine")
+        die("--similarity-measure takes shared, jaccard or cosine, not '" + c.similarity_measure + "'");
+    }
     else if (a == "--parse-only") c.parse_only = true;
     else if (a == "--dump-similarity") c.dump_similarity = one(i);
     else if (a == "--ingest-threads") c.ingest_threads = std::atoi(one(i).c_str());
@@ -254,6 +270,14 @@ Conf parse(int argc, char** argv) {
     if (c.gram == "implicit") die("--related-min-jaccard screens a stored similarity matrix: it cannot take --gram implicit");
     if (c.layout == "strips") die(kStripsRefuseRelated);
     if (!c.project_input_path.empty()) die("--related-min-jaccard screens the cohort it decomposes: it cannot take --project-input-path");
+  }
+  // --similarity-measure jaccard | cosine: likewise
+  if (c.similarity_measure != "shared") {
+    const std::string& m = c.similarity_measure;
+    if (c.gram == "implicit") die("--similarity-measure " + m + " is evaluated from a stored similarity matrix: it cannot take --gram implicit");
+    if (c.layout == "strips") die(strips_refuse_measure(m));
+    if (!c.project_input_path.empty())
+      die("--similarity-measure " + m + ": projection under a measure is not built: it cannot take --project-input-path");
   }
   if (c.gram == "implicit") {
     // one operator engine holds the carrier bitsets of every variant: what needs S, or several engines, is refused here,
@@ -1572,6 +1596,7 @@ int main(int argc, char** argv) {
     if (layout == PCOA_LAYOUT_STRIPS) {
       if (conf.outlier_iterations > 0) die(kStripsRefuseOutliers);   // --layout auto resolved to strips
       if (conf.related) die(kStripsRefuseRelated);
+      if (conf.similarity_measure != "shared") die(strips_refuse_measure(conf.similarity_measure));
       if (conf.reduce == "rccl") die("the strip layout has no reduction step: it cannot take --reduce rccl");
       for (int g = 0; g < k; ++g) strips.emplace_back(col0[(size_t)g], cols[(size_t)g]);
     }
@@ -1788,6 +1813,8 @@ int main(int argc, char** argv) {
   double gram_s_before = 0.0;             // Gram kernel seconds of engines that --outlier-iterations has replaced
   std::vector<int32_t> kept((size_t)n);   // original index of every sample of the current cohort
   for (int32_t i = 0; i < n; ++i) kept[(size_t)i] = i;
+  if (conf.similarity_measure != "shared")   // on the engine that runs computePca (engine 0 after a reduction); its subsets inherit it
+    check(ctx, pcoa_set_similarity(ctx, conf.similarity_kind()), "set-similarity");
   if (conf.related) {
     // --related-min-jaccard X, before the first computePca: the screen of S on the device.  The rule, as pcoa.h and
     // variants_pca.py's related_pairs_rule state it: with d_i = S(i, i) and U = d_i + d_j - S(i, j), the pair (i, j), i < j, is

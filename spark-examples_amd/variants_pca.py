@@ -319,6 +319,57 @@ def related_removal(pairs, n):
     return np.array(sorted(removed), dtype=np.int64)
 
 
+# --------------------------------------------------------------------------------------------- similarity measures
+SIMILARITY_MEASURES = ("shared", "jaccard", "cosine")   # PCOA_SIMILARITY_SHARED / _JACCARD / _COSINE = 0 / 1 / 2 (include/pcoa.h)
+
+
+def similarity_measure(s, kind):
+    """The rule of --similarity-measure and of pcoa_set_similarity (csrc/measure.hip restates it on the device): `s` is the
+    N x N integer matrix of TOTAL entries (the int32 matrix plus the int64 part where the engine has one), d = diag(s) the
+    number of variants each sample carries.  Returns K as float64:
+      shared   K = float64(s)
+      jaccard  U = d_i + d_j - s_ij as an integer;  K_ij = float64(s_ij) / float64(U) where U > 0, else 0.0 -- one division.
+               The diagonal follows from the formula: 1 where d_i > 0, 0 for a sample that carries nothing.  (With carrier
+               multiplicities s_ij <= (d_i + d_j) / 2 by Cauchy-Schwarz, so U >= 0, and U = 0 only when both samples are empty.)
+      cosine   q_i = 1.0 / sqrt(float64(d_i)) where d_i > 0, else 0.0;  K_ij = (float64(s_ij) * q_i) * q_j, in this order
+               (Ochiai): no division or square root per entry.
+    Every operation is one IEEE fp64 operation (numpy fuses nothing)."""
+    s = np.asarray(s, dtype=np.int64)
+    if s.ndim != 2 or s.shape[0] != s.shape[1]:
+        raise ValueError("s must be N x N")
+    if kind not in SIMILARITY_MEASURES:
+        raise ValueError("kind must be one of %s, not %r" % (", ".join(SIMILARITY_MEASURES), kind))
+    sd = s.astype(np.float64)
+    if kind == "shared":
+        return sd
+    d = np.diagonal(s)
+    if kind == "jaccard":
+        u = d[:, None] + d[None, :] - s
+        k = np.zeros(s.shape, dtype=np.float64)
+        np.divide(sd, u.astype(np.float64), out=k, where=u > 0)
+        return k
+    q = np.zeros(d.shape, dtype=np.float64)
+    np.divide(1.0, np.sqrt(d.astype(np.float64), where=d > 0, out=np.ones(d.shape, dtype=np.float64)), out=q, where=d > 0)
+    return (sd * q[:, None]) * q[None, :]
+
+
+def centred_measure(k):
+    """computePca's centring (VariantsPca.scala:206-221) of a similarity K in float64: r_i = sum_j K_ij, rowmean_i = r_i / N,
+    mm = (sum_i r_i) / N / N (the two divisions the device's stats kernel performs), B_ij = ((K_ij - rowmean_i) - rowmean_j)
+    + mm.  Returns (B, r, mm, nonzero_rows) with nonzero_rows = #{i : r_i > 0} -- for the Jaccard and cosine measures the
+    count of d_i > 0, the number the shared measure prints.  The dtype of k is kept (float64, or longdouble for a reference)."""
+    k = np.asarray(k)
+    if k.dtype not in (np.float64, np.longdouble):
+        k = k.astype(np.float64)
+    n = k.shape[0]
+    r = k.sum(axis=1)
+    nn = k.dtype.type(n)
+    rowmean = r / nn
+    mm = r.sum() / nn / nn
+    b = ((k - rowmean[:, None]) - rowmean[None, :]) + mm
+    return b, r, mm, int(np.count_nonzero(r > 0))
+
+
 # --------------------------------------------------------------------------------------------- conf
 class PcaConf(object):
     """Flags of PcaConf / GenomicsConf (GenomicsConf.scala:31-101), same names and defaults.
@@ -401,6 +452,11 @@ class PcaConf(object):
                        help="--related-min-jaccard: drop one sample of every reported pair before computePca (the sample with "
                             "the most reported partners first, ties to the highest index) and decompose S[kept, kept], "
                             "gathered on the device (pcoa_create_subset) -- no variant is read twice")
+        p.add_argument("--similarity-measure", type=str, default="shared",
+                       help="shared|jaccard|cosine: what computePca decomposes (pcoa_set_similarity).  shared: the counts S, as "
+                            "the reference; jaccard: S(i, j) / (S(i, i) + S(j, j) - S(i, j)); cosine: S(i, j) / sqrt(S(i, i) "
+                            "S(j, j)) -- evaluated on the fly from S on the device, which takes out the axis that tracks how "
+                            "many variants a sample carries.  One full engine: stored S, full layout, no projection")
         a = p.parse_args(list(arguments))
         self.__dict__.update(vars(a))
         self.numPc = a.num_pc
@@ -873,6 +929,28 @@ def check_related_conf(conf):
                          "--project-input-path")
 
 
+STRIPS_REFUSE_MEASURE = ("--similarity-measure %s needs the diagonal of one whole similarity matrix on one engine: it cannot "
+                         "take --layout strips")
+
+
+def check_measure_conf(conf):
+    """--similarity-measure: an unknown name, and what a measure cannot serve, is refused before any file is read or any
+    engine exists."""
+    m = conf.similarity_measure
+    if m not in SIMILARITY_MEASURES:
+        raise SystemExit("VariantsPcaDriver: --similarity-measure takes shared, jaccard or cosine, not '%s'" % m)
+    if m == "shared":
+        return
+    if conf.gram == "implicit":
+        raise SystemExit("VariantsPcaDriver: --similarity-measure %s is evaluated from a stored similarity matrix: it cannot take "
+                         "--gram implicit" % m)
+    if conf.layout == "strips":
+        raise SystemExit("VariantsPcaDriver: " + STRIPS_REFUSE_MEASURE % m)
+    if conf.project_input_path:
+        raise SystemExit("VariantsPcaDriver: --similarity-measure %s: projection under a measure is not built: it cannot take "
+                         "--project-input-path" % m)
+
+
 def calls_as_bits(call_rdd, n):
     """--gram implicit: an RDD[Seq[Int]] in any of the forms getCallsRdd returns, as what an operator engine stores -- raw
     PLINK rows and bitsets as they are, carrier lists packed into bitsets.  A list that names a callset twice (a merge of sets
@@ -980,6 +1058,7 @@ def main(args):
     conf = PcaConf(args)
     check_outlier_conf(conf)
     check_related_conf(conf)
+    check_measure_conf(conf)
     check_gram_conf(conf)
     if conf.project_input_path:
         check_projection_conf(conf)
@@ -1038,6 +1117,8 @@ def main(args):
         raise SystemExit("VariantsPcaDriver: " + STRIPS_REFUSE_OUTLIERS)
     if ranges is not None and conf.related_min_jaccard is not None:
         raise SystemExit("VariantsPcaDriver: " + STRIPS_REFUSE_RELATED)
+    if ranges is not None and conf.similarity_measure != "shared":
+        raise SystemExit("VariantsPcaDriver: " + STRIPS_REFUSE_MEASURE % conf.similarity_measure)
     if ranges is not None:
         owner = driver.getSimilarityMatrixStrip(calls_rdd, ranges[rank], local_rank if world > 1 else conf.gpu)
         if rank == 0:
@@ -1068,6 +1149,8 @@ def main(args):
     if rank == 0:
         if conf.dump_similarity:
             sim_matrix.gram().astype("<i8").tofile(conf.dump_similarity)
+        if conf.similarity_measure != "shared":    # on the engine that runs computePca; its subsets inherit it
+            sim_matrix.set_similarity(conf.similarity_measure)
         if conf.related_min_jaccard is not None:   # the screen first, then the rounds on the reduced cohort
             sim_matrix = driver.screenRelated(sim_matrix)
         result = driver.computePcaOutlierRounds(sim_matrix) if conf.outlier_iterations > 0 else driver.computePca(sim_matrix)
