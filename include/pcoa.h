@@ -384,6 +384,64 @@ int pcoa_get_pairs_stats(pcoa_ctx* ctx, pcoa_pairs_stats* out, size_t out_size);
 int pcoa_set_similarity(pcoa_ctx* ctx, int32_t kind);
 int pcoa_get_similarity(const pcoa_ctx* ctx, int32_t* kind_out);
 
+/* ---- per-variant loadings of the principal coordinates ---------------------------------------------------------------------
+ * Which variants drive each axis (smartpca's SNP weights, PLINK 2's --pca var-wts).  With X the V x N carrier bit matrix and
+ * J = I - 11^T / N, the decomposed matrix is B = J S J = (X J)^T (X J), so an eigenpair (u_c, lambda_c) of B is a right singular
+ * pair of X J and the matching left singular vector is the loading of every variant on axis c:
+ *   w_c = X (J u_c) / sqrt(lambda_c),     w_c[v] = (sum over the carriers i of v of (u_c[i] - mean(u_c))) / sqrt(lambda_c)
+ * -- one bit-select-sum per variant and component (csrc/loadings.hip).  The identity holds for PCOA_SIMILARITY_SHARED only.
+ *
+ * pcoa_loadings_begin: prepares and uploads the vectors once; they stay resident until pcoa_loadings_end or pcoa_destroy, so a
+ *   host can stream a cohort through many calls.  A second begin replaces the vectors.
+ *   components:  host, [num_pc][n_samples], pcoa_compute's layout; consumed when the call returns.  0 < num_pc <= n_samples.
+ *   flags:       PCOA_LOADINGS_CENTRE uses u_c - mean(u_c), the mean being ONE left-to-right fp64 sum divided by N (a function of
+ *                the vector alone); PCOA_LOADINGS_UNIT divides the sums by sqrt(eigenvalues[c]) (one correctly rounded square
+ *                root on the host, one division per entry).  With flags = 0 the output is the plain sum T[v][c] =
+ *                sum_i bit(v, i) components[c][i].  eigenvalues may be NULL without UNIT.
+ *   errors:      PCOA_ERR_INVALID_ARG for ctx or components NULL, num_pc outside (0, n_samples], an unknown flag, UNIT with
+ *                eigenvalues NULL or an eigenvalue that is <= 0 or not finite; vectors of an earlier begin stay as they were.
+ *   Every kind of ctx serves (full engine, strip owner, subset, operator): only n_samples, the device, the stream and the staging
+ *   slots of the ctx are used.  Synchronising on the ctx stream.
+ * pcoa_loadings_bits: out[v * num_pc + c] for n_variants rows of carrier bitsets in pcoa_accumulate_bits' layout (sample i = bit
+ *   i & 31 of word i >> 5, pitch ld_words >= ceil(n_samples / 32)).  Bits of samples >= n_samples and the words behind
+ *   ceil(n_samples / 32) are IGNORED, whatever they hold.  bits: host (is_device_ptr = 0; consumed when the call returns) or
+ *   device.  out: host (out_is_device = 0; filled when the call returns) or device (the work is queued on the ctx stream; the
+ *   device input must stay valid until the next synchronising call).
+ * pcoa_loadings_plink_bed: the same for raw .bed rows as they lie in the file, decoded on the device by the rule of
+ *   pcoa_accumulate_plink_bed (ref_is_a1 as there; a missing call carries nothing).  is_device_ptr: 0 or 1.
+ * pcoa_loadings_operator: the same for rows [first_variant, first_variant + n_variants) of an operator ctx's resident store,
+ *   across its segment boundaries.  PCOA_ERR_STATE on a ctx that is not an operator; PCOA_ERR_INVALID_ARG for a range that is
+ *   not inside the store.
+ *   All three: PCOA_ERR_STATE before pcoa_loadings_begin; PCOA_ERR_INVALID_ARG for a NULL pointer, n_variants < 0, ld_words /
+ *   row_bytes too small; the ctx stays usable after every error.  They never modify S or the operator store, and run behind the
+ *   accumulation queued on the ctx stream.
+ *   Results are reproducible: which additions form entry (v, c), and their order, depend on n_samples alone -- not on num_pc or
+ *   on the components that travel with c, not on the number of rows of the call or on the row's place in it, not on the grid or
+ *   the CU count, not on where the row came from (host, device, .bed, store).  No floating-point atomics.
+ * pcoa_loadings_end: releases the vectors (synchronising); a no-op without a begin.
+ * Not built: carrier lists as an input form (a host with lists packs bitsets), the JNI natives.
+ * Extends: computePca (VariantsPca.scala:224-246), which stops at the sample coordinates, by the left singular vectors of the
+ * same decomposition. */
+#define PCOA_LOADINGS_CENTRE 1u   /* use u_c - mean(u_c) */
+#define PCOA_LOADINGS_UNIT   2u   /* divide by sqrt(eigenvalues[c]) */
+int pcoa_loadings_begin(pcoa_ctx* ctx, int32_t num_pc, const double* components /* [num_pc][n], pcoa_compute's layout */,
+                        const double* eigenvalues /* may be NULL without UNIT */, uint32_t flags);
+int pcoa_loadings_bits(pcoa_ctx* ctx, const uint32_t* bits, int64_t n_variants, int64_t ld_words, int is_device_ptr,
+                       double* out /* out[v * num_pc + c] */, int out_is_device);
+int pcoa_loadings_plink_bed(pcoa_ctx* ctx, const uint8_t* bed_rows, int64_t n_variants, int64_t row_bytes, int ref_is_a1,
+                            int is_device_ptr, double* out, int out_is_device);
+int pcoa_loadings_operator(pcoa_ctx* ctx, int64_t first_variant, int64_t n_variants, double* out, int out_is_device);
+int pcoa_loadings_end(pcoa_ctx* ctx);
+
+/* What the loadings calls did on THIS engine, cumulative since pcoa_create / pcoa_reset_timings.  (A struct of its own, like
+ * pcoa_pairs_stats.)  It grows at its end; out_size = sizeof of the struct the caller compiled against.  Synchronising. */
+typedef struct pcoa_loadings_stats {
+  int64_t loadings_variants;   /* rows the loadings kernels took                                                              */
+  int64_t loadings_bytes;      /* bytes of bitsets they read: 4 ceil(N / 32) per row and chunk of <= 8 components             */
+  double loadings_seconds;     /* HIP-event time of the loadings kernels (the .bed decode is densify_seconds)                 */
+} pcoa_loadings_stats;
+int pcoa_get_loadings_stats(pcoa_ctx* ctx, pcoa_loadings_stats* out, size_t out_size);
+
 /* ---- layout of S over the engines of one job ------------------------------------------------------------------------
  * FULL: every engine holds a whole N x N partial S (4 N^2 bytes) for its share of the variants; the partials are reduced
  * into engine 0 (peer copies: engine 0 stages one more 4 N^2 matrix when the engines sit on different devices, RCCL

@@ -123,6 +123,19 @@ class PcoaPairsStats(ctypes.Structure):
     ]
 
 
+class PcoaLoadingsStats(ctypes.Structure):
+    """pcoa_loadings_stats: a struct of its own beside pcoa_timings, like pcoa_pairs_stats."""
+    _fields_ = [
+        ("loadings_variants", ctypes.c_int64),
+        ("loadings_bytes", ctypes.c_int64),
+        ("loadings_seconds", ctypes.c_double),
+    ]
+
+
+PCOA_LOADINGS_CENTRE = 1
+PCOA_LOADINGS_UNIT = 2
+
+
 class PcoaSynthParams(ctypes.Structure):
     _fields_ = [
         ("seed", ctypes.c_uint64),
@@ -147,6 +160,12 @@ _SIGNATURES = [
     ("pcoa_get_pairs_stats", ctypes.c_int, [_vp, ctypes.POINTER(PcoaPairsStats), ctypes.c_size_t]),
     ("pcoa_set_similarity", ctypes.c_int, [_vp, _i32]),
     ("pcoa_get_similarity", ctypes.c_int, [_vp, ctypes.POINTER(_i32)]),
+    ("pcoa_loadings_begin", ctypes.c_int, [_vp, _i32, _vp, _vp, ctypes.c_uint32]),
+    ("pcoa_loadings_bits", ctypes.c_int, [_vp, _vp, _i64, _i64, ctypes.c_int, _vp, ctypes.c_int]),
+    ("pcoa_loadings_plink_bed", ctypes.c_int, [_vp, _vp, _i64, _i64, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int]),
+    ("pcoa_loadings_operator", ctypes.c_int, [_vp, _i64, _i64, _vp, ctypes.c_int]),
+    ("pcoa_loadings_end", ctypes.c_int, [_vp]),
+    ("pcoa_get_loadings_stats", ctypes.c_int, [_vp, ctypes.POINTER(PcoaLoadingsStats), ctypes.c_size_t]),
     ("pcoa_operator_info", ctypes.c_int, [_vp, ctypes.POINTER(_i64), ctypes.POINTER(_i64)]),
     ("pcoa_operator_row_sums", ctypes.c_int, [_vp, _vp]),
     ("pcoa_operator_matvec_device", ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int]),

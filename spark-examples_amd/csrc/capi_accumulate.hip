@@ -39,8 +39,7 @@ static int staging_fit(pcoa_ctx* c, StagingRing::Slot& sl, int i, size_t need, s
 
 // The next slot of the ring, free to be rewritten, with `need` bytes in buffer 0 (and need1 in buffer 1).  Creates the copy
 // stream and the ring's events on first use.
-static int staging_acquire(pcoa_ctx* c, StagingRing& r, size_t need, size_t grow_to, StagingRing::Slot** out, size_t need1 = 0,
-                           size_t grow_to1 = 0) {
+int staging_acquire(pcoa_ctx* c, StagingRing& r, size_t need, size_t grow_to, StagingRing::Slot** out, size_t need1, size_t grow_to1) {
   if (!c->csr_stream) HIP_TRY(c, hipStreamCreateWithFlags(&c->csr_stream, hipStreamNonBlocking));
   for (auto& sl : r.slot)
     if (!sl.copied) {
@@ -67,13 +66,13 @@ static int staging_pin(pcoa_ctx* c, StagingRing::Slot& sl, int i, size_t need, s
 }
 
 // the slot's copies have been queued on the copy stream
-static int staging_copied(pcoa_ctx* c, StagingRing::Slot& sl) {
+int staging_copied(pcoa_ctx* c, StagingRing::Slot& sl) {
   HIP_TRY(c, hipEventRecord(sl.copied, c->csr_stream));
   return PCOA_OK;
 }
 
 // the last kernel that reads the slot has been queued on `reader`
-static int staging_released(pcoa_ctx* c, StagingRing::Slot& sl, hipStream_t reader) {
+int staging_released(pcoa_ctx* c, StagingRing::Slot& sl, hipStream_t reader) {
   HIP_TRY(c, hipEventRecord(sl.freed, reader));
   sl.used = true;
   return PCOA_OK;

@@ -225,6 +225,7 @@ void pcoa_destroy(pcoa_ctx* c) {
   for (void* b : bufs)
     if (b) dev_free(b);
   operator_destroy(c);
+  loadings_destroy(c);
   if (c->pack_stream) (void)hipStreamDestroy(c->pack_stream);
   if (c->gram_stream) (void)hipStreamDestroy(c->gram_stream);
   if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
@@ -408,6 +409,7 @@ int pcoa_reset_timings(pcoa_ctx* c) {
   c->op_products = 0;
   c->subset_bytes = 0;
   c->pairs_bytes = c->pairs_calls = 0;
+  c->ld_variants = c->ld_bytes = 0;
   c->reduce_peers_calls = c->reduce_peers_bytes_in = 0;
   return PCOA_OK;
 }

@@ -12,6 +12,7 @@
 //   capi_subset.hip      pcoa_create_subset: a new engine whose S is S[I, I] of another
 //   capi_pairs.hip       pcoa_similar_pairs: the screen of S for duplicate and related sample pairs
 //   capi_measure.hip     pcoa_set_similarity / pcoa_get_similarity and the centring of a Jaccard / cosine measure
+//   capi_loadings.hip    pcoa_loadings_*: per-variant loadings of the principal coordinates from bitsets, .bed rows, the store
 //   pcoa_capi.hip        create / destroy, errors, timings
 #pragma once
 
@@ -20,7 +21,7 @@
 
 #include "pcoa_internal.h"
 
-enum TimeCat { T_GRAM = 0, T_DENSIFY, T_SYNTH, T_FINALIZE, T_CENTER, T_TRIDIAG, T_EIG, T_BACK, T_PACK, T_LANCZOS, T_ALLREDUCE, T_OPERATOR, T_SUBSET, T_REDUCE_PEERS, T_PAIRS, T_NCAT };
+enum TimeCat { T_GRAM = 0, T_DENSIFY, T_SYNTH, T_FINALIZE, T_CENTER, T_TRIDIAG, T_EIG, T_BACK, T_PACK, T_LANCZOS, T_ALLREDUCE, T_OPERATOR, T_SUBSET, T_REDUCE_PEERS, T_PAIRS, T_LOADINGS, T_NCAT };
 
 struct EventPair {
   hipEvent_t a, b;
@@ -78,6 +79,18 @@ struct pcoa_ctx {
   int64_t op_products = 0;
   int64_t subset_bytes = 0;        // bytes the gathers of pcoa_create_subset moved into this ctx (read + written)
   int64_t pairs_bytes = 0, pairs_calls = 0;   // pcoa_similar_pairs: bytes of S its scan kernels read, calls
+  // per-variant loadings (pcoa_loadings_begin .. pcoa_loadings_end, capi_loadings.hip): the prepared vectors stay resident
+  // between begin and end; the decode and output buffers are kept until pcoa_destroy
+  bool ld_active = false;
+  int32_t ld_num_pc = 0;
+  double* ld_u = nullptr;          // [num_pc][32 ceil(n / 32)] prepared vectors (centred where asked, zero for i >= n), then num_pc divisors
+  int64_t ld_u_cap = 0;
+  const double* ld_div = nullptr;  // sqrt(eigenvalues) behind the vectors (PCOA_LOADINGS_UNIT), else NULL
+  uint32_t* ld_bits = nullptr;     // decoded .bed rows of one chunk (lazy)
+  int64_t ld_bits_cap = 0;
+  double* ld_out = nullptr;        // one chunk of results on their way to a host `out` (lazy)
+  int64_t ld_out_cap = 0;
+  int64_t ld_variants = 0, ld_bytes = 0;   // rows the loadings kernels took, bytes of bitsets they read
   int device = 0;
   uint32_t flags = 0;
   int num_cu = 256;
@@ -323,6 +336,10 @@ hipError_t launch_reduce_chunk_i64(const ReduceSources& src, bool has64, int64_t
 
 // ---- capi_accumulate.hip
 int csr_validate(pcoa_ctx* c);
+int staging_acquire(pcoa_ctx* c, StagingRing& r, size_t need, size_t grow_to, StagingRing::Slot** out, size_t need1 = 0,
+                    size_t grow_to1 = 0);
+int staging_copied(pcoa_ctx* c, StagingRing::Slot& sl);
+int staging_released(pcoa_ctx* c, StagingRing::Slot& sl, hipStream_t reader);
 int staging_wait_all(pcoa_ctx* c, StagingRing& r);
 void staging_destroy(StagingRing& r);
 
@@ -346,6 +363,9 @@ int operator_reserve(pcoa_ctx* c, int32_t num_pc);
 int operator_compute(pcoa_ctx* c, int32_t num_pc, double* out_components, double* out_eigenvalues, int32_t* out_nonzero_rows);
 void operator_destroy(pcoa_ctx* c);
 int64_t operator_store_bytes(const pcoa_ctx* c);
+
+// ---- capi_loadings.hip
+void loadings_destroy(pcoa_ctx* c);
 
 struct ScopedTimer {
   pcoa_ctx* c;

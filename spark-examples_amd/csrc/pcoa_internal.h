@@ -212,6 +212,15 @@ hipError_t launch_operator_finish(const double* ypart, int32_t nranges, int32_t 
 hipError_t launch_operator_row_sums_finish(const int64_t* ipart, int32_t nranges, int32_t n, int64_t* rs_i64, double* rs_f64,
                                            hipStream_t stream);
 
+// ---- per-variant loadings (loadings.hip): out[v * num_pc + c] = (sum_i bit(v, i) u[c * ustride + i]) / div[c] for c in [0, k) ----
+// u: prepared vectors, ustride = 32 ceil(n / 32) doubles each, zero for i >= n (that is what ignores a row's tail bits); div: k
+// divisors or NULL; k must be 1, 2, 4 or 8 (loadings_chunk picks the chunk); out / u / div point at the chunk's first component.
+// loadings_lanes(n): lanes that share a row (8, 16, 32 or 64) -- with n, all that the order of an entry's additions depends on
+int32_t loadings_lanes(int32_t n);
+int loadings_chunk(int32_t remaining);
+hipError_t launch_loadings(const uint32_t* bits, int64_t nv, int64_t ld_words, int32_t n, const double* u, int64_t ustride, int32_t k,
+                           const double* div, double* out, int32_t num_pc, hipStream_t stream);
+
 // ---- centring (center.hip) --------------------------------------------------------------------
 // s = s32 + (s64 ? s64 : 0).  row_sums[n] (fp64), stats[0] = matrix sum, stats[1] = matrix mean,
 // nz[0] = #rows with sum > 0.  b = centred matrix fp64 [n][n].

@@ -517,6 +517,14 @@ class PcoaEngine(object):
                                                           ctypes.c_void_p(y.data_ptr()), int(bool(centred))))
         return y
 
+    # ------------------------------------------------------------------ per-variant loadings
+    def loadings(self, components, eigenvalues=None, centre=True, unit=True):
+        """Per-variant loadings of the principal coordinates (pcoa_loadings_begin): `components` [N, k] and `eigenvalues` [k] are
+        what compute(k) returned.  centre: use u_c - mean(u_c); unit: divide by sqrt(eigenvalues[c]) -- both on, the rows are
+        w_c = X (J u_c) / sqrt(lambda_c), the left singular vectors of X J.  Returns a Loadings object whose .bits / .plink_bed /
+        .operator stream rows past the resident vectors; .close() releases them."""
+        return Loadings(self, components, eigenvalues, centre, unit)
+
     # ------------------------------------------------------------------ computePca
     def center(self, want_matrix=True):
         """Row sums + double-centring (VariantsPca.scala:206-223).  Returns (B, row_sums, nonzero_rows, mean)."""
@@ -568,6 +576,114 @@ class PcoaEngine(object):
 
     def reset_timings(self):
         self._check(self._lib.pcoa_reset_timings(self._ctx))
+
+
+class Loadings(object):
+    """The vectors of one pcoa_loadings_begin, resident on the engine's GPU until close().  Every method returns the loadings
+    of its rows as [rows, k]: a numpy array, or with device_out=True a float64 torch tensor on the engine's GPU (complete when
+    the method returns)."""
+
+    def __init__(self, engine, components, eigenvalues=None, centre=True, unit=True):
+        comps = np.asarray(components, dtype=np.float64)
+        if comps.ndim != 2 or comps.shape[0] != engine.n:
+            raise ValueError("components must be [N = %d, k]" % engine.n)
+        self.k = int(comps.shape[1])
+        lam = None
+        if eigenvalues is not None:
+            lam = np.ascontiguousarray(eigenvalues, dtype=np.float64)
+            if lam.shape != (self.k,):
+                raise ValueError("eigenvalues must be [k = %d]" % self.k)
+        flags = (L.PCOA_LOADINGS_CENTRE if centre else 0) | (L.PCOA_LOADINGS_UNIT if unit else 0)
+        u = np.ascontiguousarray(comps.T)   # [k][N]: the column-major layout pcoa_compute writes
+        self._eng = engine
+        self._open = False
+        engine._check(engine._lib.pcoa_loadings_begin(engine._ctx, self.k, _ptr(u), None if lam is None else _ptr(lam), flags))
+        self._open = True
+
+    def _out(self, rows, device_out):
+        if not device_out:
+            out = np.zeros((rows, self.k), dtype=np.float64)
+            return out, _ptr(out)
+        import torch  # plumbing only: device memory handles
+        out = torch.zeros((rows, self.k), dtype=torch.float64, device="cuda:%d" % self._eng.device)
+        torch.cuda.current_stream(out.device).synchronize()   # the engine runs on its own stream
+        return out, ctypes.c_void_p(out.data_ptr())
+
+    def _done(self, device_in_or_out):
+        if device_in_or_out:   # queued work: the tensors are complete / no longer read when sync returns
+            self._eng._check(self._eng._lib.pcoa_sync(self._eng._ctx))
+
+    def bits(self, bits, n_variants=None, ld_words=None, device_out=False):
+        """Rows of carrier bitsets in accumulate_bits' layout: numpy uint32 [V][W] (host) or a torch int32 CUDA tensor."""
+        e = self._eng
+        if hasattr(bits, "data_ptr") and getattr(bits, "is_cuda", False):
+            import torch  # plumbing only
+            assert bits.dtype == torch.int32 and bits.dim() == 2 and bits.stride(1) == 1
+            nv = int(bits.shape[0]) if n_variants is None else int(n_variants)
+            ldv = int(bits.stride(0)) if ld_words is None else int(ld_words)
+            out, optr = self._out(nv, device_out)
+            torch.cuda.current_stream(bits.device).synchronize()
+            e._check(e._lib.pcoa_loadings_bits(e._ctx, ctypes.c_void_p(bits.data_ptr()), nv, ldv, 1, optr, int(bool(device_out))))
+            self._done(True)
+            return out
+        a = np.ascontiguousarray(bits, dtype=np.uint32)
+        if a.ndim != 2:
+            raise ValueError("bits must be 2-D [variants][words]")
+        nv = a.shape[0] if n_variants is None else int(n_variants)
+        ldv = a.shape[1] if ld_words is None else int(ld_words)
+        out, optr = self._out(nv, device_out)
+        e._check(e._lib.pcoa_loadings_bits(e._ctx, _ptr(a), nv, ldv, 0, optr, int(bool(device_out))))
+        self._done(device_out)
+        return out
+
+    def plink_bed(self, rows, ref_is_a1=False, device_out=False):
+        """Raw variant-major PLINK .bed rows: numpy uint8 [V][row_bytes] (host) or a torch uint8 CUDA tensor."""
+        e = self._eng
+        if hasattr(rows, "data_ptr") and getattr(rows, "is_cuda", False):
+            import torch  # plumbing only
+            assert rows.dtype == torch.uint8 and rows.dim() == 2 and rows.stride(1) == 1
+            out, optr = self._out(int(rows.shape[0]), device_out)
+            torch.cuda.current_stream(rows.device).synchronize()
+            e._check(e._lib.pcoa_loadings_plink_bed(e._ctx, ctypes.c_void_p(rows.data_ptr()), int(rows.shape[0]), int(rows.stride(0)),
+                                                    int(bool(ref_is_a1)), 1, optr, int(bool(device_out))))
+            self._done(True)
+            return out
+        a = np.ascontiguousarray(rows, dtype=np.uint8)
+        if a.ndim != 2:
+            raise ValueError("rows must be [variants][row_bytes]")
+        out, optr = self._out(a.shape[0], device_out)
+        e._check(e._lib.pcoa_loadings_plink_bed(e._ctx, _ptr(a), a.shape[0], a.shape[1], int(bool(ref_is_a1)), 0, optr,
+                                                int(bool(device_out))))
+        self._done(device_out)
+        return out
+
+    def operator(self, first=0, n=None, device_out=False):
+        """Rows [first, first + n) of an operator engine's resident store (n=None: to its end)."""
+        e = self._eng
+        if n is None:
+            info = e.operator_info()
+            n = (info[0] if info else 0) - int(first)
+        out, optr = self._out(max(int(n), 0), device_out)
+        e._check(e._lib.pcoa_loadings_operator(e._ctx, int(first), int(n), optr, int(bool(device_out))))
+        self._done(device_out)
+        return out
+
+    def stats(self):
+        """pcoa_loadings_stats of the engine: loadings_variants, loadings_bytes, loadings_seconds."""
+        q = L.PcoaLoadingsStats()
+        self._eng._check(self._eng._lib.pcoa_get_loadings_stats(self._eng._ctx, ctypes.byref(q), ctypes.sizeof(q)))
+        return dict((f[0], getattr(q, f[0])) for f in L.PcoaLoadingsStats._fields_)
+
+    def close(self):
+        if self._open and getattr(self._eng, "_ctx", None):
+            self._open = False
+            self._eng._check(self._eng._lib.pcoa_loadings_end(self._eng._ctx))
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
 
 
 # ---------------------------------------------------------------------------------------------- layout of S (pcoa.h)

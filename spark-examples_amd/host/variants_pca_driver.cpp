@@ -103,6 +103,10 @@ struct Conf {  // PcaConf / GenomicsConf (GenomicsConf.scala:31-101), same flag 
   bool remove_related = false;          // --remove-related: drop one sample of every reported pair, go on with pcoa_create_subset over the rest
   std::string similarity_measure = "shared";  // --similarity-measure shared|jaccard|cosine: what computePca decomposes (pcoa_set_similarity);
                                               // jaccard / cosine are evaluated on the fly from S, set on the engine that runs computePca
+  std::string loadings_output_path;     // --loadings-output-path FILE: the loading of every variant fed to the engine on each of the --num-pc
+                                        // principal coordinates, w_c = X (J u_c) / sqrt(lambda_c) (pcoa_loadings_*), one line per variant in feed
+                                        // order.  --gram implicit reads the resident store; a stored S takes a second streaming pass over a
+                                        // single PLINK fileset
   int32_t similarity_kind() const {
     return similarity_measure == "jaccard" ? PCOA_SIMILARITY_JACCARD : similarity_measure == "cosine" ? PCOA_SIMILARITY_COSINE : PCOA_SIMILARITY_SHARED;
   }
@@ -126,6 +130,10 @@ const char* kUsage =
     "                   --similarity-measure shared|jaccard|cosine (what computePca decomposes: the counts S as the reference,\n"
     "                   S(i,j) / (S(i,i) + S(j,j) - S(i,j)), or S(i,j) / sqrt(S(i,i) S(j,j)), evaluated on the fly from S; one\n"
     "                   engine, stored S, full layout, no projection)\n"
+    "                   --loadings-output-path FILE (the loading of every variant on each of the --num-pc principal coordinates,\n"
+    "                   one line per variant in feed order: index, contig, position, id, loadings; one engine, the whole\n"
+    "                   cohort, --similarity-measure shared; --gram implicit for any input, a stored S for one streamed PLINK\n"
+    "                   fileset)\n"
     "  --project-input-path <file.vcf[.gz]> [more]\n"
     "                   place these samples onto the principal coordinates of the --input-path cohort instead of\n"
     "                   decomposing the union (one GPU, VCF inputs, full layout)\n";
@@ -231,6 +239,7 @@ Conf parse(int argc, char** argv) {
       if (c.similarity_measure != "shared" && c.similarity_measure != "jaccard" && c.similarity_measure != "cosine")
         die("--similarity-measure takes shared, jaccard or cosine, not '" + c.similarity_measure + "'");
     }
+    else if (a == "--loadings-output-path") c.loadings_output_path = one(i);
     else if (a == "--parse-only") c.parse_only = true;
     else if (a == "--dump-similarity") c.dump_similarity = one(i);
     else if (a == "--ingest-threads") c.ingest_threads = std::atoi(one(i).c_str());
@@ -278,6 +287,23 @@ Conf parse(int argc, char** argv) {
     if (c.layout == "strips") die(strips_refuse_measure(m));
     if (!c.project_input_path.empty())
       die("--similarity-measure " + m + ": projection under a measure is not built: it cannot take --project-input-path");
+  }
+  // --loadings-output-path: the identity B = (X J)^T (X J) behind the loadings holds for the shared counts of the whole cohort
+  // on one engine: likewise
+  if (!c.loadings_output_path.empty()) {
+    if (c.gpus > 1) die("--loadings-output-path streams the variants past one engine: it cannot take --gpus " + std::to_string(c.gpus));
+    if (c.layout == "strips") die("--loadings-output-path runs on one whole engine: it cannot take --layout strips");
+    if (!c.project_input_path.empty())
+      die("--loadings-output-path writes the loadings of the cohort it decomposes: it cannot take --project-input-path");
+    if (c.outlier_iterations > 0)
+      die("--loadings-output-path needs the eigenpairs of the cohort the variants were counted over: it cannot take --outlier-iterations " +
+          std::to_string(c.outlier_iterations));
+    if (c.remove_related)
+      die("--loadings-output-path needs the eigenpairs of the cohort the variants were counted over: it cannot take --remove-related");
+    if (c.similarity_measure != "shared")
+      die("--loadings-output-path: under --similarity-measure " + c.similarity_measure +
+          " the decomposed matrix is no longer (X J)^T (X J); it takes --similarity-measure shared only");
+    if (c.parse_only) die("--loadings-output-path needs the decomposition: it cannot take --parse-only");
   }
   if (c.gram == "implicit") {
     // one operator engine holds the carrier bitsets of every variant: what needs S, or several engines, is refused here,
@@ -361,8 +387,11 @@ std::string murmur3_128_hex(const std::string& data) {
 // keeps the calls with hasVariation (getCallsRdd :163-167; join / merge concatenate the call lists first, which
 // commutes with the filter because callset indices are global), so a variant stores its CARRIERS: the callset
 // indices with variation, in call order.
+struct VarMeta { std::string contig; long pos = 0; std::string id; };   // a line's first columns in the --loadings-output-path file
+bool g_want_meta = false;          // --loadings-output-path given: contig, position and id are recorded during ingest (only then)
 struct Variant {
   std::string key;                 // getVariantKey
+  VarMeta meta;                    // (g_want_meta)
   bool has_af = false; float af = 0.f;
   std::vector<int32_t> carriers;   // extractCallInfo (:56-60) filtered by hasVariation
 };
@@ -508,6 +537,7 @@ void parse_record(const char* b, const char* e, const std::vector<Region>& regio
   buf.append(f[3]);
   buf += alt;
   v.key = murmur3_128_hex(buf);
+  if (g_want_meta) v.meta = VarMeta{contig, start + 1, std::string(f[2])};
   for (const char *q = f[7].data(), *qe = q + f[7].size(); q < qe;) {
     const std::string_view item = next_field(q, qe, ';');
     if (item.size() >= 3 && item.compare(0, 3, "AF=") == 0) {
@@ -655,6 +685,7 @@ struct PlinkMeta {
   std::string prefix;
   std::vector<std::string> ids, names;
   std::vector<char> keep;  // per .bim line: inside --references and on a contig the reference keeps
+  std::vector<VarMeta> meta;   // of the kept lines, in file order (g_want_meta)
   size_t n = 0, bpv = 0;   // samples; bytes per variant row of the .bed
 };
 
@@ -693,6 +724,7 @@ PlinkMeta read_plink_meta(const std::string& path, const std::string& stem, cons
           if (r.contig == contig && r.start <= bp - 1 && bp - 1 < r.end) { ok = true; break; }
       }
       m.keep.push_back(ok ? 1 : 0);
+      if (ok && g_want_meta) m.meta.push_back(VarMeta{contig, bp, id});
     }
   }
   m.bpv = (m.n + 3) / 4;
@@ -727,6 +759,7 @@ Dataset load_plink(const std::string& path, const std::string& stem, const std::
     if ((size_t)bed.gcount() != bpv) die(m.prefix + ".bed is shorter than its .bim / .fam say");
     if (!m.keep[v]) continue;
     Variant var;
+    if (g_want_meta) var.meta = m.meta[d.variants.size()];
     for (size_t s = 0; s < n; ++s) {
       const unsigned code = (row[s >> 2] >> (2 * (s & 3))) & 3u;
       if (code == 2u || code == (ref_a1 ? 3u : 0u)) var.carriers.push_back(index_base + (int32_t)s);
@@ -1407,6 +1440,7 @@ std::vector<int32_t> related_removal(const std::vector<pcoa_pair>& pairs, int32_
 int main(int argc, char** argv) {
   const auto t_start = std::chrono::steady_clock::now();
   Conf conf = parse(argc, argv);
+  g_want_meta = !conf.loadings_output_path.empty();
   if (conf.input_path.empty())
     die("--input-path <file.vcf[.gz]> [more files] or one PLINK fileset (<prefix>.bed) is required: the Google Genomics API the reference read "
         "from has been shut down");
@@ -1425,6 +1459,11 @@ int main(int argc, char** argv) {
   // stream_plink_shard block by block, each engine its own contiguous range of variants.
   const bool stream_plink = conf.input_path.size() == 1 && is_plink_path(conf.input_path[0]) && !conf.no_stream &&
                             !conf.parse_only && !conf.has_maf;
+  if (g_want_meta && conf.gram != "implicit" && !stream_plink)
+    die("--loadings-output-path with a stored similarity matrix takes its second pass over ONE streamed PLINK fileset; for this "
+        "input use --gram implicit, which keeps the rows resident");
+  std::vector<VarMeta> fed_meta;   // --loadings-output-path: (contig, position, id) of every row fed, in feed order
+  bool fed_meta_known = true;      // joined / merged sets reach the engine partition by partition without their records: '.' columns
   PlinkMeta plink;
   if (stream_plink) {
     std::vector<Region> regions;
@@ -1526,7 +1565,10 @@ int main(int argc, char** argv) {
   // getCallsRdd (:153-168)
   std::vector<std::vector<int32_t>> callsets;
   if (data.size() == 1) {
-    for (auto& v : data[0].variants) callsets.push_back(std::move(v.carriers));
+    for (auto& v : data[0].variants) {
+      if (g_want_meta && !v.carriers.empty() && !stream_vcf && !stream_join) fed_meta.push_back(v.meta);
+      callsets.push_back(std::move(v.carriers));
+    }
   } else if (!stream_join) {  // joinDatasets (two sets) / mergeDatasets (more)
     std::vector<std::vector<Variant>> sets;
     for (auto& d : data) sets.push_back(std::move(d.variants));
@@ -1665,6 +1707,7 @@ int main(int argc, char** argv) {
           if (pl.v.carriers.empty()) continue;                                                     // getCallsRdd (:166)
           idx.insert(idx.end(), pl.v.carriers.begin(), pl.v.carriers.end());
           offs.push_back((int64_t)idx.size());
+          if (g_want_meta) fed_meta.push_back(pl.v.meta);
         }
         if (offs.size() > 1) {
           give(idx.data(), offs.data(), (int64_t)offs.size() - 1);
@@ -1769,7 +1812,8 @@ int main(int argc, char** argv) {
                  conf.input_path.size(), spill.parts, (long long)spilled_records, spill.bytes / 1e6, spill.dir.c_str());
     spill.remove_all();
   }
-  for (unsigned char* b : blocks) (void)pcoa_host_free_pinned(b);
+  if (stream_plink) fed_meta = plink.meta;                 // one engine: every kept line, in file order
+  if (stream_join || data.size() > 1) fed_meta_known = false;
   for (pcoa_ctx* o : owners) check(o, pcoa_gram_finalize(o), "getSimilarityMatrix");
   {
     struct rusage ru;
@@ -1914,6 +1958,72 @@ int main(int argc, char** argv) {
     rows.push_back({names[i], ids[i].substr(0, ids[i].find('-')), comps[(size_t)a], comps[(size_t)a + (size_t)n_out]});
   }
   emit_result(conf, rows);
+
+  // --loadings-output-path: w_c = X (J u_c) / sqrt(lambda_c) for every variant the engine was fed, from the eigenpairs above
+  if (g_want_meta) {
+    std::vector<double> w;
+    int64_t n_rows = 0;
+    check(ctx, pcoa_loadings_begin(ctx, conf.num_pc, comps.data(), lam.data(), PCOA_LOADINGS_CENTRE | PCOA_LOADINGS_UNIT), "loadings");
+    if (conf.gram == "implicit") {   // the rows are the engine's own store
+      (void)pcoa_operator_info(ctx, &n_rows, nullptr);
+      w.resize((size_t)std::max<int64_t>(n_rows, 1) * (size_t)conf.num_pc);
+      check(ctx, pcoa_loadings_operator(ctx, 0, n_rows, w.data(), 0), "loadings");
+    } else {
+      // stored S: the .bed a second time, block by block through the page-locked blocks of the first pass -- block k + 1 is read
+      // while block k's rows are decoded and summed on the device (a host `out` is filled when the call returns)
+      n_rows = (int64_t)std::count(plink.keep.begin(), plink.keep.end(), (char)1);
+      w.resize((size_t)std::max<int64_t>(n_rows, 1) * (size_t)conf.num_pc);
+      const int fd = ::open((plink.prefix + ".bed").c_str(), O_RDONLY);
+      if (fd < 0) die("cannot open " + plink.prefix + ".bed");
+      const int64_t total = (int64_t)plink.keep.size(), block = conf.stream_rows;
+      const size_t bpv = plink.bpv;
+      auto read_block = [&](int64_t b0, int which) -> int64_t {   // kept rows, compacted to the front of blocks[which]
+        const int64_t nrows = std::min(block, total - b0);
+        unsigned char* dst = blocks[(size_t)which];
+        size_t lo = 0;
+        const size_t hi = (size_t)nrows * bpv;
+        while (lo < hi) {
+          const ssize_t r = ::pread(fd, dst + lo, hi - lo, (off_t)(3 + (size_t)b0 * bpv + lo));
+          if (r <= 0) die(plink.prefix + ".bed: read error");
+          lo += (size_t)r;
+        }
+        int64_t kept_rows = 0;
+        for (int64_t r = 0; r < nrows; ++r) {
+          if (!plink.keep[(size_t)(b0 + r)]) continue;
+          if (kept_rows != r) std::memmove(dst + (size_t)kept_rows * bpv, dst + (size_t)r * bpv, bpv);
+          ++kept_rows;
+        }
+        return kept_rows;
+      };
+      int which = 0;
+      int64_t done = 0;
+      int64_t kept_rows = total > 0 ? read_block(0, 0) : 0;
+      for (int64_t b0 = 0; b0 < total; b0 += block) {
+        std::future<int64_t> next;
+        if (b0 + block < total) next = std::async(std::launch::async, read_block, b0 + block, (which + 1) & 3);
+        if (kept_rows > 0)
+          check(ctx, pcoa_loadings_plink_bed(ctx, blocks[(size_t)which], kept_rows, (int64_t)bpv, conf.plink_ref_allele == "a1" ? 1 : 0, 0,
+                                             w.data() + (size_t)done * (size_t)conf.num_pc, 0), "loadings");
+        done += kept_rows;
+        if (next.valid()) kept_rows = next.get();
+        which = (which + 1) & 3;
+      }
+      ::close(fd);
+      if (done != n_rows) die("--loadings-output-path: the second pass read " + std::to_string(done) + " rows, the first " + std::to_string(n_rows));
+    }
+    check(ctx, pcoa_loadings_end(ctx), "loadings");
+    if (fed_meta_known && (int64_t)fed_meta.size() != n_rows)
+      die("--loadings-output-path: " + std::to_string(fed_meta.size()) + " variant records for " + std::to_string(n_rows) + " rows");
+    std::ofstream out(conf.loadings_output_path);
+    for (int64_t v = 0; v < n_rows; ++v) {
+      if (fed_meta_known) out << v << "\t" << fed_meta[(size_t)v].contig << "\t" << fed_meta[(size_t)v].pos << "\t" << fed_meta[(size_t)v].id;
+      else out << v << "\t.\t.\t.";
+      for (int c = 0; c < conf.num_pc; ++c) out << "\t" << java_double(w[(size_t)v * (size_t)conf.num_pc + (size_t)c]);
+      out << "\n";
+    }
+    if (!out) die("cannot write " + conf.loadings_output_path);
+  }
+  for (unsigned char* b : blocks) (void)pcoa_host_free_pinned(b);
 
   // reportIoStats (:48) / stop (:49)
   pcoa_timings t;

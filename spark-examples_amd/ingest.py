@@ -91,9 +91,10 @@ def _carriers_of_cells(cells, gti, n_samples):
     return cols[cols < n_samples].astype(np.int32)
 
 
-def load_vcf(path, references=None):
+def load_vcf(path, references=None, variant_meta=None):
     """Minimal VCF reader: GT only.  Returns CSR carrier lists directly (one numpy pass per line over the sample
-    columns; ~40x the per-cell Python loop it replaced, same carriers as the compiled host, tests/test_host.py)."""
+    columns; ~40x the per-cell Python loop it replaced, same carriers as the compiled host, tests/test_host.py).
+    variant_meta: a list that receives (contig, POS, ID) of every variant that gets a row (--loadings-output-path)."""
     regions = parse_references(references)
     opener = gzip.open if path.endswith(".gz") else open
     set_id = set_id_of(path)
@@ -125,6 +126,8 @@ def load_vcf(path, references=None):
             if carriers.size:
                 idx_chunks.append(carriers)
                 offs.append(offs[-1] + int(carriers.size))
+                if variant_meta is not None:
+                    variant_meta.append((contig, int(head[1]), head[2].decode()))
     if samples is None:
         raise ValueError("no #CHROM header in %s" % path)
     ids = ["%s-%d" % (set_id, i) for i in range(len(samples))]
@@ -133,7 +136,7 @@ def load_vcf(path, references=None):
     return indexes, dict(zip(ids, samples)), [("csr", idx, np.asarray(offs, dtype=np.int64))]
 
 
-def load_plink(path, references=None, ref_allele="a2", chunk_variants=4096, as_bits=False, as_bed=False):
+def load_plink(path, references=None, ref_allele="a2", chunk_variants=4096, as_bits=False, as_bed=False, variant_meta=None):
     """PLINK 1 binary fileset (<prefix>.bed / .bim / .fam; `path` is the prefix or any of the three files).  The .bed is
     variant-major, two bits per genotype, four samples to a byte (sample s in bits 2 (s % 4) of byte s // 4):
     00 homozygous A1, 01 missing, 10 heterozygous, 11 homozygous A2.  hasVariation (VariantsPca.scala:56-60: some allele
@@ -147,7 +150,9 @@ def load_plink(path, references=None, ref_allele="a2", chunk_variants=4096, as_b
     genotype instead of 4 bytes per carrier; rows without a carrier stay (they add nothing to S).
     as_bed=True (r05) decodes nothing at all: [("bed", memory-mapped uint8 [variants][ceil(N / 4)] rows as they lie in the
     file, keep mask over the .bim lines, ref_is_a1)] -- what pcoa_accumulate_plink_bed takes block by block (the device
-    decodes; the numpy decode above runs at ~0.2 M variants/s, a memory-mapped block copy at GB/s)."""
+    decodes; the numpy decode above runs at ~0.2 M variants/s, a memory-mapped block copy at GB/s).
+    variant_meta: a list that receives (contig, bp, id = .bim column 2) of every kept .bim line -- the rows of the as_bed and
+    as_bits forms (--loadings-output-path)."""
     prefix = path[:-4] if path[-4:] in (".bed", ".bim", ".fam") else path
     regions = parse_references(references)
     set_id = set_id_of(prefix + ".bed")
@@ -168,6 +173,8 @@ def load_plink(path, references=None, ref_allele="a2", chunk_variants=4096, as_b
                 start = int(t[3]) - 1
                 ok = any(c == contig and s0 <= start < e for (c, s0, e) in regions)
             keep.append(ok)
+            if ok and variant_meta is not None:
+                variant_meta.append((contig, int(t[3]), t[1]))
     keep = np.asarray(keep, dtype=bool)
     bpv = (n + 3) // 4                                          # bytes per variant
     raw = np.memmap(prefix + ".bed", dtype=np.uint8, mode="r")     # a cohort's .bed can be tens of GB: read in chunks
@@ -275,7 +282,7 @@ def load_vcf_records(path, references=None, set_id=None):
                 calls.append({"callSetId": ids[i], "genotype": genotype})
             variants.append({"contig": contig, "start": start, "end": start + len(rec[3]), "referenceBases": rec[3],
                              "alternateBases": [a for a in rec[4].split(",") if a != "."], "info": info,
-                             "calls": calls})
+                             "calls": calls, "id": rec[2]})
     if samples is None:
         raise ValueError("no #CHROM header in %s" % path)
     return ids, dict(zip(ids, samples)), variants

@@ -57,7 +57,12 @@ def extract_call_info(variant, mapping):
     return out
 
 
-def prepare_call_data(py_rdd, py_id_to_index):
+def variant_meta_of(variant):
+    """(contig, 1-based position, id) of a variant record: a line's first columns in the --loadings-output-path file."""
+    return (variant["contig"], int(variant["start"]) + 1, variant.get("id", "."))
+
+
+def prepare_call_data(py_rdd, py_id_to_index, meta=None):
     """prepare_call_data (variants_pca.py:19-52) == getCallsRdd for one variant set
     (VariantsPca.scala:153-157,163-167): keep calls with variation, drop variants with none,
     map callset ids to indices.  Returns a list of index lists (RDD[Seq[Int]]).
@@ -69,6 +74,8 @@ def prepare_call_data(py_rdd, py_id_to_index):
         calls = [idx for (has_variation, idx) in extract_call_info(variant, py_id_to_index) if has_variation]
         if len(calls) > 0:
             call_rdd.append(calls)
+            if meta is not None:
+                meta.append(variant_meta_of(variant))
     return call_rdd
 
 
@@ -132,30 +139,38 @@ def get_variant_key(variant, debug=False):
     return murmur3_128_hex(buf)
 
 
-def join_datasets(datasets, indexes, debug=False):
+def join_datasets(datasets, indexes, debug=False, meta=None):
     """VariantsPcaDriver.joinDatasets (VariantsPca.scala:115-128): two-way INNER join on the variant
-    key; the joined record is calls1 ++ calls2 (cross product if a key repeats, as RDD.join does)."""
+    key; the joined record is calls1 ++ calls2 (cross product if a key repeats, as RDD.join does).
+    meta: a list that receives variant_meta_of the FIRST set's record of every joined row."""
     keyed = []
     for data in datasets[:2]:
         d = {}
         for variant in data:
-            d.setdefault(get_variant_key(variant, debug), []).append(extract_call_info(variant, indexes))
+            d.setdefault(get_variant_key(variant, debug), []).append((extract_call_info(variant, indexes), variant))
         keyed.append(d)
     out = []
     for key, calls1 in keyed[0].items():
-        for c1 in calls1:
-            for c2 in keyed[1].get(key, []):
+        for c1, v1 in calls1:
+            for c2, _ in keyed[1].get(key, []):
                 out.append(c1 + c2)
+                if meta is not None:
+                    meta.append(variant_meta_of(v1))
     return out
 
 
-def merge_datasets(datasets, variant_set_count, indexes):
+def merge_datasets(datasets, variant_set_count, indexes, meta=None):
     """VariantsPcaDriver.mergeDatasets (VariantsPca.scala:136-148): union, group by variant key, keep
-    the groups with exactly variantSetCount members, concatenate their calls."""
-    groups = {}
+    the groups with exactly variantSetCount members, concatenate their calls.
+    meta: a list that receives variant_meta_of the first record of every kept group."""
+    groups, first = {}, {}
     for data in datasets:
         for variant in data:
-            groups.setdefault(get_variant_key(variant), []).append(extract_call_info(variant, indexes))
+            key = get_variant_key(variant)
+            groups.setdefault(key, []).append(extract_call_info(variant, indexes))
+            first.setdefault(key, variant)
+    if meta is not None:
+        meta.extend(variant_meta_of(first[k]) for k, g in groups.items() if len(g) == variant_set_count)
     return [[c for calls in g for c in calls] for g in groups.values() if len(g) == variant_set_count]
 
 
@@ -457,6 +472,12 @@ class PcaConf(object):
                             "the reference; jaccard: S(i, j) / (S(i, i) + S(j, j) - S(i, j)); cosine: S(i, j) / sqrt(S(i, i) "
                             "S(j, j)) -- evaluated on the fly from S on the device, which takes out the axis that tracks how "
                             "many variants a sample carries.  One full engine: stored S, full layout, no projection")
+        p.add_argument("--loadings-output-path", type=str, default=None,
+                       help="write the loading of every variant fed to the engine on each of the --num-pc principal "
+                            "coordinates, w_c = X (J u_c) / sqrt(lambda_c) (pcoa_loadings_*), to this file: one line per "
+                            "variant in feed order -- 0-based index, contig, position, variant id, then the loadings, "
+                            "tab-separated.  One engine, --similarity-measure shared, the whole cohort: stored S takes a second "
+                            "pass over the variants, --gram implicit reads the resident store")
         a = p.parse_args(list(arguments))
         self.__dict__.update(vars(a))
         self.numPc = a.num_pc
@@ -555,7 +576,9 @@ class VariantsPcaDriver(object):
         return out
 
     # getCallsRdd, VariantsPca.scala:153-168
-    def getCallsRdd(self, data):
+    def getCallsRdd(self, data, meta=None):
+        """meta (--loadings-output-path): a list that receives (contig, position, id) of every row of the result built from
+        variant RECORDS; the carrier-only inputs recorded theirs during ingest (load_dataset)."""
         variant_set_count = len(data)
         if variant_set_count == 1:
             d = data[0]
@@ -563,18 +586,21 @@ class VariantsPcaDriver(object):
                 if d[0] == "bed":
                     return d
                 return ("bits", d[1]) if d[0] == "bits" else (d[1], d[2])
-            return prepare_call_data(d, self.indexes)
+            return prepare_call_data(d, self.indexes, meta)
         if any(isinstance(d, tuple) for d in data):
             raise ValueError("joining datasets needs variant records (contig/start/end/ref/alt), not CSR carriers")
+        joined_meta = [] if meta is not None else None
         if variant_set_count == 2:
-            callsets = join_datasets(data, self.indexes, self.conf.debug_datasets)
+            callsets = join_datasets(data, self.indexes, self.conf.debug_datasets, joined_meta)
         else:
-            callsets = merge_datasets(data, variant_set_count, self.indexes)
+            callsets = merge_datasets(data, variant_set_count, self.indexes, joined_meta)
         out = []
-        for calls in callsets:  # :164-167
+        for k, calls in enumerate(callsets):  # :164-167
             kept = [idx for (has_variation, idx) in calls if has_variation]
             if len(kept) > 0:
                 out.append(kept)
+                if meta is not None:
+                    meta.append(joined_meta[k])
         return out
 
     # getSimilarityMatrix, VariantsPca.scala:182-191
@@ -647,7 +673,8 @@ class VariantsPcaDriver(object):
     # computePca, VariantsPca.scala:198-231
     def computePca(self, sim_matrix):
         kept = self.kept if self.kept is not None else np.arange(len(self.indexes))   # (--remove-related: the kept samples)
-        comps, _, nonzero = sim_matrix.compute(self.conf.numPc)
+        comps, lam, nonzero = sim_matrix.compute(self.conf.numPc)
+        self.last_pca = (comps, lam)   # (--loadings-output-path goes on from them)
         print("Non zero rows in matrix: %d / %d." % (nonzero, kept.size))  # :208
         if comps.shape[1] < 2:
             # the reference indexes array(i + pca.numRows) unconditionally (:230) and fails for --num-pc 1
@@ -751,6 +778,28 @@ class VariantsPcaDriver(object):
                 for (name, pc1, pc2, dataset) in rows:
                     f.write("%s\t%s\t%s\t%s\n" % (name, java_double_to_string(pc1), java_double_to_string(pc2), dataset))
 
+    # --loadings-output-path: w_c = X (J u_c) / sqrt(lambda_c) for every variant the engine was fed, in feed order, from the
+    # eigenpairs computePca left.  rows: the variants as calls_as_bits returns them -- streamed past the resident vectors a
+    # second time (stored S), or None: the rows are the engine's own store (--gram implicit).
+    def emitLoadings(self, rows, meta):
+        comps, lam = self.last_pca
+        with self.engine.loadings(comps, lam, centre=True, unit=True) as ld:
+            if rows is None:
+                w = ld.operator()
+            elif rows[0] == "bed":
+                _, geno, keep, ref_is_a1 = rows
+                parts = []
+                for v0 in range(0, geno.shape[0], PLINK_BLOCK_ROWS):
+                    k = keep[v0:v0 + PLINK_BLOCK_ROWS]
+                    if k.any():
+                        parts.append(ld.plink_bed(np.ascontiguousarray(geno[v0:v0 + PLINK_BLOCK_ROWS][k]), ref_is_a1=ref_is_a1))
+                w = np.concatenate(parts) if parts else np.zeros((0, comps.shape[1]))
+            else:
+                bits = rows[1]
+                parts = [ld.bits(bits[v0:v0 + (1 << 20)]) for v0 in range(0, bits.shape[0], 1 << 20)]
+                w = np.concatenate(parts) if parts else np.zeros((0, comps.shape[1]))
+        write_loadings(self.conf.loadings_output_path, meta, w)
+
     def reportIoStats(self, out=None):
         out = out or sys.stdout
         if self.engine is not None:
@@ -769,9 +818,22 @@ class VariantsPcaDriver(object):
             self.engine = None
 
 
-def load_dataset(conf):
+def write_loadings(path, meta, w):
+    """The --loadings-output-path file: one line per variant in feed order -- 0-based index, contig, position, variant id, then
+    the loadings as Double.toString prints them, tab-separated.  meta: (contig, position, id) per row; an input that carries
+    none (.npz carriers, --synthetic) gets '.' in the three columns."""
+    if meta and len(meta) != w.shape[0]:
+        raise RuntimeError("--loadings-output-path: %d variant records for %d rows" % (len(meta), w.shape[0]))
+    with open(path, "w") as f:
+        for v in range(w.shape[0]):
+            contig, pos, vid = meta[v] if meta else (".", ".", ".")
+            f.write("%d\t%s\t%s\t%s\t%s\n" % (v, contig, pos, vid, "\t".join(java_double_to_string(x) for x in w[v])))
+
+
+def load_dataset(conf, variant_meta=None):
     """Local stand-in for VariantsCommon (VariantsCommon.scala:33-66): callset index/name maps +
-    the variant data.  Returns (indexes, names, [dataset])."""
+    the variant data.  Returns (indexes, names, [dataset]).  variant_meta: a list that receives (contig, position, id) of
+    every row of a carrier-only input (a single VCF or PLINK fileset) as it is read."""
     from . import ingest
     if conf.synthetic:
         return ingest.synthetic_dataset(conf.synthetic)
@@ -784,8 +846,8 @@ def load_dataset(conf):
         if paths[0].endswith(".npz"):
             return ingest.load_npz(paths[0])
         if paths[0][-4:] in (".bed", ".bim", ".fam"):
-            return ingest.load_plink(paths[0], refs, ref_allele=conf.plink_ref_allele, as_bed=True)
-        return ingest.load_vcf(paths[0], refs)
+            return ingest.load_plink(paths[0], refs, ref_allele=conf.plink_ref_allele, as_bed=True, variant_meta=variant_meta)
+        return ingest.load_vcf(paths[0], refs, variant_meta=variant_meta)
     # several variant sets (or the AF filter): full variant records are needed for keys and INFO/AF
     if any(p.endswith(".npz") or p[-4:] in (".bed", ".bim", ".fam") for p in paths):
         raise SystemExit("joining variant sets or filtering by allele frequency needs VCF inputs: a .npz dataset or a PLINK "
@@ -951,7 +1013,32 @@ def check_measure_conf(conf):
                          "--project-input-path" % m)
 
 
-def calls_as_bits(call_rdd, n):
+def check_loadings_conf(conf):
+    """--loadings-output-path: the identity B = (X J)^T (X J) behind the loadings holds for the shared counts of the whole
+    cohort on one engine; everything else is refused before any file is read or any device is touched."""
+    if not conf.loadings_output_path:
+        return
+    world = max(conf.gpus, int(os.environ.get("WORLD_SIZE", "1")))
+    if world > 1:
+        raise SystemExit("VariantsPcaDriver: --loadings-output-path streams the variants past one engine: it cannot take --gpus %d"
+                         % world)
+    if conf.layout == "strips":
+        raise SystemExit("VariantsPcaDriver: --loadings-output-path runs on one whole engine: it cannot take --layout strips")
+    if conf.project_input_path:
+        raise SystemExit("VariantsPcaDriver: --loadings-output-path writes the loadings of the cohort it decomposes: it cannot "
+                         "take --project-input-path")
+    if conf.outlier_iterations > 0:
+        raise SystemExit("VariantsPcaDriver: --loadings-output-path needs the eigenpairs of the cohort the variants were counted "
+                         "over: it cannot take --outlier-iterations %d" % conf.outlier_iterations)
+    if conf.remove_related:
+        raise SystemExit("VariantsPcaDriver: --loadings-output-path needs the eigenpairs of the cohort the variants were counted "
+                         "over: it cannot take --remove-related")
+    if conf.similarity_measure != "shared":
+        raise SystemExit("VariantsPcaDriver: --loadings-output-path: under --similarity-measure %s the decomposed matrix is no "
+                         "longer (X J)^T (X J); it takes --similarity-measure shared only" % conf.similarity_measure)
+
+
+def calls_as_bits(call_rdd, n, flag="--gram implicit", instead="--gram stored"):
     """--gram implicit: an RDD[Seq[Int]] in any of the forms getCallsRdd returns, as what an operator engine stores -- raw
     PLINK rows and bitsets as they are, carrier lists packed into bitsets.  A list that names a callset twice (a merge of sets
     with a repeated key; the reference counts it with multiplicity, VariantsPca.scala:187) cannot be a bitset: refused."""
@@ -969,8 +1056,8 @@ def calls_as_bits(call_rdd, n):
         raise IndexError("callset index outside [0, %d) in a carrier list" % n)   # mapping(call.callsetId) throws (:59)
     key = rows * n + idx
     if np.unique(key).size != key.size:
-        raise SystemExit("VariantsPcaDriver: --gram implicit: a carrier list names a callset twice; a carrier bitset cannot carry "
-                         "that multiplicity -- use --gram stored")
+        raise SystemExit("VariantsPcaDriver: %s: a carrier list names a callset twice; a carrier bitset cannot carry "
+                         "that multiplicity -- use %s" % (flag, instead))
     bits = np.zeros((n_rows, (n + 31) // 32), dtype=np.uint32)
     np.bitwise_or.at(bits, (rows, idx >> 5), (np.uint32(1) << (idx & 31).astype(np.uint32)))
     return ("bits", bits)
@@ -1060,6 +1147,7 @@ def main(args):
     check_related_conf(conf)
     check_measure_conf(conf)
     check_gram_conf(conf)
+    check_loadings_conf(conf)
     if conf.project_input_path:
         check_projection_conf(conf)
         return main_projection(conf)
@@ -1092,19 +1180,25 @@ def main(args):
         quiet = open(os.devnull, "w") if rank != 0 else None   # the reference's driver prints once
         if quiet is not None:
             sys.stdout = quiet
-    indexes, names, data = load_dataset(conf)
+    variant_meta = [] if conf.loadings_output_path else None   # (contig, position, id) per row, recorded only with the flag
+    indexes, names, data = load_dataset(conf, variant_meta)
     driver = VariantsPcaDriver(conf, indexes, names, data)
     filtered = [driver.filterDataset(d) for d in driver.data]
-    calls_rdd = driver.getCallsRdd(filtered)
+    calls_rdd = driver.getCallsRdd(filtered, variant_meta)
     n = len(driver.indexes)
     if conf.gram == "implicit":
         driver.engine = calculate_similarity_matrix(calls_as_bits(calls_rdd, n), n,
                                                     engine=PcoaEngine(n, device=conf.gpu, operator=True))
         result = driver.computePca(driver.engine)
         driver.emitResult(result)
+        if conf.loadings_output_path:
+            driver.emitLoadings(None, variant_meta)
         driver.reportIoStats(sys.stderr)
         driver.stop()
         return 0
+    loadings_rows = None
+    if conf.loadings_output_path:   # the second pass's rows, and the refusal of a repeated callset, before any device work
+        loadings_rows = calls_as_bits(calls_rdd, n, flag="--loadings-output-path", instead="carrier lists that are sets")
     if world > 1:
         import torch.distributed as td
         devices = [int(t) for t in conf.rank_devices.split(",")] if conf.rank_devices else list(range(world))
@@ -1119,6 +1213,8 @@ def main(args):
         raise SystemExit("VariantsPcaDriver: " + STRIPS_REFUSE_RELATED)
     if ranges is not None and conf.similarity_measure != "shared":
         raise SystemExit("VariantsPcaDriver: " + STRIPS_REFUSE_MEASURE % conf.similarity_measure)
+    if ranges is not None and conf.loadings_output_path:     # --layout auto resolved to strips
+        raise SystemExit("VariantsPcaDriver: --loadings-output-path runs on one whole engine: it cannot take --layout strips")
     if ranges is not None:
         owner = driver.getSimilarityMatrixStrip(calls_rdd, ranges[rank], local_rank if world > 1 else conf.gpu)
         if rank == 0:
@@ -1155,6 +1251,8 @@ def main(args):
             sim_matrix = driver.screenRelated(sim_matrix)
         result = driver.computePcaOutlierRounds(sim_matrix) if conf.outlier_iterations > 0 else driver.computePca(sim_matrix)
         driver.emitResult(result)
+        if conf.loadings_output_path:
+            driver.emitLoadings(loadings_rows, variant_meta)
         driver.reportIoStats(sys.stderr)
     if world > 1:
         import torch.distributed as td
