@@ -442,6 +442,65 @@ typedef struct pcoa_loadings_stats {
 } pcoa_loadings_stats;
 int pcoa_get_loadings_stats(pcoa_ctx* ctx, pcoa_loadings_stats* out, size_t out_size);
 
+/* ---- LD pruning of the variants in front of the accumulation ------------------------------------------------------------------
+ * The filter every PCA pipeline runs between the allele-frequency filter and the decomposition (PLINK --indep-pairwise,
+ * SNPRelate snpgdsLDpruning): a block of correlated variants is otherwise counted many times in S.  Variants arrive in feed order.
+ * With n = n_samples, a_v the carrier count of variant v and c_uv = popcount(row_u & row_v), both over samples < n:
+ *   D = n c_uv - a_u a_v,   p = a_u (n - a_u),   q = a_v (n - a_v)                      (int64)
+ *   exceeds(u, v)  <=>  (double)D * (double)D  >  r2_max * ((double)p * (double)q)          (three fp64 products, no sum)
+ * -- r^2 of the two carrier indicators (hasVariation), not of dosages.  The pass is forward and greedy:
+ *   a monomorphic variant (a_v = 0 or a_v = n) is removed;
+ *   a polymorphic variant v is kept iff no KEPT u with v - window <= u < v, behind the last break, has exceeds(u, v);
+ *   a variant that was itself removed blocks nobody.
+ * The result depends on the rows, window, r2_max and the breaks only: not on how the rows were split over calls, on where they
+ * came from (host, device, .bed), on the grid or on the CU count.  Integer kernels, no atomics (csrc/ld.hip).
+ *
+ * pcoa_ld_begin: 1 <= window <= PCOA_LD_MAX_WINDOW (in fed variants), 0 <= r2_max <= 1 (NaN refused), flags 0 or
+ *   PCOA_LD_ACCUMULATE.  Allocates the pruner's buffers (resident until pcoa_ld_end / pcoa_destroy); a second begin starts over.
+ *   Every kind of ctx serves.  After a refused begin an earlier pruner is as it was.
+ * pcoa_ld_bits: n_variants rows of carrier bitsets in pcoa_accumulate_bits' layout and pitch; bits of samples >= n_samples and the
+ *   words behind ceil(n_samples / 32) are IGNORED, whatever they hold.  bits: host (through the staging slots) or device.
+ *   keep_out: host, [n_variants], 1 = kept, may be NULL; n_kept_out: kept rows of THIS call, may be NULL.
+ * pcoa_ld_plink_bed: the same for raw .bed rows, decoded on the device by the rule of pcoa_accumulate_plink_bed into a buffer of
+ *   the pruner's own.  is_device_ptr: 0 or 1.
+ *   The last `window` rows, their counts and their keep flags stay on the device between calls, so a call shorter than the window
+ *   is as good as a long one.
+ * PCOA_LD_ACCUMULATE: the kept rows of a call are compacted on the device and handed to this ctx's own bitset accumulation as a
+ *   device input -- on a full engine, a strip owner or an operator ctx whatever pcoa_accumulate_bits does there (and refused, like
+ *   it, on a PCOA_FLAG_GRAM_F32_MFMA engine).  The compacted buffer is the pruner's; its only reader is the accumulation's pre-pass
+ *   on the ctx stream, and the kernels that rewrite it are queued on the same stream behind it.  Without the flag nothing is
+ *   accumulated (a dry run).
+ * pcoa_ld_break: a contig boundary: the carried rows are dropped, the parameters stay.
+ * pcoa_ld_end: releases everything (synchronising); a no-op without a begin.  pcoa_reset also drops the carried rows.
+ * pcoa_ld_bits / pcoa_ld_plink_bed are SYNCHRONISING on the ctx stream (the kept count of every chunk travels to the host).
+ * Errors: PCOA_ERR_STATE before pcoa_ld_begin; PCOA_ERR_INVALID_ARG for a NULL pointer, n_variants < 0, too small a pitch; the ctx
+ * and the carried rows stay usable after every error.
+ * Not built: windows in base pairs, dosage r^2, PLINK's MAF-ordered removal, windows across engines, the JNI natives.
+ * Extends: the filter stage in front of getCallsRdd / getSimilarityMatrix (VariantsPca.scala:96-108 has the AF filter only). */
+#define PCOA_LD_MAX_WINDOW 1024
+#define PCOA_LD_ACCUMULATE 1u
+int pcoa_ld_begin(pcoa_ctx* ctx, int32_t window, double r2_max, uint32_t flags);
+int pcoa_ld_bits(pcoa_ctx* ctx, const uint32_t* bits, int64_t n_variants, int64_t ld_words, int is_device_ptr,
+                 uint8_t* keep_out /* host, [n_variants], may be NULL */, int64_t* n_kept_out /* may be NULL */);
+int pcoa_ld_plink_bed(pcoa_ctx* ctx, const uint8_t* bed_rows, int64_t n_variants, int64_t row_bytes, int ref_is_a1,
+                      int is_device_ptr /* 0 or 1 */, uint8_t* keep_out, int64_t* n_kept_out);
+int pcoa_ld_break(pcoa_ctx* ctx);
+int pcoa_ld_end(pcoa_ctx* ctx);
+
+/* What the pruner did on THIS engine, cumulative since pcoa_create / pcoa_reset_timings.  It grows at its end; out_size = sizeof
+ * of the struct the caller compiled against.  Synchronising. */
+typedef struct pcoa_ld_stats {
+  int64_t ld_variants;          /* rows seen                                                                                 */
+  int64_t ld_kept;              /* rows kept                                                                                 */
+  int64_t ld_monomorphic;       /* rows removed because a_v = 0 or a_v = n                                                   */
+  int64_t ld_pairs;             /* (earlier row, row) pairs the band kernel evaluated: sum of min(window, rows before it)    */
+  double ld_count_seconds;      /* HIP-event time of the carrier-count kernel (it also writes the masked row)                */
+  double ld_band_seconds;       /* ... of the band kernel                                                                    */
+  double ld_resolve_seconds;    /* ... of the greedy pass                                                                    */
+  double ld_compact_seconds;    /* ... of the scan, the gather and the update of the carried rows                            */
+} pcoa_ld_stats;
+int pcoa_get_ld_stats(pcoa_ctx* ctx, pcoa_ld_stats* out, size_t out_size);
+
 /* ---- layout of S over the engines of one job ------------------------------------------------------------------------
  * FULL: every engine holds a whole N x N partial S (4 N^2 bytes) for its share of the variants; the partials are reduced
  * into engine 0 (peer copies: engine 0 stages one more 4 N^2 matrix when the engines sit on different devices, RCCL

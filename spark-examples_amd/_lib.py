@@ -123,6 +123,20 @@ class PcoaPairsStats(ctypes.Structure):
     ]
 
 
+class PcoaLdStats(ctypes.Structure):
+    """pcoa_ld_stats: what the LD pruner did, and the HIP-event time of each of its kernels."""
+    _fields_ = [
+        ("ld_variants", ctypes.c_int64),
+        ("ld_kept", ctypes.c_int64),
+        ("ld_monomorphic", ctypes.c_int64),
+        ("ld_pairs", ctypes.c_int64),
+        ("ld_count_seconds", ctypes.c_double),
+        ("ld_band_seconds", ctypes.c_double),
+        ("ld_resolve_seconds", ctypes.c_double),
+        ("ld_compact_seconds", ctypes.c_double),
+    ]
+
+
 class PcoaLoadingsStats(ctypes.Structure):
     """pcoa_loadings_stats: a struct of its own beside pcoa_timings, like pcoa_pairs_stats."""
     _fields_ = [
@@ -134,6 +148,8 @@ class PcoaLoadingsStats(ctypes.Structure):
 
 PCOA_LOADINGS_CENTRE = 1
 PCOA_LOADINGS_UNIT = 2
+PCOA_LD_MAX_WINDOW = 1024
+PCOA_LD_ACCUMULATE = 1
 
 
 class PcoaSynthParams(ctypes.Structure):
@@ -166,6 +182,12 @@ _SIGNATURES = [
     ("pcoa_loadings_operator", ctypes.c_int, [_vp, _i64, _i64, _vp, ctypes.c_int]),
     ("pcoa_loadings_end", ctypes.c_int, [_vp]),
     ("pcoa_get_loadings_stats", ctypes.c_int, [_vp, ctypes.POINTER(PcoaLoadingsStats), ctypes.c_size_t]),
+    ("pcoa_ld_begin", ctypes.c_int, [_vp, _i32, ctypes.c_double, ctypes.c_uint32]),
+    ("pcoa_ld_bits", ctypes.c_int, [_vp, _vp, _i64, _i64, ctypes.c_int, _vp, ctypes.POINTER(_i64)]),
+    ("pcoa_ld_plink_bed", ctypes.c_int, [_vp, _vp, _i64, _i64, ctypes.c_int, ctypes.c_int, _vp, ctypes.POINTER(_i64)]),
+    ("pcoa_ld_break", ctypes.c_int, [_vp]),
+    ("pcoa_ld_end", ctypes.c_int, [_vp]),
+    ("pcoa_get_ld_stats", ctypes.c_int, [_vp, ctypes.POINTER(PcoaLdStats), ctypes.c_size_t]),
     ("pcoa_operator_info", ctypes.c_int, [_vp, ctypes.POINTER(_i64), ctypes.POINTER(_i64)]),
     ("pcoa_operator_row_sums", ctypes.c_int, [_vp, _vp]),
     ("pcoa_operator_matvec_device", ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int]),

@@ -226,6 +226,7 @@ void pcoa_destroy(pcoa_ctx* c) {
     if (b) dev_free(b);
   operator_destroy(c);
   loadings_destroy(c);
+  ld_destroy(c);
   if (c->pack_stream) (void)hipStreamDestroy(c->pack_stream);
   if (c->gram_stream) (void)hipStreamDestroy(c->gram_stream);
   if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
@@ -290,6 +291,7 @@ int pcoa_reset(pcoa_ctx* c) {
   CHECK_CTX(c);
   int rc = fp4_discard(c);  // buffered or in-flight operands belong to the old S
   if (rc != PCOA_OK) return rc;
+  ld_drop_tail(c);   // an LD pruner starts a new window with the new S
   if (c->is_operator) return operator_reset(c);
   const size_t nn = s_count(c);
   HIP_TRY(c, hipMemsetAsync(c->s32, 0, sizeof(int32_t) * nn, c->stream));
@@ -410,6 +412,7 @@ int pcoa_reset_timings(pcoa_ctx* c) {
   c->subset_bytes = 0;
   c->pairs_bytes = c->pairs_calls = 0;
   c->ld_variants = c->ld_bytes = 0;
+  c->ldp_seen = c->ldp_kept = c->ldp_mono = c->ldp_pairs = 0;
   c->reduce_peers_calls = c->reduce_peers_bytes_in = 0;
   return PCOA_OK;
 }

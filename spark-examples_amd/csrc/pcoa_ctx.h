@@ -13,6 +13,7 @@
 //   capi_pairs.hip       pcoa_similar_pairs: the screen of S for duplicate and related sample pairs
 //   capi_measure.hip     pcoa_set_similarity / pcoa_get_similarity and the centring of a Jaccard / cosine measure
 //   capi_loadings.hip    pcoa_loadings_*: per-variant loadings of the principal coordinates from bitsets, .bed rows, the store
+//   capi_ld.hip          pcoa_ld_*: LD pruning of the variant rows in front of the accumulation
 //   pcoa_capi.hip        create / destroy, errors, timings
 #pragma once
 
@@ -21,7 +22,7 @@
 
 #include "pcoa_internal.h"
 
-enum TimeCat { T_GRAM = 0, T_DENSIFY, T_SYNTH, T_FINALIZE, T_CENTER, T_TRIDIAG, T_EIG, T_BACK, T_PACK, T_LANCZOS, T_ALLREDUCE, T_OPERATOR, T_SUBSET, T_REDUCE_PEERS, T_PAIRS, T_LOADINGS, T_NCAT };
+enum TimeCat { T_GRAM = 0, T_DENSIFY, T_SYNTH, T_FINALIZE, T_CENTER, T_TRIDIAG, T_EIG, T_BACK, T_PACK, T_LANCZOS, T_ALLREDUCE, T_OPERATOR, T_SUBSET, T_REDUCE_PEERS, T_PAIRS, T_LOADINGS, T_LD_COUNT, T_LD_BAND, T_LD_RESOLVE, T_LD_COMPACT, T_NCAT };
 
 struct EventPair {
   hipEvent_t a, b;
@@ -91,6 +92,27 @@ struct pcoa_ctx {
   double* ld_out = nullptr;        // one chunk of results on their way to a host `out` (lazy)
   int64_t ld_out_cap = 0;
   int64_t ld_variants = 0, ld_bytes = 0;   // rows the loadings kernels took, bytes of bitsets they read
+  // LD pruning (pcoa_ld_begin .. pcoa_ld_end, capi_ld.hip).  The work buffer holds the carried tail -- the last ldp_tail <=
+  // ldp_window rows, at rows [ldp_window - ldp_tail, ldp_window) -- in front of the rows of one chunk; every buffer is sized by
+  // pcoa_ld_begin and lives until pcoa_ld_end
+  bool ldp_active = false, ldp_accumulate = false;
+  int32_t ldp_window = 0, ldp_tail = 0;
+  double ldp_r2 = 0.0;
+  int64_t ldp_chunk = 0;           // rows of a chunk (the capacity behind the tail)
+  int64_t ldp_pos = 0;             // rows fed since the last break
+  uint32_t* ldp_wb = nullptr;      // [window + chunk][ceil(n / 32)] rows, tail bits cleared
+  int32_t* ldp_cnt = nullptr;      // [window + chunk] carrier counts
+  uint32_t* ldp_tmp = nullptr;     // [window] rows + [window] counts: the tail of a chunk shorter than the window on its way down
+  uint32_t* ldp_ex = nullptr;      // [chunk][ceil(window / 32)] band words
+  uint32_t* ldp_flags = nullptr;   // [64] keep flags of the resolve wave
+  uint32_t* ldp_kbits = nullptr;   // [chunk / 32 + 2] the chunk's keep flags as the resolve wave holds them
+  uint8_t* ldp_keep = nullptr;     // [chunk] the same as bytes
+  int32_t* ldp_scan = nullptr;     // [chunk] place among the kept rows
+  int64_t* ldp_out2 = nullptr;     // {kept, monomorphic} of a chunk
+  uint32_t* ldp_compact = nullptr; // [chunk][ceil(n / 32)] kept rows (PCOA_LD_ACCUMULATE)
+  uint32_t* ldp_bed = nullptr;     // decoded .bed rows of one chunk (lazy)
+  int64_t ldp_bed_cap = 0;
+  int64_t ldp_seen = 0, ldp_kept = 0, ldp_mono = 0, ldp_pairs = 0;
   int device = 0;
   uint32_t flags = 0;
   int num_cu = 256;
@@ -114,6 +136,7 @@ struct pcoa_ctx {
     int32_t flag, mmax, seen, nz;
     int64_t coll[2];
     double st[2];
+    int64_t ld[2];   // {kept, monomorphic} of an LD-pruning chunk
   };
   HostWords* hw = nullptr;
 
@@ -366,6 +389,10 @@ int64_t operator_store_bytes(const pcoa_ctx* c);
 
 // ---- capi_loadings.hip
 void loadings_destroy(pcoa_ctx* c);
+
+// ---- capi_ld.hip
+void ld_destroy(pcoa_ctx* c);   // every buffer of the pruner (the ctx stream is idle)
+void ld_drop_tail(pcoa_ctx* c); // the carried rows are forgotten (pcoa_ld_break, pcoa_reset)
 
 struct ScopedTimer {
   pcoa_ctx* c;

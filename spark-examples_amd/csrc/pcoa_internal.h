@@ -221,6 +221,24 @@ int loadings_chunk(int32_t remaining);
 hipError_t launch_loadings(const uint32_t* bits, int64_t nv, int64_t ld_words, int32_t n, const double* u, int64_t ustride, int32_t k,
                            const double* div, double* out, int32_t num_pc, hipStream_t stream);
 
+// ---- LD pruning (ld.hip): the kernels of pcoa_ld_* over the pruner's work buffer -- [window + C][ceil(n / 32)] dense rows, the
+// carried tail in front of the chunk's rows, and the carrier counts laid out the same way (wb_rows / cnt_rows: the chunk's
+// first row, wb / cnt: the buffer's).  tail: carried rows that exist (<= window); ex: [vc][ceil(window / 32)] band words, bit
+// d - 1 of a row set where the row at distance d exists and exceeds t; g0: rows fed since the last break; flags: 64 words; kbits:
+// [vc / 32 + 2] keep flags as the resolve wave holds them ----
+int32_t ld_band_tile_rows();     // target rows a band workgroup owns
+int32_t ld_band_chunk_words();   // words of the sample axis it stages at a time
+hipError_t launch_ld_count(const uint32_t* rows, int64_t ld, int64_t vc, int32_t n, uint32_t* wb_rows, int32_t* cnt_rows,
+                           hipStream_t stream);
+hipError_t launch_ld_band(const uint32_t* wb, const int32_t* cnt, int64_t vc, int32_t n, int32_t window, int32_t tail, double t,
+                          uint32_t* ex, hipStream_t stream);
+hipError_t launch_ld_resolve(const uint32_t* ex, const int32_t* cnt_rows, int64_t vc, int32_t n, int32_t window, int64_t g0,
+                             uint32_t* flags, uint32_t* kbits, hipStream_t stream);
+hipError_t launch_ld_scan(const uint32_t* kbits, int64_t g0, const int32_t* cnt_rows, int64_t vc, int32_t n, uint8_t* keep,
+                          int32_t* pos, int64_t* out2, hipStream_t stream);
+hipError_t launch_ld_gather(const uint32_t* wb_rows, const uint8_t* keep, const int32_t* pos, int64_t vc, int32_t n, uint32_t* out,
+                            hipStream_t stream);
+
 // ---- centring (center.hip) --------------------------------------------------------------------
 // s = s32 + (s64 ? s64 : 0).  row_sums[n] (fp64), stats[0] = matrix sum, stats[1] = matrix mean,
 // nz[0] = #rows with sum > 0.  b = centred matrix fp64 [n][n].

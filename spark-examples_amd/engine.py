@@ -525,6 +525,14 @@ class PcoaEngine(object):
         .operator stream rows past the resident vectors; .close() releases them."""
         return Loadings(self, components, eigenvalues, centre, unit)
 
+    # ------------------------------------------------------------------ LD pruning
+    def ld_pruner(self, window, r2_max, accumulate=True):
+        """LD pruning in front of the accumulation (pcoa_ld_begin): forward and greedy in feed order, a variant is removed when it
+        is monomorphic or when a KEPT variant among the `window` fed before it has r^2 of the carrier indicators above r2_max.
+        Returns an LdPruner (a context manager) whose .bits / .plink_bed take rows and return their keep mask; with accumulate
+        the kept rows also go into this engine's S (or store), without it the pass is a dry run."""
+        return LdPruner(self, window, r2_max, accumulate)
+
     # ------------------------------------------------------------------ computePca
     def center(self, want_matrix=True):
         """Row sums + double-centring (VariantsPca.scala:206-223).  Returns (B, row_sums, nonzero_rows, mean)."""
@@ -678,6 +686,85 @@ class Loadings(object):
         if self._open and getattr(self._eng, "_ctx", None):
             self._open = False
             self._eng._check(self._eng._lib.pcoa_loadings_end(self._eng._ctx))
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+class LdPruner(object):
+    """The pruner of one pcoa_ld_begin: the last `window` rows stay on the engine's GPU between calls, so rows may be fed in calls
+    of any size.  .bits / .plink_bed return the keep mask of their rows as a numpy bool array."""
+
+    def __init__(self, engine, window, r2_max, accumulate=True):
+        self._eng = engine
+        self._open = False
+        self.window, self.r2_max, self.accumulate = int(window), float(r2_max), bool(accumulate)
+        engine._check(engine._lib.pcoa_ld_begin(engine._ctx, self.window, self.r2_max, L.PCOA_LD_ACCUMULATE if accumulate else 0))
+        self._open = True
+
+    def _mask(self, rows):
+        keep = np.zeros(max(int(rows), 0), dtype=np.uint8)
+        return keep, (_ptr(keep) if keep.size else None), ctypes.c_int64(0)
+
+    def bits(self, bits, n_variants=None, ld_words=None):
+        """Rows of carrier bitsets in accumulate_bits' layout: numpy uint32 [V][W] (host) or a torch int32 CUDA tensor."""
+        e = self._eng
+        if hasattr(bits, "data_ptr") and getattr(bits, "is_cuda", False):
+            import torch  # plumbing only
+            assert bits.dtype == torch.int32 and bits.dim() == 2 and bits.stride(1) == 1
+            nv = int(bits.shape[0]) if n_variants is None else int(n_variants)
+            ldv = int(bits.stride(0)) if ld_words is None else int(ld_words)
+            keep, kptr, kept = self._mask(nv)
+            torch.cuda.current_stream(bits.device).synchronize()
+            e._check(e._lib.pcoa_ld_bits(e._ctx, ctypes.c_void_p(bits.data_ptr()), nv, ldv, 1, kptr, ctypes.byref(kept)))
+        else:
+            a = np.ascontiguousarray(bits, dtype=np.uint32)
+            if a.ndim != 2:
+                raise ValueError("bits must be 2-D [variants][words]")
+            nv = a.shape[0] if n_variants is None else int(n_variants)
+            ldv = a.shape[1] if ld_words is None else int(ld_words)
+            keep, kptr, kept = self._mask(nv)
+            e._check(e._lib.pcoa_ld_bits(e._ctx, _ptr(a), nv, ldv, 0, kptr, ctypes.byref(kept)))
+        self.last_kept = int(kept.value)
+        return keep.astype(bool)
+
+    def plink_bed(self, rows, ref_is_a1=False):
+        """Raw variant-major PLINK .bed rows: numpy uint8 [V][row_bytes] (host) or a torch uint8 CUDA tensor."""
+        e = self._eng
+        if hasattr(rows, "data_ptr") and getattr(rows, "is_cuda", False):
+            import torch  # plumbing only
+            assert rows.dtype == torch.uint8 and rows.dim() == 2 and rows.stride(1) == 1
+            keep, kptr, kept = self._mask(rows.shape[0])
+            torch.cuda.current_stream(rows.device).synchronize()
+            e._check(e._lib.pcoa_ld_plink_bed(e._ctx, ctypes.c_void_p(rows.data_ptr()), int(rows.shape[0]), int(rows.stride(0)),
+                                              int(bool(ref_is_a1)), 1, kptr, ctypes.byref(kept)))
+        else:
+            a = np.ascontiguousarray(rows, dtype=np.uint8)
+            if a.ndim != 2:
+                raise ValueError("rows must be [variants][row_bytes]")
+            keep, kptr, kept = self._mask(a.shape[0])
+            e._check(e._lib.pcoa_ld_plink_bed(e._ctx, _ptr(a), a.shape[0], a.shape[1], int(bool(ref_is_a1)), 0, kptr,
+                                              ctypes.byref(kept)))
+        self.last_kept = int(kept.value)
+        return keep.astype(bool)
+
+    def break_contig(self):
+        """A contig boundary: the next row starts a new window (pcoa_ld_break)."""
+        self._eng._check(self._eng._lib.pcoa_ld_break(self._eng._ctx))
+
+    def stats(self):
+        """pcoa_ld_stats of the engine: ld_variants, ld_kept, ld_monomorphic, ld_pairs and the seconds of each kernel."""
+        q = L.PcoaLdStats()
+        self._eng._check(self._eng._lib.pcoa_get_ld_stats(self._eng._ctx, ctypes.byref(q), ctypes.sizeof(q)))
+        return dict((f[0], getattr(q, f[0])) for f in L.PcoaLdStats._fields_)
+
+    def close(self):
+        if self._open and getattr(self._eng, "_ctx", None):
+            self._open = False
+            self._eng._check(self._eng._lib.pcoa_ld_end(self._eng._ctx))
 
     def __enter__(self):
         return self

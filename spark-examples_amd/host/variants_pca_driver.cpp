@@ -107,6 +107,10 @@ struct Conf {  // PcaConf / GenomicsConf (GenomicsConf.scala:31-101), same flag 
                                         // principal coordinates, w_c = X (J u_c) / sqrt(lambda_c) (pcoa_loadings_*), one line per variant in feed
                                         // order.  --gram implicit reads the resident store; a stored S takes a second streaming pass over a
                                         // single PLINK fileset
+  int ld_window = 0;                    // --ld-window W: LD pruning in front of the accumulation (pcoa_ld_*), W fed variants; 0 = off
+  double ld_r2 = 0.2;                   // --ld-r2 X: a variant is removed when a kept one inside the window has r^2 of the carrier indicators above X
+  bool ld_r2_given = false;
+  std::string ld_output_path;           // --ld-output-path FILE: one line per fed variant in feed order: index, contig, position, id, 1 (kept) or 0
   int32_t similarity_kind() const {
     return similarity_measure == "jaccard" ? PCOA_SIMILARITY_JACCARD : similarity_measure == "cosine" ? PCOA_SIMILARITY_COSINE : PCOA_SIMILARITY_SHARED;
   }
@@ -134,6 +138,10 @@ const char* kUsage =
     "                   one line per variant in feed order: index, contig, position, id, loadings; one engine, the whole\n"
     "                   cohort, --similarity-measure shared; --gram implicit for any input, a stored S for one streamed PLINK\n"
     "                   fileset)\n"
+    "                   --ld-window W [--ld-r2 X, default 0.2] [--ld-output-path FILE] (LD pruning on the device in front of the\n"
+    "                   accumulation: forward and greedy in feed order, a variant is removed when it is monomorphic or when a KEPT\n"
+    "                   variant among the W fed before it, on the same contig, has r^2 of the carrier indicators above X; FILE gets\n"
+    "                   one line per fed variant: index, contig, position, id, 1 or 0; one engine, one input set)\n"
     "  --project-input-path <file.vcf[.gz]> [more]\n"
     "                   place these samples onto the principal coordinates of the --input-path cohort instead of\n"
     "                   decomposing the union (one GPU, VCF inputs, full layout)\n";
@@ -240,6 +248,22 @@ Conf parse(int argc, char** argv) {
         die("--similarity-measure takes shared, jaccard or cosine, not '" + c.similarity_measure + "'");
     }
     else if (a == "--loadings-output-path") c.loadings_output_path = one(i);
+    else if (a == "--ld-window") {
+      const std::string v = one(i);
+      char* end = nullptr;
+      const long w = std::strtol(v.c_str(), &end, 10);
+      if (v.empty() || *end || w < 0 || w > PCOA_LD_MAX_WINDOW)
+        die("--ld-window takes a number of variants in [1, " + std::to_string(PCOA_LD_MAX_WINDOW) + "] (0: off), not '" + v + "'");
+      c.ld_window = (int)w;
+    }
+    else if (a == "--ld-r2") {
+      const std::string v = one(i);
+      char* end = nullptr;
+      c.ld_r2 = std::strtod(v.c_str(), &end);
+      if (v.empty() || *end || !(c.ld_r2 >= 0.0 && c.ld_r2 <= 1.0)) die("--ld-r2 takes a threshold in [0, 1], not '" + v + "'");
+      c.ld_r2_given = true;
+    }
+    else if (a == "--ld-output-path") c.ld_output_path = one(i);
     else if (a == "--parse-only") c.parse_only = true;
     else if (a == "--dump-similarity") c.dump_similarity = one(i);
     else if (a == "--ingest-threads") c.ingest_threads = std::atoi(one(i).c_str());
@@ -304,6 +328,24 @@ Conf parse(int argc, char** argv) {
       die("--loadings-output-path: under --similarity-measure " + c.similarity_measure +
           " the decomposed matrix is no longer (X J)^T (X J); it takes --similarity-measure shared only");
     if (c.parse_only) die("--loadings-output-path needs the decomposition: it cannot take --parse-only");
+  }
+  // --ld-window: the windows run over the variants in feed order on one engine: likewise
+  if (c.ld_window == 0) {
+    if (!c.ld_output_path.empty()) die("--ld-output-path needs --ld-window W (the pruning is off without it)");
+    if (c.ld_r2_given) die("--ld-r2 needs --ld-window W (the pruning is off without it)");
+  } else {
+    if (c.gpus > 1) die("--ld-window: variant shards would cut the windows: it cannot take --gpus " + std::to_string(c.gpus));
+    if (c.layout == "strips") die("--ld-window runs in front of one engine's accumulation: it cannot take --layout strips");
+    if (c.input_path.size() > 1)
+      die("--ld-window takes one input set: joined and merged sets reach the engine in hash-partition order, not in feed order");
+    if (!c.project_input_path.empty()) die("--ld-window prunes the cohort it decomposes: it cannot take --project-input-path");
+    if (c.carrier_format == "lists") die("--ld-window prunes carrier bitsets: it cannot take --carrier-format lists");
+    if (c.parse_only) die("--ld-window runs on the device: it cannot take --parse-only");
+    if (!c.loadings_output_path.empty() && c.gram == "implicit")
+      die("--loadings-output-path with --ld-window writes a line for every variant read, pruned or not, and the store of --gram implicit "
+          "holds the kept ones only: use a stored S over one streamed PLINK fileset");
+    c.carrier_format = "bits";
+    c.layout = "full";
   }
   if (c.gram == "implicit") {
     // one operator engine holds the carrier bitsets of every variant: what needs S, or several engines, is refused here,
@@ -389,6 +431,44 @@ std::string murmur3_128_hex(const std::string& data) {
 // indices with variation, in call order.
 struct VarMeta { std::string contig; long pos = 0; std::string id; };   // a line's first columns in the --loadings-output-path file
 bool g_want_meta = false;          // --loadings-output-path given: contig, position and id are recorded during ingest (only then)
+// --ld-window: every row on its way to the engine goes through the pruner (PCOA_LD_ACCUMULATE) instead of pcoa_accumulate_bits /
+// pcoa_accumulate_plink_bed, with a pcoa_ld_break wherever the contig of the next variant differs from the last one's
+struct LdFeed {
+  bool on = false;
+  const std::vector<VarMeta>* meta = nullptr;   // of every row fed so far and of the rows of the call being made, in feed order
+  std::vector<uint8_t> keep;                    // one flag per fed row
+  int64_t fed = 0;
+  std::string last_contig;
+  // rows [a, b) of a call share a contig: run(a, b, keep_out)
+  void rows_in(pcoa_ctx* ctx, int64_t rows, const std::function<void(int64_t, int64_t, uint8_t*)>& run) {
+    keep.resize((size_t)(fed + rows));
+    const bool known = meta && (int64_t)meta->size() >= fed + rows;
+    for (int64_t a = 0; a < rows;) {
+      int64_t b = rows;
+      if (known) {
+        const std::string& contig = (*meta)[(size_t)(fed + a)].contig;
+        for (b = a + 1; b < rows && (*meta)[(size_t)(fed + b)].contig == contig; ++b) {}
+        if (fed + a > 0 && contig != last_contig && pcoa_ld_break(ctx) != PCOA_OK) die(std::string("pcoa_ld_break: ") + pcoa_last_error(ctx));
+        last_contig = contig;
+      }
+      run(a, b, keep.data() + fed + a);
+      a = b;
+    }
+    fed += rows;
+  }
+  void bits(pcoa_ctx* ctx, const uint32_t* rows_ptr, int64_t rows, int64_t words) {
+    rows_in(ctx, rows, [&](int64_t a, int64_t b, uint8_t* out) {
+      if (pcoa_ld_bits(ctx, rows_ptr + a * words, b - a, words, 0, out, nullptr) != PCOA_OK) die(std::string("pcoa_ld_bits: ") + pcoa_last_error(ctx));
+    });
+  }
+  void bed(pcoa_ctx* ctx, const unsigned char* rows_ptr, int64_t rows, int64_t bpv, int ref_a1) {
+    rows_in(ctx, rows, [&](int64_t a, int64_t b, uint8_t* out) {
+      if (pcoa_ld_plink_bed(ctx, rows_ptr + a * bpv, b - a, bpv, ref_a1, 0, out, nullptr) != PCOA_OK)
+        die(std::string("pcoa_ld_plink_bed: ") + pcoa_last_error(ctx));
+    });
+  }
+};
+LdFeed g_ld;
 struct Variant {
   std::string key;                 // getVariantKey
   VarMeta meta;                    // (g_want_meta)
@@ -1045,11 +1125,14 @@ struct CarrierFeeder {
       std::thread packer;
       if (r1 < rows)
         packer = std::thread([&, r1, r2, k] { ok_next = pack(idx, offs, r1, r2, n, words, reinterpret_cast<uint32_t*>(pin[(k + 1) & 1]), threads > 1 ? threads - 1 : 1); });
+      if (!ok_cur && g_ld.on)
+        die("--ld-window: a carrier list names a callset twice; a carrier bitset cannot carry that multiplicity");
       if (!ok_cur && conf.gram == "implicit")
         die("--gram implicit: a carrier list names a callset twice (a merge of sets with a repeated key); a carrier bitset cannot "
             "carry that multiplicity -- use --gram stored");
       if (ok_cur) {
-        check(ctx, pcoa_accumulate_bits(ctx, reinterpret_cast<const uint32_t*>(pin[k & 1]), r1 - r0, words, 0), "getSimilarityMatrix");
+        if (g_ld.on) g_ld.bits(ctx, reinterpret_cast<const uint32_t*>(pin[k & 1]), r1 - r0, words);
+        else check(ctx, pcoa_accumulate_bits(ctx, reinterpret_cast<const uint32_t*>(pin[k & 1]), r1 - r0, words, 0), "getSimilarityMatrix");
         rows_as_bits += r1 - r0;
       } else {
         as_lists(r0, r1);
@@ -1164,7 +1247,8 @@ void stream_plink_shard(const Conf& conf, const PlinkMeta& m, int g, int k, pcoa
       }
       auto t1 = now();
       if (kept > 0) {
-        check(ctx, pcoa_accumulate_plink_bed(ctx, buf[w], kept, (int64_t)bpv, ref_a1 ? 1 : 0, PCOA_BED_HOST_ASYNC), "getSimilarityMatrix");
+        if (g_ld.on) g_ld.bed(ctx, buf[w], kept, (int64_t)bpv, ref_a1 ? 1 : 0);   // (synchronous: the rows are consumed when it returns)
+        else check(ctx, pcoa_accumulate_plink_bed(ctx, buf[w], kept, (int64_t)bpv, ref_a1 ? 1 : 0, PCOA_BED_HOST_ASYNC), "getSimilarityMatrix");
         total += kept;
       }
       feed_s += secs(t1, now());
@@ -1205,7 +1289,8 @@ void stream_plink_shard(const Conf& conf, const PlinkMeta& m, int g, int k, pcoa
             bed_row_to_bits(buf[which] + (size_t)r * bpv, bpv, m.n, ref_a1, bits.data() + (size_t)r * words, words);
         });
       for (auto& x : th) x.join();
-      check(ctx, pcoa_accumulate_bits(ctx, bits.data(), kept, (int64_t)words, 0), "getSimilarityMatrix");
+      if (g_ld.on) g_ld.bits(ctx, bits.data(), kept, (int64_t)words);
+      else check(ctx, pcoa_accumulate_bits(ctx, bits.data(), kept, (int64_t)words, 0), "getSimilarityMatrix");
       total += kept;
     }
     feed_s += secs(t1, now());
@@ -1440,7 +1525,9 @@ std::vector<int32_t> related_removal(const std::vector<pcoa_pair>& pairs, int32_
 int main(int argc, char** argv) {
   const auto t_start = std::chrono::steady_clock::now();
   Conf conf = parse(argc, argv);
-  g_want_meta = !conf.loadings_output_path.empty();
+  const bool want_loadings = !conf.loadings_output_path.empty();
+  g_ld.on = conf.ld_window > 0;
+  g_want_meta = want_loadings || g_ld.on;   // (--ld-window: the contigs place the breaks)
   if (conf.input_path.empty())
     die("--input-path <file.vcf[.gz]> [more files] or one PLINK fileset (<prefix>.bed) is required: the Google Genomics API the reference read "
         "from has been shut down");
@@ -1459,7 +1546,7 @@ int main(int argc, char** argv) {
   // stream_plink_shard block by block, each engine its own contiguous range of variants.
   const bool stream_plink = conf.input_path.size() == 1 && is_plink_path(conf.input_path[0]) && !conf.no_stream &&
                             !conf.parse_only && !conf.has_maf;
-  if (g_want_meta && conf.gram != "implicit" && !stream_plink)
+  if (want_loadings && conf.gram != "implicit" && !stream_plink)
     die("--loadings-output-path with a stored similarity matrix takes its second pass over ONE streamed PLINK fileset; for this "
         "input use --gram implicit, which keeps the rows resident");
   std::vector<VarMeta> fed_meta;   // --loadings-output-path: (contig, position, id) of every row fed, in feed order
@@ -1725,6 +1812,10 @@ int main(int argc, char** argv) {
   std::string how;
   double feed_s = 0, warmup_s = 0;
   auto prepare = [&](const std::vector<pcoa_ctx*>& engines) {
+    if (g_ld.on) {
+      g_ld.meta = stream_plink ? &plink.meta : &fed_meta;
+      check(engines[0], pcoa_ld_begin(engines[0], conf.ld_window, conf.ld_r2, PCOA_LD_ACCUMULATE), "pcoa_ld_begin");
+    }
     if (!stream_plink) return;
     for (int q = 0; q < 4 * conf.gpus; ++q) {
       void* b = nullptr;
@@ -1815,6 +1906,26 @@ int main(int argc, char** argv) {
   if (stream_plink) fed_meta = plink.meta;                 // one engine: every kept line, in file order
   if (stream_join || data.size() > 1) fed_meta_known = false;
   for (pcoa_ctx* o : owners) check(o, pcoa_gram_finalize(o), "getSimilarityMatrix");
+  if (g_ld.on) {
+    pcoa_ld_stats ls;
+    check(ctx, pcoa_get_ld_stats(ctx, &ls, sizeof(ls)), "pcoa_get_ld_stats");
+    check(ctx, pcoa_ld_end(ctx), "pcoa_ld_end");
+    std::printf("LD pruning: kept %lld of %lld variants (%lld monomorphic)\n", (long long)ls.ld_kept, (long long)ls.ld_variants,
+                (long long)ls.ld_monomorphic);
+    std::fprintf(stderr, "LD pruning: window %d, r2 %s; %lld pairs; count %.3f ms, band %.3f ms, resolve %.3f ms, compaction %.3f ms\n",
+                 conf.ld_window, java_double(conf.ld_r2).c_str(), (long long)ls.ld_pairs, 1e3 * ls.ld_count_seconds, 1e3 * ls.ld_band_seconds,
+                 1e3 * ls.ld_resolve_seconds, 1e3 * ls.ld_compact_seconds);
+    if (!conf.ld_output_path.empty()) {
+      const bool known = fed_meta_known && (int64_t)fed_meta.size() == g_ld.fed;
+      std::ofstream out(conf.ld_output_path);
+      for (int64_t v = 0; v < g_ld.fed; ++v) {
+        if (known) out << v << "\t" << fed_meta[(size_t)v].contig << "\t" << fed_meta[(size_t)v].pos << "\t" << fed_meta[(size_t)v].id;
+        else out << v << "\t.\t.\t.";
+        out << "\t" << (g_ld.keep[(size_t)v] ? 1 : 0) << "\n";
+      }
+      if (!out) die("cannot write " + conf.ld_output_path);
+    }
+  }
   {
     struct rusage ru;
     getrusage(RUSAGE_SELF, &ru);
@@ -1960,7 +2071,7 @@ int main(int argc, char** argv) {
   emit_result(conf, rows);
 
   // --loadings-output-path: w_c = X (J u_c) / sqrt(lambda_c) for every variant the engine was fed, from the eigenpairs above
-  if (g_want_meta) {
+  if (want_loadings) {
     std::vector<double> w;
     int64_t n_rows = 0;
     check(ctx, pcoa_loadings_begin(ctx, conf.num_pc, comps.data(), lam.data(), PCOA_LOADINGS_CENTRE | PCOA_LOADINGS_UNIT), "loadings");

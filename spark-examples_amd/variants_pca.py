@@ -478,6 +478,14 @@ class PcaConf(object):
                             "variant in feed order -- 0-based index, contig, position, variant id, then the loadings, "
                             "tab-separated.  One engine, --similarity-measure shared, the whole cohort: stored S takes a second "
                             "pass over the variants, --gram implicit reads the resident store")
+        p.add_argument("--ld-window", type=int, default=0,
+                       help="LD pruning on the device in front of the accumulation (pcoa_ld_*): forward and greedy in feed order, "
+                            "a variant is removed when it is monomorphic or when a KEPT variant among the W fed before it, on the "
+                            "same contig, has r^2 of the carrier indicators above --ld-r2.  0: off.  One engine, one input set")
+        p.add_argument("--ld-r2", type=float, default=None, help="the r^2 threshold of --ld-window, in [0, 1] (default 0.2)")
+        p.add_argument("--ld-output-path", type=str, default=None,
+                       help="--ld-window: one line per fed variant in feed order -- 0-based index, contig, position, variant id, "
+                            "1 (kept) or 0, tab-separated")
         a = p.parse_args(list(arguments))
         self.__dict__.update(vars(a))
         self.numPc = a.num_pc
@@ -1013,6 +1021,77 @@ def check_measure_conf(conf):
                          "--project-input-path" % m)
 
 
+LD_MAX_WINDOW = 1024   # PCOA_LD_MAX_WINDOW
+LD_DEFAULT_R2 = 0.2
+
+
+def check_ld_conf(conf):
+    """--ld-window: the windows run over the variants in feed order in front of one engine; everything else is refused before
+    any file is read or any device is touched."""
+    if conf.ld_window == 0:
+        if conf.ld_output_path:
+            raise SystemExit("VariantsPcaDriver: --ld-output-path needs --ld-window W (the pruning is off without it)")
+        if conf.ld_r2 is not None:
+            raise SystemExit("VariantsPcaDriver: --ld-r2 needs --ld-window W (the pruning is off without it)")
+        return
+    if not 1 <= conf.ld_window <= LD_MAX_WINDOW:
+        raise SystemExit("VariantsPcaDriver: --ld-window takes a number of variants in [1, %d] (0: off), not '%d'"
+                         % (LD_MAX_WINDOW, conf.ld_window))
+    if conf.ld_r2 is None:
+        conf.ld_r2 = LD_DEFAULT_R2
+    if not 0.0 <= conf.ld_r2 <= 1.0:      # (NaN fails both comparisons)
+        raise SystemExit("VariantsPcaDriver: --ld-r2 takes a threshold in [0, 1], not '%s'" % conf.ld_r2)
+    world = max(conf.gpus, int(os.environ.get("WORLD_SIZE", "1")))
+    if world > 1:
+        raise SystemExit("VariantsPcaDriver: --ld-window: variant shards would cut the windows: it cannot take --gpus %d" % world)
+    if conf.layout == "strips":
+        raise SystemExit("VariantsPcaDriver: --ld-window runs in front of one engine's accumulation: it cannot take --layout strips")
+    paths = conf.inputPath if isinstance(conf.inputPath, (list, tuple)) else [conf.inputPath]
+    if len(paths) > 1:
+        raise SystemExit("VariantsPcaDriver: --ld-window takes one input set: joined and merged sets reach the engine in "
+                         "hash-partition order, not in feed order")
+    if conf.project_input_path:
+        raise SystemExit("VariantsPcaDriver: --ld-window prunes the cohort it decomposes: it cannot take --project-input-path")
+
+
+def ld_accumulate(engine, rows, meta, window, r2_max):
+    """--ld-window: the rows of calls_as_bits through the pruner with PCOA_LD_ACCUMULATE, a break wherever the contig of the next
+    variant differs from the last one's (meta: (contig, position, id) per row, or none).  Returns (keep mask, pruner stats)."""
+    if rows[0] == "bed":
+        _, geno, ref_keep, ref_is_a1 = rows
+        at = np.flatnonzero(ref_keep)
+        total = int(at.size)
+        block = lambda a, b: np.ascontiguousarray(geno[at[a:b]])
+    else:
+        bits = rows[1]
+        total = int(bits.shape[0])
+        block = lambda a, b: bits[a:b]
+    contigs = [m[0] for m in meta] if meta and len(meta) == total else None
+    edges = [0] + ([v for v in range(1, total) if contigs[v] != contigs[v - 1]] if contigs else []) + [total]
+    parts = []
+    with engine.ld_pruner(window, r2_max, accumulate=True) as pr:
+        for k, (s, e) in enumerate(zip(edges[:-1], edges[1:])):
+            if k > 0:
+                pr.break_contig()
+            for a in range(s, e, PLINK_BLOCK_ROWS):
+                b = min(e, a + PLINK_BLOCK_ROWS)
+                parts.append(pr.plink_bed(block(a, b), ref_is_a1=ref_is_a1) if rows[0] == "bed" else pr.bits(block(a, b)))
+        stats = pr.stats()
+    engine.finalize()
+    return (np.concatenate(parts) if parts else np.zeros(0, dtype=bool)), stats
+
+
+def write_ld_mask(path, meta, keep):
+    """The --ld-output-path file: one line per fed variant in feed order -- 0-based index, contig, position, variant id (as
+    --loadings-output-path records them; '.' where the input carries none), 1 (kept) or 0, tab-separated."""
+    if meta and len(meta) != len(keep):
+        raise RuntimeError("--ld-output-path: %d variant records for %d rows" % (len(meta), len(keep)))
+    with open(path, "w") as f:
+        for v in range(len(keep)):
+            contig, pos, vid = meta[v] if meta else (".", ".", ".")
+            f.write("%d\t%s\t%s\t%s\t%d\n" % (v, contig, pos, vid, 1 if keep[v] else 0))
+
+
 def check_loadings_conf(conf):
     """--loadings-output-path: the identity B = (X J)^T (X J) behind the loadings holds for the shared counts of the whole
     cohort on one engine; everything else is refused before any file is read or any device is touched."""
@@ -1148,6 +1227,7 @@ def main(args):
     check_measure_conf(conf)
     check_gram_conf(conf)
     check_loadings_conf(conf)
+    check_ld_conf(conf)
     if conf.project_input_path:
         check_projection_conf(conf)
         return main_projection(conf)
@@ -1180,19 +1260,34 @@ def main(args):
         quiet = open(os.devnull, "w") if rank != 0 else None   # the reference's driver prints once
         if quiet is not None:
             sys.stdout = quiet
-    variant_meta = [] if conf.loadings_output_path else None   # (contig, position, id) per row, recorded only with the flag
+    # (contig, position, id) per row, recorded only with a flag that needs them (--ld-window: the contigs place the breaks)
+    variant_meta = [] if conf.loadings_output_path or conf.ld_window else None
     indexes, names, data = load_dataset(conf, variant_meta)
     driver = VariantsPcaDriver(conf, indexes, names, data)
     filtered = [driver.filterDataset(d) for d in driver.data]
     calls_rdd = driver.getCallsRdd(filtered, variant_meta)
     n = len(driver.indexes)
+    ld_rows = None
+    if conf.ld_window:   # the pruner's rows, and the refusal of a repeated callset, before any device work
+        ld_rows = calls_as_bits(calls_rdd, n, flag="--ld-window", instead="carrier lists that are sets")
+
+    def ld_ingest(engine):
+        keep, st = ld_accumulate(engine, ld_rows, variant_meta, conf.ld_window, conf.ld_r2)
+        print("LD pruning: kept %d of %d variants (%d monomorphic)" % (st["ld_kept"], st["ld_variants"], st["ld_monomorphic"]))
+        if conf.ld_output_path:
+            write_ld_mask(conf.ld_output_path, variant_meta, keep)
+        return engine
+
     if conf.gram == "implicit":
-        driver.engine = calculate_similarity_matrix(calls_as_bits(calls_rdd, n), n,
-                                                    engine=PcoaEngine(n, device=conf.gpu, operator=True))
+        if conf.ld_window:
+            driver.engine = ld_ingest(PcoaEngine(n, device=conf.gpu, operator=True))
+        else:
+            driver.engine = calculate_similarity_matrix(calls_as_bits(calls_rdd, n), n,
+                                                        engine=PcoaEngine(n, device=conf.gpu, operator=True))
         result = driver.computePca(driver.engine)
         driver.emitResult(result)
-        if conf.loadings_output_path:
-            driver.emitLoadings(None, variant_meta)
+        if conf.loadings_output_path:   # (--ld-window: every variant read gets its line, so the rows are streamed again)
+            driver.emitLoadings(ld_rows, variant_meta)
         driver.reportIoStats(sys.stderr)
         driver.stop()
         return 0
@@ -1213,6 +1308,8 @@ def main(args):
         raise SystemExit("VariantsPcaDriver: " + STRIPS_REFUSE_RELATED)
     if ranges is not None and conf.similarity_measure != "shared":
         raise SystemExit("VariantsPcaDriver: " + STRIPS_REFUSE_MEASURE % conf.similarity_measure)
+    if ranges is not None and conf.ld_window:
+        raise SystemExit("VariantsPcaDriver: --ld-window runs in front of one engine's accumulation: it cannot take --layout strips")
     if ranges is not None and conf.loadings_output_path:     # --layout auto resolved to strips
         raise SystemExit("VariantsPcaDriver: --loadings-output-path runs on one whole engine: it cannot take --layout strips")
     if ranges is not None:
@@ -1240,6 +1337,8 @@ def main(args):
             sys.stderr.write("Reduced over %d ranks (RCCL communicator: %s ranks): all-reduce %.3f ms; per-rank accumulate "
                              "%.3f .. %.3f s\n" % (world, tele["rccl_ranks"], tele["allreduce_ms"], tele["rank_elapsed_min_s"],
                                                    tele["rank_elapsed_max_s"]))
+    elif conf.ld_window:
+        sim_matrix = driver.engine = ld_ingest(PcoaEngine(n, device=conf.gpu))
     else:
         sim_matrix = driver.getSimilarityMatrix(calls_rdd)
     if rank == 0:
