@@ -384,6 +384,55 @@ int pcoa_get_pairs_stats(pcoa_ctx* ctx, pcoa_pairs_stats* out, size_t out_size);
 int pcoa_set_similarity(pcoa_ctx* ctx, int32_t kind);
 int pcoa_get_similarity(const pcoa_ctx* ctx, int32_t* kind_out);
 
+/* ---- the pairwise-complete similarity: S normalised by the jointly called variants ------------------------------------------
+ * "A missing call carries nothing": a PLINK .bed code 01 is decoded as a non-carrier, so a sample with 20 % missing genotypes
+ * has a uniformly smaller row of S, and after centring a leading axis tracks call rate instead of ancestry.  The remedy every
+ * GRM / IBS tool applies: divide each pair's shared count by the number of variants at which BOTH samples were called.  With
+ * s = S(i, j) the TOTAL entry of this ctx (the int32 matrix plus the int64 part where there is one), Q the finalized S of a
+ * second ordinary engine -- the COMPANION, fed the bitsets of the missing calls -- and V the number of variants fed:
+ *   c_i     = V - Q(i, i)                       (int64; the variants at which sample i is called)
+ *   M(i, j) = c_i + c_j - V + Q(i, j)           (int64; both called)
+ *   K(i, j) = M > 0 ? (double)s / (double)M : 0.0                          one IEEE fp64 division, no contraction
+ *   centring  r_i = sum_j K(i, j);  mm = (sum_i r_i) / N / N;  B(i, j) = ((K(i, j) - r_i / N) - r_j / N) + mm
+ * -- variants_pca.call_complete_measure / centred_measure are the numpy statement; nonzero_rows = #{r_i > 0}.  K is never in
+ * memory: the mat-vecs, the row sums and the centring evaluate it per entry from the two integer matrices (csrc/complete.hip).
+ * Unlike Jaccard and cosine this K is NOT positive semi-definite in general (on the test cohorts the most negative eigenvalue of
+ * B is about 1 % of lambda_1); pcoa_compute selects by |lambda| as it always has.
+ *
+ * pcoa_set_call_companion: binds `missing` as ctx's companion with V = n_variants; missing == NULL unbinds.  From then on
+ *   pcoa_compute, pcoa_center_read_f64 and pcoa_debug_centred_matvec (forms 0, 1, 2 with the preconditions they have) use the
+ *   rule.  Like the measure it is a property of how the ctx DECOMPOSES, not of how it accumulates: it may be set at any time and
+ *   survives pcoa_reset; the caller binds again when V changes.  At each centring the companion is finalized and its input
+ *   checks are read; an error of the companion is reported on ctx and says where it came from.  With no companion bound every
+ *   call returns the bits it returned before.  pcoa_similar_pairs, pcoa_gram_* and the reductions never look at the binding.
+ *   Refused before any device work, the ctx stays usable:
+ *     PCOA_ERR_INVALID_ARG  ctx NULL (on pcoa_last_error(NULL)), missing == ctx, differing N, n_variants < 0
+ *     PCOA_ERR_STATE        either ctx is a strip owner or an operator ctx; the two are on different devices; the companion
+ *                           itself has a companion; ctx has a Jaccard / cosine measure set (and pcoa_set_similarity(JACCARD |
+ *                           COSINE) on a bound ctx is refused the same way: the combination is not built)
+ *   At centring time: a companion with an int64 part: PCOA_ERR_STATE (not built; ctx's own int64 part IS supported, in the row
+ *   form); Q(i, i) > V for some i: PCOA_ERR_INVALID_ARG ("n_variants is smaller than a sample's missing count").
+ *   pcoa_project with a bound ref: PCOA_ERR_STATE (not built).
+ *   pcoa_create_subset(src) with src bound: the result gets a companion of its own, Q[keep, keep] with the same V, gathered by
+ *   the same kernel, OWNED by the result and destroyed with it (or when the result is bound again or unbound).
+ *   Destroying a caller-owned companion that is still bound is the caller's error: unbind first.
+ *   memory: N int64, allocated by the first centring under a binding.
+ * pcoa_get_call_companion: *missing_out = the companion bound (NULL: none), *n_variants_out = its V (0: none); either may be NULL.
+ *
+ * pcoa_accumulate_plink_bed_calls: pcoa_accumulate_plink_bed -- the same arguments, chunking, staging slots, lifetime rules and
+ *   PCOA_BED_HOST_ASYNC behaviour -- feeding TWO engines from one read of the rows: host rows cross the link once, one decode
+ *   kernel reads each raw row once and writes the carrier bitsets (bit for bit those of pcoa_accumulate_plink_bed) into ctx and
+ *   the missing bitsets (code 01, samples >= N masked) into `missing`.  The order between the two engines' streams is kept by
+ *   events; there is no host wait beyond the existing call's.  `missing` must be an ordinary packed-operand full engine on
+ *   ctx's device with ctx's N (else PCOA_ERR_INVALID_ARG); it need not be bound.  Callers that hold bitsets already feed the
+ *   companion through pcoa_accumulate_bits.
+ * Extends: hasVariation (VariantsPca.scala:56-60), for which a missing call is a non-carrier, and computePca
+ * (VariantsPca.scala:198-231), which centres and decomposes the shared counts only, by the pairwise-complete normalisation. */
+int pcoa_set_call_companion(pcoa_ctx* ctx, pcoa_ctx* missing, int64_t n_variants);
+int pcoa_get_call_companion(const pcoa_ctx* ctx, pcoa_ctx** missing_out, int64_t* n_variants_out);
+int pcoa_accumulate_plink_bed_calls(pcoa_ctx* ctx, pcoa_ctx* missing, const uint8_t* bed_rows, int64_t n_variants,
+                                    int64_t row_bytes, int ref_is_a1, int is_device_ptr);
+
 /* ---- per-variant loadings of the principal coordinates ---------------------------------------------------------------------
  * Which variants drive each axis (smartpca's SNP weights, PLINK 2's --pca var-wts).  With X the V x N carrier bit matrix and
  * J = I - 11^T / N, the decomposed matrix is B = J S J = (X J)^T (X J), so an eigenpair (u_c, lambda_c) of B is a right singular

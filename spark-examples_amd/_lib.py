@@ -176,6 +176,9 @@ _SIGNATURES = [
     ("pcoa_get_pairs_stats", ctypes.c_int, [_vp, ctypes.POINTER(PcoaPairsStats), ctypes.c_size_t]),
     ("pcoa_set_similarity", ctypes.c_int, [_vp, _i32]),
     ("pcoa_get_similarity", ctypes.c_int, [_vp, ctypes.POINTER(_i32)]),
+    ("pcoa_set_call_companion", ctypes.c_int, [_vp, _vp, _i64]),
+    ("pcoa_get_call_companion", ctypes.c_int, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(_i64)]),
+    ("pcoa_accumulate_plink_bed_calls", ctypes.c_int, [_vp, _vp, _vp, _i64, _i64, ctypes.c_int, ctypes.c_int]),
     ("pcoa_loadings_begin", ctypes.c_int, [_vp, _i32, _vp, _vp, ctypes.c_uint32]),
     ("pcoa_loadings_bits", ctypes.c_int, [_vp, _vp, _i64, _i64, ctypes.c_int, _vp, ctypes.c_int]),
     ("pcoa_loadings_plink_bed", ctypes.c_int, [_vp, _vp, _i64, _i64, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int]),

@@ -157,7 +157,7 @@ int pcoa_center_read_f64(pcoa_ctx* c, double* out_b, double* out_row_sums, int32
   const size_t n = (size_t)c->n;
   {
     ScopedTimer t(c, T_CENTER);
-    if (c->similarity != PCOA_SIMILARITY_SHARED) {   // the measure's row sums, mean, non-zero rows and B (capi_measure.hip)
+    if (measured(c)) {   // the measure's row sums, mean, non-zero rows and B (capi_measure.hip, capi_complete.hip)
       if ((rc = measure_centre(c, false, out_b ? c->ws.a : nullptr)) != PCOA_OK) return rc;
     } else {
       HIP_TRY(c, launch_center(c->s32, c->s64, c->n, c->row_sums, c->stats, c->nz, out_b ? c->ws.a : nullptr,
@@ -219,7 +219,7 @@ int pcoa_compute(pcoa_ctx* c, int32_t num_pc, double* out_components, double* ou
   const int sym_min = debug_knobs().symv_sym_min_n > 0 ? debug_knobs().symv_sym_min_n : 16384;
   const bool sym_form = !explicit_b && !c->s64 && n >= sym_min && (n & 3) == 0;
   if (sym_form && (rc = ensure(c, &c->sym_part, &c->sym_part_cap, (int64_t)symv_sym_workspace_doubles(n))) != PCOA_OK) return rc;
-  const bool measured = c->similarity != PCOA_SIMILARITY_SHARED;   // Jaccard / cosine: the centring and the mat-vecs of measure.hip
+  const bool measured = pcoa::measured(c);   // Jaccard / cosine, or a call companion: the centring and the mat-vecs of measure.hip / complete.hip
   {
     ScopedTimer t(c, T_CENTER);
     if (measured) {
@@ -461,6 +461,9 @@ int pcoa_project(pcoa_ctx* ref, pcoa_ctx* cross, int32_t num_pc, const double* c
   if (ref->similarity != PCOA_SIMILARITY_SHARED)
     return fail(ref, PCOA_ERR_STATE, "project: ref decomposes a Jaccard / cosine measure (pcoa_set_similarity); projection under a "
                                      "measure is not built");
+  if (ref->companion)
+    return fail(ref, PCOA_ERR_STATE, "project: ref has a call companion bound (pcoa_set_call_companion); projection under the "
+                                     "pairwise-complete similarity is not built");
   const int32_t n_ref = ref->n, cols = cross->s_cols;
   if (cross->n < n_ref)
     return fail(ref, PCOA_ERR_INVALID_ARG, "project: cross has N = " + std::to_string(cross->n) + " rows, fewer than ref's " +
@@ -793,14 +796,14 @@ int pcoa_debug_centred_matvec(pcoa_ctx* c, const double* x, double* y, int form)
     if ((rc = ensure(c, &c->sym_part, &c->sym_part_cap, (int64_t)symv_sym_workspace_doubles(n))) != PCOA_OK) return rc;
     wl.sym_part = c->sym_part;
     // the large-N form of computePca's first pass as well: row sums from the upper-triangular tiles
-    if (c->similarity == PCOA_SIMILARITY_SHARED)
+    if (!measured(c))
       HIP_TRY(c, launch_row_sums_sym(c->s32, n, c->sym_part, c->row_sums, reinterpret_cast<int64_t*>(c->stats + 2), c->stream));
   }
   if (form == 2) {
     if ((rc = ensure_b(c)) != PCOA_OK) return rc;
     wl.a = c->ws.a;
   }
-  if (c->similarity != PCOA_SIMILARITY_SHARED) {   // the measure's centring, by the same forms (capi_measure.hip)
+  if (measured(c)) {   // the measure's centring, by the same forms (capi_measure.hip, capi_complete.hip)
     if ((rc = measure_centre(c, upper_triangle_form, wl.a)) != PCOA_OK) return rc;
     measure_bind(c, &wl);
   } else {

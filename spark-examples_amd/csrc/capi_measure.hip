@@ -11,18 +11,21 @@ using namespace pcoa;
 namespace pcoa {
 
 void measure_bind(const pcoa_ctx* c, EigWorkspace* ws) {
+  if (c->companion) return complete_bind(c, ws);
   ws->measure = c->similarity;
   ws->diag = c->measure_diag;
   ws->qcos = c->measure_q;
 }
 
 int measure_b(pcoa_ctx* c, double* b) {
+  if (c->companion) return complete_b(c, b);
   HIP_TRY(c, launch_measure_center(c->s32, c->s64, c->n, c->similarity, c->measure_diag, c->measure_q, c->colmean, c->stats, b,
                                    c->stream));
   return PCOA_OK;
 }
 
 int measure_centre(pcoa_ctx* c, bool sym_form, double* b) {
+  if (c->companion) return complete_centre(c, sym_form, b);
   const int32_t n = c->n;
   if (!c->measure_diag) HIP_TRY(c, dev_alloc((void**)&c->measure_diag, sizeof(int64_t) * (size_t)n, c->device));
   if (c->similarity == PCOA_SIMILARITY_COSINE && !c->measure_q)
@@ -55,6 +58,9 @@ int pcoa_set_similarity(pcoa_ctx* c, int32_t kind) {
     if (c->is_strip)
       return fail(c, PCOA_ERR_STATE, "pcoa_set_similarity: a strip owner holds N x cols of S, not the diagonal of every sample: a "
                                      "measure over strips is not built; use a full engine (pcoa_create)");
+    if (c->companion)
+      return fail(c, PCOA_ERR_STATE, "pcoa_set_similarity: a call companion is bound (pcoa_set_call_companion): a Jaccard / cosine "
+                                     "measure of the pairwise-complete similarity is not built; unbind the companion first");
   }
   c->similarity = kind;
   return PCOA_OK;

@@ -82,6 +82,15 @@ int pcoa_create_subset(pcoa_ctx** out, pcoa_ctx* src, const int32_t* keep, int32
     if (rc == PCOA_OK && (e = hipStreamSynchronize(sub->stream)) != hipSuccess) rc = hip_fail(sub, e, "hipStreamSynchronize");
     if (rc != PCOA_OK) return bail(rc, sub->last_error);
   }
+  if (src->companion) {
+    // a bound src: the result gets a companion of its own, Q[keep, keep] by the same gather, with the same V; the result owns it
+    pcoa_ctx* subq = nullptr;
+    rc = pcoa_create_subset(&subq, src->companion, keep, n_keep);
+    if (rc != PCOA_OK) return bail(rc, "the call companion: " + src->companion->last_error);
+    sub->companion = subq;
+    sub->companion_v = src->companion_v;
+    sub->companion_owned = true;
+  }
   (void)hipSetDevice(src->device);
   *out = sub;
   return PCOA_OK;

@@ -456,6 +456,8 @@ void launch_symv(const EigWorkspace& ws, int n, const double* x, double* y, hipS
     hipLaunchKernelGGL(symv_kernel, dim3(rows4), dim3(256), 0, stream, ws.a, n, x, y);
   } else if (ws.measure != PCOA_SIMILARITY_SHARED) {   // Jaccard / cosine: the kernels of measure.hip (a host-side branch)
     (void)launch_measure_symv(ws, n, x, y, stream);
+  } else if (ws.comp_q32) {   // a call companion is bound: the kernels of complete.hip (a host-side branch)
+    (void)launch_complete_symv(ws, n, x, y, stream);
   } else if (ws.s64) {
     hipLaunchKernelGGL(symv_centered_kernel<true>, dim3(rows4), dim3(256), 0, stream, ws.s32, ws.s64, n, ws.colmean,
                        ws.stats, x, y);

@@ -227,6 +227,7 @@ void pcoa_destroy(pcoa_ctx* c) {
   operator_destroy(c);
   loadings_destroy(c);
   ld_destroy(c);
+  complete_destroy(c);
   if (c->pack_stream) (void)hipStreamDestroy(c->pack_stream);
   if (c->gram_stream) (void)hipStreamDestroy(c->gram_stream);
   if (c->own_stream) (void)hipStreamDestroy(c->own_stream);

@@ -14,6 +14,7 @@
 //   capi_measure.hip     pcoa_set_similarity / pcoa_get_similarity and the centring of a Jaccard / cosine measure
 //   capi_loadings.hip    pcoa_loadings_*: per-variant loadings of the principal coordinates from bitsets, .bed rows, the store
 //   capi_ld.hip          pcoa_ld_*: LD pruning of the variant rows in front of the accumulation
+//   capi_complete.hip    pcoa_set_call_companion / pcoa_accumulate_plink_bed_calls: the pairwise-complete similarity
 //   pcoa_capi.hip        create / destroy, errors, timings
 #pragma once
 
@@ -137,6 +138,7 @@ struct pcoa_ctx {
     int64_t coll[2];
     double st[2];
     int64_t ld[2];   // {kept, monomorphic} of an LD-pruning chunk
+    int32_t cflag;   // complete_diag_kernel's flag: some Q(i, i) > V
   };
   HostWords* hw = nullptr;
 
@@ -245,6 +247,19 @@ struct pcoa_ctx {
   int32_t similarity = 0;
   int64_t* measure_diag = nullptr;   // [n] (lazy)
   double* measure_q = nullptr;       // [n] (lazy)
+  // pcoa_set_call_companion (capi_complete.hip): the engine that holds Q, the Gram matrix of the missing-call bitsets, and V.
+  // Like the measure a property of how the ctx decomposes: it survives pcoa_reset; a subset gets a companion of its own
+  // (Q[keep, keep]), which it owns and destroys.
+  pcoa_ctx* companion = nullptr;
+  int64_t companion_v = 0;
+  bool companion_owned = false;
+  int64_t* complete_c = nullptr;     // [n] c_i = V - Q(i, i), then the diagonal kernel's flag word (lazy)
+  // pcoa_accumulate_plink_bed_calls: the missing-call rows of one chunk (the carrier rows go to `tile`), and the two events
+  // that order this ctx's stream and the companion's around that buffer
+  uint32_t* calls_bits = nullptr;
+  int64_t calls_bits_cap = 0;
+  hipEvent_t calls_decoded = nullptr, calls_read = nullptr;
+  bool calls_read_pending = false;   // the companion's pre-pass of the last chunk may still be reading calls_bits
 
   // timings
   std::vector<EventPair> pending;
@@ -378,6 +393,15 @@ int lanczos_over(pcoa_ctx* c, int32_t num_pc, const LanczosMatvec& mv, double* o
 int measure_centre(pcoa_ctx* c, bool sym_form, double* b);
 int measure_b(pcoa_ctx* c, double* b);
 void measure_bind(const pcoa_ctx* c, EigWorkspace* ws);   // ws->measure / diag / q from c
+// a Jaccard / cosine measure is set or a call companion is bound: the three functions above serve both (a bound ctx goes to
+// capi_complete.hip through them), the centring and the mat-vecs are not the shared count's
+inline bool measured(const pcoa_ctx* c) { return c->similarity != PCOA_SIMILARITY_SHARED || c->companion != nullptr; }
+
+// ---- capi_complete.hip: the same three for a ctx with a call companion (c->companion != nullptr)
+int complete_centre(pcoa_ctx* c, bool sym_form, double* b);
+int complete_b(pcoa_ctx* c, double* b);
+void complete_bind(const pcoa_ctx* c, EigWorkspace* ws);
+void complete_destroy(pcoa_ctx* c);   // the buffers, the events and an owned companion
 
 // ---- capi_operator.hip
 int operator_append(pcoa_ctx* c, const uint32_t* bits_dev, int64_t nv, int64_t ld_words);

@@ -316,6 +316,11 @@ struct EigWorkspace {
   int measure = 0;                 // PCOA_SIMILARITY_*
   const int64_t* diag = nullptr;   // [n] d_i = S(i, i), the total entry
   const double* qcos = nullptr;    // [n] cosine: q_i = d_i > 0 ? 1 / sqrt(d_i) : 0  (q is the tridiagonalisation's)
+  // The pairwise-complete similarity (pcoa_set_call_companion, complete.hip): the implicit forms evaluate K(i, j) from S(i, j),
+  // the companion's Q(i, j) and the two samples' called counts before they centre it; colmean / stats are then K's.
+  const int32_t* comp_q32 = nullptr;   // [n][n] the companion's finalized int32 S, or nullptr: no companion bound
+  const int64_t* comp_c = nullptr;     // [n] c_i = V - Q(i, i)
+  int64_t comp_v = 0;                  // V, the variants fed
 };
 size_t symv_sym_workspace_doubles(int32_t n);
 // exact row sums of a finalized (symmetric) int32 S from its upper-triangular tiles: half the bytes of launch_center's row
@@ -350,6 +355,26 @@ hipError_t launch_measure_center(const int32_t* s32, const int64_t* s64_or_null,
                                  const double* q, const double* cm, const double* stats, double* b, hipStream_t stream);
 // y = B x through the implicit forms: upper-triangular tiles when ws.sym_part is set (int32 S, n % 4 == 0), else one wave per row
 hipError_t launch_measure_symv(const EigWorkspace& ws, int32_t n, const double* x, double* y, hipStream_t stream);
+
+// ---- the pairwise-complete similarity, evaluated on the fly from S and the companion's Q (complete.hip; pcoa_set_call_companion)
+//   c_i = V - Q(i, i);  M = c_i + c_j - V + Q(i, j) (int64);  K = M > 0 ? (double)s / (double)M : 0.0;  centred as above
+// s = the total entry (s32 + s64 where there is one); q32 = the companion's finalized int32 matrix (it has no int64 part)
+// c[i] = V - Q(i, i) for the n samples; flag[0] = 1 if some Q(i, i) > V, else 0
+hipError_t launch_complete_diag(const int32_t* q32, int32_t n, int64_t v, int64_t* c, int32_t* flag, hipStream_t stream);
+// row_sums[i] = sum_j K(i, j), one wave per row, added in row_dot's order (ones: n doubles the call fills with 1.0)
+hipError_t launch_complete_row_sums(const int32_t* s32, const int64_t* s64_or_null, const int32_t* q32, int32_t n, const int64_t* c,
+                                    int64_t v, double* ones, double* row_sums, hipStream_t stream);
+// the same from the upper-triangular tiles of the two int32 matrices, n % 4 == 0, in symv_sym_gather_kernel's order
+hipError_t launch_complete_row_sums_sym(const int32_t* s32, const int32_t* q32, int32_t n, const int64_t* c, int64_t v, double* ones,
+                                        double* sym_part, double* row_sums, hipStream_t stream);
+// b = B, [n][n] fp64 (cm = row_sums / N: launch_col_means; stats: launch_measure_stats)
+hipError_t launch_complete_center(const int32_t* s32, const int64_t* s64_or_null, const int32_t* q32, int32_t n, const int64_t* c,
+                                  int64_t v, const double* cm, const double* stats, double* b, hipStream_t stream);
+// y = B x through the implicit forms (ws.comp_*): upper-triangular tiles when ws.sym_part is set, else one wave per row
+hipError_t launch_complete_symv(const EigWorkspace& ws, int32_t n, const double* x, double* y, hipStream_t stream);
+// PLINK .bed rows -> carrier bitsets (bit for bit launch_plink_bed_to_bits) and missing-call bitsets (code 01), one read
+hipError_t launch_plink_bed_to_bits_pair(const uint8_t* bed, int64_t row_bytes, int64_t nv, int32_t n, int64_t words, int ref_a1,
+                                         uint32_t* bits, uint32_t* miss, hipStream_t stream);
 // form (optional): the launcher ORs in the EIG_FORM_* bits (pcoa.h, pcoa_timings.eig_dense_form) of the form it launched
 hipError_t launch_tridiagonalize(const EigWorkspace& ws, int32_t n, hipStream_t stream, int32_t* form = nullptr);
 // eigenvalues with ascending indices idx[0..count) of T -> lam_out[0..count) (device)

@@ -93,7 +93,8 @@ class PcoaEngine(object):
 
     def close(self):
         if getattr(self, "_ctx", None):
-            self._lib.pcoa_destroy(self._ctx)
+            if not getattr(self, "_borrowed", False):   # (a view of a companion the library owns is not destroyed here)
+                self._lib.pcoa_destroy(self._ctx)
             self._ctx = None
 
     def __del__(self):
@@ -259,6 +260,30 @@ class PcoaEngine(object):
             raise ValueError("rows must be [variants][row_bytes]")
         self._check(self._lib.pcoa_accumulate_plink_bed(self._ctx, _ptr(a), a.shape[0], a.shape[1], int(bool(ref_is_a1)), 0))
 
+    def accumulate_plink_bed_calls(self, rows, companion, ref_is_a1=False, asynchronous=False):
+        """accumulate_plink_bed feeding two engines from one read of the rows (pcoa_accumulate_plink_bed_calls): the carrier
+        bitsets into this engine, the missing-call bitsets (code 01) into `companion`, an ordinary full engine with this one's
+        N on this one's device.  The same three forms of `rows`, the same lifetime rules."""
+        fn, q = self._lib.pcoa_accumulate_plink_bed_calls, companion._ctx
+        if asynchronous:
+            import torch  # plumbing only
+            assert rows.dtype == torch.uint8 and rows.dim() == 2 and rows.stride(1) == 1 and rows.is_pinned()
+            self._check(fn(self._ctx, q, ctypes.c_void_p(rows.data_ptr()), int(rows.shape[0]), int(rows.stride(0)),
+                           int(bool(ref_is_a1)), L.PCOA_BED_HOST_ASYNC))
+            return
+        if hasattr(rows, "data_ptr") and getattr(rows, "is_cuda", False):
+            import torch  # plumbing only
+            assert rows.dtype == torch.uint8 and rows.dim() == 2 and rows.stride(1) == 1
+            self._keepalive.append(rows)
+            torch.cuda.current_stream(rows.device).synchronize()
+            self._check(fn(self._ctx, q, ctypes.c_void_p(rows.data_ptr()), int(rows.shape[0]), int(rows.stride(0)),
+                           int(bool(ref_is_a1)), 1))
+            return
+        a = np.ascontiguousarray(rows, dtype=np.uint8)
+        if a.ndim != 2:
+            raise ValueError("rows must be [variants][row_bytes]")
+        self._check(fn(self._ctx, q, _ptr(a), a.shape[0], a.shape[1], int(bool(ref_is_a1)), 0))
+
     def accumulate_dense_device_ptr(self, ptr, n_variants, ld):
         self._check(self._lib.pcoa_accumulate_dense_f32(self._ctx, ctypes.c_void_p(int(ptr)), int(n_variants),
                                                         int(ld), 1))
@@ -414,6 +439,34 @@ class PcoaEngine(object):
         kind = ctypes.c_int32(-1)
         self._check(self._lib.pcoa_get_similarity(self._ctx, ctypes.byref(kind)))
         return dict((v, k) for k, v in self.SIMILARITY_KINDS.items())[int(kind.value)]
+
+    def set_call_companion(self, other, n_variants=0):
+        """The pairwise-complete similarity (pcoa_set_call_companion): `other` is an ordinary engine fed the bitsets of the
+        MISSING calls, n_variants the number of variants fed.  From now on compute(), center() and debug_centred_matvec() use
+        K(i, j) = S(i, j) / M(i, j), M = the variants at which both samples were called; variants_pca.call_complete_measure is
+        the rule.  other=None unbinds.  Survives reset(); subset() of a bound engine gets a companion of its own.  The caller
+        keeps `other` alive while it is bound."""
+        self._check(self._lib.pcoa_set_call_companion(self._ctx, other._ctx if other is not None else None, int(n_variants)))
+        self._companion = other
+
+    def get_call_companion(self):
+        """(companion, n_variants) as bound (pcoa_get_call_companion), (None, 0) where none is.  The companion is the engine
+        given to set_call_companion; for the result of subset() it is a view of the companion the library owns (closing the
+        view does nothing, closing the subset destroys it)."""
+        ctx, v = ctypes.c_void_p(), ctypes.c_int64(0)
+        self._check(self._lib.pcoa_get_call_companion(self._ctx, ctypes.byref(ctx), ctypes.byref(v)))
+        if not ctx.value:
+            return None, 0
+        mine = getattr(self, "_companion", None)
+        if mine is not None and mine._ctx is not None and mine._ctx.value == ctx.value:
+            return mine, int(v.value)
+        view = object.__new__(PcoaEngine)
+        view._lib, view._ctx, view._borrowed = self._lib, ctx, True
+        view.strip, view.operator = None, False
+        view.n = view.cols = self.n
+        view.device = self.device
+        view._keepalive = []
+        return view, int(v.value)
 
     def export_device(self, dst_ptr):
         self._check(self._lib.pcoa_gram_export_device_i64(self._ctx, ctypes.c_void_p(int(dst_ptr))))

@@ -111,6 +111,10 @@ struct Conf {  // PcaConf / GenomicsConf (GenomicsConf.scala:31-101), same flag 
   double ld_r2 = 0.2;                   // --ld-r2 X: a variant is removed when a kept one inside the window has r^2 of the carrier indicators above X
   bool ld_r2_given = false;
   std::string ld_output_path;           // --ld-output-path FILE: one line per fed variant in feed order: index, contig, position, id, 1 (kept) or 0
+  std::string missing_calls = "ignore";  // --missing-calls ignore|pairwise: pairwise decomposes S(i, j) / M(i, j), M the variants at which both
+                                         // samples were called (pcoa_set_call_companion); a second engine, the companion, takes the
+                                         // missing-call bitsets of the same streamed .bed blocks (pcoa_accumulate_plink_bed_calls)
+  std::string call_rate_output_path;     // --call-rate-output-path FILE: name, called variants, variants fed, call rate per sample
   int32_t similarity_kind() const {
     return similarity_measure == "jaccard" ? PCOA_SIMILARITY_JACCARD : similarity_measure == "cosine" ? PCOA_SIMILARITY_COSINE : PCOA_SIMILARITY_SHARED;
   }
@@ -142,6 +146,11 @@ const char* kUsage =
     "                   accumulation: forward and greedy in feed order, a variant is removed when it is monomorphic or when a KEPT\n"
     "                   variant among the W fed before it, on the same contig, has r^2 of the carrier indicators above X; FILE gets\n"
     "                   one line per fed variant: index, contig, position, id, 1 or 0; one engine, one input set)\n"
+    "                   --missing-calls ignore|pairwise [--call-rate-output-path FILE] (pairwise: computePca decomposes\n"
+    "                   S(i,j) / M(i,j), M the variants at which both samples were called, evaluated on the fly from S and the\n"
+    "                   Gram matrix of the missing calls; FILE gets one line per sample: name, called variants, variants fed,\n"
+    "                   call rate; one streamed PLINK fileset, one engine, stored S, full layout, --similarity-measure shared, no\n"
+    "                   projection, loadings or LD pruning)\n"
     "  --project-input-path <file.vcf[.gz]> [more]\n"
     "                   place these samples onto the principal coordinates of the --input-path cohort instead of\n"
     "                   decomposing the union (one GPU, VCF inputs, full layout)\n";
@@ -155,6 +164,7 @@ const char* kStripsRefuseOutliers = "--outlier-iterations subsets one whole simi
 std::string strips_refuse_measure(const std::string& m) {
   return "--similarity-measure " + m + " needs the diagonal of one whole similarity matrix on one engine: it cannot take --layout strips";
 }
+const char* kStripsRefuseMissing = "--missing-calls pairwise needs two whole similarity matrices on one device: it cannot take --layout strips";
 const char* kStripsRefuseRelated = "--related-min-jaccard screens one whole similarity matrix on one engine: it cannot take --layout strips";
 
 Conf parse(int argc, char** argv) {
@@ -247,6 +257,12 @@ Conf parse(int argc, char** argv) {
       if (c.similarity_measure != "shared" && c.similarity_measure != "jaccard" && c.similarity_measure != "cosine")
         die("--similarity-measure takes shared, jaccard or cosine, not '" + c.similarity_measure + "'");
     }
+    else if (a == "--missing-calls") {
+      c.missing_calls = one(i);
+      if (c.missing_calls != "ignore" && c.missing_calls != "pairwise")
+        die("--missing-calls takes ignore or pairwise, not '" + c.missing_calls + "'");
+    }
+    else if (a == "--call-rate-output-path") c.call_rate_output_path = one(i);
     else if (a == "--loadings-output-path") c.loadings_output_path = one(i);
     else if (a == "--ld-window") {
       const std::string v = one(i);
@@ -314,6 +330,28 @@ Conf parse(int argc, char** argv) {
   }
   // --loadings-output-path: the identity B = (X J)^T (X J) behind the loadings holds for the shared counts of the whole cohort
   // on one engine: likewise
+  // --missing-calls pairwise: likewise, naming both flags
+  if (c.missing_calls != "pairwise") {
+    if (!c.call_rate_output_path.empty()) die("--call-rate-output-path needs --missing-calls pairwise");
+  } else {
+    if (c.gram == "implicit") die("--missing-calls pairwise is evaluated from two stored similarity matrices: it cannot take --gram implicit");
+    if (c.layout == "strips") die(kStripsRefuseMissing);
+    if (c.gpus > 1) die("--missing-calls pairwise runs on one engine and its companion: it cannot take --gpus " + std::to_string(c.gpus));
+    if (!c.project_input_path.empty())
+      die("--missing-calls pairwise: projection under the pairwise-complete similarity is not built: it cannot take --project-input-path");
+    if (c.similarity_measure != "shared")
+      die("--missing-calls pairwise: its combination with a measure is not built: it cannot take --similarity-measure " + c.similarity_measure);
+    if (c.ld_window > 0) die("--missing-calls pairwise: LD pruning in front of a paired accumulation is not built: it cannot take --ld-window");
+    if (!c.loadings_output_path.empty())
+      die("--missing-calls pairwise: the decomposed matrix is no longer (X J)^T (X J): it cannot take --loadings-output-path");
+    const std::string ext = c.input_path.size() == 1 && c.input_path[0].size() >= 4 ? c.input_path[0].substr(c.input_path[0].size() - 4) : "";
+    if (c.has_maf || (ext != ".bed" && ext != ".bim" && ext != ".fam"))
+      die("--missing-calls pairwise reads the missing calls of one PLINK fileset: --input-path must name a single .bed / .bim / .fam "
+          "(missing calls from VCF ingest are not built)");
+    if (c.no_stream) die("--missing-calls pairwise feeds the streamed .bed blocks to two engines: it cannot take --no-stream");
+    if (c.parse_only) die("--missing-calls pairwise runs on the device: it cannot take --parse-only");
+    if (c.plink_decode == "host") die("--missing-calls pairwise decodes both bitsets on the device: it cannot take --plink-decode host");
+  }
   if (!c.loadings_output_path.empty()) {
     if (c.gpus > 1) die("--loadings-output-path streams the variants past one engine: it cannot take --gpus " + std::to_string(c.gpus));
     if (c.layout == "strips") die("--loadings-output-path runs on one whole engine: it cannot take --layout strips");
@@ -469,6 +507,13 @@ struct LdFeed {
   }
 };
 LdFeed g_ld;
+
+// --missing-calls pairwise: the companion engine every streamed .bed block's missing-call bitsets go to
+struct CallsFeed {
+  bool on = false;
+  pcoa_ctx* companion = nullptr;
+};
+CallsFeed g_calls;
 struct Variant {
   std::string key;                 // getVariantKey
   VarMeta meta;                    // (g_want_meta)
@@ -1248,6 +1293,9 @@ void stream_plink_shard(const Conf& conf, const PlinkMeta& m, int g, int k, pcoa
       auto t1 = now();
       if (kept > 0) {
         if (g_ld.on) g_ld.bed(ctx, buf[w], kept, (int64_t)bpv, ref_a1 ? 1 : 0);   // (synchronous: the rows are consumed when it returns)
+        else if (g_calls.on)
+          check(ctx, pcoa_accumulate_plink_bed_calls(ctx, g_calls.companion, buf[w], kept, (int64_t)bpv, ref_a1 ? 1 : 0, PCOA_BED_HOST_ASYNC),
+                "getSimilarityMatrix");
         else check(ctx, pcoa_accumulate_plink_bed(ctx, buf[w], kept, (int64_t)bpv, ref_a1 ? 1 : 0, PCOA_BED_HOST_ASYNC), "getSimilarityMatrix");
         total += kept;
       }
@@ -1269,6 +1317,7 @@ void stream_plink_shard(const Conf& conf, const PlinkMeta& m, int g, int k, pcoa
     reader.join();
     auto t3 = now();
     check(ctx, pcoa_sync(ctx), "getSimilarityMatrix");  // the blocks are released by the caller next
+    if (g_calls.on) check(g_calls.companion, pcoa_sync(g_calls.companion), "getSimilarityMatrix");
     feed_s += secs(t3, now());
   } else {
   int which = 0;
@@ -1527,6 +1576,7 @@ int main(int argc, char** argv) {
   Conf conf = parse(argc, argv);
   const bool want_loadings = !conf.loadings_output_path.empty();
   g_ld.on = conf.ld_window > 0;
+  g_calls.on = conf.missing_calls == "pairwise";
   g_want_meta = want_loadings || g_ld.on;   // (--ld-window: the contigs place the breaks)
   if (conf.input_path.empty())
     die("--input-path <file.vcf[.gz]> [more files] or one PLINK fileset (<prefix>.bed) is required: the Google Genomics API the reference read "
@@ -1726,6 +1776,7 @@ int main(int argc, char** argv) {
       if (conf.outlier_iterations > 0) die(kStripsRefuseOutliers);   // --layout auto resolved to strips
       if (conf.related) die(kStripsRefuseRelated);
       if (conf.similarity_measure != "shared") die(strips_refuse_measure(conf.similarity_measure));
+      if (g_calls.on) die(kStripsRefuseMissing);
       if (conf.reduce == "rccl") die("the strip layout has no reduction step: it cannot take --reduce rccl");
       for (int g = 0; g < k; ++g) strips.emplace_back(col0[(size_t)g], cols[(size_t)g]);
     }
@@ -1815,6 +1866,11 @@ int main(int argc, char** argv) {
     if (g_ld.on) {
       g_ld.meta = stream_plink ? &plink.meta : &fed_meta;
       check(engines[0], pcoa_ld_begin(engines[0], conf.ld_window, conf.ld_r2, PCOA_LD_ACCUMULATE), "pcoa_ld_begin");
+    }
+    if (g_calls.on) {   // the companion beside engine 0, with its operand buffers
+      if (pcoa_create(&g_calls.companion, n, conf.gpu_map[0], PCOA_FLAG_DEFAULT) != PCOA_OK)
+        die(std::string("pcoa_create (the call companion): ") + pcoa_last_error(nullptr));
+      check(g_calls.companion, pcoa_reserve(g_calls.companion, (int64_t)1 << 20, 0), "pcoa_reserve");
     }
     if (!stream_plink) return;
     for (int q = 0; q < 4 * conf.gpus; ++q) {
@@ -1970,6 +2026,29 @@ int main(int argc, char** argv) {
   for (int32_t i = 0; i < n; ++i) kept[(size_t)i] = i;
   if (conf.similarity_measure != "shared")   // on the engine that runs computePca (engine 0 after a reduction); its subsets inherit it
     check(ctx, pcoa_set_similarity(ctx, conf.similarity_kind()), "set-similarity");
+  if (g_calls.on) {
+    // --missing-calls pairwise: bound just before the screen and the rounds, V = the variants fed; the subsets get companions
+    // of their own (pcoa_create_subset).  diag(Q) = the missing calls of every sample, by the screen's count-only call
+    pcoa_ctx* q = g_calls.companion;
+    check(q, pcoa_gram_finalize(q), "getSimilarityMatrix");
+    const int64_t fed = (int64_t)std::count(plink.keep.begin(), plink.keep.end(), (char)1);
+    std::vector<int64_t> miss((size_t)n);
+    int64_t none = 0, total_missing = 0;
+    check(q, pcoa_similar_pairs(q, 1.0, nullptr, 0, &none, miss.data()), "pcoa_similar_pairs");
+    for (int64_t m : miss) total_missing += m;
+    check(ctx, pcoa_set_call_companion(ctx, q, fed), "pcoa_set_call_companion");
+    std::printf("Missing calls: %lld of %lld genotypes (pairwise-complete similarity)\n", (long long)total_missing, (long long)(fed * n));
+    if (!conf.call_rate_output_path.empty()) {
+      std::ofstream out(conf.call_rate_output_path);
+      char buf[64];
+      for (int32_t i = 0; i < n; ++i) {
+        const int64_t c = fed - miss[(size_t)i];
+        std::snprintf(buf, sizeof(buf), "%.6f", fed ? (double)c / (double)fed : 0.0);
+        out << names[(size_t)i] << "\t" << c << "\t" << fed << "\t" << buf << "\n";
+      }
+      if (!out) die("cannot write " + conf.call_rate_output_path);
+    }
+  }
   if (conf.related) {
     // --related-min-jaccard X, before the first computePca: the screen of S on the device.  The rule, as pcoa.h and
     // variants_pca.py's related_pairs_rule state it: with d_i = S(i, i) and U = d_i + d_j - S(i, j), the pair (i, j), i < j, is
@@ -2155,5 +2234,6 @@ int main(int argc, char** argv) {
                    t.lanczos_steps);
   }
   for (pcoa_ctx* o : owners) pcoa_destroy(o);
+  if (g_calls.companion) pcoa_destroy(g_calls.companion);   // (after the engine it was bound to)
   return 0;
 }

@@ -205,6 +205,29 @@ def calculate_similarity_matrix(call_rdd, matrix_size, engine=None, device=0):
     return eng
 
 
+def calculate_similarity_matrix_calls(call_rdd, matrix_size, device=0):
+    """--missing-calls pairwise: getSimilarityMatrix over a PLINK fileset with the companion beside it.  Every block of raw
+    .bed rows crosses the link once and is decoded once into the carrier bitsets (the engine) and the missing-call bitsets
+    (the companion): pcoa_accumulate_plink_bed_calls.  Returns (engine, companion, variants fed)."""
+    _, geno, keep, ref_is_a1 = call_rdd
+    eng = PcoaEngine(matrix_size, device=device)
+    companion = PcoaEngine(matrix_size, device=device)
+    fed = 0
+    all_kept = bool(keep.all())
+    for v0 in range(0, geno.shape[0], PLINK_BLOCK_ROWS):
+        rows = geno[v0:v0 + PLINK_BLOCK_ROWS]
+        if not all_kept:
+            k = keep[v0:v0 + PLINK_BLOCK_ROWS]
+            if not k.any():
+                continue
+            rows = rows[k]
+        eng.accumulate_plink_bed_calls(np.ascontiguousarray(rows), companion, ref_is_a1=ref_is_a1)
+        fed += int(rows.shape[0])
+    eng.finalize()
+    companion.finalize()
+    return eng, companion, fed
+
+
 def shard_calls(call_rdd, rank, world):
     """Rank `rank`'s partition of an RDD[Seq[Int]] in any of the forms getCallsRdd returns -- the contiguous range
     dist.shard_range(rank, world, rows), as the reference's partitions are contiguous ranges of the variant stream
@@ -368,6 +391,29 @@ def similarity_measure(s, kind):
     return (sd * q[:, None]) * q[None, :]
 
 
+MISSING_CALLS = ("ignore", "pairwise")   # --missing-calls
+
+
+def call_complete_measure(s, q, n_variants):
+    """The rule of --missing-calls pairwise and of pcoa_set_call_companion (csrc/complete.hip restates it on the device): `s`
+    is the N x N integer matrix of TOTAL entries of the carrier engine, `q` the Gram matrix of the missing-call bitsets (the
+    companion's S), n_variants = V the number of variants fed.  With c_i = V - q_ii the variants at which sample i is called
+    and M_ij = c_i + c_j - V + q_ij the variants at which both are (integers), K_ij = float64(s_ij) / float64(M_ij) where
+    M_ij > 0, else 0.0 -- one IEEE fp64 division.  Returns K as float64.  K need not be positive semi-definite."""
+    s = np.asarray(s, dtype=np.int64)
+    q = np.asarray(q, dtype=np.int64)
+    if s.ndim != 2 or s.shape[0] != s.shape[1] or q.shape != s.shape:
+        raise ValueError("s and q must be N x N")
+    v = int(n_variants)
+    c = v - np.diagonal(q)
+    if v < 0 or (c < 0).any():
+        raise ValueError("n_variants is smaller than a sample's missing count")
+    m = c[:, None] + c[None, :] - v + q
+    k = np.zeros(s.shape, dtype=np.float64)
+    np.divide(s.astype(np.float64), m.astype(np.float64), out=k, where=m > 0)
+    return k
+
+
 def centred_measure(k):
     """computePca's centring (VariantsPca.scala:206-221) of a similarity K in float64: r_i = sum_j K_ij, rowmean_i = r_i / N,
     mm = (sum_i r_i) / N / N (the two divisions the device's stats kernel performs), B_ij = ((K_ij - rowmean_i) - rowmean_j)
@@ -472,6 +518,15 @@ class PcaConf(object):
                             "the reference; jaccard: S(i, j) / (S(i, i) + S(j, j) - S(i, j)); cosine: S(i, j) / sqrt(S(i, i) "
                             "S(j, j)) -- evaluated on the fly from S on the device, which takes out the axis that tracks how "
                             "many variants a sample carries.  One full engine: stored S, full layout, no projection")
+        p.add_argument("--missing-calls", type=str, default="ignore",
+                       help="ignore|pairwise: what a missing call (PLINK .bed code 01) means.  ignore: a non-carrier, as the "
+                            "reference; pairwise: computePca decomposes the pairwise-complete similarity S(i, j) / M(i, j), M the "
+                            "number of variants at which both samples were called (pcoa_set_call_companion), which takes out "
+                            "the axis that tracks a sample's call rate.  One PLINK fileset, one full engine: stored S, full "
+                            "layout, --similarity-measure shared, no projection, loadings or LD pruning")
+        p.add_argument("--call-rate-output-path", type=str, default=None,
+                       help="--missing-calls pairwise: one line per sample -- name, called variants, variants fed, call rate "
+                            "with six decimals, tab-separated")
         p.add_argument("--loadings-output-path", type=str, default=None,
                        help="write the loading of every variant fed to the engine on each of the --num-pc principal "
                             "coordinates, w_c = X (J u_c) / sqrt(lambda_c) (pcoa_loadings_*), to this file: one line per "
@@ -824,6 +879,9 @@ class VariantsPcaDriver(object):
         if self.engine is not None:
             self.engine.close()
             self.engine = None
+        if getattr(self, "companion", None) is not None:   # (--missing-calls pairwise: after the engine it was bound to)
+            self.companion.close()
+            self.companion = None
 
 
 def write_loadings(path, meta, w):
@@ -1019,6 +1077,58 @@ def check_measure_conf(conf):
     if conf.project_input_path:
         raise SystemExit("VariantsPcaDriver: --similarity-measure %s: projection under a measure is not built: it cannot take "
                          "--project-input-path" % m)
+
+
+STRIPS_REFUSE_MISSING = ("--missing-calls pairwise needs two whole similarity matrices on one device: it cannot take --layout "
+                         "strips")
+
+
+def is_plink_path(path):
+    return path[-4:] in (".bed", ".bim", ".fam")
+
+
+def check_missing_conf(conf):
+    """--missing-calls: an unknown value, and what the pairwise-complete similarity cannot serve, is refused before any file
+    is read or any engine exists."""
+    m = conf.missing_calls
+    if m not in MISSING_CALLS:
+        raise SystemExit("VariantsPcaDriver: --missing-calls takes ignore or pairwise, not '%s'" % m)
+    if m == "ignore":
+        if conf.call_rate_output_path:
+            raise SystemExit("VariantsPcaDriver: --call-rate-output-path needs --missing-calls pairwise")
+        return
+    if conf.gram == "implicit":
+        raise SystemExit("VariantsPcaDriver: --missing-calls pairwise is evaluated from two stored similarity matrices: it cannot "
+                         "take --gram implicit")
+    if conf.layout == "strips":
+        raise SystemExit("VariantsPcaDriver: " + STRIPS_REFUSE_MISSING)
+    if conf.gpus > 1:
+        raise SystemExit("VariantsPcaDriver: --missing-calls pairwise runs on one engine and its companion: it cannot take --gpus %d"
+                         % conf.gpus)
+    if conf.project_input_path:
+        raise SystemExit("VariantsPcaDriver: --missing-calls pairwise: projection under the pairwise-complete similarity is not "
+                         "built: it cannot take --project-input-path")
+    if conf.similarity_measure != "shared":
+        raise SystemExit("VariantsPcaDriver: --missing-calls pairwise: its combination with a measure is not built: it cannot take "
+                         "--similarity-measure %s" % conf.similarity_measure)
+    if conf.ld_window:
+        raise SystemExit("VariantsPcaDriver: --missing-calls pairwise: LD pruning in front of a paired accumulation is not built: it "
+                         "cannot take --ld-window")
+    if conf.loadings_output_path:
+        raise SystemExit("VariantsPcaDriver: --missing-calls pairwise: the decomposed matrix is no longer (X J)^T (X J): it cannot "
+                         "take --loadings-output-path")
+    paths = conf.inputPath or []
+    if conf.synthetic or conf.minAlleleFrequency is not None or len(paths) != 1 or not is_plink_path(paths[0]):
+        raise SystemExit("VariantsPcaDriver: --missing-calls pairwise reads the missing calls of one PLINK fileset: --input-path must "
+                         "name a single .bed / .bim / .fam (missing calls from VCF ingest are not built)")
+
+
+def write_call_rates(path, names, called, n_variants):
+    """The --call-rate-output-path file: one line per sample in callset order -- name, called variants c_i, variants fed V,
+    c_i / V with six decimals (0.000000 where V = 0), tab-separated."""
+    with open(path, "w") as f:
+        for name, c in zip(names, called):
+            f.write("%s\t%d\t%d\t%.6f\n" % (name, int(c), int(n_variants), (float(c) / float(n_variants)) if n_variants else 0.0))
 
 
 LD_MAX_WINDOW = 1024   # PCOA_LD_MAX_WINDOW
@@ -1225,6 +1335,7 @@ def main(args):
     check_outlier_conf(conf)
     check_related_conf(conf)
     check_measure_conf(conf)
+    check_missing_conf(conf)
     check_gram_conf(conf)
     check_loadings_conf(conf)
     check_ld_conf(conf)
@@ -1308,6 +1419,8 @@ def main(args):
         raise SystemExit("VariantsPcaDriver: " + STRIPS_REFUSE_RELATED)
     if ranges is not None and conf.similarity_measure != "shared":
         raise SystemExit("VariantsPcaDriver: " + STRIPS_REFUSE_MEASURE % conf.similarity_measure)
+    if ranges is not None and conf.missing_calls == "pairwise":   # --layout auto resolved to strips
+        raise SystemExit("VariantsPcaDriver: " + STRIPS_REFUSE_MISSING)
     if ranges is not None and conf.ld_window:
         raise SystemExit("VariantsPcaDriver: --ld-window runs in front of one engine's accumulation: it cannot take --layout strips")
     if ranges is not None and conf.loadings_output_path:     # --layout auto resolved to strips
@@ -1339,6 +1452,9 @@ def main(args):
                                                    tele["rank_elapsed_max_s"]))
     elif conf.ld_window:
         sim_matrix = driver.engine = ld_ingest(PcoaEngine(n, device=conf.gpu))
+    elif conf.missing_calls == "pairwise":
+        sim_matrix, driver.companion, fed = calculate_similarity_matrix_calls(calls_rdd, n, device=conf.gpu)
+        driver.engine = sim_matrix
     else:
         sim_matrix = driver.getSimilarityMatrix(calls_rdd)
     if rank == 0:
@@ -1346,6 +1462,13 @@ def main(args):
             sim_matrix.gram().astype("<i8").tofile(conf.dump_similarity)
         if conf.similarity_measure != "shared":    # on the engine that runs computePca; its subsets inherit it
             sim_matrix.set_similarity(conf.similarity_measure)
+        if conf.missing_calls == "pairwise":       # bound just before the screen and the rounds; the subsets get their own
+            missing = driver.companion.similar_pairs(1.0, capacity=0)[2]      # diag(Q): the missing calls of every sample
+            sim_matrix.set_call_companion(driver.companion, fed)
+            print("Missing calls: %d of %d genotypes (pairwise-complete similarity)" % (int(missing.sum()), fed * n))
+            if conf.call_rate_output_path:
+                reverse = dict((v, k) for (k, v) in driver.indexes.items())
+                write_call_rates(conf.call_rate_output_path, [driver.names[reverse[i]] for i in range(n)], fed - missing, fed)
         if conf.related_min_jaccard is not None:   # the screen first, then the rounds on the reduced cohort
             sim_matrix = driver.screenRelated(sim_matrix)
         result = driver.computePcaOutlierRounds(sim_matrix) if conf.outlier_iterations > 0 else driver.computePca(sim_matrix)
