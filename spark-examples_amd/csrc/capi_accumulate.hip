@@ -1,12 +1,13 @@
 // capi_accumulate.hip -- the input boundaries of the C ABI: dense fp32 / uint8 tiles, bitsets, PLINK .bed rows, carrier
 // lists, the synthetic model.  Device inputs go straight to operand.hip; host inputs are staged, the asynchronous ones
-// through a ring of two staging slots (StagingRing, pcoa_ctx.h).
+// through a ring of two staging slots (StagingRing, pcoa_ctx.h): host bitsets and .bed rows by the row feed (row_feed.h).
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
 #include <thread>
 
 #include "pcoa_ctx.h"
+#include "row_feed.h"
 
 using namespace pcoa;
 
@@ -25,76 +26,6 @@ static int64_t staging_rows(int64_t n_variants, int64_t ld4) {
 static int not_a_bitset_boundary(pcoa_ctx* c, const char* call, const char* why = "") {
   return fail(c, PCOA_ERR_STATE, std::string(call) + ": an operator ctx (pcoa_create_operator) stores carrier BITSETS: feed it "
                                  "through pcoa_accumulate_bits or pcoa_accumulate_plink_bed" + why);
-}
-
-// ---- the staging ring (protocol: StagingRing, pcoa_ctx.h) ---------------------------------------------------------------
-// buffer i of a slot whose last reader is done: regrown to grow_to bytes unless it holds `need` already
-static int staging_fit(pcoa_ctx* c, StagingRing::Slot& sl, int i, size_t need, size_t grow_to) {
-  if (need <= sl.dev_bytes[i]) return PCOA_OK;
-  sl.dev_bytes[i] = 0;
-  const int rc = regrow(c, &sl.dev[i], grow_to, false);
-  if (rc == PCOA_OK) sl.dev_bytes[i] = grow_to;
-  return rc;
-}
-
-// The next slot of the ring, free to be rewritten, with `need` bytes in buffer 0 (and need1 in buffer 1).  Creates the copy
-// stream and the ring's events on first use.
-int staging_acquire(pcoa_ctx* c, StagingRing& r, size_t need, size_t grow_to, StagingRing::Slot** out, size_t need1, size_t grow_to1) {
-  if (!c->csr_stream) HIP_TRY(c, hipStreamCreateWithFlags(&c->csr_stream, hipStreamNonBlocking));
-  for (auto& sl : r.slot)
-    if (!sl.copied) {
-      HIP_TRY(c, hipEventCreateWithFlags(&sl.copied, hipEventDisableTiming));
-      HIP_TRY(c, hipEventCreateWithFlags(&sl.freed, hipEventDisableTiming));
-    }
-  StagingRing::Slot& sl = r.slot[r.next++ & 1];
-  if (sl.used) HIP_TRY(c, hipEventSynchronize(sl.freed));   // the kernels that read the slot last are done (its H2D long before)
-  int rc = staging_fit(c, sl, 0, need, grow_to);
-  if (rc == PCOA_OK) rc = staging_fit(c, sl, 1, need1, grow_to1);
-  *out = &sl;
-  return rc;
-}
-
-// the page-locked twin of buffer i (pageable sources are copied into it by the host before the H2D)
-static int staging_pin(pcoa_ctx* c, StagingRing::Slot& sl, int i, size_t need, size_t grow_to) {
-  if (need <= sl.pin_bytes[i]) return PCOA_OK;
-  if (sl.pin[i]) (void)hipHostFree(sl.pin[i]);
-  sl.pin[i] = nullptr;
-  sl.pin_bytes[i] = 0;
-  HIP_TRY(c, hipHostMalloc(&sl.pin[i], grow_to, hipHostMallocDefault));
-  sl.pin_bytes[i] = grow_to;
-  return PCOA_OK;
-}
-
-// the slot's copies have been queued on the copy stream
-int staging_copied(pcoa_ctx* c, StagingRing::Slot& sl) {
-  HIP_TRY(c, hipEventRecord(sl.copied, c->csr_stream));
-  return PCOA_OK;
-}
-
-// the last kernel that reads the slot has been queued on `reader`
-int staging_released(pcoa_ctx* c, StagingRing::Slot& sl, hipStream_t reader) {
-  HIP_TRY(c, hipEventRecord(sl.freed, reader));
-  sl.used = true;
-  return PCOA_OK;
-}
-
-// every reader of every slot is done
-int staging_wait_all(pcoa_ctx* c, StagingRing& r) {
-  for (auto& sl : r.slot)
-    if (sl.used) HIP_TRY(c, hipEventSynchronize(sl.freed));
-  return PCOA_OK;
-}
-
-void staging_destroy(StagingRing& r) {
-  for (auto& sl : r.slot) {
-    if (sl.copied) (void)hipEventDestroy(sl.copied);
-    if (sl.freed) (void)hipEventDestroy(sl.freed);
-    for (void* d : sl.dev)
-      if (d) dev_free(d);
-    for (void* h : sl.pin)
-      if (h) (void)hipHostFree(h);
-    sl = StagingRing::Slot();
-  }
 }
 
 // sample -> population map on the device; uploaded again only when the offsets differ from the last call's
@@ -521,41 +452,22 @@ int pcoa_accumulate_bits(pcoa_ctx* c, const uint32_t* bits, int64_t n_variants, 
   CHECK_CTX(c);
   if (n_variants < 0 || (n_variants > 0 && !bits))
     return fail(c, PCOA_ERR_INVALID_ARG, "bits is NULL or n_variants < 0");
-  const int64_t need_words = ((int64_t)c->n + 31) / 32;
-  if (ld_words < need_words) return fail(c, PCOA_ERR_INVALID_ARG, "ld_words must be >= ceil(n_samples / 32)");
+  int rc = check_ld_words(c, "", ld_words);
+  if (rc != PCOA_OK) return rc;
   if (!c->use_i8)
     return fail(c, PCOA_ERR_INVALID_ARG, "the bit-packed boundary needs a packed-operand engine (not PCOA_FLAG_GRAM_F32_MFMA)");
   if (n_variants == 0) return PCOA_OK;
   if (is_device_ptr) return gram_device_bits(c, bits, n_variants, ld_words, true);
-  // host bitsets: dense rows (ceil(N/32) words each) through two device slots on the copy stream, <= 2^17 rows and <= 256 MiB
-  // per slot at a time (r06: the copy of chunk k + 1 runs beside the transpose and the contraction of chunk k, as the .bed rows
-  // of pcoa_accumulate_plink_bed do; r05 staged 64-MiB-word chunks on the ctx stream, copy and kernels in series).  The byte
-  // cap binds only for wide rows: 2^17 rows of N = 250,000 would be 4.1 GB per slot, beside a strip owner's matrix.
-  const int64_t slot_rows = std::min<int64_t>((int64_t)1 << 17, ((int64_t)256 << 20) / (need_words * 4));
+  // host bitsets: <= 2^17 rows and <= 256 MiB per slot at a time (r06: the copy of chunk k + 1 runs beside the transpose and the
+  // contraction of chunk k, as the .bed rows of pcoa_accumulate_plink_bed do; r05 staged 64-MiB-word chunks on the ctx stream,
+  // copy and kernels in series).  The byte cap binds only for wide rows: 2^17 rows of N = 250,000 would be 4.1 GB per slot,
+  // beside a strip owner's matrix.
+  const int64_t slot_rows = std::min<int64_t>((int64_t)1 << 17, ((int64_t)256 << 20) / (words_of(c) * 4));
   const int64_t rows_cap = std::max<int64_t>(1, std::min<int64_t>(n_variants, slot_rows));
-  StagingRing::Slot* last = nullptr;
-  int rc = PCOA_OK;
-  for (int64_t v0 = 0; v0 < n_variants; v0 += rows_cap) {
-    const int64_t rows = std::min(rows_cap, n_variants - v0);
-    const int64_t need_bytes = rows * need_words * 4;
-    StagingRing::Slot* sl = nullptr;   // (its last reader: the transpose of the chunk before last)
-    if ((rc = staging_acquire(c, c->bs, (size_t)need_bytes, (size_t)(rows_cap * need_words * 4), &sl)) != PCOA_OK) return rc;
-    uint32_t* stage = static_cast<uint32_t*>(sl->dev[0]);
-    if (ld_words == need_words)   // dense rows: one linear copy (the strided form crosses the link at ~30 GB/s, this one at ~55)
-      HIP_TRY(c, hipMemcpyAsync(stage, bits + v0 * ld_words, (size_t)need_bytes, hipMemcpyHostToDevice, c->csr_stream));
-    else
-      HIP_TRY(c, hipMemcpy2DAsync(stage, (size_t)need_words * 4, bits + v0 * ld_words, (size_t)ld_words * 4,
-                                  (size_t)need_words * 4, (size_t)rows, hipMemcpyHostToDevice, c->csr_stream));
-    if ((rc = staging_copied(c, *sl)) != PCOA_OK) return rc;
-    HIP_TRY(c, hipStreamWaitEvent(c->stream, sl->copied, 0));
-    rc = gram_device_bits(c, stage, rows, need_words, false);   // (its transpose runs on the ctx stream, behind the wait)
-    if (rc != PCOA_OK) return rc;
-    if ((rc = staging_released(c, *sl, c->stream)) != PCOA_OK) return rc;
-    last = sl;
-  }
-  // host rows are consumed once their copy is done (copies complete in order on the copy stream); the kernels are queued
-  if (last) HIP_TRY(c, hipEventSynchronize(last->copied));
-  return PCOA_OK;
+  // host rows are consumed once their copy is done; the kernels are queued (the transpose runs on the ctx stream)
+  return feed_bits(c, bits, n_variants, ld_words, rows_cap, false, true, [&](const uint32_t* stage, int64_t ld, int64_t, int64_t rows) {
+    return gram_device_bits(c, stage, rows, ld, false);
+  });
 }
 
 // PLINK 1 .bed rows as they lie in the file (r04): decoded on the device.  The host's share of a whole-genome fileset is
@@ -565,57 +477,21 @@ int pcoa_accumulate_plink_bed(pcoa_ctx* c, const uint8_t* bed_rows, int64_t n_va
                               int is_device_ptr) {
   CHECK_CTX(c);
   if (n_variants < 0 || (n_variants > 0 && !bed_rows)) return fail(c, PCOA_ERR_INVALID_ARG, "bed_rows is NULL or n_variants < 0");
-  if (row_bytes < ((int64_t)c->n + 3) / 4) return fail(c, PCOA_ERR_INVALID_ARG, "row_bytes must be >= ceil(n_samples / 4)");
+  int rc = check_row_bytes(c, "", row_bytes);
+  if (rc != PCOA_OK) return rc;
   if (!c->use_i8)
     return fail(c, PCOA_ERR_INVALID_ARG, "the PLINK boundary needs a packed-operand engine (not PCOA_FLAG_GRAM_F32_MFMA)");
-  if (is_device_ptr != 0 && is_device_ptr != 1 && is_device_ptr != PCOA_BED_HOST_ASYNC)
-    return fail(c, PCOA_ERR_INVALID_ARG, "is_device_ptr must be 0, 1 or PCOA_BED_HOST_ASYNC");
-  bool host_async = is_device_ptr == PCOA_BED_HOST_ASYNC;
-  if (host_async) is_device_ptr = 0;
+  if ((rc = check_bed_source(c, "", is_device_ptr, true)) != PCOA_OK) return rc;
   if (n_variants == 0) return PCOA_OK;
-  if (host_async) {
-    // the queued form is only safe for page-locked rows: pageable memory goes through the runtime's staging copy, whose
-    // timing the "second later call" rule does not cover -- such rows are consumed before the call returns
-    hipPointerAttribute_t attr;
-    const hipError_t pe = hipPointerGetAttributes(&attr, bed_rows);
-    if (pe != hipSuccess || attr.type != hipMemoryTypeHost) {
-      (void)hipGetLastError();
-      host_async = false;
-    }
-  }
-  const int64_t words = ((int64_t)c->n + 31) / 32;
+  const int64_t words = words_of(c);
   const int64_t rows_cap = std::min<int64_t>(n_variants, (int64_t)1 << 17);
-  int rc = ensure(c, &c->tile, &c->tile_elems, rows_cap * words);
-  if (rc != PCOA_OK) return rc;
+  if ((rc = ensure(c, &c->tile, &c->tile_elems, rows_cap * words)) != PCOA_OK) return rc;
   uint32_t* bits = reinterpret_cast<uint32_t*>(c->tile);
-  StagingRing::Slot* last = nullptr;
-  for (int64_t v0 = 0; v0 < n_variants; v0 += rows_cap) {
-    const int64_t rows = std::min(rows_cap, n_variants - v0);
-    const uint8_t* src = bed_rows + v0 * row_bytes;
-    StagingRing::Slot* sl = nullptr;
-    if (!is_device_ptr) {
-      // r05: the copy travels on the copy stream into one of two slots -- beside the decode, transpose and contraction of
-      // the chunk (or the call) before; the r04 form queued everything on the ctx stream and drained it before returning
-      // (the slot's last reader: the decode of the chunk before last)
-      if ((rc = staging_acquire(c, c->bs, (size_t)(rows * row_bytes), (size_t)(rows_cap * row_bytes), &sl)) != PCOA_OK) return rc;
-      HIP_TRY(c, hipMemcpyAsync(sl->dev[0], src, (size_t)(rows * row_bytes), hipMemcpyHostToDevice, c->csr_stream));
-      if ((rc = staging_copied(c, *sl)) != PCOA_OK) return rc;
-      HIP_TRY(c, hipStreamWaitEvent(c->stream, sl->copied, 0));
-      src = static_cast<const uint8_t*>(sl->dev[0]);
-      last = sl;
-    }
-    {
-      ScopedTimer t(c, T_DENSIFY);
-      HIP_TRY(c, launch_plink_bed_to_bits(src, row_bytes, rows, c->n, words, ref_is_a1 ? 1 : 0, bits, c->stream));
-    }
-    if (sl && (rc = staging_released(c, *sl, c->stream)) != PCOA_OK) return rc;   // the decode is the slot's only reader
-    if ((rc = gram_device_bits(c, bits, rows, words, false)) != PCOA_OK) return rc;
-  }
-  // host rows are consumed once their copy is done (copies complete in order on the copy stream); what the device still
-  // has to do with them is queued.  A device input (read by the decode kernel only) follows the lifetime rule of every
-  // device input
-  if (last && !host_async) HIP_TRY(c, hipEventSynchronize(last->copied));
-  return PCOA_OK;
+  // r05: a host chunk travels on the copy stream beside the decode, transpose and contraction of the chunk (or the call)
+  // before; the r04 form queued everything on the ctx stream and drained it before returning.  Host rows are consumed once
+  // their copy is done; a device input (read by the decode kernel only) follows the lifetime rule of every device input
+  return feed_bed(c, bed_rows, n_variants, row_bytes, rows_cap, is_device_ptr, true, bed_decoder(c, row_bytes, ref_is_a1, bits),
+                  [&](int64_t, int64_t rows) { return gram_device_bits(c, bits, rows, words, false); });
 }
 
 int pcoa_accumulate_calls_ex(pcoa_ctx* c, const int32_t* sample_idx, const int64_t* row_offsets, int64_t n_variants,

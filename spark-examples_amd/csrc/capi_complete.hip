@@ -3,10 +3,11 @@
 // bitsets; from then on pcoa_compute, pcoa_center_read_f64 and pcoa_debug_centred_matvec centre and decompose
 // K(i, j) = S(i, j) / M(i, j), M the number of variants at which both samples were called.  Like the measure, the binding
 // says how the ctx DECOMPOSES S, not how it accumulates it: S, the reductions, the reads and the screen never look at it.
-// pcoa_accumulate_plink_bed_calls feeds both engines from one read of the raw .bed rows.
+// pcoa_accumulate_plink_bed_calls feeds both engines from one read of the raw .bed rows, through the row feed (row_feed.h).
 #include <string>
 
 #include "pcoa_ctx.h"
+#include "row_feed.h"
 
 using namespace pcoa;
 
@@ -57,29 +58,8 @@ int complete_centre(pcoa_ctx* c, bool sym_form, double* b) {
   return PCOA_OK;
 }
 
-void complete_destroy(pcoa_ctx* c) {
-  if (c->complete_c) dev_free(c->complete_c);
-  if (c->calls_bits) dev_free(c->calls_bits);
-  if (c->calls_decoded) (void)hipEventDestroy(c->calls_decoded);
-  if (c->calls_read) (void)hipEventDestroy(c->calls_read);
-  c->complete_c = nullptr;
-  c->calls_bits = nullptr;
-  c->calls_decoded = c->calls_read = nullptr;
-  if (c->companion && c->companion_owned) {
-    pcoa_destroy(c->companion);
-    (void)hipSetDevice(c->device);
-  }
-  c->companion = nullptr;
-  c->companion_owned = false;
-}
-
-}  // namespace pcoa
-
-namespace {
-
-const char* engine_kind(const pcoa_ctx* c) { return c->is_operator ? "an operator ctx (pcoa_create_operator)" : "a strip owner (pcoa_create_strip)"; }
-
-void drop_companion(pcoa_ctx* c) {
+// the binding, and the companion with it where the ctx owns it (a subset's)
+static void drop_companion(pcoa_ctx* c) {
   if (c->companion && c->companion_owned) {
     pcoa_destroy(c->companion);
     (void)hipSetDevice(c->device);
@@ -88,6 +68,23 @@ void drop_companion(pcoa_ctx* c) {
   c->companion_owned = false;
   c->companion_v = 0;
 }
+
+void complete_destroy(pcoa_ctx* c) {
+  if (c->complete_c) dev_free(c->complete_c);
+  if (c->calls_bits) dev_free(c->calls_bits);
+  if (c->calls_decoded) (void)hipEventDestroy(c->calls_decoded);
+  if (c->calls_read) (void)hipEventDestroy(c->calls_read);
+  c->complete_c = nullptr;
+  c->calls_bits = nullptr;
+  c->calls_decoded = c->calls_read = nullptr;
+  drop_companion(c);
+}
+
+}  // namespace pcoa
+
+namespace {
+
+const char* engine_kind(const pcoa_ctx* c) { return c->is_operator ? "an operator ctx (pcoa_create_operator)" : "a strip owner (pcoa_create_strip)"; }
 
 }  // namespace
 
@@ -131,9 +128,9 @@ int pcoa_get_call_companion(const pcoa_ctx* c, pcoa_ctx** missing_out, int64_t* 
   return PCOA_OK;
 }
 
-// pcoa_accumulate_plink_bed's chunking, staging slots and lifetime rules (capi_accumulate.hip), with the pair decode: the raw
-// rows cross the link once, one kernel reads them once and writes the carrier rows (c->tile) and the missing rows
-// (c->calls_bits).  The carrier rows go into c on its stream, the missing rows into the companion on ITS stream:
+// pcoa_accumulate_plink_bed through the same row feed (row_feed.h) with the pair decode: the raw rows cross the link once, one
+// kernel reads them once and writes the carrier rows (c->tile) and the missing rows (c->calls_bits).  The carrier rows go into c
+// on its stream, the missing rows into the companion on ITS stream:
 //   calls_decoded  recorded on c's stream behind the decode; the companion's stream waits for it before its pre-pass
 //   calls_read     recorded on the companion's stream behind that pre-pass; c's stream waits for it before the next decode
 //                  rewrites calls_bits (in this call or a later one)
@@ -149,63 +146,45 @@ int pcoa_accumulate_plink_bed_calls(pcoa_ctx* c, pcoa_ctx* missing, const uint8_
     return fail(c, PCOA_ERR_INVALID_ARG, std::string(fn) + "the companion must be an ordinary packed-operand full engine "
                                                            "(pcoa_create, not PCOA_FLAG_GRAM_F32_MFMA) on ctx's device");
   if (n_variants < 0 || (n_variants > 0 && !bed_rows)) return fail(c, PCOA_ERR_INVALID_ARG, "bed_rows is NULL or n_variants < 0");
-  if (row_bytes < ((int64_t)c->n + 3) / 4) return fail(c, PCOA_ERR_INVALID_ARG, "row_bytes must be >= ceil(n_samples / 4)");
+  int rc = check_row_bytes(c, "", row_bytes);
+  if (rc != PCOA_OK) return rc;
   if (!c->use_i8)
     return fail(c, PCOA_ERR_INVALID_ARG, "the PLINK boundary needs a packed-operand engine (not PCOA_FLAG_GRAM_F32_MFMA)");
-  if (is_device_ptr != 0 && is_device_ptr != 1 && is_device_ptr != PCOA_BED_HOST_ASYNC)
-    return fail(c, PCOA_ERR_INVALID_ARG, "is_device_ptr must be 0, 1 or PCOA_BED_HOST_ASYNC");
-  bool host_async = is_device_ptr == PCOA_BED_HOST_ASYNC;
-  if (host_async) is_device_ptr = 0;
+  if ((rc = check_bed_source(c, "", is_device_ptr, true)) != PCOA_OK) return rc;
   if (n_variants == 0) return PCOA_OK;
-  if (host_async) {   // the queued form is only safe for page-locked rows (pcoa_accumulate_plink_bed)
-    hipPointerAttribute_t attr;
-    const hipError_t pe = hipPointerGetAttributes(&attr, bed_rows);
-    if (pe != hipSuccess || attr.type != hipMemoryTypeHost) {
-      (void)hipGetLastError();
-      host_async = false;
-    }
-  }
-  const int64_t words = ((int64_t)c->n + 31) / 32;
+  const int64_t words = words_of(c);
   const int64_t rows_cap = std::min<int64_t>(n_variants, (int64_t)1 << 17);
   if (c->calls_read_pending && rows_cap * words > c->calls_bits_cap) {   // the buffer is about to be replaced: its reader first
     HIP_TRY(c, hipEventSynchronize(c->calls_read));
     c->calls_read_pending = false;
   }
-  int rc = ensure(c, &c->tile, &c->tile_elems, rows_cap * words);
+  rc = ensure(c, &c->tile, &c->tile_elems, rows_cap * words);
   if (rc == PCOA_OK) rc = ensure(c, &c->calls_bits, &c->calls_bits_cap, rows_cap * words);
   if (rc != PCOA_OK) return rc;
   if (!c->calls_decoded) HIP_TRY(c, hipEventCreateWithFlags(&c->calls_decoded, hipEventDisableTiming));
   if (!c->calls_read) HIP_TRY(c, hipEventCreateWithFlags(&c->calls_read, hipEventDisableTiming));
   uint32_t* bits = reinterpret_cast<uint32_t*>(c->tile);
-  StagingRing::Slot* last = nullptr;
-  for (int64_t v0 = 0; v0 < n_variants; v0 += rows_cap) {
-    const int64_t rows = std::min(rows_cap, n_variants - v0);
-    const uint8_t* src = bed_rows + v0 * row_bytes;
-    StagingRing::Slot* sl = nullptr;
-    if (!is_device_ptr) {
-      if ((rc = staging_acquire(c, c->bs, (size_t)(rows * row_bytes), (size_t)(rows_cap * row_bytes), &sl)) != PCOA_OK) return rc;
-      HIP_TRY(c, hipMemcpyAsync(sl->dev[0], src, (size_t)(rows * row_bytes), hipMemcpyHostToDevice, c->csr_stream));
-      if ((rc = staging_copied(c, *sl)) != PCOA_OK) return rc;
-      HIP_TRY(c, hipStreamWaitEvent(c->stream, sl->copied, 0));
-      src = static_cast<const uint8_t*>(sl->dev[0]);
-      last = sl;
-    }
-    if (c->calls_read_pending) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->calls_read, 0));
-    {
-      ScopedTimer t(c, T_DENSIFY);
-      HIP_TRY(c, launch_plink_bed_to_bits_pair(src, row_bytes, rows, c->n, words, ref_is_a1 ? 1 : 0, bits, c->calls_bits, c->stream));
-    }
-    HIP_TRY(c, hipEventRecord(c->calls_decoded, c->stream));
-    if (sl && (rc = staging_released(c, *sl, c->stream)) != PCOA_OK) return rc;   // the decode is the slot's only reader
-    if ((rc = gram_device_bits(c, bits, rows, words, false)) != PCOA_OK) return rc;
-    HIP_TRY(c, hipStreamWaitEvent(missing->stream, c->calls_decoded, 0));
-    if ((rc = gram_device_bits(missing, c->calls_bits, rows, words, false)) != PCOA_OK)
-      return fail(c, rc, std::string(fn) + "the companion: " + missing->last_error);
-    HIP_TRY(c, hipEventRecord(c->calls_read, missing->stream));
-    c->calls_read_pending = true;
-  }
-  if (last && !host_async) HIP_TRY(c, hipEventSynchronize(last->copied));
-  return PCOA_OK;
+  return feed_bed(
+      c, bed_rows, n_variants, row_bytes, rows_cap, is_device_ptr, true,
+      [&](const uint8_t* src, int64_t, int64_t rows) -> int {
+        if (c->calls_read_pending) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->calls_read, 0));
+        {
+          ScopedTimer t(c, T_DENSIFY);
+          HIP_TRY(c, launch_plink_bed_to_bits_pair(src, row_bytes, rows, c->n, words, ref_is_a1 ? 1 : 0, bits, c->calls_bits, c->stream));
+        }
+        HIP_TRY(c, hipEventRecord(c->calls_decoded, c->stream));
+        return PCOA_OK;
+      },
+      [&](int64_t, int64_t rows) -> int {
+        int rc2 = gram_device_bits(c, bits, rows, words, false);
+        if (rc2 != PCOA_OK) return rc2;
+        HIP_TRY(c, hipStreamWaitEvent(missing->stream, c->calls_decoded, 0));
+        if ((rc2 = gram_device_bits(missing, c->calls_bits, rows, words, false)) != PCOA_OK)
+          return fail(c, rc2, std::string(fn) + "the companion: " + missing->last_error);
+        HIP_TRY(c, hipEventRecord(c->calls_read, missing->stream));
+        c->calls_read_pending = true;
+        return PCOA_OK;
+      });
 }
 
 }  // extern "C"

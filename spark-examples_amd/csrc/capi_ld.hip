@@ -7,12 +7,15 @@
 // All of it is queued on the ctx stream; the chunk then ends with ONE host wait, for its kept count and its keep flags, and with
 // PCOA_LD_ACCUMULATE the compacted rows go to gram_device_bits as a device input whose pre-pass runs on the ctx stream (can_defer
 // = false: no side stream, no second read), so the next chunk's gather, queued on the same stream, cannot overtake its reader.
-// Only n, the device, the ctx stream and the staging slots of the ctx are used besides: every kind of ctx serves.
+// The rows reach run_chunk through the row feed (row_feed.h), host and device rows in the same chunks of ldp_chunk; the feed
+// ends without a host wait of its own, since every chunk's wait has covered the copy.  Only n, the device, the ctx stream and
+// the staging slots of the ctx are used besides: every kind of ctx serves.
 #include <cmath>
 #include <cstring>
 #include <string>
 
 #include "pcoa_ctx.h"
+#include "row_feed.h"
 
 using namespace pcoa;
 
@@ -20,8 +23,6 @@ namespace {
 
 constexpr int64_t kLdChunkRows = (int64_t)1 << 16;     // rows per chunk at most
 constexpr int64_t kLdChunkBytes = (int64_t)256 << 20;  // and bytes of rows per chunk
-
-inline int64_t words_of(const pcoa_ctx* c) { return ((int64_t)c->n + 31) / 32; }
 
 int not_begun(pcoa_ctx* c, const char* call) {
   return fail(c, PCOA_ERR_STATE, std::string(call) + ": no pruner is active; call pcoa_ld_begin first");
@@ -185,37 +186,15 @@ int pcoa_ld_bits(pcoa_ctx* c, const uint32_t* bits, int64_t n_variants, int64_t 
   CHECK_CTX(c);
   int rc = check_rows_call(c, "pcoa_ld_bits", bits, n_variants);
   if (rc != PCOA_OK) return rc;
-  const int64_t words = words_of(c);
-  if (ld_words < words) return fail(c, PCOA_ERR_INVALID_ARG, "pcoa_ld_bits: ld_words must be >= ceil(n_samples / 32)");
+  if ((rc = check_ld_words(c, "pcoa_ld_bits: ", ld_words)) != PCOA_OK) return rc;
   int64_t kept = 0;
   if (n_kept_out) *n_kept_out = 0;
-  const int64_t rows_cap = std::min(n_variants, c->ldp_chunk);
-  for (int64_t v0 = 0; v0 < n_variants; v0 += rows_cap) {
-    const int64_t rows = std::min(rows_cap, n_variants - v0);
-    uint8_t* ko = keep_out ? keep_out + v0 : nullptr;
-    if (is_device_ptr) {
-      if ((rc = run_chunk(c, bits + v0 * ld_words, ld_words, rows, ko, &kept)) != PCOA_OK) return rc;
-      continue;
-    }
-    // host bitsets: dense rows through the staging slots of pcoa_accumulate_bits
-    const int64_t need_bytes = rows * words * 4;
-    StagingRing::Slot* sl = nullptr;
-    if ((rc = staging_acquire(c, c->bs, (size_t)need_bytes, (size_t)(rows_cap * words * 4), &sl)) != PCOA_OK) return rc;
-    uint32_t* stage = static_cast<uint32_t*>(sl->dev[0]);
-    if (ld_words == words)
-      HIP_TRY(c, hipMemcpyAsync(stage, bits + v0 * ld_words, (size_t)need_bytes, hipMemcpyHostToDevice, c->csr_stream));
-    else
-      HIP_TRY(c, hipMemcpy2DAsync(stage, (size_t)words * 4, bits + v0 * ld_words, (size_t)ld_words * 4, (size_t)words * 4, (size_t)rows,
-                                  hipMemcpyHostToDevice, c->csr_stream));
-    if ((rc = staging_copied(c, *sl)) != PCOA_OK) return rc;
-    HIP_TRY(c, hipStreamWaitEvent(c->stream, sl->copied, 0));
-    rc = run_chunk(c, stage, words, rows, ko, &kept);
-    const int rc2 = staging_released(c, *sl, c->stream);   // (also after a failure: the slot's reader is whatever was queued)
-    if (rc != PCOA_OK) return rc;
-    if (rc2 != PCOA_OK) return rc2;
-  }
-  if (n_kept_out) *n_kept_out = kept;
-  return PCOA_OK;
+  rc = feed_bits(c, bits, n_variants, ld_words, std::min(n_variants, c->ldp_chunk), is_device_ptr != 0, false,
+                 [&](const uint32_t* rows_dev, int64_t ld, int64_t v0, int64_t rows) {
+                   return run_chunk(c, rows_dev, ld, rows, keep_out ? keep_out + v0 : nullptr, &kept);
+                 });
+  if (rc == PCOA_OK && n_kept_out) *n_kept_out = kept;
+  return rc;
 }
 
 int pcoa_ld_plink_bed(pcoa_ctx* c, const uint8_t* bed_rows, int64_t n_variants, int64_t row_bytes, int ref_is_a1, int is_device_ptr,
@@ -223,36 +202,18 @@ int pcoa_ld_plink_bed(pcoa_ctx* c, const uint8_t* bed_rows, int64_t n_variants, 
   CHECK_CTX(c);
   int rc = check_rows_call(c, "pcoa_ld_plink_bed", bed_rows, n_variants);
   if (rc != PCOA_OK) return rc;
-  if (row_bytes < ((int64_t)c->n + 3) / 4)
-    return fail(c, PCOA_ERR_INVALID_ARG, "pcoa_ld_plink_bed: row_bytes must be >= ceil(n_samples / 4)");
-  if (is_device_ptr != 0 && is_device_ptr != 1)
-    return fail(c, PCOA_ERR_INVALID_ARG, "pcoa_ld_plink_bed: is_device_ptr must be 0 or 1");
+  if ((rc = check_row_bytes(c, "pcoa_ld_plink_bed: ", row_bytes)) != PCOA_OK) return rc;
+  if ((rc = check_bed_source(c, "pcoa_ld_plink_bed: ", is_device_ptr, false)) != PCOA_OK) return rc;
   int64_t kept = 0;
   if (n_kept_out) *n_kept_out = 0;
   if (n_variants == 0) return PCOA_OK;
   const int64_t words = words_of(c);
   const int64_t rows_cap = std::min(n_variants, c->ldp_chunk);
   if ((rc = ensure(c, &c->ldp_bed, &c->ldp_bed_cap, rows_cap * words)) != PCOA_OK) return rc;
-  for (int64_t v0 = 0; v0 < n_variants; v0 += rows_cap) {
-    const int64_t rows = std::min(rows_cap, n_variants - v0);
-    const uint8_t* src = bed_rows + v0 * row_bytes;
-    StagingRing::Slot* sl = nullptr;
-    if (!is_device_ptr) {
-      if ((rc = staging_acquire(c, c->bs, (size_t)(rows * row_bytes), (size_t)(rows_cap * row_bytes), &sl)) != PCOA_OK) return rc;
-      HIP_TRY(c, hipMemcpyAsync(sl->dev[0], src, (size_t)(rows * row_bytes), hipMemcpyHostToDevice, c->csr_stream));
-      if ((rc = staging_copied(c, *sl)) != PCOA_OK) return rc;
-      HIP_TRY(c, hipStreamWaitEvent(c->stream, sl->copied, 0));
-      src = static_cast<const uint8_t*>(sl->dev[0]);
-    }
-    {
-      ScopedTimer t(c, T_DENSIFY);
-      HIP_TRY(c, launch_plink_bed_to_bits(src, row_bytes, rows, c->n, words, ref_is_a1 ? 1 : 0, c->ldp_bed, c->stream));
-    }
-    if (sl && (rc = staging_released(c, *sl, c->stream)) != PCOA_OK) return rc;   // the decode is the slot's only reader
-    if ((rc = run_chunk(c, c->ldp_bed, words, rows, keep_out ? keep_out + v0 : nullptr, &kept)) != PCOA_OK) return rc;
-  }
-  if (n_kept_out) *n_kept_out = kept;
-  return PCOA_OK;
+  rc = feed_bed(c, bed_rows, n_variants, row_bytes, rows_cap, is_device_ptr, false, bed_decoder(c, row_bytes, ref_is_a1, c->ldp_bed),
+                [&](int64_t v0, int64_t rows) { return run_chunk(c, c->ldp_bed, words, rows, keep_out ? keep_out + v0 : nullptr, &kept); });
+  if (rc == PCOA_OK && n_kept_out) *n_kept_out = kept;
+  return rc;
 }
 
 int pcoa_get_ld_stats(pcoa_ctx* c, pcoa_ld_stats* out_user, size_t out_size) {

@@ -4,8 +4,8 @@
 // component (loadings.hip).  pcoa_loadings_begin prepares the vectors ONCE on the host -- the mean as one left-to-right sum
 // divided by N, u - mean, zero beyond N, the divisors sqrt(lambda_c) -- and uploads them; the calls between begin and end stream
 // rows past them: caller's bitsets, raw .bed rows (decoded by plink_bed_to_bits_kernel, the rule of pcoa_accumulate_plink_bed) or
-// the rows of an operator ctx's store.  Only n, the device, the ctx stream and the staging slots of the ctx are used, so every
-// kind of ctx serves; nothing here reads or writes S or the store's contents.  All device work is queued on the ctx stream,
+// the rows of an operator ctx's store; host rows come through the row feed (row_feed.h).  Only n, the device, the ctx stream and
+// the staging slots of the ctx are used, so every kind of ctx serves; nothing here reads or writes S or the store's contents.  All device work is queued on the ctx stream,
 // behind whatever accumulation is queued there.
 #include <cmath>
 #include <cstring>
@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "pcoa_ctx.h"
+#include "row_feed.h"
 
 using namespace pcoa;
 
@@ -21,8 +22,6 @@ namespace {
 constexpr int64_t kLoadingsLaunchRows = (int64_t)1 << 22;   // rows per launch (the grid stays far inside 2^31 blocks)
 constexpr int64_t kLoadingsOutRows = (int64_t)1 << 16;      // rows whose results travel to a host `out` at a time
 constexpr int64_t kLoadingsSlotRows = (int64_t)1 << 17;     // host rows per staging slot (and <= 256 MiB)
-
-inline int64_t words_of(const pcoa_ctx* c) { return ((int64_t)c->n + 31) / 32; }
 
 int not_begun(pcoa_ctx* c, const char* call) {
   return fail(c, PCOA_ERR_STATE, std::string(call) + ": no vectors are resident; call pcoa_loadings_begin first");
@@ -148,36 +147,15 @@ int pcoa_loadings_bits(pcoa_ctx* c, const uint32_t* bits, int64_t n_variants, in
   CHECK_CTX(c);
   int rc = check_rows_call(c, "pcoa_loadings_bits", bits, n_variants, out);
   if (rc != PCOA_OK) return rc;
-  const int64_t words = words_of(c);
-  if (ld_words < words) return fail(c, PCOA_ERR_INVALID_ARG, "pcoa_loadings_bits: ld_words must be >= ceil(n_samples / 32)");
+  if ((rc = check_ld_words(c, "pcoa_loadings_bits: ", ld_words)) != PCOA_OK) return rc;
   if (n_variants == 0) return PCOA_OK;
   if (is_device_ptr) return run_rows(c, bits, n_variants, ld_words, out, out_is_device);
-  // host bitsets: dense rows through the two staging slots of pcoa_accumulate_bits, the copy of one chunk beside the kernels of
-  // the chunk before
-  const int64_t slot_rows = std::min<int64_t>(kLoadingsSlotRows, std::max<int64_t>(1, ((int64_t)256 << 20) / (words * 4)));
-  const int64_t rows_cap = std::min(n_variants, slot_rows);
-  StagingRing::Slot* last = nullptr;
-  for (int64_t v0 = 0; v0 < n_variants; v0 += rows_cap) {
-    const int64_t rows = std::min(rows_cap, n_variants - v0);
-    const int64_t need_bytes = rows * words * 4;
-    StagingRing::Slot* sl = nullptr;
-    if ((rc = staging_acquire(c, c->bs, (size_t)need_bytes, (size_t)(rows_cap * words * 4), &sl)) != PCOA_OK) return rc;
-    uint32_t* stage = static_cast<uint32_t*>(sl->dev[0]);
-    if (ld_words == words)
-      HIP_TRY(c, hipMemcpyAsync(stage, bits + v0 * ld_words, (size_t)need_bytes, hipMemcpyHostToDevice, c->csr_stream));
-    else
-      HIP_TRY(c, hipMemcpy2DAsync(stage, (size_t)words * 4, bits + v0 * ld_words, (size_t)ld_words * 4, (size_t)words * 4, (size_t)rows,
-                                  hipMemcpyHostToDevice, c->csr_stream));
-    if ((rc = staging_copied(c, *sl)) != PCOA_OK) return rc;
-    HIP_TRY(c, hipStreamWaitEvent(c->stream, sl->copied, 0));
-    rc = run_rows(c, stage, rows, words, out + v0 * c->ld_num_pc, out_is_device);
-    const int rc2 = staging_released(c, *sl, c->stream);   // (also after a failure: the slot's reader is whatever was queued)
-    if (rc != PCOA_OK) return rc;
-    if (rc2 != PCOA_OK) return rc2;
-    last = sl;
-  }
-  if (last) HIP_TRY(c, hipEventSynchronize(last->copied));   // the caller's rows have been read
-  return PCOA_OK;
+  // host rows: the copy of one chunk beside the kernels of the chunk before; the caller's rows have been read on return
+  const int64_t slot_rows = std::min<int64_t>(kLoadingsSlotRows, std::max<int64_t>(1, ((int64_t)256 << 20) / (words_of(c) * 4)));
+  return feed_bits(c, bits, n_variants, ld_words, std::min(n_variants, slot_rows), false, true,
+                   [&](const uint32_t* stage, int64_t ld, int64_t v0, int64_t rows) {
+                     return run_rows(c, stage, rows, ld, out + v0 * c->ld_num_pc, out_is_device);
+                   });
 }
 
 int pcoa_loadings_plink_bed(pcoa_ctx* c, const uint8_t* bed_rows, int64_t n_variants, int64_t row_bytes, int ref_is_a1,
@@ -185,37 +163,15 @@ int pcoa_loadings_plink_bed(pcoa_ctx* c, const uint8_t* bed_rows, int64_t n_vari
   CHECK_CTX(c);
   int rc = check_rows_call(c, "pcoa_loadings_plink_bed", bed_rows, n_variants, out);
   if (rc != PCOA_OK) return rc;
-  if (row_bytes < ((int64_t)c->n + 3) / 4)
-    return fail(c, PCOA_ERR_INVALID_ARG, "pcoa_loadings_plink_bed: row_bytes must be >= ceil(n_samples / 4)");
-  if (is_device_ptr != 0 && is_device_ptr != 1)
-    return fail(c, PCOA_ERR_INVALID_ARG, "pcoa_loadings_plink_bed: is_device_ptr must be 0 or 1");
+  if ((rc = check_row_bytes(c, "pcoa_loadings_plink_bed: ", row_bytes)) != PCOA_OK) return rc;
+  if ((rc = check_bed_source(c, "pcoa_loadings_plink_bed: ", is_device_ptr, false)) != PCOA_OK) return rc;
   if (n_variants == 0) return PCOA_OK;
   const int64_t words = words_of(c);
   const int64_t slot_rows = std::min<int64_t>(kLoadingsSlotRows, std::max<int64_t>(1, ((int64_t)256 << 20) / row_bytes));
   const int64_t rows_cap = std::min(n_variants, slot_rows);
   if ((rc = ensure(c, &c->ld_bits, &c->ld_bits_cap, rows_cap * words)) != PCOA_OK) return rc;
-  StagingRing::Slot* last = nullptr;
-  for (int64_t v0 = 0; v0 < n_variants; v0 += rows_cap) {
-    const int64_t rows = std::min(rows_cap, n_variants - v0);
-    const uint8_t* src = bed_rows + v0 * row_bytes;
-    StagingRing::Slot* sl = nullptr;
-    if (!is_device_ptr) {
-      if ((rc = staging_acquire(c, c->bs, (size_t)(rows * row_bytes), (size_t)(rows_cap * row_bytes), &sl)) != PCOA_OK) return rc;
-      HIP_TRY(c, hipMemcpyAsync(sl->dev[0], src, (size_t)(rows * row_bytes), hipMemcpyHostToDevice, c->csr_stream));
-      if ((rc = staging_copied(c, *sl)) != PCOA_OK) return rc;
-      HIP_TRY(c, hipStreamWaitEvent(c->stream, sl->copied, 0));
-      src = static_cast<const uint8_t*>(sl->dev[0]);
-      last = sl;
-    }
-    {
-      ScopedTimer t(c, T_DENSIFY);
-      HIP_TRY(c, launch_plink_bed_to_bits(src, row_bytes, rows, c->n, words, ref_is_a1 ? 1 : 0, c->ld_bits, c->stream));
-    }
-    if (sl && (rc = staging_released(c, *sl, c->stream)) != PCOA_OK) return rc;   // the decode is the slot's only reader
-    if ((rc = run_rows(c, c->ld_bits, rows, words, out + v0 * c->ld_num_pc, out_is_device)) != PCOA_OK) return rc;
-  }
-  if (last) HIP_TRY(c, hipEventSynchronize(last->copied));   // the caller's rows have been read
-  return PCOA_OK;
+  return feed_bed(c, bed_rows, n_variants, row_bytes, rows_cap, is_device_ptr, true, bed_decoder(c, row_bytes, ref_is_a1, c->ld_bits),
+                  [&](int64_t v0, int64_t rows) { return run_rows(c, c->ld_bits, rows, words, out + v0 * c->ld_num_pc, out_is_device); });
 }
 
 int pcoa_loadings_operator(pcoa_ctx* c, int64_t first_variant, int64_t n_variants, double* out, int out_is_device) {

@@ -4,7 +4,8 @@
 // stream ordering.  Who defines what:
 //   devmem.hip           the allocator (guard pages), regrow, debug_knobs
 //   operand.hip          S and its int64 fold, the operand buffers, the contractions, finalize
-//   capi_accumulate.hip  the staging ring and the input boundaries
+//   row_feed.hip         the staging ring; row_feed.h beside it: the loop that brings bitset / .bed rows through the ring
+//   capi_accumulate.hip  the input boundaries
 //   capi_reduce.hip      RCCL, reductions, export / import / read / load
 //   reduce_peers.hip     the partition and the chunk kernel of pcoa_gram_reduce_peers
 //   capi_compute.hip     the eigensolver workspace, computePca, strips, projection
@@ -32,7 +33,7 @@ struct EventPair {
 
 // A ring of two staging slots: the double-buffered host-to-device staging of a host caller's input on the copy stream
 // (pcoa_ctx::csr_stream), so that the copy of one chunk runs beside the kernels of the chunk before.  The protocol, in the
-// order a boundary goes through it (capi_accumulate.hip):
+// order a boundary goes through it (row_feed.hip; the bitset and .bed boundaries go through it in row_feed.h):
 //   staging_acquire    the next slot; the host waits for the slot's last reader (`freed`) before the slot may be rewritten
 //                      or regrown -- sizes are the boundary's own policy: it names what it needs and what to grow to
 //   (the copies, on the copy stream)
@@ -307,6 +308,7 @@ constexpr int64_t kCoresideMaxNpad = 16384;            // co-resident pipeline: 
 
 inline int64_t round_up(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
 inline double wall_now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+inline int64_t words_of(const pcoa_ctx* c) { return ((int64_t)c->n + 31) / 32; }   // words of a carrier bitset row
 inline size_t s_count(const pcoa_ctx* c) { return (size_t)c->n * (size_t)c->s_cols; }
 inline GramStrip strip_of(const pcoa_ctx* c) {
   GramStrip st;
@@ -374,10 +376,14 @@ hipError_t launch_reduce_chunk_i64(const ReduceSources& src, bool has64, int64_t
 
 // ---- capi_accumulate.hip
 int csr_validate(pcoa_ctx* c);
+
+// ---- row_feed.hip: the staging ring (protocol: StagingRing above)
 int staging_acquire(pcoa_ctx* c, StagingRing& r, size_t need, size_t grow_to, StagingRing::Slot** out, size_t need1 = 0,
                     size_t grow_to1 = 0);
 int staging_copied(pcoa_ctx* c, StagingRing::Slot& sl);
 int staging_released(pcoa_ctx* c, StagingRing::Slot& sl, hipStream_t reader);
+// hidden: shared between two translation units of the library and called from nowhere else, so it stays out of the dynamic symbols
+__attribute__((visibility("hidden"))) int staging_pin(pcoa_ctx* c, StagingRing::Slot& sl, int i, size_t need, size_t grow_to);
 int staging_wait_all(pcoa_ctx* c, StagingRing& r);
 void staging_destroy(StagingRing& r);
 

@@ -25,6 +25,30 @@ def _ptr(a):
     return ctypes.c_void_p(a.ctypes.data)
 
 
+_BITS_ROWS = (np.uint32, "int32", "bits must be 2-D [variants][words]")
+_BED_ROWS = (np.uint8, "uint8", "rows must be [variants][row_bytes]")
+
+
+def _rows_arg(rows, np_dtype, torch_dtype, what, pinned=False):
+    """The rows of a bitset / .bed boundary as (pointer, n_rows, row_stride, is_device, keepalive).  A torch CUDA tensor (dtype
+    torch.<torch_dtype>, unit inner stride) is read in place: the engine runs on its own stream, so whatever torch queued to
+    produce it is waited for.  pinned: a page-locked CPU tensor, taken as it lies (the queued form of the .bed boundaries).
+    Anything else goes through numpy; `what` is the ValueError of an array that is not 2-D.  keepalive owns the memory."""
+    if pinned or (hasattr(rows, "data_ptr") and getattr(rows, "is_cuda", False)):
+        import torch  # plumbing only: memory handles
+        assert rows.dtype == getattr(torch, torch_dtype) and rows.dim() == 2 and rows.stride(1) == 1
+        if pinned:
+            assert rows.is_pinned()
+        else:
+            torch.cuda.current_stream(rows.device).synchronize()
+        is_device = not pinned          # a page-locked tensor is host memory
+        return ctypes.c_void_p(rows.data_ptr()), int(rows.shape[0]), int(rows.stride(0)), is_device, rows
+    a = np.ascontiguousarray(rows, dtype=np_dtype)
+    if a.ndim != 2:
+        raise ValueError(what)
+    return _ptr(a), a.shape[0], a.shape[1], False, a
+
+
 class PcoaEngine(object):
     def __init__(self, n_samples, device=0, flags=L.PCOA_FLAG_DEFAULT, gram_kernel=None, eig=None, strip=None,
                  pipeline=True, operand=None, operator=False):
@@ -221,68 +245,32 @@ class PcoaEngine(object):
     def accumulate_bits(self, bits, n_variants=None, ld_words=None):
         """Bit-packed tile: row v = carrier bitset of variant v, sample i = bit (i & 31) of word i >> 5
         (`ingest.pack_bits` builds it).  numpy uint32 [V][W] (host) or a torch int32 CUDA tensor (read in place)."""
-        if hasattr(bits, "data_ptr") and getattr(bits, "is_cuda", False):
-            import torch  # plumbing only
-            assert bits.dtype == torch.int32 and bits.dim() == 2 and bits.stride(1) == 1
-            nv = int(bits.shape[0]) if n_variants is None else int(n_variants)
-            ldv = int(bits.stride(0)) if ld_words is None else int(ld_words)
-            self._keepalive.append(bits)
-            torch.cuda.current_stream(bits.device).synchronize()  # see accumulate_dense
-            self._check(self._lib.pcoa_accumulate_bits(self._ctx, ctypes.c_void_p(bits.data_ptr()), nv, ldv, 1))
-            return
-        a = np.ascontiguousarray(bits, dtype=np.uint32)
-        if a.ndim != 2:
-            raise ValueError("bits must be 2-D [variants][words]")
-        nv = a.shape[0] if n_variants is None else int(n_variants)
-        ldv = a.shape[1] if ld_words is None else int(ld_words)
-        self._check(self._lib.pcoa_accumulate_bits(self._ctx, _ptr(a), nv, ldv, 0))
+        ptr, nv, ldv, dev, keep = _rows_arg(bits, *_BITS_ROWS)
+        if dev:
+            self._keepalive.append(keep)
+        self._check(self._lib.pcoa_accumulate_bits(self._ctx, ptr, nv if n_variants is None else int(n_variants),
+                                                   ldv if ld_words is None else int(ld_words), int(dev)))
 
     def accumulate_plink_bed(self, rows, ref_is_a1=False, asynchronous=False):
         """Raw variant-major PLINK .bed rows, numpy uint8 [V][row_bytes] (host) or a torch uint8 CUDA tensor: decoded on the
         device (pcoa_accumulate_plink_bed).  asynchronous=True: a PINNED torch uint8 CPU tensor that is only queued
         (PCOA_BED_HOST_ASYNC): it must stay unmodified until the second later call has returned, or the next sync()."""
-        if asynchronous:
-            import torch  # plumbing only
-            assert rows.dtype == torch.uint8 and rows.dim() == 2 and rows.stride(1) == 1 and rows.is_pinned()
-            self._check(self._lib.pcoa_accumulate_plink_bed(self._ctx, ctypes.c_void_p(rows.data_ptr()), int(rows.shape[0]),
-                                                            int(rows.stride(0)), int(bool(ref_is_a1)), L.PCOA_BED_HOST_ASYNC))
-            return
-        if hasattr(rows, "data_ptr") and getattr(rows, "is_cuda", False):
-            import torch  # plumbing only
-            assert rows.dtype == torch.uint8 and rows.dim() == 2 and rows.stride(1) == 1
-            self._keepalive.append(rows)
-            torch.cuda.current_stream(rows.device).synchronize()
-            self._check(self._lib.pcoa_accumulate_plink_bed(self._ctx, ctypes.c_void_p(rows.data_ptr()), int(rows.shape[0]),
-                                                            int(rows.stride(0)), int(bool(ref_is_a1)), 1))
-            return
-        a = np.ascontiguousarray(rows, dtype=np.uint8)
-        if a.ndim != 2:
-            raise ValueError("rows must be [variants][row_bytes]")
-        self._check(self._lib.pcoa_accumulate_plink_bed(self._ctx, _ptr(a), a.shape[0], a.shape[1], int(bool(ref_is_a1)), 0))
+        ptr, nv, stride, source = self._bed_arg(rows, asynchronous)
+        self._check(self._lib.pcoa_accumulate_plink_bed(self._ctx, ptr, nv, stride, int(bool(ref_is_a1)), source))
+
+    def _bed_arg(self, rows, asynchronous):
+        """(pointer, rows, row_bytes, is_device_ptr) of the two accumulate_plink_bed* calls; a device tensor is kept alive."""
+        ptr, nv, stride, dev, keep = _rows_arg(rows, *_BED_ROWS, pinned=asynchronous)
+        if dev:
+            self._keepalive.append(keep)
+        return ptr, nv, stride, L.PCOA_BED_HOST_ASYNC if asynchronous else int(dev)
 
     def accumulate_plink_bed_calls(self, rows, companion, ref_is_a1=False, asynchronous=False):
         """accumulate_plink_bed feeding two engines from one read of the rows (pcoa_accumulate_plink_bed_calls): the carrier
         bitsets into this engine, the missing-call bitsets (code 01) into `companion`, an ordinary full engine with this one's
         N on this one's device.  The same three forms of `rows`, the same lifetime rules."""
-        fn, q = self._lib.pcoa_accumulate_plink_bed_calls, companion._ctx
-        if asynchronous:
-            import torch  # plumbing only
-            assert rows.dtype == torch.uint8 and rows.dim() == 2 and rows.stride(1) == 1 and rows.is_pinned()
-            self._check(fn(self._ctx, q, ctypes.c_void_p(rows.data_ptr()), int(rows.shape[0]), int(rows.stride(0)),
-                           int(bool(ref_is_a1)), L.PCOA_BED_HOST_ASYNC))
-            return
-        if hasattr(rows, "data_ptr") and getattr(rows, "is_cuda", False):
-            import torch  # plumbing only
-            assert rows.dtype == torch.uint8 and rows.dim() == 2 and rows.stride(1) == 1
-            self._keepalive.append(rows)
-            torch.cuda.current_stream(rows.device).synchronize()
-            self._check(fn(self._ctx, q, ctypes.c_void_p(rows.data_ptr()), int(rows.shape[0]), int(rows.stride(0)),
-                           int(bool(ref_is_a1)), 1))
-            return
-        a = np.ascontiguousarray(rows, dtype=np.uint8)
-        if a.ndim != 2:
-            raise ValueError("rows must be [variants][row_bytes]")
-        self._check(fn(self._ctx, q, _ptr(a), a.shape[0], a.shape[1], int(bool(ref_is_a1)), 0))
+        ptr, nv, stride, source = self._bed_arg(rows, asynchronous)
+        self._check(self._lib.pcoa_accumulate_plink_bed_calls(self._ctx, companion._ctx, ptr, nv, stride, int(bool(ref_is_a1)), source))
 
     def accumulate_dense_device_ptr(self, ptr, n_variants, ld):
         self._check(self._lib.pcoa_accumulate_dense_f32(self._ctx, ctypes.c_void_p(int(ptr)), int(n_variants),
@@ -677,45 +665,20 @@ class Loadings(object):
     def bits(self, bits, n_variants=None, ld_words=None, device_out=False):
         """Rows of carrier bitsets in accumulate_bits' layout: numpy uint32 [V][W] (host) or a torch int32 CUDA tensor."""
         e = self._eng
-        if hasattr(bits, "data_ptr") and getattr(bits, "is_cuda", False):
-            import torch  # plumbing only
-            assert bits.dtype == torch.int32 and bits.dim() == 2 and bits.stride(1) == 1
-            nv = int(bits.shape[0]) if n_variants is None else int(n_variants)
-            ldv = int(bits.stride(0)) if ld_words is None else int(ld_words)
-            out, optr = self._out(nv, device_out)
-            torch.cuda.current_stream(bits.device).synchronize()
-            e._check(e._lib.pcoa_loadings_bits(e._ctx, ctypes.c_void_p(bits.data_ptr()), nv, ldv, 1, optr, int(bool(device_out))))
-            self._done(True)
-            return out
-        a = np.ascontiguousarray(bits, dtype=np.uint32)
-        if a.ndim != 2:
-            raise ValueError("bits must be 2-D [variants][words]")
-        nv = a.shape[0] if n_variants is None else int(n_variants)
-        ldv = a.shape[1] if ld_words is None else int(ld_words)
+        ptr, nv, ldv, dev, _keep = _rows_arg(bits, *_BITS_ROWS)
+        nv, ldv = nv if n_variants is None else int(n_variants), ldv if ld_words is None else int(ld_words)
         out, optr = self._out(nv, device_out)
-        e._check(e._lib.pcoa_loadings_bits(e._ctx, _ptr(a), nv, ldv, 0, optr, int(bool(device_out))))
-        self._done(device_out)
+        e._check(e._lib.pcoa_loadings_bits(e._ctx, ptr, nv, ldv, int(dev), optr, int(bool(device_out))))
+        self._done(dev or device_out)
         return out
 
     def plink_bed(self, rows, ref_is_a1=False, device_out=False):
         """Raw variant-major PLINK .bed rows: numpy uint8 [V][row_bytes] (host) or a torch uint8 CUDA tensor."""
         e = self._eng
-        if hasattr(rows, "data_ptr") and getattr(rows, "is_cuda", False):
-            import torch  # plumbing only
-            assert rows.dtype == torch.uint8 and rows.dim() == 2 and rows.stride(1) == 1
-            out, optr = self._out(int(rows.shape[0]), device_out)
-            torch.cuda.current_stream(rows.device).synchronize()
-            e._check(e._lib.pcoa_loadings_plink_bed(e._ctx, ctypes.c_void_p(rows.data_ptr()), int(rows.shape[0]), int(rows.stride(0)),
-                                                    int(bool(ref_is_a1)), 1, optr, int(bool(device_out))))
-            self._done(True)
-            return out
-        a = np.ascontiguousarray(rows, dtype=np.uint8)
-        if a.ndim != 2:
-            raise ValueError("rows must be [variants][row_bytes]")
-        out, optr = self._out(a.shape[0], device_out)
-        e._check(e._lib.pcoa_loadings_plink_bed(e._ctx, _ptr(a), a.shape[0], a.shape[1], int(bool(ref_is_a1)), 0, optr,
-                                                int(bool(device_out))))
-        self._done(device_out)
+        ptr, nv, stride, dev, _keep = _rows_arg(rows, *_BED_ROWS)
+        out, optr = self._out(nv, device_out)
+        e._check(e._lib.pcoa_loadings_plink_bed(e._ctx, ptr, nv, stride, int(bool(ref_is_a1)), int(dev), optr, int(bool(device_out))))
+        self._done(dev or device_out)
         return out
 
     def operator(self, first=0, n=None, device_out=False):
@@ -765,42 +728,19 @@ class LdPruner(object):
     def bits(self, bits, n_variants=None, ld_words=None):
         """Rows of carrier bitsets in accumulate_bits' layout: numpy uint32 [V][W] (host) or a torch int32 CUDA tensor."""
         e = self._eng
-        if hasattr(bits, "data_ptr") and getattr(bits, "is_cuda", False):
-            import torch  # plumbing only
-            assert bits.dtype == torch.int32 and bits.dim() == 2 and bits.stride(1) == 1
-            nv = int(bits.shape[0]) if n_variants is None else int(n_variants)
-            ldv = int(bits.stride(0)) if ld_words is None else int(ld_words)
-            keep, kptr, kept = self._mask(nv)
-            torch.cuda.current_stream(bits.device).synchronize()
-            e._check(e._lib.pcoa_ld_bits(e._ctx, ctypes.c_void_p(bits.data_ptr()), nv, ldv, 1, kptr, ctypes.byref(kept)))
-        else:
-            a = np.ascontiguousarray(bits, dtype=np.uint32)
-            if a.ndim != 2:
-                raise ValueError("bits must be 2-D [variants][words]")
-            nv = a.shape[0] if n_variants is None else int(n_variants)
-            ldv = a.shape[1] if ld_words is None else int(ld_words)
-            keep, kptr, kept = self._mask(nv)
-            e._check(e._lib.pcoa_ld_bits(e._ctx, _ptr(a), nv, ldv, 0, kptr, ctypes.byref(kept)))
+        ptr, nv, ldv, dev, _keep = _rows_arg(bits, *_BITS_ROWS)
+        nv, ldv = nv if n_variants is None else int(n_variants), ldv if ld_words is None else int(ld_words)
+        keep, kptr, kept = self._mask(nv)
+        e._check(e._lib.pcoa_ld_bits(e._ctx, ptr, nv, ldv, int(dev), kptr, ctypes.byref(kept)))
         self.last_kept = int(kept.value)
         return keep.astype(bool)
 
     def plink_bed(self, rows, ref_is_a1=False):
         """Raw variant-major PLINK .bed rows: numpy uint8 [V][row_bytes] (host) or a torch uint8 CUDA tensor."""
         e = self._eng
-        if hasattr(rows, "data_ptr") and getattr(rows, "is_cuda", False):
-            import torch  # plumbing only
-            assert rows.dtype == torch.uint8 and rows.dim() == 2 and rows.stride(1) == 1
-            keep, kptr, kept = self._mask(rows.shape[0])
-            torch.cuda.current_stream(rows.device).synchronize()
-            e._check(e._lib.pcoa_ld_plink_bed(e._ctx, ctypes.c_void_p(rows.data_ptr()), int(rows.shape[0]), int(rows.stride(0)),
-                                              int(bool(ref_is_a1)), 1, kptr, ctypes.byref(kept)))
-        else:
-            a = np.ascontiguousarray(rows, dtype=np.uint8)
-            if a.ndim != 2:
-                raise ValueError("rows must be [variants][row_bytes]")
-            keep, kptr, kept = self._mask(a.shape[0])
-            e._check(e._lib.pcoa_ld_plink_bed(e._ctx, _ptr(a), a.shape[0], a.shape[1], int(bool(ref_is_a1)), 0, kptr,
-                                              ctypes.byref(kept)))
+        ptr, nv, stride, dev, _keep = _rows_arg(rows, *_BED_ROWS)
+        keep, kptr, kept = self._mask(nv)
+        e._check(e._lib.pcoa_ld_plink_bed(e._ctx, ptr, nv, stride, int(bool(ref_is_a1)), int(dev), kptr, ctypes.byref(kept)))
         self.last_kept = int(kept.value)
         return keep.astype(bool)
 

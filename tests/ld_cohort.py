@@ -12,8 +12,8 @@ import numpy as np
 
 from loadings_cohort import decode_bed, encode_bed, pack_rows   # (re-exported for the tests)
 
-__all__ = ["exceeds_matrix", "ld_rule", "ld_rule_nongreedy", "ld_pairs", "ld_cohort", "write_plink", "decode_bed", "encode_bed",
-           "pack_rows"]
+__all__ = ["exceeds_matrix", "ld_rule", "ld_rule_banded", "ld_rule_nongreedy", "ld_pairs", "ld_cohort", "write_plink",
+           "decode_bed", "encode_bed", "pack_rows"]
 
 
 def exceeds_matrix(x, t):
@@ -51,6 +51,29 @@ def ld_rule(x, window, t, breaks=()):
             continue
         s = _window_start(v, window, breaks)
         keep[v] = not (ex[v, s:v] & keep[s:v]).any()
+    return keep
+
+
+def ld_rule_banded(x, window, t, breaks=()):
+    """ld_rule without the V x V matrix, for cohorts of 10^5 rows: exceeds(v - d, v) is evaluated for d = 1 .. window only,
+    by the same three-product expression in the same dtypes, and the same greedy pass runs over the band."""
+    x = np.asarray(x)
+    v_total, n = x.shape
+    n64 = np.int64(n)
+    a = x.sum(axis=1, dtype=np.int64)
+    pf = (a * (n64 - a)).astype(np.float64)
+    ex = np.zeros((v_total, window), dtype=bool)        # ex[v, d - 1] = exceeds(v - d, v)
+    for d in range(1, min(window, v_total - 1) + 1):
+        c = (x[d:] & x[:-d]).sum(axis=1, dtype=np.int64)      # 0 / 1 rows: the AND is the product
+        df = (n64 * c - a[d:] * a[:-d]).astype(np.float64)
+        ex[d:, d - 1] = (df * df) > (np.float64(t) * (pf[d:] * pf[:-d]))
+    keep = np.zeros(v_total, dtype=bool)
+    breaks = sorted(int(b) for b in breaks)
+    for v in range(v_total):
+        if a[v] == 0 or a[v] == n:
+            continue
+        s = _window_start(v, window, breaks)
+        keep[v] = not (ex[v, :v - s] & keep[s:v][::-1]).any()
     return keep
 
 

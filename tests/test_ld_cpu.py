@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT, load_pkg
-from ld_cohort import exceeds_matrix, ld_cohort, ld_pairs, ld_rule, ld_rule_nongreedy
+from ld_cohort import exceeds_matrix, ld_cohort, ld_pairs, ld_rule, ld_rule_banded, ld_rule_nongreedy
 from test_operator_cpu import _run_driver, _run_python
 
 SHAPES = [(33, 300, 1, 0.5), (70, 700, 7, 0.2), (130, 1000, 64, 0.5), (260, 1000, 65, 0.8), (2504, 600, 50, 0.2),
@@ -50,6 +50,17 @@ def test_a_break_starts_a_new_window():
     for cut in (1, 50, 199):
         assert np.array_equal(ld_rule(x, 7, 0.2, breaks=[cut]), np.concatenate([ld_rule(x[:cut], 7, 0.2), ld_rule(x[cut:], 7, 0.2)]))
     assert np.array_equal(ld_rule(x, 7, 0.2, breaks=[0]), whole)
+
+
+@pytest.mark.parametrize("breaks", [(), (1, 50, 299, 300, 599)])
+@pytest.mark.parametrize("t", [0.1, 0.5])
+@pytest.mark.parametrize("w", [1, 5, 50])
+def test_the_banded_rule_is_the_rule(w, t, breaks):
+    """ld_rule_banded (the reference of the multi-chunk GPU tests, where a V x V matrix cannot be built) against ld_rule."""
+    x = ld_cohort(70, 600, 77)
+    keep = ld_rule(x, w, t, breaks=breaks)
+    assert 0 < keep.sum() < 600
+    assert np.array_equal(ld_rule_banded(x, w, t, breaks=breaks), keep)
 
 
 # ---- host logic -------------------------------------------------------------------------------------------------------------
