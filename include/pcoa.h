@@ -433,6 +433,82 @@ int pcoa_get_call_companion(const pcoa_ctx* ctx, pcoa_ctx** missing_out, int64_t
 int pcoa_accumulate_plink_bed_calls(pcoa_ctx* ctx, pcoa_ctx* missing, const uint8_t* bed_rows, int64_t n_variants,
                                     int64_t row_bytes, int ref_is_a1, int is_device_ptr);
 
+/* ---- KING-robust kinship screen from PLINK genotypes -----------------------------------------------------------------------------
+ * The carrier-Jaccard screen (pcoa_similar_pairs) depends on allele frequencies: on a cohort with population structure an
+ * unrelated pair of one population can share more carriers than a parent and a child.  The KING-robust coefficient does not.
+ * Per variant every sample is in exactly one class by its .bed code: R = 00 (hom A1), M = 01 (missing), H = 10 (het),
+ * A = 11 (hom A2); KING is symmetric in the two alleles, so there is no ref_is_a1.  Five PLANES -- bitsets of one class, one bit
+ * per sample and variant -- are accumulated into five ordinary full engines, in this order:
+ *   PCOA_KING_HET 0: H    PCOA_KING_MISSING 1: M    PCOA_KING_HET_OR_MISSING 2: H u M    PCOA_KING_HOM_A1 3: R    PCOA_KING_HOM_A2 4: A
+ * With G_p the finalized S of plane p and lower-case letters its diagonal (h_i = G_H(i, i), hm_i = G_HM(i, i), ...):
+ *   V        = r_i + a_i + hm_i                                          (int64; must be the same for every i)
+ *   hethet   = G_H(i, j)                                                 (both heterozygous)
+ *   s_hm     = G_HM(i, j) - G_H(i, j) - G_M(i, j)                        (one het, the other missing; H, M disjoint)
+ *   het_sum  = h_i + h_j - s_hm                                          (hets of i where j is called + hets of j where i is called)
+ *   ibs0     = (V - hm_i - hm_j + G_HM(i, j)) - G_R(i, j) - G_A(i, j)    (opposite homozygotes: the complement of H u M is R u A)
+ *   num      = hethet - 2 ibs0                                           (int64, may be negative)
+ *   the pair (i, j), i < j, is REPORTED iff het_sum > 0 and (double)num >= min_kinship * (double)het_sum
+ *   kinship  = (double)num / (double)het_sum                             (hosts only; the library returns the integers)
+ * -- one IEEE fp64 multiplication and one comparison, every integer below 2^53: variants_pca.king_counts / king_pairs_rule are
+ * the numpy statement and report the same pairs, bit for bit.  num / het_sum is the KING-robust estimator over the jointly
+ * called sites.  The rule above is the contract, not any tool's output.
+ *
+ * The planes: the caller creates five engines with pcoa_create (the same N, the same device, packed-operand) and owns them.
+ *   Refused before any device work by both calls, reported on planes[0] (on pcoa_last_error(NULL) where planes or planes[0] is
+ *   NULL), PCOA_ERR_INVALID_ARG: a NULL array or entry, a ctx that appears twice, differing N or device, a strip owner or an
+ *   operator ctx, a PCOA_FLAG_GRAM_F32_MFMA engine.
+ * pcoa_accumulate_plink_bed_king: pcoa_accumulate_plink_bed -- the same rows, chunking through the staging slots of planes[0],
+ *   lifetime rules and PCOA_BED_HOST_ASYNC behaviour -- feeding the FIVE planes from one read of the rows: host rows cross the
+ *   link once, one decode kernel reads each raw row once and writes the five bitset rows (samples >= N masked in every plane:
+ *   the padding codes of a row's last byte are 00 and would land in R), plane p's rows go into plane p on its own stream.  The
+ *   order between the streams is kept by events (one "decoded" event the planes 1 - 4 wait for, one "read" event per plane that
+ *   planes[0]'s stream waits for before the next decode); there is no host wait beyond the existing call's.  A chunk holds at
+ *   most 2^17 rows, and fewer where five plane buffers of that many rows would pass 1 GiB together.  An error of a plane is
+ *   reported on planes[0] and names the plane.
+ * pcoa_king_pairs: finalizes the five planes and reads their input checks (an invalidated S is never screened), then one
+ *   memory-bound screen of the upper triangle of the five matrices on planes[0]'s stream (diagonal, count, scan, write:
+ *   csrc/king.hip).
+ *   min_kinship: finite, in (0, 0.5].
+ *   out_pairs / capacity / *n_found_out: as pcoa_similar_pairs -- the first min(n_found, capacity) pairs in increasing (i, j)
+ *            order, the rest untouched; capacity == 0 counts only; *n_found_out is always the full count.
+ *   *n_variants_out: V, or NULL.  out_het: N entries h_0 .. h_{N-1}, or NULL.
+ *   PCOA_ERR_INVALID_ARG before any device work: n_found_out NULL, capacity < 0, capacity > 0 with out_pairs NULL, min_kinship
+ *            not finite or outside (0, 0.5].
+ *   PCOA_ERR_STATE: a plane has an int64 part (more than 2^30 variants; not built).
+ *   PCOA_ERR_INVALID_ARG behind the kernels, the message names the check: the planes were not fed the same rows -- V differs
+ *            between samples, or some ibs0, het_sum or s_hm is negative.  Nothing is written to the outputs then.
+ *   memory:  FIVE N x N int32 matrices (plus the main engine's where a PCA runs beside the screen): at N = 100,000 that is
+ *            200 GB (+ 40 GB).  The screen itself: N ceil(N / 1024) int32 counts, 3 N + 5 int64 and min(capacity, N (N - 1) / 2)
+ *            pairs of 32 bytes, allocated before the first launch and freed before the call returns.
+ * Content and order are a function of the five matrices and min_kinship alone.  The matrices are unchanged and the planes stay
+ * usable, also after an error.  Synchronising.  Statistics (on planes[0]): pcoa_get_king_stats.
+ * Not built: strips, operator engines, several devices, an int64 part in a plane, VCF input (carriers only), the
+ * min-heterozygosity ("between-family") variant, IBD-segment or PI_HAT estimates.
+ * Extends: computePca (VariantsPca.scala:198-231) by the relatedness screen the field runs before a PCA (PLINK 2 --king-cutoff,
+ * KING, SNPRelate), over Gram matrices built the way getSimilarityMatrix (:182-191) builds S; with pcoa_create_subset on the main
+ * engine: screen, drop one of each pair, decompose S[kept, kept]. */
+#define PCOA_KING_HET            0
+#define PCOA_KING_MISSING        1
+#define PCOA_KING_HET_OR_MISSING 2
+#define PCOA_KING_HOM_A1         3
+#define PCOA_KING_HOM_A2         4
+#define PCOA_KING_PLANES         5
+typedef struct pcoa_king_pair { int32_t i, j; int64_t hethet, ibs0, het_sum; } pcoa_king_pair;   /* i < j; 32 bytes */
+int pcoa_accumulate_plink_bed_king(pcoa_ctx* const* planes /* [PCOA_KING_PLANES] */, const uint8_t* bed_rows,
+                                   int64_t n_variants, int64_t row_bytes, int is_device_ptr);
+int pcoa_king_pairs(pcoa_ctx* const* planes, double min_kinship, pcoa_king_pair* out_pairs, int64_t capacity,
+                    int64_t* n_found_out, int64_t* n_variants_out /* V or NULL */, int64_t* out_het /* N x h_i or NULL */);
+
+/* What pcoa_king_pairs did, cumulative on planes[0] since pcoa_create / pcoa_reset_timings (a struct of its own, like
+ * pcoa_pairs_stats; it grows at its end; out_size = sizeof of the struct the caller compiled against).  Synchronising. */
+typedef struct pcoa_king_stats {
+  double king_seconds;   /* HIP-event time of the screens: diagonal, count, scans, write                                        */
+  int64_t king_bytes;    /* bytes of the five matrices the scan kernels read: 20 per entry of the count pass's (band, tile)
+                            blocks above the diagonal and of the (row, tile) cells the write pass read again                    */
+  int64_t king_calls;
+} pcoa_king_stats;
+int pcoa_get_king_stats(pcoa_ctx* plane0, pcoa_king_stats* out, size_t out_size);
+
 /* ---- per-variant loadings of the principal coordinates ---------------------------------------------------------------------
  * Which variants drive each axis (smartpca's SNP weights, PLINK 2's --pca var-wts).  With X the V x N carrier bit matrix and
  * J = I - 11^T / N, the decomposed matrix is B = J S J = (X J)^T (X J), so an eigenpair (u_c, lambda_c) of B is a right singular

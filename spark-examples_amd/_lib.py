@@ -123,6 +123,34 @@ class PcoaPairsStats(ctypes.Structure):
     ]
 
 
+PCOA_KING_HET = 0
+PCOA_KING_MISSING = 1
+PCOA_KING_HET_OR_MISSING = 2
+PCOA_KING_HOM_A1 = 3
+PCOA_KING_HOM_A2 = 4
+PCOA_KING_PLANES = 5
+
+
+class PcoaKingPair(ctypes.Structure):
+    """pcoa_king_pair: one reported pair of pcoa_king_pairs, i < j, with the three counts of the rule; 32 bytes."""
+    _fields_ = [
+        ("i", ctypes.c_int32),
+        ("j", ctypes.c_int32),
+        ("hethet", ctypes.c_int64),
+        ("ibs0", ctypes.c_int64),
+        ("het_sum", ctypes.c_int64),
+    ]
+
+
+class PcoaKingStats(ctypes.Structure):
+    """pcoa_king_stats: a struct of its own beside pcoa_timings, like pcoa_pairs_stats."""
+    _fields_ = [
+        ("king_seconds", ctypes.c_double),
+        ("king_bytes", ctypes.c_int64),
+        ("king_calls", ctypes.c_int64),
+    ]
+
+
 class PcoaLdStats(ctypes.Structure):
     """pcoa_ld_stats: what the LD pruner did, and the HIP-event time of each of its kernels."""
     _fields_ = [
@@ -179,6 +207,9 @@ _SIGNATURES = [
     ("pcoa_set_call_companion", ctypes.c_int, [_vp, _vp, _i64]),
     ("pcoa_get_call_companion", ctypes.c_int, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(_i64)]),
     ("pcoa_accumulate_plink_bed_calls", ctypes.c_int, [_vp, _vp, _vp, _i64, _i64, ctypes.c_int, ctypes.c_int]),
+    ("pcoa_accumulate_plink_bed_king", ctypes.c_int, [_vp, _vp, _i64, _i64, ctypes.c_int]),
+    ("pcoa_king_pairs", ctypes.c_int, [_vp, ctypes.c_double, _vp, _i64, ctypes.POINTER(_i64), ctypes.POINTER(_i64), _vp]),
+    ("pcoa_get_king_stats", ctypes.c_int, [_vp, ctypes.POINTER(PcoaKingStats), ctypes.c_size_t]),
     ("pcoa_loadings_begin", ctypes.c_int, [_vp, _i32, _vp, _vp, ctypes.c_uint32]),
     ("pcoa_loadings_bits", ctypes.c_int, [_vp, _vp, _i64, _i64, ctypes.c_int, _vp, ctypes.c_int]),
     ("pcoa_loadings_plink_bed", ctypes.c_int, [_vp, _vp, _i64, _i64, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int]),

@@ -228,6 +228,7 @@ void pcoa_destroy(pcoa_ctx* c) {
   loadings_destroy(c);
   ld_destroy(c);
   complete_destroy(c);
+  king_destroy(c);
   if (c->pack_stream) (void)hipStreamDestroy(c->pack_stream);
   if (c->gram_stream) (void)hipStreamDestroy(c->gram_stream);
   if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
@@ -412,6 +413,7 @@ int pcoa_reset_timings(pcoa_ctx* c) {
   c->op_products = 0;
   c->subset_bytes = 0;
   c->pairs_bytes = c->pairs_calls = 0;
+  c->king_bytes = c->king_calls = 0;
   c->ld_variants = c->ld_bytes = 0;
   c->ldp_seen = c->ldp_kept = c->ldp_mono = c->ldp_pairs = 0;
   c->reduce_peers_calls = c->reduce_peers_bytes_in = 0;

@@ -16,6 +16,7 @@
 //   capi_loadings.hip    pcoa_loadings_*: per-variant loadings of the principal coordinates from bitsets, .bed rows, the store
 //   capi_ld.hip          pcoa_ld_*: LD pruning of the variant rows in front of the accumulation
 //   capi_complete.hip    pcoa_set_call_companion / pcoa_accumulate_plink_bed_calls: the pairwise-complete similarity
+//   capi_king.hip        pcoa_accumulate_plink_bed_king / pcoa_king_pairs: the KING-robust kinship screen over five planes
 //   pcoa_capi.hip        create / destroy, errors, timings
 #pragma once
 
@@ -24,7 +25,7 @@
 
 #include "pcoa_internal.h"
 
-enum TimeCat { T_GRAM = 0, T_DENSIFY, T_SYNTH, T_FINALIZE, T_CENTER, T_TRIDIAG, T_EIG, T_BACK, T_PACK, T_LANCZOS, T_ALLREDUCE, T_OPERATOR, T_SUBSET, T_REDUCE_PEERS, T_PAIRS, T_LOADINGS, T_LD_COUNT, T_LD_BAND, T_LD_RESOLVE, T_LD_COMPACT, T_NCAT };
+enum TimeCat { T_GRAM = 0, T_DENSIFY, T_SYNTH, T_FINALIZE, T_CENTER, T_TRIDIAG, T_EIG, T_BACK, T_PACK, T_LANCZOS, T_ALLREDUCE, T_OPERATOR, T_SUBSET, T_REDUCE_PEERS, T_PAIRS, T_LOADINGS, T_LD_COUNT, T_LD_BAND, T_LD_RESOLVE, T_LD_COMPACT, T_KING, T_NCAT };
 
 struct EventPair {
   hipEvent_t a, b;
@@ -140,6 +141,8 @@ struct pcoa_ctx {
     double st[2];
     int64_t ld[2];   // {kept, monomorphic} of an LD-pruning chunk
     int32_t cflag;   // complete_diag_kernel's flag: some Q(i, i) > V
+    int32_t kflag[pcoa::kKingFlagWords];   // the four consistency checks of the kinship screen
+    int64_t king[3]; // its V, n_found and the entries the write pass read again
   };
   HostWords* hw = nullptr;
 
@@ -261,6 +264,13 @@ struct pcoa_ctx {
   int64_t calls_bits_cap = 0;
   hipEvent_t calls_decoded = nullptr, calls_read = nullptr;
   bool calls_read_pending = false;   // the companion's pre-pass of the last chunk may still be reading calls_bits
+  // pcoa_accumulate_plink_bed_king, on planes[0] (capi_king.hip): the five planes' rows of one chunk, [plane][rows][words]; the
+  // event the planes 1 - 4 wait for behind the decode, and the event each of them records behind its pre-pass of the chunk
+  uint32_t* king_bits = nullptr;
+  int64_t king_bits_cap = 0;
+  hipEvent_t king_decoded = nullptr, king_read[PCOA_KING_PLANES] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  bool king_read_pending = false;    // those pre-passes may still be reading king_bits
+  int64_t king_bytes = 0, king_calls = 0;   // pcoa_king_pairs: bytes of the five matrices its scan kernels read, calls
 
   // timings
   std::vector<EventPair> pending;
@@ -408,6 +418,9 @@ int complete_centre(pcoa_ctx* c, bool sym_form, double* b);
 int complete_b(pcoa_ctx* c, double* b);
 void complete_bind(const pcoa_ctx* c, EigWorkspace* ws);
 void complete_destroy(pcoa_ctx* c);   // the buffers, the events and an owned companion
+
+// ---- capi_king.hip
+void king_destroy(pcoa_ctx* c);   // the plane rows and the events, behind their last readers
 
 // ---- capi_operator.hip
 int operator_append(pcoa_ctx* c, const uint32_t* bits_dev, int64_t nv, int64_t ld_words);

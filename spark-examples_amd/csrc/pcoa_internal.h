@@ -185,6 +185,23 @@ hipError_t launch_pairs_write(const int32_t* s32, const int64_t* s64_or_null, in
                               const int32_t* prefix, const int64_t* rowoff, int64_t capacity, pcoa_pair* out,
                               unsigned long long* entries_read, hipStream_t stream);
 
+// ---- the KING-robust kinship screen over five Gram matrices (king.hip; the rule is stated at the top of that file).  The
+// matrices and the decode's five output buffers travel by value in the kernels' arguments, indexed by PCOA_KING_*.  The grid,
+// cnt and rowoff are the pairs screen's (pairs_tiles, launch_pairs_scan).  flag: four int32 words zeroed by the caller, one per
+// consistency check; h, hm: n int64 each; v: one int64 (V), written by the diagonal kernel and read by the two passes
+struct KingMatrices { const int32_t* p[PCOA_KING_PLANES]; };
+struct KingPlaneRows { uint32_t* p[PCOA_KING_PLANES]; };
+constexpr int kKingFlagV = 0, kKingFlagIbs0 = 1, kKingFlagHetSum = 2, kKingFlagSHm = 3, kKingFlagWords = 4;
+// PLINK .bed rows -> the five class bitsets (dense rows of `words` words, samples >= n masked in every plane), one read
+hipError_t launch_plink_bed_to_king_planes(const uint8_t* bed, int64_t row_bytes, int64_t nv, int32_t n, int64_t words,
+                                           const KingPlaneRows& out, hipStream_t stream);
+hipError_t launch_king_diag(const KingMatrices& g, int32_t n, int64_t* h, int64_t* hm, int64_t* v, int32_t* flag, hipStream_t stream);
+hipError_t launch_king_count(const KingMatrices& g, int32_t n, const int64_t* h, const int64_t* hm, const int64_t* v, double x,
+                             int32_t* cnt, int32_t* flag, hipStream_t stream);
+hipError_t launch_king_write(const KingMatrices& g, int32_t n, const int64_t* h, const int64_t* hm, const int64_t* v, double x,
+                             const int32_t* prefix, const int64_t* rowoff, int64_t capacity, pcoa_king_pair* out,
+                             unsigned long long* entries_read, hipStream_t stream);
+
 // ---- implicit similarity operator (operator_bits.hip): y = X^T (X v) from the carrier bitsets, S never formed -------------
 // The store is a list of segments, each rows x operator_pitch_words(n) words; bits of samples >= n and the pitch's padding are
 // zero.  A product's additions are ordered by sample group (kOperatorGroupWords word columns), segment and range of

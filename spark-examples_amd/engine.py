@@ -409,6 +409,67 @@ class PcoaEngine(object):
         n_found = int(found.value)
         return pairs[:min(n_found, cap)], n_found, diag
 
+    # ------------------------------------------------------------------ KING-robust kinship over five planes
+    KING_PAIR_DTYPE = np.dtype([("i", np.int32), ("j", np.int32), ("hethet", np.int64), ("ibs0", np.int64),
+                                ("het_sum", np.int64)])   # pcoa_king_pair
+
+    @staticmethod
+    def _king_planes(planes):
+        """(the library, planes[0] or None, the ctx array) of a sequence of five engines; an entry may be None (the library
+        refuses it).  Errors are reported on planes[0], or on the thread where there is none."""
+        planes = list(planes) if planes is not None else None
+        if planes is not None and len(planes) != L.PCOA_KING_PLANES:
+            raise ValueError("planes must be %d engines (het, missing, het_or_missing, hom_a1, hom_a2)" % L.PCOA_KING_PLANES)
+        lib = L.load()
+        if planes is None:
+            return lib, None, None
+        arr = (ctypes.c_void_p * L.PCOA_KING_PLANES)(*[p._ctx if p is not None else None for p in planes])
+        return lib, planes[0], arr
+
+    @staticmethod
+    def _king_check(lib, first, rc):
+        if rc != L.PCOA_OK:
+            msg = lib.pcoa_last_error(first._ctx if first is not None else None)
+            raise PcoaError(rc, msg.decode() if msg else "")
+
+    @staticmethod
+    def accumulate_plink_bed_king(planes, rows, asynchronous=False):
+        """accumulate_plink_bed feeding the five genotype-class planes from one read of the rows
+        (pcoa_accumulate_plink_bed_king): `planes` are five ordinary engines of one N on one device, in the order het, missing,
+        het_or_missing, hom_a1, hom_a2 (variants_pca.king_planes is the decode).  The same three forms of `rows`, the same
+        lifetime rules; the staging and the keep-alive are planes[0]'s."""
+        lib, first, arr = PcoaEngine._king_planes(planes)
+        if first is not None:
+            ptr, nv, stride, source = first._bed_arg(rows, asynchronous)
+        else:
+            a = np.ascontiguousarray(rows, dtype=np.uint8)
+            ptr, nv, stride, source = _ptr(a), a.shape[0], a.shape[1], 0
+        PcoaEngine._king_check(lib, first, lib.pcoa_accumulate_plink_bed_king(arr, ptr, nv, stride, source))
+
+    @staticmethod
+    def king_pairs(planes, min_kinship, capacity=1 << 20):
+        """The KING-robust kinship screen (pcoa_king_pairs) over the five planes' matrices: the pairs i < j with het_sum > 0
+        and hethet - 2 ibs0 >= min_kinship * het_sum (variants_pca.king_counts / king_pairs_rule are the rule), found on the
+        device in one pass over the upper triangles.  Returns (pairs, n_found, n_variants, het): `pairs` a structured array
+        (fields i, j, hethet, ibs0, het_sum) of the first min(n_found, capacity) pairs in increasing (i, j) order, `n_found` the
+        full count whatever the capacity, n_variants = V, `het` int64 [N] the heterozygous calls of each sample."""
+        lib, first, arr = PcoaEngine._king_planes(planes)
+        cap = int(capacity)
+        pairs = np.zeros(max(cap, 0), dtype=PcoaEngine.KING_PAIR_DTYPE)
+        n = first.n if first is not None else 0
+        het = np.zeros(n, dtype=np.int64)
+        found, v = ctypes.c_int64(0), ctypes.c_int64(0)
+        PcoaEngine._king_check(lib, first, lib.pcoa_king_pairs(arr, float(min_kinship), _ptr(pairs) if cap > 0 else None, cap,
+                                                                ctypes.byref(found), ctypes.byref(v), _ptr(het) if n else None))
+        n_found = int(found.value)
+        return pairs[:min(n_found, cap)], n_found, int(v.value), het
+
+    def king_stats(self):
+        """pcoa_get_king_stats of this engine as planes[0]: king_seconds / king_bytes / king_calls."""
+        k = L.PcoaKingStats()
+        self._check(self._lib.pcoa_get_king_stats(self._ctx, ctypes.byref(k), ctypes.sizeof(k)))
+        return dict((f[0], getattr(k, f[0])) for f in L.PcoaKingStats._fields_)
+
     SIMILARITY_KINDS = {"shared": 0, "jaccard": 1, "cosine": 2}   # PCOA_SIMILARITY_*
 
     def set_similarity(self, kind):

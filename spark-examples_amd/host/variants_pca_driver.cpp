@@ -101,6 +101,12 @@ struct Conf {  // PcaConf / GenomicsConf (GenomicsConf.scala:31-101), same flag 
   int64_t related_max_pairs = 1048576;  // --related-max-pairs M: the capacity handed to the library; more reported pairs stop the job
   bool related_max_pairs_given = false;
   bool remove_related = false;          // --remove-related: drop one sample of every reported pair, go on with pcoa_create_subset over the rest
+  bool king = false;                    // --king-cutoff X given: the KING-robust kinship screen before computePca (pcoa_king_pairs) over five
+  double king_cutoff = 0.0;             // plane engines fed the same streamed .bed blocks (pcoa_accumulate_plink_bed_king); X in (0, 0.5]
+  std::string king_output_path;         // --king-output-path FILE: the reported pairs, one line each
+  int64_t king_max_pairs = 1048576;     // --king-max-pairs M: the capacity handed to the library; more reported pairs stop the job
+  bool king_max_pairs_given = false;
+  bool king_remove = false;             // --king-remove: the rule of --remove-related over the pairs of the kinship screen
   std::string similarity_measure = "shared";  // --similarity-measure shared|jaccard|cosine: what computePca decomposes (pcoa_set_similarity);
                                               // jaccard / cosine are evaluated on the fly from S, set on the engine that runs computePca
   std::string loadings_output_path;     // --loadings-output-path FILE: the loading of every variant fed to the engine on each of the --num-pc
@@ -135,6 +141,10 @@ const char* kUsage =
     "                   (before computePca: report the sample pairs whose carrier sets have a Jaccard index >= X, X in (0, 1];\n"
     "                   --remove-related drops one sample of each pair and decomposes S[kept, kept]; one engine, stored S,\n"
     "                   full layout)\n"
+    "                   --king-cutoff X [--king-output-path FILE] [--king-max-pairs M] [--king-remove]\n"
+    "                   (before computePca: report the sample pairs whose KING-robust kinship (hethet - 2 ibs0) / het_sum is >= X,\n"
+    "                   X in (0, 0.5], 0.177 = first degree; independent of allele frequencies; --king-remove drops one sample of\n"
+    "                   each pair as --remove-related does; one streamed PLINK fileset, one device, five more N x N matrices)\n"
     "                   --similarity-measure shared|jaccard|cosine (what computePca decomposes: the counts S as the reference,\n"
     "                   S(i,j) / (S(i,i) + S(j,j) - S(i,j)), or S(i,j) / sqrt(S(i,i) S(j,j)), evaluated on the fly from S; one\n"
     "                   engine, stored S, full layout, no projection)\n"
@@ -166,6 +176,7 @@ std::string strips_refuse_measure(const std::string& m) {
 }
 const char* kStripsRefuseMissing = "--missing-calls pairwise needs two whole similarity matrices on one device: it cannot take --layout strips";
 const char* kStripsRefuseRelated = "--related-min-jaccard screens one whole similarity matrix on one engine: it cannot take --layout strips";
+const char* kStripsRefuseKing = "--king-cutoff screens five whole Gram matrices on one device: it cannot take --layout strips";
 
 Conf parse(int argc, char** argv) {
   Conf c;
@@ -252,6 +263,24 @@ Conf parse(int argc, char** argv) {
       c.related_max_pairs_given = true;
     }
     else if (a == "--remove-related") c.remove_related = true;
+    else if (a == "--king-cutoff") {   // a value that does not parse must not silently mean "off"
+      const std::string v = one(i);
+      char* end = nullptr;
+      c.king_cutoff = std::strtod(v.c_str(), &end);
+      if (v.empty() || *end != 0) die("--king-cutoff takes a number in (0, 0.5], not '" + v + "'");
+      c.king = true;
+    }
+    else if (a == "--king-output-path") c.king_output_path = one(i);
+    else if (a == "--king-max-pairs") {
+      const std::string v = one(i);
+      char* end = nullptr;
+      errno = 0;
+      const long long m = std::strtoll(v.c_str(), &end, 10);
+      if (v.empty() || *end != 0 || errno != 0) die("--king-max-pairs takes an integer >= 0, not '" + v + "'");
+      c.king_max_pairs = (int64_t)m;
+      c.king_max_pairs_given = true;
+    }
+    else if (a == "--king-remove") c.king_remove = true;
     else if (a == "--similarity-measure") {
       c.similarity_measure = one(i);
       if (c.similarity_measure != "shared" && c.similarity_measure != "jaccard" && c.similarity_measure != "cosine")
@@ -319,6 +348,28 @@ Conf parse(int argc, char** argv) {
     if (c.gram == "implicit") die("--related-min-jaccard screens a stored similarity matrix: it cannot take --gram implicit");
     if (c.layout == "strips") die(kStripsRefuseRelated);
     if (!c.project_input_path.empty()) die("--related-min-jaccard screens the cohort it decomposes: it cannot take --project-input-path");
+  }
+  // --king-cutoff and its companions: likewise, naming both flags
+  if (!c.king) {
+    if (!c.king_output_path.empty()) die("--king-output-path needs --king-cutoff X (the screen is off without it)");
+    if (c.king_max_pairs_given) die("--king-max-pairs needs --king-cutoff X (the screen is off without it)");
+    if (c.king_remove) die("--king-remove needs --king-cutoff X (the screen is off without it)");
+  } else {
+    if (!(c.king_cutoff > 0 && c.king_cutoff <= 0.5)) die("--king-cutoff must be a finite number in (0, 0.5]");
+    if (c.king_max_pairs < 0) die("--king-max-pairs must be >= 0 (the pairs --king-cutoff may report)");
+    if (c.gram == "implicit") die("--king-cutoff screens stored Gram matrices: it cannot take --gram implicit");
+    if (c.layout == "strips") die(kStripsRefuseKing);
+    if (c.gpus > 1) die("--king-cutoff runs on one engine and its five planes: it cannot take --gpus " + std::to_string(c.gpus));
+    if (c.ld_window > 0) die("--king-cutoff: the planes would need the pruned rows: it cannot take --ld-window");
+    if (c.related) die("--king-cutoff: one relatedness screen per run: it cannot take --related-min-jaccard");
+    if (!c.project_input_path.empty()) die("--king-cutoff screens the cohort it decomposes: it cannot take --project-input-path");
+    const std::string ext = c.input_path.size() == 1 && c.input_path[0].size() >= 4 ? c.input_path[0].substr(c.input_path[0].size() - 4) : "";
+    if (c.has_maf || (ext != ".bed" && ext != ".bim" && ext != ".fam"))
+      die("--king-cutoff reads the genotype classes of one PLINK fileset: --input-path must name a single .bed / .bim / .fam "
+          "(VCF ingest yields carriers only)");
+    if (c.no_stream) die("--king-cutoff feeds the streamed .bed blocks to the five planes: it cannot take --no-stream");
+    if (c.parse_only) die("--king-cutoff runs on the device: it cannot take --parse-only");
+    if (c.plink_decode == "host") die("--king-cutoff decodes the five planes on the device: it cannot take --plink-decode host");
   }
   // --similarity-measure jaccard | cosine: likewise
   if (c.similarity_measure != "shared") {
@@ -514,6 +565,13 @@ struct CallsFeed {
   pcoa_ctx* companion = nullptr;
 };
 CallsFeed g_calls;
+// --king-cutoff: the five plane engines (PCOA_KING_*) that take the genotype-class bitsets of the same streamed .bed blocks;
+// created beside engine 0, destroyed right after the screen
+struct KingFeed {
+  bool on = false;
+  pcoa_ctx* planes[PCOA_KING_PLANES] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+};
+KingFeed g_king;
 struct Variant {
   std::string key;                 // getVariantKey
   VarMeta meta;                    // (g_want_meta)
@@ -1297,6 +1355,9 @@ void stream_plink_shard(const Conf& conf, const PlinkMeta& m, int g, int k, pcoa
           check(ctx, pcoa_accumulate_plink_bed_calls(ctx, g_calls.companion, buf[w], kept, (int64_t)bpv, ref_a1 ? 1 : 0, PCOA_BED_HOST_ASYNC),
                 "getSimilarityMatrix");
         else check(ctx, pcoa_accumulate_plink_bed(ctx, buf[w], kept, (int64_t)bpv, ref_a1 ? 1 : 0, PCOA_BED_HOST_ASYNC), "getSimilarityMatrix");
+        if (g_king.on)   // the same block to the five planes: it crosses the link a second time, through planes[0]'s staging slots
+          check(g_king.planes[0], pcoa_accumulate_plink_bed_king(g_king.planes, buf[w], kept, (int64_t)bpv, PCOA_BED_HOST_ASYNC),
+                "getSimilarityMatrix");
         total += kept;
       }
       feed_s += secs(t1, now());
@@ -1318,6 +1379,8 @@ void stream_plink_shard(const Conf& conf, const PlinkMeta& m, int g, int k, pcoa
     auto t3 = now();
     check(ctx, pcoa_sync(ctx), "getSimilarityMatrix");  // the blocks are released by the caller next
     if (g_calls.on) check(g_calls.companion, pcoa_sync(g_calls.companion), "getSimilarityMatrix");
+    if (g_king.on)
+      for (pcoa_ctx* p : g_king.planes) check(p, pcoa_sync(p), "getSimilarityMatrix");
     feed_s += secs(t3, now());
   } else {
   int which = 0;
@@ -1577,6 +1640,7 @@ int main(int argc, char** argv) {
   const bool want_loadings = !conf.loadings_output_path.empty();
   g_ld.on = conf.ld_window > 0;
   g_calls.on = conf.missing_calls == "pairwise";
+  g_king.on = conf.king;
   g_want_meta = want_loadings || g_ld.on;   // (--ld-window: the contigs place the breaks)
   if (conf.input_path.empty())
     die("--input-path <file.vcf[.gz]> [more files] or one PLINK fileset (<prefix>.bed) is required: the Google Genomics API the reference read "
@@ -1775,6 +1839,7 @@ int main(int argc, char** argv) {
     if (layout == PCOA_LAYOUT_STRIPS) {
       if (conf.outlier_iterations > 0) die(kStripsRefuseOutliers);   // --layout auto resolved to strips
       if (conf.related) die(kStripsRefuseRelated);
+      if (conf.king) die(kStripsRefuseKing);
       if (conf.similarity_measure != "shared") die(strips_refuse_measure(conf.similarity_measure));
       if (g_calls.on) die(kStripsRefuseMissing);
       if (conf.reduce == "rccl") die("the strip layout has no reduction step: it cannot take --reduce rccl");
@@ -1872,6 +1937,12 @@ int main(int argc, char** argv) {
         die(std::string("pcoa_create (the call companion): ") + pcoa_last_error(nullptr));
       check(g_calls.companion, pcoa_reserve(g_calls.companion, (int64_t)1 << 20, 0), "pcoa_reserve");
     }
+    if (g_king.on)      // the five planes beside engine 0, with their operand buffers
+      for (pcoa_ctx*& p : g_king.planes) {
+        if (pcoa_create(&p, n, conf.gpu_map[0], PCOA_FLAG_DEFAULT) != PCOA_OK)
+          die(std::string("pcoa_create (a plane of --king-cutoff): ") + pcoa_last_error(nullptr));
+        check(p, pcoa_reserve(p, (int64_t)1 << 20, 0), "pcoa_reserve");
+      }
     if (!stream_plink) return;
     for (int q = 0; q < 4 * conf.gpus; ++q) {
       void* b = nullptr;
@@ -2049,6 +2120,29 @@ int main(int argc, char** argv) {
       if (!out) die("cannot write " + conf.call_rate_output_path);
     }
   }
+  // --remove-related / --king-remove: the engine replaced by its subset over the samples a screen keeps (one gather of S, no
+  // variant read twice); `gone` is sorted
+  auto drop_samples = [&](const std::vector<int32_t>& gone, const char* remove_flag, const char* threshold_flag) {
+    if (gone.empty()) return;
+    const int32_t least = std::max(3, conf.num_pc + 1);
+    if (n - (int32_t)gone.size() < least)
+      die(std::string(remove_flag) + " would leave " + std::to_string(n - (int32_t)gone.size()) + " of " + std::to_string(n) +
+          " samples, fewer than the " + std::to_string(least) + " that " + std::to_string(conf.num_pc) +
+          " principal components need; raise " + threshold_flag);
+    std::vector<int32_t> keep;
+    size_t g = 0;
+    for (int32_t i = 0; i < n; ++i) {
+      if (g < gone.size() && gone[g] == i) ++g;
+      else keep.push_back(i);
+    }
+    pcoa_ctx* sub = nullptr;
+    check(ctx, pcoa_create_subset(&sub, ctx, keep.data(), (int32_t)keep.size()), "pcoa_create_subset");
+    pcoa_timings tp;   // the Gram kernels ran on the predecessor: its time goes into the closing line
+    if (pcoa_get_timings(ctx, &tp) == PCOA_OK) gram_s_before += tp.gram_kernel_seconds;
+    pcoa_destroy(ctx);
+    ctx = owners[0] = sub;
+    kept.swap(keep);
+  };
   if (conf.related) {
     // --related-min-jaccard X, before the first computePca: the screen of S on the device.  The rule, as pcoa.h and
     // variants_pca.py's related_pairs_rule state it: with d_i = S(i, i) and U = d_i + d_j - S(i, j), the pair (i, j), i < j, is
@@ -2078,26 +2172,41 @@ int main(int argc, char** argv) {
     for (int32_t i : gone) gone_names += (gone_names.empty() ? ": " : ", ") + names[(size_t)i];
     std::fprintf(stderr, "Related pairs: %lld at jaccard >= %s; removed %zu sample(s)%s\n", (long long)n_found,
                  java_double(conf.related_min_jaccard).c_str(), gone.size(), gone_names.c_str());
-    if (!gone.empty()) {
-      const int32_t least = std::max(3, conf.num_pc + 1);
-      if (n - (int32_t)gone.size() < least)
-        die("--remove-related would leave " + std::to_string(n - (int32_t)gone.size()) + " of " + std::to_string(n) +
-            " samples, fewer than the " + std::to_string(least) + " that " + std::to_string(conf.num_pc) +
-            " principal components need; raise --related-min-jaccard");
-      std::vector<int32_t> keep;
-      size_t g = 0;
-      for (int32_t i = 0; i < n; ++i) {
-        if (g < gone.size() && gone[g] == i) ++g;
-        else keep.push_back(i);
-      }
-      pcoa_ctx* sub = nullptr;
-      check(ctx, pcoa_create_subset(&sub, ctx, keep.data(), (int32_t)keep.size()), "pcoa_create_subset");
-      pcoa_timings tp;   // the Gram kernels ran on the predecessor: its time goes into the closing line
-      if (pcoa_get_timings(ctx, &tp) == PCOA_OK) gram_s_before += tp.gram_kernel_seconds;
-      pcoa_destroy(ctx);
-      ctx = owners[0] = sub;
-      kept.swap(keep);
+    drop_samples(gone, "--remove-related", "--related-min-jaccard");
+  }
+  if (conf.king) {
+    // --king-cutoff X, before the first computePca: the KING-robust screen over the five planes.  The rule, as pcoa.h and
+    // variants_pca.py's king_pairs_rule state it: the pair (i, j), i < j, is reported iff het_sum > 0 and
+    // (double)(hethet - 2 ibs0) >= X * (double)het_sum.  The planes are destroyed right after the screen; then the pair file,
+    // one stderr line, and with --king-remove the removal rule and the subset of --remove-related
+    std::vector<pcoa_king_pair> found((size_t)std::min<int64_t>(conf.king_max_pairs, (int64_t)n * (n - 1) / 2));
+    int64_t n_found = 0;
+    check(g_king.planes[0], pcoa_king_pairs(g_king.planes, conf.king_cutoff, found.empty() ? nullptr : found.data(), (int64_t)found.size(),
+                                            &n_found, nullptr, nullptr), "pcoa_king_pairs");
+    for (pcoa_ctx*& p : g_king.planes) {
+      pcoa_destroy(p);
+      p = nullptr;
     }
+    if (n_found > conf.king_max_pairs)
+      die("--king-cutoff " + java_double(conf.king_cutoff) + " reports " + std::to_string(n_found) + " pairs, more than --king-max-pairs " +
+          std::to_string(conf.king_max_pairs) + " takes; raise --king-max-pairs or the cutoff");
+    found.resize((size_t)n_found);
+    if (!conf.king_output_path.empty()) {
+      std::ofstream out(conf.king_output_path);
+      out << "name_i\tname_j\thethet\tibs0\thet_sum\tkinship\n";
+      for (const pcoa_king_pair& p : found)
+        out << names[(size_t)p.i] << "\t" << names[(size_t)p.j] << "\t" << p.hethet << "\t" << p.ibs0 << "\t" << p.het_sum << "\t"
+            << java_double((double)(p.hethet - 2 * p.ibs0) / (double)p.het_sum) << "\n";
+      if (!out) die("cannot write " + conf.king_output_path);
+    }
+    std::vector<pcoa_pair> pairs(found.size());
+    for (size_t k = 0; k < found.size(); ++k) pairs[k] = pcoa_pair{found[k].i, found[k].j, 0};
+    const std::vector<int32_t> gone = conf.king_remove ? related_removal(pairs, n) : std::vector<int32_t>();
+    std::string gone_names;
+    for (int32_t i : gone) gone_names += (gone_names.empty() ? ": " : ", ") + names[(size_t)i];
+    std::fprintf(stderr, "KING pairs: %lld at kinship >= %s; removed %zu sample(s)%s\n", (long long)n_found,
+                 java_double(conf.king_cutoff).c_str(), gone.size(), gone_names.c_str());
+    drop_samples(gone, "--king-remove", "--king-cutoff");
   }
   if (!strips.empty()) {
     check(ctx, pcoa_compute_strips(owners.data(), (int32_t)owners.size(), conf.num_pc, comps.data(), lam.data(), &nonzero), "computePca");

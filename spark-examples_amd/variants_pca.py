@@ -357,8 +357,76 @@ def related_removal(pairs, n):
     return np.array(sorted(removed), dtype=np.int64)
 
 
+# --------------------------------------------------------------------------------------------- KING-robust kinship
+KING_PLANES = ("het", "missing", "het_or_missing", "hom_a1", "hom_a2")   # PCOA_KING_HET .. PCOA_KING_HOM_A2 = 0 .. 4 (include/pcoa.h)
+KING_PAIR_DTYPE = np.dtype([("i", np.int32), ("j", np.int32), ("hethet", np.int64), ("ibs0", np.int64),
+                            ("het_sum", np.int64)])                      # pcoa_king_pair
+
+
+def king_planes(code):
+    """The five genotype-class planes of --king-cutoff and of pcoa_accumulate_plink_bed_king (csrc/king.hip restates the decode
+    on the device): `code` is [V][N] uint8 of PLINK .bed codes, 0 = 00 hom A1 (R), 1 = 01 missing (M), 2 = 10 het (H),
+    3 = 11 hom A2 (A).  Returns five bool arrays [V][N] in the order of KING_PLANES: H, M, H u M, R, A."""
+    code = np.asarray(code, dtype=np.uint8)
+    if code.ndim != 2 or code.size and int(code.max()) > 3:
+        raise ValueError("code must be [V][N] with values 0 .. 3")
+    het, mis = code == 2, code == 1
+    return het, mis, het | mis, code == 0, code == 3
+
+
+def king_counts(grams):
+    """The integer counts of the KING-robust rule from the five N x N Gram matrices of the planes, G_p = X_p^T X_p in the order
+    of KING_PLANES; lower-case letters are diagonals (h_i = G_H[i, i], ...):
+      V        = r_i + a_i + hm_i                                   the same for every i
+      hethet   = G_H[i, j]                                          both heterozygous
+      s_hm     = G_HM[i, j] - G_H[i, j] - G_M[i, j]                 one het, the other missing (H and M are disjoint)
+      het_sum  = h_i + h_j - s_hm                                   hets of i where j is called + hets of j where i is called
+      ibs0     = (V - hm_i - hm_j + G_HM[i, j]) - G_R[i, j] - G_A[i, j]     opposite homozygotes
+    Returns (V, h, hethet, ibs0, het_sum), all int64.  The planes were not built from the same codes if V differs between the
+    samples or some ibs0, het_sum or s_hm off the diagonal is negative: ValueError naming the check (pcoa_king_pairs reports
+    the same four as PCOA_ERR_INVALID_ARG)."""
+    g = [np.asarray(m, dtype=np.int64) for m in grams]
+    if len(g) != len(KING_PLANES) or g[0].ndim != 2 or g[0].shape[0] != g[0].shape[1] or any(m.shape != g[0].shape for m in g):
+        raise ValueError("grams must be five N x N matrices")
+    gh, gm, ghm, gr, ga = g
+    h, hm = np.diagonal(gh), np.diagonal(ghm)
+    vs = np.diagonal(gr) + np.diagonal(ga) + hm
+    if vs.size and (vs != vs[0]).any():
+        raise ValueError("the planes were not fed the same rows: V = r_i + a_i + hm_i is not the same for every sample")
+    v = int(vs[0]) if vs.size else 0
+    s_hm = ghm - gh - gm
+    het_sum = h[:, None] + h[None, :] - s_hm
+    ibs0 = (v - hm[:, None] - hm[None, :] + ghm) - gr - ga
+    off = ~np.eye(gh.shape[0], dtype=bool)
+    for name, m in (("ibs0", ibs0), ("het_sum", het_sum), ("s_hm", s_hm)):
+        if (m[off] < 0).any():
+            raise ValueError("the planes were not fed the same rows: %s < 0 for some pair" % name)
+    return v, h.copy(), gh.copy(), ibs0, het_sum
+
+
+def king_pairs_rule(grams, x):
+    """The rule of --king-cutoff and of pcoa_king_pairs (the library and the compiled host restate it): with the counts of
+    king_counts and num = hethet - 2 ibs0 (int64, may be negative), the pair (i, j), i < j, is reported iff het_sum > 0 and
+    float64(num) >= x * float64(het_sum): one multiplication and one comparison in double, every integer below 2^53 -- the
+    KING-robust kinship num / het_sum over the jointly called sites against the threshold x without a division.  Returns the
+    reported pairs in increasing (i, j) order as a structured array KING_PAIR_DTYPE."""
+    _, _, hethet, ibs0, het_sum = king_counts(grams)
+    num = hethet - 2 * ibs0
+    hit = (het_sum > 0) & (num.astype(np.float64) >= np.float64(x) * het_sum.astype(np.float64))
+    hit &= np.triu(np.ones(hethet.shape, dtype=bool), 1)
+    i, j = np.nonzero(hit)                      # row-major: increasing (i, j)
+    out = np.zeros(i.size, dtype=KING_PAIR_DTYPE)
+    out["i"], out["j"], out["hethet"], out["ibs0"], out["het_sum"] = i, j, hethet[i, j], ibs0[i, j], het_sum[i, j]
+    return out
+
+
+def king_kinship(pairs):
+    """float64(hethet - 2 ibs0) / float64(het_sum) of reported pairs: what the hosts print."""
+    return (pairs["hethet"] - 2 * pairs["ibs0"]).astype(np.float64) / pairs["het_sum"].astype(np.float64)
+
+
 # --------------------------------------------------------------------------------------------- similarity measures
-SIMILARITY_MEASURES = ("shared", "jaccard", "cosine")   # PCOA_SIMILARITY_SHARED / _JACCARD / _COSINE = 0 / 1 / 2 (include/pcoa.h)
+SIMILARITY_MEASURES =("shared", "jaccard", "cosine")   # PCOA_SIMILARITY_SHARED / _JACCARD / _COSINE = 0 / 1 / 2 (include/pcoa.h)
 
 
 def similarity_measure(s, kind):
@@ -513,6 +581,21 @@ class PcaConf(object):
                        help="--related-min-jaccard: drop one sample of every reported pair before computePca (the sample with "
                             "the most reported partners first, ties to the highest index) and decompose S[kept, kept], "
                             "gathered on the device (pcoa_create_subset) -- no variant is read twice")
+        p.add_argument("--king-cutoff", type=float, default=None,
+                       help="X in (0, 0.5]: screen the cohort for relatives by the KING-robust kinship coefficient before "
+                            "computePca (pcoa_king_pairs): a pair is reported when (hethet - 2 ibs0) / het_sum over the jointly "
+                            "called variants is at least X (0.177: first degree).  It does not depend on allele frequencies, "
+                            "so it holds on a cohort with population structure where --related-min-jaccard does not.  Off by "
+                            "default.  One PLINK fileset, one device: stored S, full layout, five more N x N int32 matrices")
+        p.add_argument("--king-output-path", type=str, default=None,
+                       help="--king-cutoff: write the reported pairs to this file, one line per pair in (i, j) order: "
+                            "name_i, name_j, hethet, ibs0, het_sum, kinship (tab-separated, one header line)")
+        p.add_argument("--king-max-pairs", type=int, default=None,
+                       help="--king-cutoff: the most pairs the job takes from the library (default 1048576); if more are "
+                            "reported the job stops")
+        p.add_argument("--king-remove", action="store_true",
+                       help="--king-cutoff: drop one sample of every reported pair before computePca (the rule of "
+                            "--remove-related) and decompose S[kept, kept], gathered on the device (pcoa_create_subset)")
         p.add_argument("--similarity-measure", type=str, default="shared",
                        help="shared|jaccard|cosine: what computePca decomposes (pcoa_set_similarity).  shared: the counts S, as "
                             "the reference; jaccard: S(i, j) / (S(i, i) + S(j, j) - S(i, j)); cosine: S(i, j) / sqrt(S(i, i) "
@@ -550,6 +633,9 @@ class PcaConf(object):
         self.related_max_pairs_given = a.related_max_pairs is not None
         if a.related_max_pairs is None:
             self.related_max_pairs = RELATED_MAX_PAIRS
+        self.king_max_pairs_given = a.king_max_pairs is not None
+        if a.king_max_pairs is None:
+            self.king_max_pairs = RELATED_MAX_PAIRS
 
 
 RELATED_MAX_PAIRS = 1 << 20   # default of --related-max-pairs
@@ -775,6 +861,46 @@ class VariantsPcaDriver(object):
         if n - gone.size < min_cohort(self.conf.numPc):
             raise SystemExit("VariantsPcaDriver: --remove-related would leave %d of %d samples, fewer than the %d that %d "
                              "principal components need; raise --related-min-jaccard"
+                             % (n - gone.size, n, min_cohort(self.conf.numPc), self.conf.numPc))
+        keep = np.setdiff1d(np.arange(n), gone)
+        sub = sim_matrix.subset(keep)
+        self.gram_seconds_before += sim_matrix.timings()["gram_kernel_seconds"]
+        sim_matrix.close()
+        self.engine = sub
+        self.kept = keep
+        return sub
+
+    # --king-cutoff X, before the first computePca: the KING-robust screen over the five planes (pcoa_king_pairs), the pair file,
+    # one stderr line, and with --king-remove the rule and the subset of screenRelated.  `king` holds the planes (KingPlanes, or
+    # anything with its king_pairs and close); it is closed right after the screen.  Returns the engine to decompose.
+    def screenKing(self, sim_matrix, king, err=None):
+        err = err or sys.stderr
+        x, cap = self.conf.king_cutoff, self.conf.king_max_pairs
+        n = len(self.indexes)
+        reverse = dict((v, k) for (k, v) in self.indexes.items())
+        name = lambda i: self.names[reverse[int(i)]]
+        try:
+            pairs, n_found, _, _ = king.king_pairs(x, capacity=cap)
+        finally:
+            king.close()
+        if n_found > cap:
+            raise SystemExit("VariantsPcaDriver: --king-cutoff %s reports %d pairs, more than --king-max-pairs %d "
+                             "takes; raise --king-max-pairs or the cutoff" % (java_double_to_string(x), n_found, cap))
+        if self.conf.king_output_path:
+            kinship = king_kinship(pairs)
+            with open(self.conf.king_output_path, "w") as f:
+                f.write("name_i\tname_j\thethet\tibs0\thet_sum\tkinship\n")
+                for p, k in zip(pairs, kinship):
+                    f.write("%s\t%s\t%d\t%d\t%d\t%s\n" % (name(p["i"]), name(p["j"]), p["hethet"], p["ibs0"], p["het_sum"],
+                                                          java_double_to_string(float(k))))
+        gone = related_removal(pairs, n) if self.conf.king_remove else np.zeros(0, dtype=np.int64)
+        err.write("KING pairs: %d at kinship >= %s; removed %d sample(s)%s\n"
+                  % (n_found, java_double_to_string(x), gone.size, (": " + ", ".join(name(i) for i in gone)) if gone.size else ""))
+        if gone.size == 0:
+            return sim_matrix
+        if n - gone.size < min_cohort(self.conf.numPc):
+            raise SystemExit("VariantsPcaDriver: --king-remove would leave %d of %d samples, fewer than the %d that %d "
+                             "principal components need; raise --king-cutoff"
                              % (n - gone.size, n, min_cohort(self.conf.numPc), self.conf.numPc))
         keep = np.setdiff1d(np.arange(n), gone)
         sub = sim_matrix.subset(keep)
@@ -1057,6 +1183,82 @@ def check_related_conf(conf):
                          "--project-input-path")
 
 
+STRIPS_REFUSE_KING = "--king-cutoff screens five whole Gram matrices on one device: it cannot take --layout strips"
+
+
+def check_king_conf(conf):
+    """--king-cutoff and its companions: what cannot be served is refused before any file is read or any engine exists."""
+    x = conf.king_cutoff
+    if x is None:
+        for flag, given in (("--king-output-path", conf.king_output_path is not None),
+                            ("--king-max-pairs", conf.king_max_pairs_given), ("--king-remove", conf.king_remove)):
+            if given:
+                raise SystemExit("VariantsPcaDriver: %s needs --king-cutoff X (the screen is off without it)" % flag)
+        return
+    if not (x > 0 and x <= 0.5):   # (NaN fails both comparisons)
+        raise SystemExit("VariantsPcaDriver: --king-cutoff must be a finite number in (0, 0.5]")
+    if conf.king_max_pairs < 0:
+        raise SystemExit("VariantsPcaDriver: --king-max-pairs must be >= 0 (the pairs --king-cutoff may report)")
+    if conf.gram == "implicit":
+        raise SystemExit("VariantsPcaDriver: --king-cutoff screens stored Gram matrices: it cannot take --gram implicit")
+    if conf.layout == "strips":
+        raise SystemExit("VariantsPcaDriver: " + STRIPS_REFUSE_KING)
+    world = max(conf.gpus, int(os.environ.get("WORLD_SIZE", "1")))
+    if world > 1:
+        raise SystemExit("VariantsPcaDriver: --king-cutoff runs on one engine and its five planes: it cannot take --gpus %d" % world)
+    if conf.ld_window:
+        raise SystemExit("VariantsPcaDriver: --king-cutoff: the planes would need the pruned rows: it cannot take --ld-window")
+    if conf.related_min_jaccard is not None:
+        raise SystemExit("VariantsPcaDriver: --king-cutoff: one relatedness screen per run: it cannot take --related-min-jaccard")
+    if conf.project_input_path:
+        raise SystemExit("VariantsPcaDriver: --king-cutoff screens the cohort it decomposes: it cannot take --project-input-path")
+    paths = conf.inputPath or []
+    if conf.synthetic or conf.minAlleleFrequency is not None or len(paths) != 1 or not is_plink_path(paths[0]):
+        raise SystemExit("VariantsPcaDriver: --king-cutoff reads the genotype classes of one PLINK fileset: --input-path must name a "
+                         "single .bed / .bim / .fam (VCF ingest yields carriers only)")
+
+
+class KingPlanes(object):
+    """The five plane engines of --king-cutoff (PCOA_KING_*): created together, fed together, closed together."""
+
+    def __init__(self, n, device=0):
+        self.engines = []
+        try:
+            for _ in KING_PLANES:
+                self.engines.append(PcoaEngine(n, device=device))
+        except Exception:
+            self.close()
+            raise
+
+    def accumulate(self, rows):
+        PcoaEngine.accumulate_plink_bed_king(self.engines, rows)
+
+    def king_pairs(self, x, capacity):
+        return PcoaEngine.king_pairs(self.engines, x, capacity=capacity)
+
+    def close(self):
+        for e in self.engines:
+            e.close()
+        self.engines = []
+
+
+def king_accumulate(call_rdd, matrix_size, device=0):
+    """--king-cutoff: the blocks of raw .bed rows the main engine was fed, fed to the five planes
+    (pcoa_accumulate_plink_bed_king).  Returns the KingPlanes."""
+    _, geno, keep, _ = call_rdd
+    king = KingPlanes(matrix_size, device=device)
+    all_kept = bool(keep.all())
+    for v0 in range(0, geno.shape[0], PLINK_BLOCK_ROWS):
+        rows = geno[v0:v0 + PLINK_BLOCK_ROWS]
+        if not all_kept:
+            k = keep[v0:v0 + PLINK_BLOCK_ROWS]
+            if not k.any():
+                continue
+            rows = rows[k]
+        king.accumulate(np.ascontiguousarray(rows))
+    return king
+
+
 STRIPS_REFUSE_MEASURE = ("--similarity-measure %s needs the diagonal of one whole similarity matrix on one engine: it cannot "
                          "take --layout strips")
 
@@ -1334,6 +1536,7 @@ def main(args):
     conf = PcaConf(args)
     check_outlier_conf(conf)
     check_related_conf(conf)
+    check_king_conf(conf)
     check_measure_conf(conf)
     check_missing_conf(conf)
     check_gram_conf(conf)
@@ -1417,6 +1620,8 @@ def main(args):
         raise SystemExit("VariantsPcaDriver: " + STRIPS_REFUSE_OUTLIERS)
     if ranges is not None and conf.related_min_jaccard is not None:
         raise SystemExit("VariantsPcaDriver: " + STRIPS_REFUSE_RELATED)
+    if ranges is not None and conf.king_cutoff is not None:     # --layout auto resolved to strips
+        raise SystemExit("VariantsPcaDriver: " + STRIPS_REFUSE_KING)
     if ranges is not None and conf.similarity_measure != "shared":
         raise SystemExit("VariantsPcaDriver: " + STRIPS_REFUSE_MEASURE % conf.similarity_measure)
     if ranges is not None and conf.missing_calls == "pairwise":   # --layout auto resolved to strips
@@ -1471,6 +1676,8 @@ def main(args):
                 write_call_rates(conf.call_rate_output_path, [driver.names[reverse[i]] for i in range(n)], fed - missing, fed)
         if conf.related_min_jaccard is not None:   # the screen first, then the rounds on the reduced cohort
             sim_matrix = driver.screenRelated(sim_matrix)
+        if conf.king_cutoff is not None:           # likewise; the planes live from here to the end of the screen
+            sim_matrix = driver.screenKing(sim_matrix, king_accumulate(calls_rdd, n, device=conf.gpu))
         result = driver.computePcaOutlierRounds(sim_matrix) if conf.outlier_iterations > 0 else driver.computePca(sim_matrix)
         driver.emitResult(result)
         if conf.loadings_output_path:
