@@ -35,7 +35,7 @@ extern "C" {
 #endif
 
 #define PCOA_VERSION_MAJOR 0
-#define PCOA_VERSION_MINOR 9
+#define PCOA_VERSION_MINOR 10
 
 typedef struct pcoa_ctx pcoa_ctx;
 
@@ -271,6 +271,62 @@ int pcoa_operator_row_sums(pcoa_ctx* ctx, int64_t* out_n);
  * combined by one all-reduce of an N-vector per product.  Replaces: the products inside MLlib's computePrincipalComponents
  * (VariantsPca.scala:224-227). */
 int pcoa_operator_matvec_device(pcoa_ctx* ctx, const double* v_dev, double* y_dev, int centred);
+
+/* ---- standardised-genotype PCA (the genetic relationship matrix) as an implicit operator -----------------------------------
+ * The PCA of smartpca, plink --pca, GCTA and flashpca decomposes K = Z^T Z / M over allele-frequency-standardised dosages,
+ * missing calls mean-imputed -- not the carrier-sharing counts S every other engine here holds.  With the store's V rows of N
+ * genotypes, for sample i at variant v:
+ *   c_iv in {0, 1}     1 when the sample is called (its .bed code is not 01)
+ *   g_iv in {0, 1, 2}  copies of the non-reference allele, chosen by ref_is_a1 as pcoa_accumulate_plink_bed documents; 0 where
+ *                      the sample is not called
+ * per variant, exact int32:  n_v = sum_i c_iv,  h_v heterozygous samples,  o_v homozygous non-reference samples,  a_v = h_v + 2 o_v
+ * per variant, fp64, in exactly these expressions:
+ *   mu_v   = a_v / n_v
+ *   used_v = n_v > 0 and 0 < a_v < 2 n_v and min(a_v, 2 n_v - a_v) >= min_maf * (2.0 * n_v)
+ *   d_v    = used_v ? 1.0 / (mu_v * (1.0 - 0.5 * mu_v)) : 0.0
+ *   M'     = sum_v used_v
+ * and A_vi = g_iv - mu_v c_iv,  K = A^T diag(d) A / M'.  There is no double centring: every row of A has mean 0 over its called
+ * samples.  d_v is applied once, between the two passes of a product, not as a square root in both.
+ *
+ * pcoa_create_grm: a ctx that holds 2 bits per genotype of every variant it has been fed (626 MB at 2,504 x 10^6) and NO N x N
+ * matrix; n_samples < 32 is PCOA_ERR_INVALID_ARG (computePca is the Lanczos iteration), and so are the flags
+ * pcoa_create_operator refuses.
+ *   input:  pcoa_accumulate_plink_bed only (host, device, PCOA_BED_HOST_ASYNC; the same lifetime rules).  Padding bits of a
+ *           row and bytes beyond ceil(N / 4) are ignored.  Every other accumulate call returns PCOA_ERR_STATE.
+ *   store:  as an operator ctx's: segments of about 256 MiB, allocated as the store grows and never reallocated or copied; rows
+ *           at a pitch of ceil(N / 4) bytes rounded up to 16, in one coding whatever ref_is_a1 was; an append that cannot get
+ *           its segments leaves the store as it was (PCOA_ERR_OUT_OF_MEMORY).  pcoa_reset empties the store and keeps min_maf.
+ *   pcoa_compute: the outputs of a full engine ([num_pc][N] unit sign-normalised columns, eigenvalues of K) by the Lanczos
+ *           iteration over the product; *out_nonzero_rows = the samples called at one or more used variants;
+ *           PCOA_FLAG_EIG_BAND is honoured; M' = 0 is PCOA_ERR_STATE; PCOA_ERR_NOT_CONVERGED if no verified pair is reached
+ *           (no dense fallback: there is no matrix).
+ *   pcoa_reserve, pcoa_sync, pcoa_gram_finalize, pcoa_destroy: as on an operator ctx.  Products count under
+ *           operator_products / operator_matvec_seconds of pcoa_timings.
+ *   not available (PCOA_ERR_STATE, the ctx stays usable): everything that reads or moves S, and the pcoa_operator_*, strip,
+ *           project, subset, pairs, king, similarity, companion, loadings and LD calls.
+ *   results are reproducible: the same store, min_maf and x give bit-identical y, run to run and whatever the sizes of the
+ *           accumulate calls were (no floating-point atomics; the order of every addition is fixed by N, the segment size
+ *           and a row's index in the store).
+ * Not built: JNI / Scala natives, SNP weights, projection of new samples, LD pruning in front of the store, variant sharding
+ * over engines, reading K out. */
+int pcoa_create_grm(pcoa_ctx** out, int32_t n_samples, int32_t device_ordinal, uint32_t flags);
+
+/* Returns 1 for a GRM ctx, 0 otherwise (like pcoa_operator_info).  *variants_out: rows in the store; *used_out: M' under the
+ * current min_maf (computes the counts and weights if they are not resident); *store_bytes_out: the HBM the segments hold.
+ * Any pointer may be NULL. */
+int pcoa_grm_info(pcoa_ctx* ctx, int64_t* variants_out, int64_t* used_out, int64_t* store_bytes_out);
+
+/* 0 <= maf < 0.5 (default 0): a variant is used only if its minor-allele count is at least maf * 2 n_v.  A property of the ctx:
+ * it survives pcoa_reset. */
+int pcoa_grm_set_min_maf(pcoa_ctx* ctx, double maf);
+
+/* out[(v - first_variant) * 3 + {0, 1, 2}] = n_v, h_v, o_v (called, heterozygous, homozygous non-reference) of the store's rows
+ * [first_variant, first_variant + n_variants); host memory. */
+int pcoa_grm_counts(pcoa_ctx* ctx, int64_t first_variant, int64_t n_variants, int32_t* out /* [n_variants][3] */);
+
+/* y = K x on DEVICE vectors of N doubles on the ctx's GPU; returns when y is complete (synchronous on the ctx stream), x must
+ * be complete when it is called.  M' = 0 gives y = 0. */
+int pcoa_grm_matvec_device(pcoa_ctx* ctx, const double* x_dev, double* y_dev);
 
 /* ---- PCoA over a sample subset of a stored S ------------------------------------------------------------------------------
  * For a kept index set I, S[I, I] is exactly the similarity matrix of the reduced cohort (an entry counts the variants two
@@ -1005,6 +1061,7 @@ int pcoa_debug_guard_mode(void);
  *   PCOA_SYNTH_TILE             1: pcoa_accumulate_synthetic through the fp32 staging tile and the pre-pass
  *   PCOA_NO_NARROW              1: an int64 S that fits int32 stays int64
  *   PCOA_OPERATOR_SEGMENT_ROWS  rows per segment of an operator ctx's bit store (crosses segment boundaries with a few hundred rows)
+ *   PCOA_GRM_SEGMENT_ROWS       the same for a GRM ctx's genotype store
  *   PCOA_KBITS_MODE             0 | 2 | 4 | 5: launch form of the k-bits contraction (split-K, lock-step, even split, even split
  *                               per XCD k-segment)
  *   PCOA_KBITS_W4               0 | 1: the one-wave-per-SIMD k-bits contraction never | wherever it has its CUs to itself (default)

@@ -28,6 +28,12 @@ static int not_a_bitset_boundary(pcoa_ctx* c, const char* call, const char* why 
                                  "through pcoa_accumulate_bits or pcoa_accumulate_plink_bed" + why);
 }
 
+// a GRM ctx (pcoa_create_grm) stores 2-bit genotypes: carriers alone do not say whether a call is missing or homozygous
+static int not_the_bed_boundary(pcoa_ctx* c, const char* call) {
+  return fail(c, PCOA_ERR_STATE, std::string(call) + ": a GRM ctx (pcoa_create_grm) stores 2-bit GENOTYPES (dosage and missing "
+                                 "calls): feed it through pcoa_accumulate_plink_bed, the .bed boundary, only");
+}
+
 // sample -> population map on the device; uploaded again only when the offsets differ from the last call's
 static int upload_sample_pop(pcoa_ctx* c, const pcoa_synth_params* p) {
   if (!p || !p->pop_offsets || !p->thresholds || p->n_pops <= 0)
@@ -432,6 +438,7 @@ extern "C" {
 
 int pcoa_accumulate_dense_f32(pcoa_ctx* c, const float* x, int64_t n_variants, int64_t ld, int is_device_ptr) {
   CHECK_CTX(c);
+  if (c->is_grm) return not_the_bed_boundary(c, "pcoa_accumulate_dense_f32");
   if (c->is_operator) return not_a_bitset_boundary(c, "pcoa_accumulate_dense_f32");
   if (n_variants < 0 || (n_variants > 0 && !x)) return fail(c, PCOA_ERR_INVALID_ARG, "x is NULL or n_variants < 0");
   if (ld < c->n) return fail(c, PCOA_ERR_INVALID_ARG, "ld must be >= n_samples");
@@ -441,6 +448,7 @@ int pcoa_accumulate_dense_f32(pcoa_ctx* c, const float* x, int64_t n_variants, i
 
 int pcoa_accumulate_dense_u8(pcoa_ctx* c, const uint8_t* x, int64_t n_variants, int64_t ld, int is_device_ptr) {
   CHECK_CTX(c);
+  if (c->is_grm) return not_the_bed_boundary(c, "pcoa_accumulate_dense_u8");
   if (c->is_operator) return not_a_bitset_boundary(c, "pcoa_accumulate_dense_u8");
   if (n_variants < 0 || (n_variants > 0 && !x)) return fail(c, PCOA_ERR_INVALID_ARG, "x is NULL or n_variants < 0");
   if (ld < c->n) return fail(c, PCOA_ERR_INVALID_ARG, "ld must be >= n_samples");
@@ -450,6 +458,7 @@ int pcoa_accumulate_dense_u8(pcoa_ctx* c, const uint8_t* x, int64_t n_variants, 
 
 int pcoa_accumulate_bits(pcoa_ctx* c, const uint32_t* bits, int64_t n_variants, int64_t ld_words, int is_device_ptr) {
   CHECK_CTX(c);
+  if (c->is_grm) return not_the_bed_boundary(c, "pcoa_accumulate_bits");
   if (n_variants < 0 || (n_variants > 0 && !bits))
     return fail(c, PCOA_ERR_INVALID_ARG, "bits is NULL or n_variants < 0");
   int rc = check_ld_words(c, "", ld_words);
@@ -483,6 +492,7 @@ int pcoa_accumulate_plink_bed(pcoa_ctx* c, const uint8_t* bed_rows, int64_t n_va
     return fail(c, PCOA_ERR_INVALID_ARG, "the PLINK boundary needs a packed-operand engine (not PCOA_FLAG_GRAM_F32_MFMA)");
   if ((rc = check_bed_source(c, "", is_device_ptr, true)) != PCOA_OK) return rc;
   if (n_variants == 0) return PCOA_OK;
+  if (c->is_grm) return grm_accumulate_bed(c, bed_rows, n_variants, row_bytes, ref_is_a1, is_device_ptr);
   const int64_t words = words_of(c);
   const int64_t rows_cap = std::min<int64_t>(n_variants, (int64_t)1 << 17);
   if ((rc = ensure(c, &c->tile, &c->tile_elems, rows_cap * words)) != PCOA_OK) return rc;
@@ -497,6 +507,7 @@ int pcoa_accumulate_plink_bed(pcoa_ctx* c, const uint8_t* bed_rows, int64_t n_va
 int pcoa_accumulate_calls_ex(pcoa_ctx* c, const int32_t* sample_idx, const int64_t* row_offsets, int64_t n_variants,
                              uint32_t flags) {
   CHECK_CTX(c);
+  if (c->is_grm) return not_the_bed_boundary(c, "pcoa_accumulate_calls");
   if (c->is_operator) return not_a_bitset_boundary(c, "pcoa_accumulate_calls",
                                                         " (a carrier list can repeat a callset, a bitset cannot)");
   if (n_variants < 0 || !row_offsets) return fail(c, PCOA_ERR_INVALID_ARG, "row_offsets is NULL or n_variants < 0");
@@ -551,6 +562,7 @@ int pcoa_synth_fill_f32(pcoa_ctx* c, const pcoa_synth_params* p, int64_t first_v
 
 int pcoa_accumulate_synthetic(pcoa_ctx* c, const pcoa_synth_params* p, int64_t first_variant, int64_t n_variants) {
   CHECK_CTX(c);
+  if (c->is_grm) return not_the_bed_boundary(c, "pcoa_accumulate_synthetic");
   if (c->is_operator) return not_a_bitset_boundary(c, "pcoa_accumulate_synthetic",
                                                         " (the generator writes the contraction operand, not variant-major bitsets)");
   if (n_variants < 0 || first_variant < 0) return fail(c, PCOA_ERR_INVALID_ARG, "synthetic: negative range");

@@ -97,6 +97,7 @@ int pcoa_set_call_companion(pcoa_ctx* c, pcoa_ctx* missing, int64_t n_variants) 
     return PCOA_OK;
   }
   if (missing == c) return fail(c, PCOA_ERR_INVALID_ARG, "pcoa_set_call_companion: missing is ctx itself");
+  NOT_ON_GRM(c, "pcoa_set_call_companion");
   if (missing->n != c->n)
     return fail(c, PCOA_ERR_INVALID_ARG, "pcoa_set_call_companion: the companion has N = " + std::to_string(missing->n) +
                                          " samples, ctx has " + std::to_string(c->n));
@@ -141,6 +142,7 @@ int pcoa_accumulate_plink_bed_calls(pcoa_ctx* c, pcoa_ctx* missing, const uint8_
   const char* fn = "pcoa_accumulate_plink_bed_calls: ";
   if (!missing) return fail(c, PCOA_ERR_INVALID_ARG, std::string(fn) + "missing is NULL");
   if (missing == c) return fail(c, PCOA_ERR_INVALID_ARG, std::string(fn) + "missing is ctx itself");
+  NOT_ON_GRM(c, "pcoa_accumulate_plink_bed_calls");
   if (missing->n != c->n) return fail(c, PCOA_ERR_INVALID_ARG, std::string(fn) + "the companion's N differs from ctx's");
   if (missing->is_operator || missing->is_strip || !missing->use_i8 || missing->device != c->device)
     return fail(c, PCOA_ERR_INVALID_ARG, std::string(fn) + "the companion must be an ordinary packed-operand full engine "

@@ -185,6 +185,7 @@ int pcoa_compute(pcoa_ctx* c, int32_t num_pc, double* out_components, double* ou
     return fail(c, PCOA_ERR_INVALID_ARG, buf);
   }
   if (!out_components) return fail(c, PCOA_ERR_INVALID_ARG, "out_components is NULL");
+  if (c->is_grm) return grm_compute(c, num_pc, out_components, out_eigenvalues, out_nonzero_rows);
   if (c->is_operator) return operator_compute(c, num_pc, out_components, out_eigenvalues, out_nonzero_rows);
   if (c->is_strip)
     return fail(c, PCOA_ERR_STATE, "a strip owner holds N x cols of S: the eigensolve over strips is driven by the host "
@@ -353,6 +354,7 @@ int pcoa_compute(pcoa_ctx* c, int32_t num_pc, double* out_components, double* ou
 int pcoa_lanczos_with_matvec(pcoa_ctx* c, int32_t num_pc, pcoa_matvec_fn fn, void* user, double* out_components,
                              double* out_eigenvalues, int32_t* steps_out) {
   CHECK_CTX(c);
+  NOT_ON_GRM(c, "pcoa_lanczos_with_matvec");
   const int32_t n = c->n;
   if (!fn || !out_components) return fail(c, PCOA_ERR_INVALID_ARG, "fn or out_components is NULL");
   if (num_pc <= 0 || num_pc > n) return fail(c, PCOA_ERR_INVALID_ARG, "num_pc must be in (0, n]");

@@ -53,6 +53,7 @@ int check_planes(pcoa_ctx* const* planes, const std::string& fn) {
         return fail(c0, PCOA_ERR_INVALID_ARG, fn + plane_name(p) + " and " + plane_name(q) + " are the same ctx: five engines are needed");
   for (int p = 0; p < PCOA_KING_PLANES; ++p) {
     const pcoa_ctx* c = planes[p];
+    if (c->is_grm) return fail(c0, PCOA_ERR_STATE, fn + plane_name(p) + " is a GRM ctx (pcoa_create_grm), which holds no S; use a full engine (pcoa_create)");
     if (c->is_operator || c->is_strip)
       return fail(c0, PCOA_ERR_INVALID_ARG, fn + plane_name(p) + " is " +
                                                 (c->is_operator ? "an operator ctx (pcoa_create_operator)" : "a strip owner (pcoa_create_strip)") +

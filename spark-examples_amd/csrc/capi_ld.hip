@@ -132,6 +132,7 @@ extern "C" {
 
 int pcoa_ld_begin(pcoa_ctx* c, int32_t window, double r2_max, uint32_t flags) {
   CHECK_CTX(c);
+  NOT_ON_GRM(c, "pcoa_ld_begin");
   if (window < 1 || window > PCOA_LD_MAX_WINDOW)
     return fail(c, PCOA_ERR_INVALID_ARG, "pcoa_ld_begin: window = " + std::to_string(window) + " is outside [1, " +
                                              std::to_string(PCOA_LD_MAX_WINDOW) + "]");

@@ -90,6 +90,7 @@ extern "C" {
 
 int pcoa_loadings_begin(pcoa_ctx* c, int32_t num_pc, const double* components, const double* eigenvalues, uint32_t flags) {
   CHECK_CTX(c);
+  NOT_ON_GRM(c, "pcoa_loadings_begin");
   if (num_pc <= 0 || num_pc > c->n)
     return fail(c, PCOA_ERR_INVALID_ARG, "pcoa_loadings_begin: num_pc = " + std::to_string(num_pc) + " is outside (0, n_samples]");
   if (!components) return fail(c, PCOA_ERR_INVALID_ARG, "pcoa_loadings_begin: components is NULL");

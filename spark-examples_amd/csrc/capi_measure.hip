@@ -52,6 +52,7 @@ int pcoa_set_similarity(pcoa_ctx* c, int32_t kind) {
     return fail(c, PCOA_ERR_INVALID_ARG, "pcoa_set_similarity: kind = " + std::to_string(kind) +
                                          " is none of PCOA_SIMILARITY_SHARED, _JACCARD, _COSINE");
   if (kind != PCOA_SIMILARITY_SHARED) {
+    NOT_ON_GRM(c, "pcoa_set_similarity");
     if (c->is_operator)
       return fail(c, PCOA_ERR_STATE, "pcoa_set_similarity: an operator ctx (pcoa_create_operator) holds the carrier bitsets, not S: "
                                      "a measure over the implicit operator is not built; use a full engine (pcoa_create)");

@@ -12,7 +12,7 @@ using namespace pcoa;
 
 namespace {
 
-int64_t seg_bytes(const pcoa_ctx* c) { return c->op_seg_rows * (int64_t)operator_pitch_words(c->n) * 4; }
+int64_t seg_bytes(const pcoa_ctx* c) { return c->op_seg_rows * store_pitch_words(c) * 4; }
 
 // ranges of the second pass over the whole store: every segment is cut into ranges of kOperatorRangeRows rows of its own
 int64_t store_ranges(const pcoa_ctx* c) {
@@ -118,13 +118,11 @@ namespace pcoa {
 
 int64_t operator_store_bytes(const pcoa_ctx* c) { return c->is_operator ? (int64_t)c->op_segs.size() * seg_bytes(c) : 0; }
 
-// Appends nv variant-major bitset rows (device, on the ctx stream) to the store.  Every segment the rows need is allocated
-// before the first row moves: a failed allocation leaves the store as it was.
-int operator_append(pcoa_ctx* c, const uint32_t* bits_dev, int64_t nv, int64_t ld_words) {
-  if (nv <= 0) return PCOA_OK;
-  const int64_t pitch = operator_pitch_words(c->n);
-  const int64_t room = c->op_segs.empty() ? 0 : c->op_seg_rows - c->op_segs.back().rows;
+// The store has room for nv more rows: every segment they need is allocated now, and a failed allocation leaves the store as
+// it was.  Rows fill the segments in order, so the room is what the segments hold beyond op_variants.
+int store_grow(pcoa_ctx* c, int64_t nv) {
   const size_t held = c->op_segs.size();
+  const int64_t room = (int64_t)held * c->op_seg_rows - c->op_variants;
   const int64_t fresh = nv > room ? (nv - room + c->op_seg_rows - 1) / c->op_seg_rows : 0;
   for (int64_t i = 0; i < fresh; ++i) {
     void* p = nullptr;
@@ -141,7 +139,17 @@ int operator_append(pcoa_ctx* c, const uint32_t* bits_dev, int64_t nv, int64_t l
     }
     c->op_segs.push_back({static_cast<uint32_t*>(p), 0});
   }
-  size_t si = room > 0 ? held - 1 : held;
+  return PCOA_OK;
+}
+
+// Appends nv rows (written on the ctx stream by the kernels `repitch` queues) to the store.  Every segment the rows need is
+// allocated before the first row moves (store_grow).
+int store_append(pcoa_ctx* c, int64_t nv, const std::function<hipError_t(int64_t, int64_t, uint32_t*)>& repitch) {
+  if (nv <= 0) return PCOA_OK;
+  const int64_t pitch = store_pitch_words(c);
+  const int rc = store_grow(c, nv);
+  if (rc != PCOA_OK) return rc;
+  size_t si = (size_t)(c->op_variants / c->op_seg_rows);
   int64_t done = 0;
   ScopedTimer t(c, T_PACK);
   while (done < nv) {
@@ -151,13 +159,20 @@ int operator_append(pcoa_ctx* c, const uint32_t* bits_dev, int64_t nv, int64_t l
       ++si;
       continue;
     }
-    HIP_TRY(c, launch_operator_append(bits_dev + done * ld_words, ld_words, cur, c->n, s.p + s.rows * pitch, c->stream));
+    HIP_TRY(c, repitch(done, cur, s.p + s.rows * pitch));
     s.rows += cur;
     c->op_variants += cur;
     done += cur;
   }
   c->op_centering_set = false;
   return PCOA_OK;
+}
+
+// nv variant-major bitset rows (device) join the store
+int operator_append(pcoa_ctx* c, const uint32_t* bits_dev, int64_t nv, int64_t ld_words) {
+  return store_append(c, nv, [&](int64_t done, int64_t cur, uint32_t* dst) {
+    return launch_operator_append(bits_dev + done * ld_words, ld_words, cur, c->n, dst, c->stream);
+  });
 }
 
 // pcoa_reset: the store is empty again; the first segment stays for the next fill
@@ -237,13 +252,15 @@ extern "C" {
 
 int pcoa_operator_info(const pcoa_ctx* c, int64_t* variants_out, int64_t* store_bytes_out) {
   if (!c) return fail(nullptr, PCOA_ERR_INVALID_ARG, "ctx is NULL");
-  if (variants_out) *variants_out = c->is_operator ? c->op_variants : 0;
-  if (store_bytes_out) *store_bytes_out = operator_store_bytes(c);
-  return c->is_operator ? 1 : 0;
+  const bool op = c->is_operator && !c->is_grm;
+  if (variants_out) *variants_out = op ? c->op_variants : 0;
+  if (store_bytes_out) *store_bytes_out = op ? operator_store_bytes(c) : 0;
+  return op ? 1 : 0;
 }
 
 int pcoa_operator_row_sums(pcoa_ctx* c, int64_t* out_n) {
   CHECK_CTX(c);
+  NOT_ON_GRM(c, "pcoa_operator_row_sums");
   if (!c->is_operator) return fail(c, PCOA_ERR_STATE, "not an operator ctx (pcoa_create_operator)");
   if (!out_n) return fail(c, PCOA_ERR_INVALID_ARG, "out_n is NULL");
   int rc = check_device_flags(c);
@@ -256,6 +273,7 @@ int pcoa_operator_row_sums(pcoa_ctx* c, int64_t* out_n) {
 
 int pcoa_operator_matvec_device(pcoa_ctx* c, const double* v_dev, double* y_dev, int centred) {
   CHECK_CTX(c);
+  NOT_ON_GRM(c, "pcoa_operator_matvec_device");
   if (!c->is_operator) return fail(c, PCOA_ERR_STATE, "not an operator ctx (pcoa_create_operator)");
   if (!v_dev || !y_dev) return fail(c, PCOA_ERR_INVALID_ARG, "v_dev or y_dev is NULL");
   int rc = check_device_flags(c);

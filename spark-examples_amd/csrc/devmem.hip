@@ -161,6 +161,7 @@ const DebugKnobs& debug_knobs() {
     if (const char* v = std::getenv("PCOA_SYMV_SYM_MIN_N")) k.symv_sym_min_n = std::atoi(v);
     if (const char* v = std::getenv("PCOA_KBITS_CORESIDE")) k.kbits_coreside = std::atoi(v) != 0;
     k.operator_segment_rows = num("PCOA_OPERATOR_SEGMENT_ROWS");
+    k.grm_segment_rows = num("PCOA_GRM_SEGMENT_ROWS");
     k.no_narrow = (int)num("PCOA_NO_NARROW");
     k.synth_tile = (int)num("PCOA_SYNTH_TILE");
     if (const char* v = std::getenv("PCOA_LANCZOS_BAND")) k.lanczos_band = std::atoi(v);

@@ -1,6 +1,6 @@
 // pcoa_capi.hip -- the C ABI of include/pcoa.h on top of the HIP kernels: an engine's life (create / destroy / reset /
 // reserve / set_stream / sync), error reporting, and the timings.  The rest of the ABI lives in capi_accumulate.hip,
-// capi_reduce.hip, capi_compute.hip, capi_operator.hip, capi_subset.hip, capi_pairs.hip and devmem.hip (map: pcoa_ctx.h).  There is deliberately NO CPU fallback: without a HIP
+// capi_reduce.hip, capi_compute.hip, capi_operator.hip, capi_grm.hip, capi_subset.hip, capi_pairs.hip and devmem.hip (map: pcoa_ctx.h).  There is deliberately NO CPU fallback: without a HIP
 // device pcoa_create fails with PCOA_ERR_NO_DEVICE.
 #include <cstdio>
 #include <cstring>
@@ -76,10 +76,13 @@ void drain_events(pcoa_ctx* c, bool wait) {
 // ================================================================================================
 // zero_s = false (pcoa_create_subset): S is allocated but not zeroed -- the caller overwrites every entry before anything reads it
 static int create_impl(pcoa_ctx** out, int32_t n_samples, int32_t device_ordinal, uint32_t flags, int32_t col0, int32_t cols,
-                       bool op = false, bool zero_s = true) {
+                       bool op = false, bool zero_s = true, bool grm = false) {
   if (!out) return fail(nullptr, PCOA_ERR_INVALID_ARG, "out is NULL");
   *out = nullptr;
   if (n_samples <= 0) return fail(nullptr, PCOA_ERR_INVALID_ARG, "n_samples must be positive");
+  if (grm && n_samples < 32)
+    return fail(nullptr, PCOA_ERR_INVALID_ARG, "a GRM ctx needs n_samples >= 32: its computePca is the Lanczos iteration, which "
+                                               "starts at 32 samples, and there is no matrix for the dense solver below that");
   if (op && n_samples >= 32 && (flags & PCOA_FLAG_EIG_HOUSEHOLDER))
     return fail(nullptr, PCOA_ERR_INVALID_ARG, "an operator ctx has no N x N matrix for the dense Householder solver "
                                                "(PCOA_FLAG_EIG_HOUSEHOLDER); its computePca is the Lanczos iteration");
@@ -104,6 +107,7 @@ static int create_impl(pcoa_ctx** out, int32_t n_samples, int32_t device_ordinal
   c->n = n_samples;
   c->is_strip = strip;
   c->is_operator = op;
+  c->is_grm = grm;
   c->s_cols = strip ? cols : n_samples;
   c->strip_col0 = strip ? col0 : 0;
   c->device = device_ordinal;
@@ -122,10 +126,11 @@ static int create_impl(pcoa_ctx** out, int32_t n_samples, int32_t device_ordinal
     c->packed_mode = 3;
     c->gram_kind = 0;
     // rows per segment: ~256 MiB, whole ranges of the second pass where a segment holds several
-    const int64_t row_bytes = (int64_t)operator_pitch_words(n_samples) * 4;
+    const int64_t row_bytes = store_pitch_words(c) * 4;
+    const int64_t align = grm ? kGrmSegmentAlign : kOperatorSegmentAlign, knob = grm ? knobs.grm_segment_rows : knobs.operator_segment_rows;
     int64_t rows = std::max<int64_t>(1, ((int64_t)256 << 20) / row_bytes);
-    if (rows >= kOperatorSegmentAlign) rows -= rows % kOperatorSegmentAlign;
-    if (knobs.operator_segment_rows > 0) rows = std::min<int64_t>(knobs.operator_segment_rows, (int64_t)1 << 24);
+    if (rows >= align) rows -= rows % align;
+    if (knob > 0) rows = std::min<int64_t>(knob, (int64_t)1 << 24);
     c->op_seg_rows = rows;
   }
   {
@@ -176,11 +181,15 @@ namespace pcoa {
 int create_full_engine_unfilled(pcoa_ctx** out, int32_t n_samples, int32_t device_ordinal, uint32_t flags) {
   return create_impl(out, n_samples, device_ordinal, flags, 0, -1, false, false);
 }
+// pcoa_create_grm (capi_grm.hip): an operator ctx whose store holds 2-bit genotype rows
+int create_grm_engine(pcoa_ctx** out, int32_t n_samples, int32_t device_ordinal, uint32_t flags) {
+  return create_impl(out, n_samples, device_ordinal, flags, 0, -1, true, true, true);
+}
 }  // namespace pcoa
 
 extern "C" {
 
-const char* pcoa_version(void) { return "pcoa_hip 0.9 (gfx950)"; }
+const char* pcoa_version(void) { return "pcoa_hip 0.10 (gfx950)"; }
 
 int pcoa_create(pcoa_ctx** out, int32_t n_samples, int32_t device_ordinal, uint32_t flags) {
   return create_impl(out, n_samples, device_ordinal, flags, 0, -1);
@@ -225,6 +234,7 @@ void pcoa_destroy(pcoa_ctx* c) {
   for (void* b : bufs)
     if (b) dev_free(b);
   operator_destroy(c);
+  grm_destroy(c);
   loadings_destroy(c);
   ld_destroy(c);
   complete_destroy(c);

@@ -10,6 +10,7 @@
 //   reduce_peers.hip     the partition and the chunk kernel of pcoa_gram_reduce_peers
 //   capi_compute.hip     the eigensolver workspace, computePca, strips, projection
 //   capi_operator.hip    the implicit similarity operator: the bit store, its products, computePca over it
+//   capi_grm.hip         the standardised-genotype operator (pcoa_create_grm): the 2-bit store, its counts and weights, K x
 //   capi_subset.hip      pcoa_create_subset: a new engine whose S is S[I, I] of another
 //   capi_pairs.hip       pcoa_similar_pairs: the screen of S for duplicate and related sample pairs
 //   capi_measure.hip     pcoa_set_similarity / pcoa_get_similarity and the centring of a Jaccard / cosine measure
@@ -81,6 +82,17 @@ struct pcoa_ctx {
   double* op_ws = nullptr;         // t, the passes' partials, the two dots (sized by the store, lazy)
   int64_t op_ws_cap = 0;
   int64_t op_products = 0;
+  // standardised-genotype operator (pcoa_create_grm, capi_grm.hip): is_operator is set too -- the ctx keeps rows in the same
+  // segmented store (op_segs .. op_ws, op_centering_set: the counts belong to the current store) and no N x N matrix -- but the
+  // rows are 2-bit genotypes at grm_pitch_words(n) words and the product is K x, K = A^T diag(d) A / M'
+  bool is_grm = false;
+  double grm_min_maf = 0.0;        // pcoa_grm_set_min_maf; survives pcoa_reset
+  bool grm_weights_set = false;    // mu / d / used / M' belong to the current counts and grm_min_maf
+  int32_t* grm_cnt = nullptr;      // [V][3] called, het, hom non-reference, then [V] used (lazy, sized by the store)
+  int64_t grm_cnt_cap = 0;
+  double* grm_par = nullptr;       // [V] mu, [V] d, then M' (one 64-bit count)
+  int64_t grm_par_cap = 0;
+  int64_t grm_used = 0;            // M' of the current weights
   int64_t subset_bytes = 0;        // bytes the gathers of pcoa_create_subset moved into this ctx (read + written)
   int64_t pairs_bytes = 0, pairs_calls = 0;   // pcoa_similar_pairs: bytes of S its scan kernels read, calls
   // per-variant loadings (pcoa_loadings_begin .. pcoa_loadings_end, capi_loadings.hip): the prepared vectors stay resident
@@ -143,6 +155,7 @@ struct pcoa_ctx {
     int32_t cflag;   // complete_diag_kernel's flag: some Q(i, i) > V
     int32_t kflag[pcoa::kKingFlagWords];   // the four consistency checks of the kinship screen
     int64_t king[3]; // its V, n_found and the entries the write pass read again
+    int64_t grm[2];  // M' of a GRM ctx's weights
   };
   HostWords* hw = nullptr;
 
@@ -301,9 +314,19 @@ struct pcoa_ctx {
 // the calls that read or move S do not exist on an operator ctx
 #define NOT_ON_OPERATOR(ctx, what)                                                                                       \
   do {                                                                                                                   \
+    NOT_ON_GRM(ctx, what);                                                                                               \
     if ((ctx)->is_operator)                                                                                              \
       return fail((ctx), PCOA_ERR_STATE, what ": an operator ctx (pcoa_create_operator) holds the carrier bitsets, not " \
                                          "S; use a full engine (pcoa_create) for this call");                         \
+  } while (0)
+
+// nor on a GRM ctx, which also has none of the calls that take or read carrier bitsets
+#define NOT_ON_GRM(ctx, what)                                                                                              \
+  do {                                                                                                                     \
+    if ((ctx)->is_grm)                                                                                                     \
+      return fail((ctx), PCOA_ERR_STATE, what ": a GRM ctx (pcoa_create_grm) holds 2-bit genotype rows fed through "       \
+                                         "pcoa_accumulate_plink_bed, no S and no carrier bitsets; its calls are "         \
+                                         "pcoa_grm_* and pcoa_compute");                                                  \
   } while (0)
 
 namespace pcoa {
@@ -338,6 +361,7 @@ hipError_t dev_grant_peer(void* p, int owner_device, int peer_device);
 int fail(pcoa_ctx* c, int code, const std::string& msg);
 int hip_fail(pcoa_ctx* c, hipError_t e, const char* what);
 int create_full_engine_unfilled(pcoa_ctx** out, int32_t n_samples, int32_t device_ordinal, uint32_t flags);   // pcoa_create, S not zeroed
+int create_grm_engine(pcoa_ctx** out, int32_t n_samples, int32_t device_ordinal, uint32_t flags);             // pcoa_create_grm
 hipEvent_t get_event(pcoa_ctx* c);
 void drain_events(pcoa_ctx* c, bool wait);
 
@@ -423,12 +447,22 @@ void complete_destroy(pcoa_ctx* c);   // the buffers, the events and an owned co
 void king_destroy(pcoa_ctx* c);   // the plane rows and the events, behind their last readers
 
 // ---- capi_operator.hip
+// words between two rows of c's store: carrier bitsets, or the 2-bit genotypes of a GRM ctx
+inline int64_t store_pitch_words(const pcoa_ctx* c) { return c->is_grm ? grm_pitch_words(c->n) : operator_pitch_words(c->n); }
+int store_grow(pcoa_ctx* c, int64_t nv);   // room for nv more rows, or PCOA_ERR_OUT_OF_MEMORY and the store as it was
+// appends nv rows: repitch(done, cur, dst) queues the kernel that writes rows [done, done + cur) of the call at dst
+int store_append(pcoa_ctx* c, int64_t nv, const std::function<hipError_t(int64_t, int64_t, uint32_t*)>& repitch);
 int operator_append(pcoa_ctx* c, const uint32_t* bits_dev, int64_t nv, int64_t ld_words);
 int operator_reset(pcoa_ctx* c);
 int operator_reserve(pcoa_ctx* c, int32_t num_pc);
 int operator_compute(pcoa_ctx* c, int32_t num_pc, double* out_components, double* out_eigenvalues, int32_t* out_nonzero_rows);
 void operator_destroy(pcoa_ctx* c);
 int64_t operator_store_bytes(const pcoa_ctx* c);
+
+// ---- capi_grm.hip
+int grm_accumulate_bed(pcoa_ctx* c, const uint8_t* bed_rows, int64_t n_variants, int64_t row_bytes, int ref_is_a1, int source);
+int grm_compute(pcoa_ctx* c, int32_t num_pc, double* out_components, double* out_eigenvalues, int32_t* out_nonzero_rows);
+void grm_destroy(pcoa_ctx* c);
 
 // ---- capi_loadings.hip
 void loadings_destroy(pcoa_ctx* c);

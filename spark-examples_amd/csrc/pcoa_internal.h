@@ -40,6 +40,7 @@ struct DebugKnobs {
   int lanczos_band = 1;            // PCOA_LANCZOS_BAND = 0: no band-Lanczos fallback (r05 behaviour); 2: ONLY the band iteration (tests)
   int synth_tile = 0;              // PCOA_SYNTH_TILE = 1: pcoa_accumulate_synthetic through the fp32 staging tile + pre-pass (r05 path) instead of generating the k-bits operand directly
   int64_t operator_segment_rows = 0;  // PCOA_OPERATOR_SEGMENT_ROWS: rows per segment of an operator ctx's bit store (tests: segment boundaries with a few hundred rows)
+  int64_t grm_segment_rows = 0;    // PCOA_GRM_SEGMENT_ROWS: the same for a GRM ctx's genotype store
   int no_narrow = 0;               // PCOA_NO_NARROW = 1: an int64 S that fits int32 stays int64 and pcoa_gram_reduce_from always widens (r05 behaviour; tests of the int64 kernels)
 };
 const DebugKnobs& debug_knobs();
@@ -228,6 +229,39 @@ hipError_t launch_operator_finish(const double* ypart, int32_t nranges, int32_t 
                                   const double* dots, int centred, double* y, hipStream_t stream);
 hipError_t launch_operator_row_sums_finish(const int64_t* ipart, int32_t nranges, int32_t n, int64_t* rs_i64, double* rs_f64,
                                            hipStream_t stream);
+
+// ---- standardised-genotype operator (grm_bits.hip): y = A^T diag(d) A x / M' from 2-bit genotype rows, K never formed ------
+// The store is a list of segments, each rows x grm_pitch_words(n) words of 16 genotypes in one coding (00 g = 0, 01 not called,
+// 10 g = 1, 11 g = 2); slots of samples >= n and the pitch's padding hold 01.  A product's additions are ordered by sample group
+// (kGrmGroupWords word columns), segment and range of kGrmRangeRows rows -- never by the grid.
+constexpr int32_t kGrmRangeRows = 512;       // rows of a segment whose pass-2 partial vector one wave accumulates in order
+constexpr int32_t kGrmSegmentAlign = 2048;   // a segment that holds this many rows holds a whole multiple of them (whole ranges)
+constexpr int32_t kGrmGroupWords = 256;      // word columns (4,096 samples) a pass-1 workgroup reduces before it writes
+int32_t grm_pitch_words(int32_t n);
+int32_t grm_groups(int32_t n);
+// raw .bed rows -> store rows; swap: exchange 00 and 11 (the non-reference allele is A1)
+hipError_t launch_grm_append(const uint8_t* src, int64_t row_bytes, int64_t nv, int32_t n, int swap, uint32_t* dst, hipStream_t stream);
+// cnt[r * 3 + {0, 1, 2}] = called, het, hom non-reference of row r
+hipError_t launch_grm_counts(const uint32_t* seg, int32_t rows, int32_t n, int32_t* cnt, hipStream_t stream);
+// mu, d, used per variant; *mprime (zeroed by the caller) += the used variants
+hipError_t launch_grm_weights(const int32_t* cnt, int64_t rows, double min_maf, double* mu, double* d, int32_t* used,
+                              unsigned long long* mprime, hipStream_t stream);
+// tpart[g * vstride + r] = the part of (A x)[r] from sample group g, r in [0, rows) of this segment (mu: the segment's first row)
+hipError_t launch_grm_ax(const uint32_t* seg, int32_t rows, int32_t n, const double* mu, const double* x, double* tpart,
+                         int64_t vstride, hipStream_t stream);
+// t = d * (the groups' partials in order), s = -(mu t)
+hipError_t launch_grm_combine_t(const double* tpart, int64_t vstride, int32_t n, int64_t rows, const double* mu, const double* d,
+                                double* t, double* s, hipStream_t stream);
+// ypart[q * pitch * 16 + i] = sum over the rows r of range q of this segment of g(r, i) t[r] + c(r, i) s[r]
+hipError_t launch_grm_at(const uint32_t* seg, int32_t rows, int32_t n, const double* t, const double* s, double* ypart,
+                         hipStream_t stream);
+// the same over c(r, i) used[r], int32
+hipError_t launch_grm_called(const uint32_t* seg, int32_t rows, int32_t n, const int32_t* used, int32_t* ipart, hipStream_t stream);
+// y = the ranges' partials added in order, over M' (M' = 0: y = 0)
+hipError_t launch_grm_finish(const double* ypart, int32_t nranges, int32_t n, const unsigned long long* mprime, double* y,
+                             hipStream_t stream);
+// *nz (zeroed by the caller) += the samples whose summed partials are positive
+hipError_t launch_grm_called_finish(const int32_t* ipart, int32_t nranges, int32_t n, int32_t* nz, hipStream_t stream);
 
 // ---- per-variant loadings (loadings.hip): out[v * num_pc + c] = (sum_i bit(v, i) u[c * ustride + i]) / div[c] for c in [0, k) ----
 // u: prepared vectors, ustride = 32 ceil(n / 32) doubles each, zero for i >= n (that is what ignores a row's tail bits); div: k

@@ -51,7 +51,7 @@ def _rows_arg(rows, np_dtype, torch_dtype, what, pinned=False):
 
 class PcoaEngine(object):
     def __init__(self, n_samples, device=0, flags=L.PCOA_FLAG_DEFAULT, gram_kernel=None, eig=None, strip=None,
-                 pipeline=True, operand=None, operator=False):
+                 pipeline=True, operand=None, operator=False, grm=False):
         """gram_kernel: None/"auto" (MX-FP4 MFMA for binary tiles, int8 MFMA for multiplicities; both exact),
         "fp4", "i8" (force one of them) or "f32" (fp32-MFMA path).
         eig: None/"auto" (Lanczos with verified residual -- single vector, then the band iteration --, Householder fallback),
@@ -61,7 +61,10 @@ class PcoaEngine(object):
         operand: None/"bits" (binary tiles are re-laid out to 1 bit per genotype and expanded to MX-FP4 inside the
         contraction) or "fp4" (PCOA_FLAG_OPERAND_FP4: the operand is stored as MX-FP4, 4 bits per genotype).
         operator=True: the implicit similarity operator (pcoa_create_operator): the engine keeps the carrier bitsets it is fed
-        (accumulate_bits / accumulate_plink_bed) and no N x N matrix; compute() runs over the products S v = X^T (X v)."""
+        (accumulate_bits / accumulate_plink_bed) and no N x N matrix; compute() runs over the products S v = X^T (X v).
+        grm=True: the standardised-genotype operator (pcoa_create_grm): the engine keeps the 2-bit genotypes of the .bed rows it is
+        fed (accumulate_plink_bed only) and compute() decomposes K = A^T diag(d) A / M', the genetic relationship matrix of
+        smartpca / plink --pca / GCTA / flashpca, through the products K x."""
         if not pipeline:
             flags |= L.PCOA_FLAG_NO_PIPELINE
         if operand == "fp4":
@@ -88,9 +91,14 @@ class PcoaEngine(object):
         self._ctx = ctypes.c_void_p()
         self.strip = None if strip is None else (int(strip[0]), int(strip[1]))
         self.operator = bool(operator)
+        self.grm = bool(grm)
         if self.operator and self.strip is not None:
             raise ValueError("operator=True and strip= exclude each other")
-        if self.operator:
+        if self.grm and (self.operator or self.strip is not None):
+            raise ValueError("grm=True excludes operator=True and strip=")
+        if self.grm:
+            rc = self._lib.pcoa_create_grm(ctypes.byref(self._ctx), int(n_samples), int(device), int(flags))
+        elif self.operator:
             rc = self._lib.pcoa_create_operator(ctypes.byref(self._ctx), int(n_samples), int(device), int(flags))
         elif self.strip is None:
             rc = self._lib.pcoa_create(ctypes.byref(self._ctx), int(n_samples), int(device), int(flags))
@@ -617,6 +625,40 @@ class PcoaEngine(object):
         torch.cuda.current_stream(v_dev.device).synchronize()   # the engine runs on its own stream
         self._check(self._lib.pcoa_operator_matvec_device(self._ctx, ctypes.c_void_p(v_dev.data_ptr()),
                                                           ctypes.c_void_p(y.data_ptr()), int(bool(centred))))
+        return y
+
+    # ------------------------------------------------------------------ standardised genotypes (GRM)
+    def grm_info(self):
+        """(variants in the genotype store, variants used under the current min MAF, bytes of HBM the store's segments hold), or
+        None on an engine that is not a GRM engine."""
+        nv, nu, nb = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
+        rc = self._lib.pcoa_grm_info(self._ctx, ctypes.byref(nv), ctypes.byref(nu), ctypes.byref(nb))
+        if rc < 0:
+            self._check(rc)
+        return (int(nv.value), int(nu.value), int(nb.value)) if rc == 1 else None
+
+    def grm_set_min_maf(self, maf):
+        """A variant is used only if its minor-allele frequency among the called samples is at least maf (0 <= maf < 0.5)."""
+        self._check(self._lib.pcoa_grm_set_min_maf(self._ctx, float(maf)))
+
+    def grm_counts(self, first_variant=0, n_variants=None):
+        """[n, 3] int32: called, heterozygous and homozygous non-reference samples of the store's rows."""
+        if n_variants is None:
+            n_variants = self.grm_info()[0] - int(first_variant)
+        out = np.zeros((max(int(n_variants), 0), 3), dtype=np.int32)
+        self._check(self._lib.pcoa_grm_counts(self._ctx, int(first_variant), int(n_variants), _ptr(out)))
+        return out
+
+    def grm_matvec_device(self, x_dev):
+        """y = K x for a float64 torch tensor x of N entries on this engine's GPU; returns a device tensor."""
+        import torch  # plumbing only: device memory handles
+        assert x_dev.is_cuda and x_dev.dtype == torch.float64 and x_dev.dim() == 1 and x_dev.shape[0] == self.n
+        if x_dev.device.index != self.device:
+            raise ValueError("x lives on cuda:%d, this engine on cuda:%d" % (x_dev.device.index, self.device))
+        x_dev = x_dev.contiguous()
+        y = torch.empty(self.n, dtype=torch.float64, device=x_dev.device)
+        torch.cuda.current_stream(x_dev.device).synchronize()   # the engine runs on its own stream
+        self._check(self._lib.pcoa_grm_matvec_device(self._ctx, ctypes.c_void_p(x_dev.data_ptr()), ctypes.c_void_p(y.data_ptr())))
         return y
 
     # ------------------------------------------------------------------ per-variant loadings

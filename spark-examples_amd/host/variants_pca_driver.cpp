@@ -92,6 +92,11 @@ struct Conf {  // PcaConf / GenomicsConf (GenomicsConf.scala:31-101), same flag 
                                         // operator engine (pcoa_create_operator) keeps the carrier bitsets and computePca runs over the
                                         // products S v = X^T (X v): no N x N matrix exists.  No auto: which form is faster at which N
                                         // has not been measured
+  bool grm = false;                     // --grm: standardised-genotype PCA: one GRM engine (pcoa_create_grm) keeps the 2-bit genotypes of ONE
+                                        // streamed PLINK fileset and computePca decomposes K = Z^T Z / M (the matrix of smartpca, plink --pca,
+                                        // GCTA, flashpca) through the products K x: no N x N matrix exists
+  double grm_min_maf = 0.0;             // --grm-min-maf X: --grm uses only variants whose minor-allele frequency is at least X, in [0, 0.5)
+  bool has_grm_min_maf = false;
   int outlier_iterations = 0;           // --outlier-iterations K: up to K rounds of outlier removal around computePca; a round replaces the engine by
                                         // its subset over the kept samples (pcoa_create_subset: one gather of S, no variant read twice).  0 = off
   double outlier_sigma = 6.0;           // --outlier-sigma X: a sample further than X population standard deviations from the mean of an axis goes
@@ -145,6 +150,10 @@ const char* kUsage =
     "                   (before computePca: report the sample pairs whose KING-robust kinship (hethet - 2 ibs0) / het_sum is >= X,\n"
     "                   X in (0, 0.5], 0.177 = first degree; independent of allele frequencies; --king-remove drops one sample of\n"
     "                   each pair as --remove-related does; one streamed PLINK fileset, one device, five more N x N matrices)\n"
+    "                   --grm [--grm-min-maf X] (standardised-genotype PCA: decompose K = Z^T Z / M over allele-frequency-standardised\n"
+    "                   dosages, missing calls mean-imputed -- the matrix of smartpca, plink --pca, GCTA, flashpca -- through the\n"
+    "                   products K x of one GRM engine that keeps 2 bits per genotype; X in [0, 0.5); one streamed PLINK fileset,\n"
+    "                   one device, no N x N matrix)\n"
     "                   --similarity-measure shared|jaccard|cosine (what computePca decomposes: the counts S as the reference,\n"
     "                   S(i,j) / (S(i,i) + S(j,j) - S(i,j)), or S(i,j) / sqrt(S(i,i) S(j,j)), evaluated on the fly from S; one\n"
     "                   engine, stored S, full layout, no projection)\n"
@@ -230,6 +239,15 @@ Conf parse(int argc, char** argv) {
     else if (a == "--gram") {
       c.gram = one(i);
       if (c.gram != "stored" && c.gram != "implicit") die("--gram takes stored or implicit");
+    }
+    else if (a == "--grm") c.grm = true;
+    else if (a == "--grm-min-maf") {
+      const std::string v = one(i);
+      char* end = nullptr;
+      c.grm_min_maf = std::strtod(v.c_str(), &end);
+      c.has_grm_min_maf = true;
+      if (v.empty() || *end != 0 || !(c.grm_min_maf >= 0.0 && c.grm_min_maf < 0.5))
+        die("--grm-min-maf takes a frequency in [0, 0.5), not '" + v + "'");
     }
     else if (a == "--outlier-iterations") {   // a value that does not parse must not silently mean "off"
       const std::string v = one(i);
@@ -328,6 +346,33 @@ Conf parse(int argc, char** argv) {
   if (c.layout == "strips" && c.reduce == "rccl") die("--layout strips has no reduction step: it cannot take --reduce rccl");
   if (c.plink_decode != "device" && c.plink_decode != "host") die("--plink-decode takes device or host");
   if (c.stream_rows < 1) die("--stream-rows must be >= 1");
+  // --grm: one GRM engine holds the 2-bit genotypes of one PLINK fileset: what needs S, carrier bitsets or several engines is
+  // refused here, before any file is read or any engine exists, in a message that names --grm and the other flag
+  if (!c.grm && c.has_grm_min_maf) die("--grm-min-maf needs --grm (the standardised-genotype PCA is off without it)");
+  if (c.grm) {
+    if (c.gpus > 1) die("--grm runs on one GRM engine: it cannot take --gpus " + std::to_string(c.gpus));
+    if (c.layout == "strips") die("--grm holds no similarity matrix to tile: it cannot take --layout strips");
+    if (c.gram == "implicit") die("--grm is an operator of its own over 2-bit genotypes: it cannot take --gram implicit");
+    if (!c.project_input_path.empty()) die("--grm: projection onto the coordinates of K is not built: it cannot take --project-input-path");
+    if (!c.dump_similarity.empty()) die("--grm never forms a matrix: it cannot take --dump-similarity");
+    if (c.similarity_measure != "shared")
+      die("--grm decomposes K, not a measure over the shared counts: it cannot take --similarity-measure " + c.similarity_measure);
+    if (c.missing_calls != "ignore") die("--grm mean-imputes missing calls itself: it cannot take --missing-calls " + c.missing_calls);
+    if (c.outlier_iterations != 0) die("--grm holds no matrix to subset: it cannot take --outlier-iterations");
+    if (c.related) die("--grm holds no shared counts to screen: it cannot take --related-min-jaccard");
+    if (c.king) die("--grm holds no genotype-class matrices to screen: it cannot take --king-cutoff");
+    if (c.ld_window > 0) die("--grm: LD pruning in front of the genotype store is not built: it cannot take --ld-window");
+    if (!c.loadings_output_path.empty()) die("--grm: SNP weights are not built: it cannot take --loadings-output-path");
+    if (c.carrier_format == "lists") die("--grm stores 2-bit genotypes: it cannot take --carrier-format lists");
+    const std::string ext = c.input_path.size() == 1 && c.input_path[0].size() >= 4 ? c.input_path[0].substr(c.input_path[0].size() - 4) : "";
+    if (c.has_maf || (ext != ".bed" && ext != ".bim" && ext != ".fam"))
+      die("--grm reads the genotypes of one PLINK fileset: --input-path must name a single .bed / .bim / .fam (dosages from VCF "
+          "ingest are not built)");
+    if (c.no_stream) die("--grm feeds the streamed .bed blocks to the engine: it cannot take --no-stream");
+    if (c.parse_only) die("--grm runs on the device: it cannot take --parse-only");
+    if (c.plink_decode == "host") die("--grm keeps the genotypes as they lie in the file: it cannot take --plink-decode host");
+    c.layout = "full";
+  }
   // --outlier-iterations: what cannot be served is refused here, before any file is read or any engine exists
   if (c.outlier_iterations < 0) die("--outlier-iterations must be >= 0 (0 = off)");
   if (!(c.outlier_sigma > 0) || !std::isfinite(c.outlier_sigma))
@@ -1491,10 +1536,11 @@ std::vector<pcoa_ctx*> run_engines(const Conf& conf, int32_t n, const std::vecto
     const bool op = conf.gram == "implicit";
     const int rc = tiled ? pcoa_create_strip(&ctx[(size_t)g], n, strips[(size_t)g].first, strips[(size_t)g].second,
                                              conf.gpu_map[(size_t)g], PCOA_FLAG_DEFAULT)
+                   : conf.grm ? pcoa_create_grm(&ctx[(size_t)g], n, conf.gpu_map[(size_t)g], PCOA_FLAG_DEFAULT)
                    : op  ? pcoa_create_operator(&ctx[(size_t)g], n, conf.gpu_map[(size_t)g], PCOA_FLAG_DEFAULT)
                          : pcoa_create(&ctx[(size_t)g], n, conf.gpu_map[(size_t)g], PCOA_FLAG_DEFAULT);
     if (rc != PCOA_OK)
-      die(std::string(tiled ? "pcoa_create_strip" : op ? "pcoa_create_operator" : "pcoa_create") + " on device " + std::to_string(conf.gpu_map[(size_t)g]) +
+      die(std::string(tiled ? "pcoa_create_strip" : conf.grm ? "pcoa_create_grm" : op ? "pcoa_create_operator" : "pcoa_create") + " on device " + std::to_string(conf.gpu_map[(size_t)g]) +
           ": " + pcoa_last_error(nullptr));
   }
   // operand buffers and the computePca workspace now, not inside the first accumulate calls (pcoa_reserve: the warm-up a Spark
@@ -1553,7 +1599,8 @@ std::vector<pcoa_ctx*> run_engines(const Conf& conf, int32_t n, const std::vecto
       *how = "peer reduction of " + std::to_string(k) + " engines into engine 0";
     }
   } else {
-    *how = conf.gram == "implicit" ? "one operator engine: the carrier bitsets kept, no similarity matrix" : "one engine";
+    *how = conf.grm ? "one GRM engine: the 2-bit genotypes kept, no matrix"
+           : conf.gram == "implicit" ? "one operator engine: the carrier bitsets kept, no similarity matrix" : "one engine";
   }
   for (int g = 0; g < (tiled ? k : 1); ++g) check(ctx[(size_t)g], pcoa_gram_finalize(ctx[(size_t)g]), "getSimilarityMatrix");
   *feed_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_feed).count();
@@ -2033,6 +2080,13 @@ int main(int argc, char** argv) {
   if (stream_plink) fed_meta = plink.meta;                 // one engine: every kept line, in file order
   if (stream_join || data.size() > 1) fed_meta_known = false;
   for (pcoa_ctx* o : owners) check(o, pcoa_gram_finalize(o), "getSimilarityMatrix");
+  if (conf.grm) {
+    int64_t variants = 0, used = 0, store = 0;
+    check(ctx, pcoa_grm_set_min_maf(ctx, conf.grm_min_maf), "pcoa_grm_set_min_maf");
+    if (pcoa_grm_info(ctx, &variants, &used, &store) != 1) die(std::string("pcoa_grm_info: ") + pcoa_last_error(ctx));
+    std::fprintf(stderr, "Standardised genotypes: %lld of %lld variants used (min MAF %g), store %lld bytes\n", (long long)used,
+                 (long long)variants, conf.grm_min_maf, (long long)store);
+  }
   if (g_ld.on) {
     pcoa_ld_stats ls;
     check(ctx, pcoa_get_ld_stats(ctx, &ls, sizeof(ls)), "pcoa_get_ld_stats");

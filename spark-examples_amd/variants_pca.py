@@ -553,6 +553,14 @@ class PcaConf(object):
                             "(pcoa_create_operator) keeps the carrier bitsets and computePca runs over the products "
                             "S v = X^T (X v), no N x N matrix exists.  One GPU, full layout; there is no auto: which form is "
                             "faster at which N has not been measured")
+        p.add_argument("--grm", action="store_true",
+                       help="standardised-genotype PCA: one GRM engine (pcoa_create_grm) keeps the 2-bit genotypes of ONE PLINK "
+                            "fileset and computePca decomposes K = Z^T Z / M over allele-frequency-standardised dosages, missing "
+                            "calls mean-imputed (the matrix of smartpca, plink --pca, GCTA, flashpca), through the products K x; "
+                            "no N x N matrix exists.  One GPU")
+        p.add_argument("--grm-min-maf", type=float, default=None,
+                       help="--grm: use only variants whose minor-allele frequency among the called samples is at least this, "
+                            "in [0, 0.5) (default 0)")
         p.add_argument("--dump-similarity", type=str, default=None,
                        help="write S (N x N int64, little-endian, row-major) to this file (parity tests)")
         p.add_argument("--project-input-path", type=str, nargs="+", default=None,
@@ -1117,6 +1125,62 @@ def resolve_layout(conf, n, world, devices):
     return ranges if layout == "strips" else None
 
 
+def check_grm_conf(conf):
+    """--grm: one GRM engine holds the 2-bit genotypes of one PLINK fileset.  What needs S, carrier bitsets or several engines is
+    refused before any file is read or any device is touched, in a message that names --grm and the other flag."""
+    if not conf.grm:
+        if conf.grm_min_maf is not None:
+            raise SystemExit("VariantsPcaDriver: --grm-min-maf needs --grm (the standardised-genotype PCA is off without it)")
+        return
+    world = max(conf.gpus, int(os.environ.get("WORLD_SIZE", "1")))
+    refused = [
+        (world > 1, "runs on one GRM engine: it cannot take --gpus %d" % world),
+        (conf.layout == "strips", "holds no similarity matrix to tile: it cannot take --layout strips"),
+        (conf.gram == "implicit", "is an operator of its own over 2-bit genotypes: it cannot take --gram implicit"),
+        (bool(conf.project_input_path), "projection onto the coordinates of K is not built: it cannot take --project-input-path"),
+        (bool(conf.dump_similarity), "never forms a matrix: it cannot take --dump-similarity"),
+        (conf.similarity_measure != "shared", "decomposes K, not a measure over the shared counts: it cannot take "
+                                              "--similarity-measure %s" % conf.similarity_measure),
+        (conf.missing_calls != "ignore", "mean-imputes missing calls itself: it cannot take --missing-calls %s" % conf.missing_calls),
+        (conf.outlier_iterations != 0, "holds no matrix to subset: it cannot take --outlier-iterations"),
+        (conf.related_min_jaccard is not None, "holds no shared counts to screen: it cannot take --related-min-jaccard"),
+        (conf.king_cutoff is not None, "holds no genotype-class matrices to screen: it cannot take --king-cutoff"),
+        (bool(conf.ld_window), "LD pruning in front of the genotype store is not built: it cannot take --ld-window"),
+        (bool(conf.loadings_output_path), "SNP weights are not built: it cannot take --loadings-output-path"),
+    ]
+    for hit, why in refused:
+        if hit:
+            raise SystemExit("VariantsPcaDriver: --grm " + why)
+    if conf.grm_min_maf is not None and not (0.0 <= conf.grm_min_maf < 0.5):
+        raise SystemExit("VariantsPcaDriver: --grm-min-maf takes a frequency in [0, 0.5), not '%s'" % conf.grm_min_maf)
+    paths = conf.inputPath or []
+    if conf.synthetic or conf.minAlleleFrequency is not None or len(paths) != 1 or not is_plink_path(paths[0]):
+        raise SystemExit("VariantsPcaDriver: --grm reads the genotypes of one PLINK fileset: --input-path must name a single "
+                         ".bed / .bim / .fam (dosages from VCF ingest are not built)")
+
+
+def grm_accumulate(call_rdd, matrix_size, min_maf, device=0, err=None):
+    """--grm: the raw .bed rows of a PLINK fileset into one GRM engine, block by block (pcoa_accumulate_plink_bed), and the
+    stderr line that says what the engine will decompose."""
+    _, geno, keep, ref_is_a1 = call_rdd
+    eng = PcoaEngine(matrix_size, device=device, grm=True)
+    eng.grm_set_min_maf(min_maf)
+    all_kept = bool(keep.all())
+    for v0 in range(0, geno.shape[0], PLINK_BLOCK_ROWS):
+        rows = geno[v0:v0 + PLINK_BLOCK_ROWS]
+        if not all_kept:
+            k = keep[v0:v0 + PLINK_BLOCK_ROWS]
+            if not k.any():
+                continue
+            rows = rows[k]
+        eng.accumulate_plink_bed(np.ascontiguousarray(rows), ref_is_a1=ref_is_a1)
+    eng.finalize()
+    variants, used, store = eng.grm_info()
+    (err or sys.stderr).write("Standardised genotypes: %d of %d variants used (min MAF %g), store %d bytes\n"
+                              % (used, variants, min_maf, store))
+    return eng
+
+
 def check_gram_conf(conf):
     """--gram implicit: one operator engine holds the carrier bitsets of every variant.  What needs S, or several engines, is
     refused before any file is read or any device is touched."""
@@ -1534,6 +1598,7 @@ def main_projection(conf):
 def main(args):
     """VariantsPcaDriver.main (VariantsPca.scala:38-50)."""
     conf = PcaConf(args)
+    check_grm_conf(conf)
     check_outlier_conf(conf)
     check_related_conf(conf)
     check_king_conf(conf)
@@ -1592,6 +1657,12 @@ def main(args):
             write_ld_mask(conf.ld_output_path, variant_meta, keep)
         return engine
 
+    if conf.grm:
+        driver.engine = grm_accumulate(calls_rdd, n, conf.grm_min_maf or 0.0, device=conf.gpu)
+        driver.emitResult(driver.computePca(driver.engine))
+        driver.reportIoStats(sys.stderr)
+        driver.stop()
+        return 0
     if conf.gram == "implicit":
         if conf.ld_window:
             driver.engine = ld_ingest(PcoaEngine(n, device=conf.gpu, operator=True))
