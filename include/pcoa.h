@@ -35,7 +35,7 @@ extern "C" {
 #endif
 
 #define PCOA_VERSION_MAJOR 0
-#define PCOA_VERSION_MINOR 10
+#define PCOA_VERSION_MINOR 11
 
 typedef struct pcoa_ctx pcoa_ctx;
 
@@ -307,8 +307,8 @@ int pcoa_operator_matvec_device(pcoa_ctx* ctx, const double* v_dev, double* y_de
  *   results are reproducible: the same store, min_maf and x give bit-identical y, run to run and whatever the sizes of the
  *           accumulate calls were (no floating-point atomics; the order of every addition is fixed by N, the segment size
  *           and a row's index in the store).
- * Not built: JNI / Scala natives, SNP weights, projection of new samples, LD pruning in front of the store, variant sharding
- * over engines, reading K out. */
+ * SNP weights and the projection of new samples: pcoa_grm_weights / pcoa_grm_project below.
+ * Not built: JNI / Scala natives, LD pruning in front of the store, variant sharding over engines, reading K out. */
 int pcoa_create_grm(pcoa_ctx** out, int32_t n_samples, int32_t device_ordinal, uint32_t flags);
 
 /* Returns 1 for a GRM ctx, 0 otherwise (like pcoa_operator_info).  *variants_out: rows in the store; *used_out: M' under the
@@ -327,6 +327,41 @@ int pcoa_grm_counts(pcoa_ctx* ctx, int64_t first_variant, int64_t n_variants, in
 /* y = K x on DEVICE vectors of N doubles on the ctx's GPU; returns when y is complete (synchronous on the ctx stream), x must
  * be complete when it is called.  M' = 0 gives y = 0. */
 int pcoa_grm_matvec_device(pcoa_ctx* ctx, const double* x_dev, double* y_dev);
+
+/* ---- SNP weights of the axes of K, and new samples projected onto them -------------------------------------
+ * With K u_c = lambda_c u_c (what pcoa_compute returned on the panel) and Z = D^1/2 A / sqrt(M'):
+ *   t_vc = d_v (A u_c)_v                                  the first pass of the product applied to u_c
+ *   w_vc = sqrt(d_v) (A u_c)_v / sqrt(M' lambda_c)         the left singular vectors of Z: smartpca's snpweightoutname, plink2's
+ *                                                          --pca var-wts (up to their scaling conventions)
+ *   u_c[i] = sum_v A_vi t_vc / (M' lambda_c), so a sample q genotyped at the same variants is placed at
+ *   coord(q, c) = sum_v (g_vq - mu_v c_vq) t_vc / (M' lambda_c)
+ * with mu, d and M' the PANEL's; a missing call of q contributes 0 (mean imputation, as in K itself).  The panel's own samples
+ * come back as u_c.  The panel's counts and weights are recomputed, if they are not resident, under its current min_maf, as
+ * pcoa_compute does.  Both calls run the passes for two components at a time; every column is added in the order of the
+ * one-vector product, so component c has the same bits whatever num_pc is, and a study store that holds the panel's own rows
+ * gives pcoa_grm_matvec_device(u_c) / lambda_c bit for bit.  Neither call writes a store, and every error leaves both ctxs
+ * usable.  PCOA_ERR_STATE: panel is not a pcoa_create_grm ctx.  PCOA_ERR_INVALID_ARG: num_pc < 1, an eigenvalue that is not
+ * positive and finite, M' = 0, a window outside the store, a NULL output.
+ *
+ * pcoa_create_grm_study: a GRM store of n_samples >= 1 study samples: pcoa_accumulate_plink_bed, pcoa_grm_info (used_out = 0),
+ * pcoa_grm_counts, pcoa_reset / reserve / sync / destroy as on a GRM ctx; it has no weights of its own: pcoa_compute,
+ * pcoa_grm_matvec_device and pcoa_grm_set_min_maf return PCOA_ERR_STATE with their own message.  Flags as pcoa_create_grm.
+ * Not built: a least-squares projection for sparsely called samples (out_called lets a host report the shrinkage), a saved
+ * model, allele flipping between the two filesets, multi-GPU, JNI / Scala natives. */
+int pcoa_create_grm_study(pcoa_ctx** out, int32_t n_samples, int32_t device_ordinal, uint32_t flags);
+
+/* scaled = 0: out[(v - first_variant) * num_pc + c] = t_vc (the vector the projection uses; 0 for an unused variant)
+ * scaled = 1: w_vc = used_v ? t_vc / sqrt(d_v * ((double)M' * lambda_c)) : 0.0   in exactly this expression, no contraction
+ * components: host [num_pc][N]; eigenvalues: host [num_pc]; out: host [n_variants][num_pc]. */
+int pcoa_grm_weights(pcoa_ctx* panel, int32_t num_pc, const double* components, const double* eigenvalues, int32_t scaled,
+                     int64_t first_variant, int64_t n_variants, double* out);
+
+/* out_coords[c * N_study + q] = (sum_v g_vq t_vc + sum_v c_vq s_vc) / M' / lambda_c with s_vc = -(mu_v t_vc), the partial sums
+ * added in (segment, range) order of the STUDY's store; out_called[q] (may be NULL) = the panel's USED variants at which q is
+ * called.  study: either GRM kind (the panel itself included), on the panel's device (PCOA_ERR_INVALID_ARG otherwise), holding
+ * exactly as many rows as the panel, fed in the same order (PCOA_ERR_STATE otherwise). */
+int pcoa_grm_project(pcoa_ctx* panel, pcoa_ctx* study, int32_t num_pc, const double* components, const double* eigenvalues,
+                     double* out_coords /* [num_pc][N_study] */, int32_t* out_called /* [N_study] */);
 
 /* ---- PCoA over a sample subset of a stored S ------------------------------------------------------------------------------
  * For a kept index set I, S[I, I] is exactly the similarity matrix of the reduced cohort (an entry counts the variants two

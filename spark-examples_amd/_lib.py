@@ -230,6 +230,9 @@ _SIGNATURES = [
     ("pcoa_grm_set_min_maf", ctypes.c_int, [_vp, ctypes.c_double]),
     ("pcoa_grm_counts", ctypes.c_int, [_vp, _i64, _i64, _vp]),
     ("pcoa_grm_matvec_device", ctypes.c_int, [_vp, _vp, _vp]),
+    ("pcoa_create_grm_study", ctypes.c_int, [ctypes.POINTER(_vp), _i32, _i32, ctypes.c_uint32]),
+    ("pcoa_grm_weights", ctypes.c_int, [_vp, _i32, _vp, _vp, _i32, _i64, _i64, _vp]),
+    ("pcoa_grm_project", ctypes.c_int, [_vp, _vp, _i32, _vp, _vp, _vp, _vp]),
     ("pcoa_strip_info", ctypes.c_int, [_vp, ctypes.POINTER(_i32), ctypes.POINTER(_i32)]),
     ("pcoa_strip_col_sums", ctypes.c_int, [_vp, _vp]),
     ("pcoa_strip_matvec", ctypes.c_int, [_vp, _vp, _vp, ctypes.c_double, _vp]),

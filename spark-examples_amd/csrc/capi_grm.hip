@@ -139,9 +139,29 @@ int grm_called_samples(pcoa_ctx* c, const GrmWorkspace& w) {
 
 const char* kNotGrm = "not a GRM ctx (pcoa_create_grm)";
 
+// a study store (pcoa_create_grm_study) has no weights of its own: the panel's are applied to it
+int no_weights_on_study(pcoa_ctx* c, const char* call) {
+  return fail(c, PCOA_ERR_STATE, std::string(call) + ": a GRM study ctx (pcoa_create_grm_study) holds the genotypes of study samples and "
+                                     "no weights of its own; pass it to pcoa_grm_project beside the panel's ctx");
+}
+
 }  // namespace
 
 namespace pcoa {
+
+int64_t grm_store_ranges(const pcoa_ctx* c) { return store_ranges(c); }
+
+int grm_resident_params(pcoa_ctx* c, GrmParams* out, int64_t* used_out) {
+  const int rc = grm_weights(c);
+  if (rc != PCOA_OK) return rc;
+  const GrmWeights w = weights_of(c);
+  out->mprime = w.mprime;
+  out->mu = w.mu;
+  out->d = w.d;
+  out->used = w.used;
+  if (used_out) *used_out = c->grm_used;
+  return PCOA_OK;
+}
 
 // pcoa_accumulate_plink_bed on a GRM ctx: the raw rows of a chunk are re-pitched straight into the store (the append kernel is
 // the staging slot's only reader).  Every segment the call needs is allocated before its first row moves.
@@ -164,6 +184,7 @@ int grm_accumulate_bed(pcoa_ctx* c, const uint8_t* bed_rows, int64_t n_variants,
 // back only with its true residual verified; there is no dense fallback (no matrix).
 int grm_compute(pcoa_ctx* c, int32_t num_pc, double* out_components, double* out_eigenvalues, int32_t* out_nonzero_rows) {
   const double t0 = wall_now();
+  if (c->is_grm_study) return no_weights_on_study(c, "pcoa_compute");
   int rc = check_device_flags(c);
   if (rc != PCOA_OK) return rc;
   if ((rc = ensure_workspace(c, num_pc)) != PCOA_OK) return rc;
@@ -196,8 +217,10 @@ int grm_compute(pcoa_ctx* c, int32_t num_pc, double* out_components, double* out
 void grm_destroy(pcoa_ctx* c) {
   if (c->grm_cnt) dev_free(c->grm_cnt);
   if (c->grm_par) dev_free(c->grm_par);
+  if (c->grm_mw) dev_free(c->grm_mw);
   c->grm_cnt = nullptr;
   c->grm_par = nullptr;
+  c->grm_mw = nullptr;
 }
 
 }  // namespace pcoa
@@ -214,7 +237,7 @@ int pcoa_grm_info(pcoa_ctx* c, int64_t* variants_out, int64_t* used_out, int64_t
   if (used_out) *used_out = 0;
   if (store_bytes_out) *store_bytes_out = c->is_grm ? operator_store_bytes(c) : 0;
   if (!c->is_grm) return 0;
-  if (used_out) {
+  if (used_out && !c->is_grm_study) {
     int rc = check_device_flags(c);
     if (rc != PCOA_OK) return rc;
     if ((rc = grm_weights(c)) != PCOA_OK) return rc;
@@ -226,6 +249,7 @@ int pcoa_grm_info(pcoa_ctx* c, int64_t* variants_out, int64_t* used_out, int64_t
 int pcoa_grm_set_min_maf(pcoa_ctx* c, double maf) {
   CHECK_CTX(c);
   if (!c->is_grm) return fail(c, PCOA_ERR_STATE, std::string("pcoa_grm_set_min_maf: ") + kNotGrm);
+  if (c->is_grm_study) return no_weights_on_study(c, "pcoa_grm_set_min_maf");
   if (!(maf >= 0.0 && maf < 0.5))
     return fail(c, PCOA_ERR_INVALID_ARG, "pcoa_grm_set_min_maf: maf = " + std::to_string(maf) + " is outside [0, 0.5)");
   if (maf != c->grm_min_maf) c->grm_weights_set = false;
@@ -254,6 +278,7 @@ int pcoa_grm_counts(pcoa_ctx* c, int64_t first_variant, int64_t n_variants, int3
 int pcoa_grm_matvec_device(pcoa_ctx* c, const double* x_dev, double* y_dev) {
   CHECK_CTX(c);
   if (!c->is_grm) return fail(c, PCOA_ERR_STATE, std::string("pcoa_grm_matvec_device: ") + kNotGrm);
+  if (c->is_grm_study) return no_weights_on_study(c, "pcoa_grm_matvec_device");
   if (!x_dev || !y_dev) return fail(c, PCOA_ERR_INVALID_ARG, "pcoa_grm_matvec_device: x_dev or y_dev is NULL");
   int rc = check_device_flags(c);
   if (rc != PCOA_OK) return rc;

@@ -21,6 +21,7 @@
 // count).  The masks are spent as AND masks from a sign-extended bit-field extract, the idiom of loadings.hip.
 #include <algorithm>
 
+#include "grm_slots.h"
 #include "pcoa_internal.h"
 
 namespace pcoa {
@@ -31,18 +32,7 @@ int32_t grm_groups(int32_t n) { return ((n + 15) / 16 + kGrmGroupWords - 1) / kG
 namespace {
 
 constexpr int kRowsPerBlock1 = 512;          // rows a pass-1 workgroup streams past its x registers (16 butterfly blocks)
-constexpr uint32_t kLo = 0x55555555u;        // the low bit of every slot; as a word: 16 slots of 01 (not called)
-
-__device__ __forceinline__ double and_mask(double v, int m) {
-  return __hiloint2double(__double2hiint(v) & m, __double2loint(v) & m);
-}
-
-// the three slot masks of a word, each at the slots' even bit positions
-__device__ __forceinline__ void slot_masks(uint32_t w, uint32_t& hi, uint32_t& both, uint32_t& called) {
-  hi = (w >> 1) & kLo;
-  both = hi & w;
-  called = (hi | ~w) & kLo;
-}
+// (kLo, and_mask and slot_masks: grm_slots.h, shared with grm_multi.hip)
 
 // Repitch raw .bed rows [nv][row_bytes] -> [nv][pitch] words.  Bytes beyond ceil(n / 4) and slots of samples >= n become 01;
 // swap (the non-reference allele is A1, ref_is_a1 = 0): 00 <-> 11, so that 11 is the homozygous non-reference code

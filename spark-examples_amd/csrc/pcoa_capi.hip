@@ -76,11 +76,11 @@ void drain_events(pcoa_ctx* c, bool wait) {
 // ================================================================================================
 // zero_s = false (pcoa_create_subset): S is allocated but not zeroed -- the caller overwrites every entry before anything reads it
 static int create_impl(pcoa_ctx** out, int32_t n_samples, int32_t device_ordinal, uint32_t flags, int32_t col0, int32_t cols,
-                       bool op = false, bool zero_s = true, bool grm = false) {
+                       bool op = false, bool zero_s = true, bool grm = false, bool grm_study = false) {
   if (!out) return fail(nullptr, PCOA_ERR_INVALID_ARG, "out is NULL");
   *out = nullptr;
   if (n_samples <= 0) return fail(nullptr, PCOA_ERR_INVALID_ARG, "n_samples must be positive");
-  if (grm && n_samples < 32)
+  if (grm && !grm_study && n_samples < 32)
     return fail(nullptr, PCOA_ERR_INVALID_ARG, "a GRM ctx needs n_samples >= 32: its computePca is the Lanczos iteration, which "
                                                "starts at 32 samples, and there is no matrix for the dense solver below that");
   if (op && n_samples >= 32 && (flags & PCOA_FLAG_EIG_HOUSEHOLDER))
@@ -108,6 +108,7 @@ static int create_impl(pcoa_ctx** out, int32_t n_samples, int32_t device_ordinal
   c->is_strip = strip;
   c->is_operator = op;
   c->is_grm = grm;
+  c->is_grm_study = grm_study;
   c->s_cols = strip ? cols : n_samples;
   c->strip_col0 = strip ? col0 : 0;
   c->device = device_ordinal;
@@ -185,11 +186,15 @@ int create_full_engine_unfilled(pcoa_ctx** out, int32_t n_samples, int32_t devic
 int create_grm_engine(pcoa_ctx** out, int32_t n_samples, int32_t device_ordinal, uint32_t flags) {
   return create_impl(out, n_samples, device_ordinal, flags, 0, -1, true, true, true);
 }
+// pcoa_create_grm_study (capi_grm_project.hip): the same store for study samples; it runs no eigensolver, so any n_samples >= 1
+int create_grm_study_engine(pcoa_ctx** out, int32_t n_samples, int32_t device_ordinal, uint32_t flags) {
+  return create_impl(out, n_samples, device_ordinal, flags, 0, -1, true, true, true, true);
+}
 }  // namespace pcoa
 
 extern "C" {
 
-const char* pcoa_version(void) { return "pcoa_hip 0.10 (gfx950)"; }
+const char* pcoa_version(void) { return "pcoa_hip 0.11 (gfx950)"; }
 
 int pcoa_create(pcoa_ctx** out, int32_t n_samples, int32_t device_ordinal, uint32_t flags) {
   return create_impl(out, n_samples, device_ordinal, flags, 0, -1);

@@ -11,6 +11,7 @@
 //   capi_compute.hip     the eigensolver workspace, computePca, strips, projection
 //   capi_operator.hip    the implicit similarity operator: the bit store, its products, computePca over it
 //   capi_grm.hip         the standardised-genotype operator (pcoa_create_grm): the 2-bit store, its counts and weights, K x
+//   capi_grm_project.hip SNP weights of K's axes and the projection of a study store onto them (pcoa_create_grm_study, pcoa_grm_weights / _project)
 //   capi_subset.hip      pcoa_create_subset: a new engine whose S is S[I, I] of another
 //   capi_pairs.hip       pcoa_similar_pairs: the screen of S for duplicate and related sample pairs
 //   capi_measure.hip     pcoa_set_similarity / pcoa_get_similarity and the centring of a Jaccard / cosine measure
@@ -93,6 +94,9 @@ struct pcoa_ctx {
   double* grm_par = nullptr;       // [V] mu, [V] d, then M' (one 64-bit count)
   int64_t grm_par_cap = 0;
   int64_t grm_used = 0;            // M' of the current weights
+  bool is_grm_study = false;       // pcoa_create_grm_study: a GRM store of study samples with no weights of its own (capi_grm_project.hip)
+  double* grm_mw = nullptr;        // pcoa_grm_weights / pcoa_grm_project on a panel: components, t, s, the passes' partials, results (lazy)
+  int64_t grm_mw_cap = 0;
   int64_t subset_bytes = 0;        // bytes the gathers of pcoa_create_subset moved into this ctx (read + written)
   int64_t pairs_bytes = 0, pairs_calls = 0;   // pcoa_similar_pairs: bytes of S its scan kernels read, calls
   // per-variant loadings (pcoa_loadings_begin .. pcoa_loadings_end, capi_loadings.hip): the prepared vectors stay resident
@@ -362,6 +366,7 @@ int fail(pcoa_ctx* c, int code, const std::string& msg);
 int hip_fail(pcoa_ctx* c, hipError_t e, const char* what);
 int create_full_engine_unfilled(pcoa_ctx** out, int32_t n_samples, int32_t device_ordinal, uint32_t flags);   // pcoa_create, S not zeroed
 int create_grm_engine(pcoa_ctx** out, int32_t n_samples, int32_t device_ordinal, uint32_t flags);             // pcoa_create_grm
+int create_grm_study_engine(pcoa_ctx** out, int32_t n_samples, int32_t device_ordinal, uint32_t flags);       // pcoa_create_grm_study
 hipEvent_t get_event(pcoa_ctx* c);
 void drain_events(pcoa_ctx* c, bool wait);
 
@@ -463,6 +468,15 @@ int64_t operator_store_bytes(const pcoa_ctx* c);
 int grm_accumulate_bed(pcoa_ctx* c, const uint8_t* bed_rows, int64_t n_variants, int64_t row_bytes, int ref_is_a1, int source);
 int grm_compute(pcoa_ctx* c, int32_t num_pc, double* out_components, double* out_eigenvalues, int32_t* out_nonzero_rows);
 void grm_destroy(pcoa_ctx* c);
+// the panel's resident per-variant parameters under its current min_maf, recomputed if the store or min_maf changed (the
+// pointers stay valid until the store grows); *used_out = M'
+struct GrmParams {
+  const unsigned long long* mprime;
+  const double *mu, *d;
+  const int32_t* used;
+};
+int grm_resident_params(pcoa_ctx* c, GrmParams* out, int64_t* used_out);
+int64_t grm_store_ranges(const pcoa_ctx* c);   // ranges of kGrmRangeRows rows over the segments of c's store
 
 // ---- capi_loadings.hip
 void loadings_destroy(pcoa_ctx* c);

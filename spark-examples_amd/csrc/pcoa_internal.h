@@ -263,6 +263,28 @@ hipError_t launch_grm_finish(const double* ypart, int32_t nranges, int32_t n, co
 // *nz (zeroed by the caller) += the samples whose summed partials are positive
 hipError_t launch_grm_called_finish(const int32_t* ipart, int32_t nranges, int32_t n, int32_t* nz, hipStream_t stream);
 
+// ---- the two passes for k vectors at once (grm_multi.hip): SNP weights and the projection of new samples ------
+// k must be 1 or 2 (grm_multi_chunk picks the chunk).  Every column is added in the order of the one-vector kernels, so column c
+// of any chunk has the bits of a one-vector run.
+int grm_multi_chunk(int32_t remaining);
+// tpart[c * cstride + g * vstride + r] = the part of (A x_c)[r] from sample group g; x_c = x + c * xstride, c in [0, k)
+hipError_t launch_grm_ax_multi(const uint32_t* seg, int32_t rows, int32_t n, const double* mu, const double* x, int64_t xstride, int32_t k,
+                               double* tpart, int64_t vstride, int64_t cstride, hipStream_t stream);
+// ypart[c * cstride + q * pitch * 16 + i] = sum over the rows r of range q of g(r, i) t_c[r] + c(r, i) s_c[r]; t_c = t + c * tstride,
+// s_c = s + c * tstride
+hipError_t launch_grm_at_multi(const uint32_t* seg, int32_t rows, int32_t n, const double* t, const double* s, int64_t tstride, int32_t k,
+                               double* ypart, int64_t cstride, hipStream_t stream);
+// out[c * n + i] = (the ranges' partials of column c added in order) / M' / lam[c], c in [0, k)
+hipError_t launch_grm_project_finish(const double* ypart, int32_t nranges, int64_t cstride, int32_t n, int32_t k,
+                                     const unsigned long long* mprime, const double* lam, double* out, hipStream_t stream);
+// called[i] = the ranges' integer partials added
+hipError_t launch_grm_called_sum(const int32_t* ipart, int32_t nranges, int32_t n, int32_t* called, hipStream_t stream);
+// out[v * num_pc + c] for the rows [first, first + nv): t_c[first + v], or with scaled the unit weight
+// used ? t / sqrt(d * ((double)M' * lam[c])) : 0.0
+hipError_t launch_grm_weights_out(const double* t, int64_t tstride, const double* d, const int32_t* used,
+                                  const unsigned long long* mprime, const double* lam, int scaled, int64_t first, int64_t nv,
+                                  int32_t num_pc, double* out, hipStream_t stream);
+
 // ---- per-variant loadings (loadings.hip): out[v * num_pc + c] = (sum_i bit(v, i) u[c * ustride + i]) / div[c] for c in [0, k) ----
 // u: prepared vectors, ustride = 32 ceil(n / 32) doubles each, zero for i >= n (that is what ignores a row's tail bits); div: k
 // divisors or NULL; k must be 1, 2, 4 or 8 (loadings_chunk picks the chunk); out / u / div point at the chunk's first component.

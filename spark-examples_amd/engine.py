@@ -51,7 +51,7 @@ def _rows_arg(rows, np_dtype, torch_dtype, what, pinned=False):
 
 class PcoaEngine(object):
     def __init__(self, n_samples, device=0, flags=L.PCOA_FLAG_DEFAULT, gram_kernel=None, eig=None, strip=None,
-                 pipeline=True, operand=None, operator=False, grm=False):
+                 pipeline=True, operand=None, operator=False, grm=False, grm_study=False):
         """gram_kernel: None/"auto" (MX-FP4 MFMA for binary tiles, int8 MFMA for multiplicities; both exact),
         "fp4", "i8" (force one of them) or "f32" (fp32-MFMA path).
         eig: None/"auto" (Lanczos with verified residual -- single vector, then the band iteration --, Householder fallback),
@@ -64,7 +64,9 @@ class PcoaEngine(object):
         (accumulate_bits / accumulate_plink_bed) and no N x N matrix; compute() runs over the products S v = X^T (X v).
         grm=True: the standardised-genotype operator (pcoa_create_grm): the engine keeps the 2-bit genotypes of the .bed rows it is
         fed (accumulate_plink_bed only) and compute() decomposes K = A^T diag(d) A / M', the genetic relationship matrix of
-        smartpca / plink --pca / GCTA / flashpca, through the products K x."""
+        smartpca / plink --pca / GCTA / flashpca, through the products K x.
+        grm_study=True: a GRM store of study samples (pcoa_create_grm_study, any n_samples >= 1): it is fed like a GRM engine and
+        has no weights of its own; a GRM engine's grm_project(study, ...) places its samples on that engine's axes."""
         if not pipeline:
             flags |= L.PCOA_FLAG_NO_PIPELINE
         if operand == "fp4":
@@ -91,12 +93,15 @@ class PcoaEngine(object):
         self._ctx = ctypes.c_void_p()
         self.strip = None if strip is None else (int(strip[0]), int(strip[1]))
         self.operator = bool(operator)
-        self.grm = bool(grm)
+        self.grm_study = bool(grm_study)
+        self.grm = bool(grm) or self.grm_study
         if self.operator and self.strip is not None:
             raise ValueError("operator=True and strip= exclude each other")
         if self.grm and (self.operator or self.strip is not None):
             raise ValueError("grm=True excludes operator=True and strip=")
-        if self.grm:
+        if self.grm_study:
+            rc = self._lib.pcoa_create_grm_study(ctypes.byref(self._ctx), int(n_samples), int(device), int(flags))
+        elif self.grm:
             rc = self._lib.pcoa_create_grm(ctypes.byref(self._ctx), int(n_samples), int(device), int(flags))
         elif self.operator:
             rc = self._lib.pcoa_create_operator(ctypes.byref(self._ctx), int(n_samples), int(device), int(flags))
@@ -660,6 +665,39 @@ class PcoaEngine(object):
         torch.cuda.current_stream(x_dev.device).synchronize()   # the engine runs on its own stream
         self._check(self._lib.pcoa_grm_matvec_device(self._ctx, ctypes.c_void_p(x_dev.data_ptr()), ctypes.c_void_p(y.data_ptr())))
         return y
+
+    def _grm_axes(self, components, eigenvalues):
+        """components [N, k] and eigenvalues [k] as compute(k) returned them -> ([k][N] contiguous, [k], k)."""
+        comps = np.asarray(components, dtype=np.float64)
+        if comps.ndim == 1:
+            comps = comps[:, None]
+        lam = np.ascontiguousarray(np.asarray(eigenvalues, dtype=np.float64).reshape(-1))
+        if comps.ndim != 2 or comps.shape[0] != self.n or comps.shape[1] != lam.shape[0]:
+            raise ValueError("components must be [N = %d, k] and eigenvalues [k], not %s and %s" % (self.n, comps.shape, lam.shape))
+        return np.ascontiguousarray(comps.T), lam, int(lam.shape[0])
+
+    def grm_weights(self, components, eigenvalues, scaled=True, first_variant=0, n_variants=None):
+        """[n_variants, k] float64: the SNP weights of the axes compute(k) returned (pcoa_grm_weights).  scaled=True: the left
+        singular vectors w_c = sqrt(d) (A u_c) / sqrt(M' lambda_c), orthonormal over the used variants and 0.0 at an unused one;
+        scaled=False: t_c = d (A u_c), the vector the projection uses."""
+        u, lam, k = self._grm_axes(components, eigenvalues)
+        if n_variants is None:
+            info = self.grm_info()   # (None: not a GRM engine -- the call itself says so)
+            n_variants = info[0] - int(first_variant) if info else 0
+        out = np.zeros((max(int(n_variants), 0), k), dtype=np.float64)
+        self._check(self._lib.pcoa_grm_weights(self._ctx, k, _ptr(u), _ptr(lam), int(bool(scaled)), int(first_variant),
+                                               int(n_variants), _ptr(out)))
+        return out
+
+    def grm_project(self, study, components, eigenvalues):
+        """(coords [N_study, k] float64, called [N_study] int32): the samples of `study` -- a grm_study=True engine, or a GRM
+        engine, fed the same variants in the same order -- on the axes compute(k) returned for this engine (pcoa_grm_project);
+        called[q]: this engine's used variants at which sample q is called."""
+        u, lam, k = self._grm_axes(components, eigenvalues)
+        coords = np.zeros((k, study.n), dtype=np.float64)
+        called = np.zeros(study.n, dtype=np.int32)
+        self._check(self._lib.pcoa_grm_project(self._ctx, study._ctx, k, _ptr(u), _ptr(lam), _ptr(coords), _ptr(called)))
+        return np.ascontiguousarray(coords.T), called
 
     # ------------------------------------------------------------------ per-variant loadings
     def loadings(self, components, eigenvalues=None, centre=True, unit=True):

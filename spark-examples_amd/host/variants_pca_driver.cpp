@@ -97,6 +97,8 @@ struct Conf {  // PcaConf / GenomicsConf (GenomicsConf.scala:31-101), same flag 
                                         // GCTA, flashpca) through the products K x: no N x N matrix exists
   double grm_min_maf = 0.0;             // --grm-min-maf X: --grm uses only variants whose minor-allele frequency is at least X, in [0, 0.5)
   bool has_grm_min_maf = false;
+  std::string grm_weights_output_path;  // --grm-weights-output-path FILE: --grm: the SNP weight of every variant on each of the --num-pc axes of K
+  std::string grm_project_path;         // --grm-project-path STUDY.bed: --grm: a second PLINK fileset whose samples are placed onto the panel's axes
   int outlier_iterations = 0;           // --outlier-iterations K: up to K rounds of outlier removal around computePca; a round replaces the engine by
                                         // its subset over the kept samples (pcoa_create_subset: one gather of S, no variant read twice).  0 = off
   double outlier_sigma = 6.0;           // --outlier-sigma X: a sample further than X population standard deviations from the mean of an axis goes
@@ -154,6 +156,10 @@ const char* kUsage =
     "                   dosages, missing calls mean-imputed -- the matrix of smartpca, plink --pca, GCTA, flashpca -- through the\n"
     "                   products K x of one GRM engine that keeps 2 bits per genotype; X in [0, 0.5); one streamed PLINK fileset,\n"
     "                   one device, no N x N matrix)\n"
+    "                   --grm-weights-output-path FILE (--grm: the SNP weight of every variant on each of the --num-pc axes of K, in the\n"
+    "                   format of --loadings-output-path; an unused variant prints 0.0)\n"
+    "                   --grm-project-path STUDY.bed (--grm: a second PLINK fileset whose samples are placed onto the panel's axes\n"
+    "                   without moving them; its .bim must equal the panel's line by line; its rows follow the panel's)\n"
     "                   --similarity-measure shared|jaccard|cosine (what computePca decomposes: the counts S as the reference,\n"
     "                   S(i,j) / (S(i,i) + S(j,j) - S(i,j)), or S(i,j) / sqrt(S(i,i) S(j,j)), evaluated on the fly from S; one\n"
     "                   engine, stored S, full layout, no projection)\n"
@@ -241,6 +247,8 @@ Conf parse(int argc, char** argv) {
       if (c.gram != "stored" && c.gram != "implicit") die("--gram takes stored or implicit");
     }
     else if (a == "--grm") c.grm = true;
+    else if (a == "--grm-weights-output-path") c.grm_weights_output_path = one(i);
+    else if (a == "--grm-project-path") c.grm_project_path = one(i);
     else if (a == "--grm-min-maf") {
       const std::string v = one(i);
       char* end = nullptr;
@@ -349,11 +357,17 @@ Conf parse(int argc, char** argv) {
   // --grm: one GRM engine holds the 2-bit genotypes of one PLINK fileset: what needs S, carrier bitsets or several engines is
   // refused here, before any file is read or any engine exists, in a message that names --grm and the other flag
   if (!c.grm && c.has_grm_min_maf) die("--grm-min-maf needs --grm (the standardised-genotype PCA is off without it)");
+  if (!c.grm && !c.grm_weights_output_path.empty())
+    die("--grm-weights-output-path needs --grm (the SNP weights are those of the axes of K; the loadings of the carrier counts go to "
+        "--loadings-output-path)");
+  if (!c.grm && !c.grm_project_path.empty())
+    die("--grm-project-path needs --grm (it places a second PLINK fileset on the axes of K; VCFs are placed on the principal "
+        "coordinates of S by --project-input-path)");
   if (c.grm) {
     if (c.gpus > 1) die("--grm runs on one GRM engine: it cannot take --gpus " + std::to_string(c.gpus));
     if (c.layout == "strips") die("--grm holds no similarity matrix to tile: it cannot take --layout strips");
     if (c.gram == "implicit") die("--grm is an operator of its own over 2-bit genotypes: it cannot take --gram implicit");
-    if (!c.project_input_path.empty()) die("--grm: projection onto the coordinates of K is not built: it cannot take --project-input-path");
+    if (!c.project_input_path.empty()) die("--grm places a second PLINK fileset on the axes of K with --grm-project-path: it cannot take --project-input-path");
     if (!c.dump_similarity.empty()) die("--grm never forms a matrix: it cannot take --dump-similarity");
     if (c.similarity_measure != "shared")
       die("--grm decomposes K, not a measure over the shared counts: it cannot take --similarity-measure " + c.similarity_measure);
@@ -362,7 +376,7 @@ Conf parse(int argc, char** argv) {
     if (c.related) die("--grm holds no shared counts to screen: it cannot take --related-min-jaccard");
     if (c.king) die("--grm holds no genotype-class matrices to screen: it cannot take --king-cutoff");
     if (c.ld_window > 0) die("--grm: LD pruning in front of the genotype store is not built: it cannot take --ld-window");
-    if (!c.loadings_output_path.empty()) die("--grm: SNP weights are not built: it cannot take --loadings-output-path");
+    if (!c.loadings_output_path.empty()) die("--grm writes the SNP weights of K with --grm-weights-output-path: it cannot take --loadings-output-path");
     if (c.carrier_format == "lists") die("--grm stores 2-bit genotypes: it cannot take --carrier-format lists");
     const std::string ext = c.input_path.size() == 1 && c.input_path[0].size() >= 4 ? c.input_path[0].substr(c.input_path[0].size() - 4) : "";
     if (c.has_maf || (ext != ".bed" && ext != ".bim" && ext != ".fam"))
@@ -1611,8 +1625,11 @@ std::vector<pcoa_ctx*> run_engines(const Conf& conf, int32_t n, const std::vecto
 
 // emitResult (:233-246): name, dataset, pc1, pc2 sorted by name on stdout (+ <output-path>-pca.tsv)
 struct OutRow { std::string name, dataset; double pc1, pc2; };
-void emit_result(const Conf& conf, std::vector<OutRow>& rows) {
-  std::stable_sort(rows.begin(), rows.end(), [](const OutRow& a, const OutRow& b) { return a.name < b.name; });
+// n_study (--grm-project-path): the last n_study rows are the projected samples: they follow the panel's, sorted among themselves
+void emit_result(const Conf& conf, std::vector<OutRow>& rows, size_t n_study = 0) {
+  const auto by_name = [](const OutRow& a, const OutRow& b) { return a.name < b.name; };
+  std::stable_sort(rows.begin(), rows.end() - (std::ptrdiff_t)n_study, by_name);
+  std::stable_sort(rows.end() - (std::ptrdiff_t)n_study, rows.end(), by_name);
   for (const auto& r : rows)
     std::printf("%s\t%s\t%s\t%s\n", r.name.c_str(), r.dataset.c_str(), java_double(r.pc1).c_str(), java_double(r.pc2).c_str());
   if (!conf.output_path.empty()) {
@@ -1681,14 +1698,107 @@ std::vector<int32_t> related_removal(const std::vector<pcoa_pair>& pairs, int32_
   return removed;
 }
 
+// --grm-project-path, before any engine exists: the study is a PLINK fileset whose .bim equals the panel's line by line in contig,
+// id, position and both alleles (a fileset with the alleles exchanged is refused, not flipped), and none of its sample names
+// repeats a panel name
+void check_grm_study(const std::string& panel_path, const std::string& study_path) {
+  if (!is_plink_path(study_path)) die("--grm --grm-project-path must name a PLINK .bed / .bim / .fam, not " + study_path);
+  const std::string panel = panel_path.substr(0, panel_path.size() - 4), study = study_path.substr(0, study_path.size() - 4);
+  auto fields = [](const std::string& file) {
+    std::ifstream in(file);
+    if (!in) die("cannot open " + file);
+    std::vector<std::vector<std::string>> out;
+    std::string line;
+    while (std::getline(in, line)) {
+      std::istringstream is(line);
+      std::vector<std::string> t;
+      std::string w;
+      while (is >> w) t.push_back(w);
+      if (!t.empty()) out.push_back(t);
+    }
+    return out;
+  };
+  const auto a = fields(panel + ".bim"), b = fields(study + ".bim");
+  const std::string head = "--grm --grm-project-path: " + study + ".bim and " + panel + ".bim differ at line ";
+  for (size_t k = 0; k < std::max(a.size(), b.size()); ++k) {
+    if (k >= a.size() || k >= b.size())
+      die(head + std::to_string(k + 1) + ": " + (k >= b.size() ? study : panel) + ".bim ends after " +
+          std::to_string(std::min(a.size(), b.size())) + " lines (both filesets must hold the same variants in the same order)");
+    const auto& x = a[k];
+    const auto& y = b[k];
+    if (x.size() < 6 || y.size() < 6) die(head + std::to_string(k + 1) + ": a .bim line has six columns");
+    const bool same3 = x[0] == y[0] && x[1] == y[1] && x[3] == y[3];
+    if (same3 && x[4] == y[4] && x[5] == y[5]) continue;
+    const bool swapped = same3 && x[4] == y[5] && x[5] == y[4];
+    die(head + std::to_string(k + 1) + ": study '" + y[0] + " " + y[1] + " " + y[3] + " " + y[4] + " " + y[5] + "', panel '" + x[0] + " " +
+        x[1] + " " + x[3] + " " + x[4] + " " + x[5] + "'" + (swapped ? ": the alleles are exchanged, and genotypes are not flipped" : "") +
+        " (contig, id, position and both alleles must agree)");
+  }
+  std::set<std::string> seen;
+  for (const auto& t : fields(panel + ".fam"))
+    if (t.size() >= 2) seen.insert(t[1]);
+  for (const auto& t : fields(study + ".fam"))
+    if (t.size() >= 2 && seen.count(t[1]))
+      die("--grm --grm-project-path: the study sample '" + t[1] + "' of " + study + ".fam repeats a sample name of the panel");
+}
+
+// --grm-project-path: the study's kept .bed rows into a GRM study store, block by block, and its samples onto the panel's axes.
+// comps / lam: what pcoa_compute returned on the panel.  Returns the study's rows in .fam order; *called_share: the mean over
+// the samples of (used variants at which the sample is called) / (used variants)
+std::vector<OutRow> grm_project_study(const Conf& conf, pcoa_ctx* panel, const PlinkMeta& panel_meta, const std::vector<double>& comps,
+                                      const std::vector<double>& lam, std::set<std::string>& used_stems) {
+  const PlinkMeta sm = read_plink_meta(conf.grm_project_path, set_id_of(conf.grm_project_path, 1, used_stems), {});
+  if (sm.keep.size() != panel_meta.keep.size()) die("--grm-project-path: the study's .bim changed while the job ran");
+  const int32_t nq = (int32_t)sm.n;
+  pcoa_ctx* study = nullptr;
+  if (pcoa_create_grm_study(&study, nq, conf.gpu_map[0], PCOA_FLAG_DEFAULT) != PCOA_OK)
+    die(std::string("pcoa_create_grm_study: ") + pcoa_last_error(nullptr));
+  {
+    std::ifstream bed(sm.prefix + ".bed", std::ios::binary);
+    bed.seekg(3);
+    const size_t bpv = sm.bpv, total = sm.keep.size(), block = (size_t)conf.stream_rows;
+    std::vector<unsigned char> buf(std::min(block, std::max<size_t>(total, 1)) * bpv);
+    for (size_t b0 = 0; b0 < total; b0 += block) {
+      const size_t nrows = std::min(block, total - b0);
+      bed.read(reinterpret_cast<char*>(buf.data()), (std::streamsize)(nrows * bpv));
+      if ((size_t)bed.gcount() != nrows * bpv) die(sm.prefix + ".bed: read error");
+      size_t kept_rows = 0;
+      for (size_t r = 0; r < nrows; ++r) {
+        if (!panel_meta.keep[b0 + r]) continue;   // (the panel's mask: the .bim files are equal)
+        if (kept_rows != r) std::memmove(buf.data() + kept_rows * bpv, buf.data() + r * bpv, bpv);
+        ++kept_rows;
+      }
+      if (kept_rows > 0)
+        check(study, pcoa_accumulate_plink_bed(study, buf.data(), (int64_t)kept_rows, (int64_t)bpv, conf.plink_ref_allele == "a1" ? 1 : 0, 0),
+              "pcoa_accumulate_plink_bed (study)");
+    }
+  }
+  check(study, pcoa_gram_finalize(study), "pcoa_gram_finalize (study)");
+  std::vector<double> coords((size_t)conf.num_pc * (size_t)nq);
+  std::vector<int32_t> called((size_t)nq);
+  check(panel, pcoa_grm_project(panel, study, conf.num_pc, comps.data(), lam.data(), coords.data(), called.data()), "pcoa_grm_project");
+  pcoa_destroy(study);
+  int64_t used = 0, total_called = 0;
+  if (pcoa_grm_info(panel, nullptr, &used, nullptr) != 1) die(std::string("pcoa_grm_info: ") + pcoa_last_error(panel));
+  for (int32_t c : called) total_called += c;
+  std::fprintf(stderr, "Projected %d samples over %lld used variants (mean call share %.4f)\n", nq, (long long)used,
+               (double)total_called / (double)nq / (double)used);
+  std::vector<OutRow> rows;
+  for (int32_t q = 0; q < nq; ++q)
+    rows.push_back({sm.names[(size_t)q], sm.ids[(size_t)q].substr(0, sm.ids[(size_t)q].find('-')), coords[(size_t)q],
+                    coords[(size_t)q + (size_t)nq]});
+  return rows;
+}
+
 int main(int argc, char** argv) {
   const auto t_start = std::chrono::steady_clock::now();
   Conf conf = parse(argc, argv);
+  if (conf.grm && !conf.grm_project_path.empty()) check_grm_study(conf.input_path[0], conf.grm_project_path);
   const bool want_loadings = !conf.loadings_output_path.empty();
   g_ld.on = conf.ld_window > 0;
   g_calls.on = conf.missing_calls == "pairwise";
   g_king.on = conf.king;
-  g_want_meta = want_loadings || g_ld.on;   // (--ld-window: the contigs place the breaks)
+  g_want_meta = want_loadings || g_ld.on || !conf.grm_weights_output_path.empty();   // (--ld-window: the contigs place the breaks)
   if (conf.input_path.empty())
     die("--input-path <file.vcf[.gz]> [more files] or one PLINK fileset (<prefix>.bed) is required: the Google Genomics API the reference read "
         "from has been shut down");
@@ -2310,7 +2420,30 @@ int main(int argc, char** argv) {
     const size_t i = (size_t)kept[(size_t)a];
     rows.push_back({names[i], ids[i].substr(0, ids[i].find('-')), comps[(size_t)a], comps[(size_t)a + (size_t)n_out]});
   }
-  emit_result(conf, rows);
+  size_t n_study = 0;
+  if (conf.grm && !conf.grm_project_path.empty()) {
+    const std::vector<OutRow> study_rows = grm_project_study(conf, ctx, plink, comps, lam, used_stems);
+    rows.insert(rows.end(), study_rows.begin(), study_rows.end());
+    n_study = study_rows.size();
+  }
+  emit_result(conf, rows, n_study);
+
+  // --grm-weights-output-path: the left singular vectors of the standardised genotype matrix, one line per variant of the store
+  if (conf.grm && !conf.grm_weights_output_path.empty()) {
+    int64_t n_rows = 0;
+    if (pcoa_grm_info(ctx, &n_rows, nullptr, nullptr) != 1) die(std::string("pcoa_grm_info: ") + pcoa_last_error(ctx));
+    if ((int64_t)fed_meta.size() != n_rows)
+      die("--grm-weights-output-path: " + std::to_string(fed_meta.size()) + " variant records for " + std::to_string(n_rows) + " rows");
+    std::vector<double> w((size_t)std::max<int64_t>(n_rows, 1) * (size_t)conf.num_pc);
+    check(ctx, pcoa_grm_weights(ctx, conf.num_pc, comps.data(), lam.data(), 1, 0, n_rows, w.data()), "pcoa_grm_weights");
+    std::ofstream out(conf.grm_weights_output_path);
+    for (int64_t v = 0; v < n_rows; ++v) {
+      out << v << "\t" << fed_meta[(size_t)v].contig << "\t" << fed_meta[(size_t)v].pos << "\t" << fed_meta[(size_t)v].id;
+      for (int c = 0; c < conf.num_pc; ++c) out << "\t" << java_double(w[(size_t)v * (size_t)conf.num_pc + (size_t)c]);
+      out << "\n";
+    }
+    if (!out) die("cannot write " + conf.grm_weights_output_path);
+  }
 
   // --loadings-output-path: w_c = X (J u_c) / sqrt(lambda_c) for every variant the engine was fed, from the eigenpairs above
   if (want_loadings) {

@@ -561,6 +561,16 @@ class PcaConf(object):
         p.add_argument("--grm-min-maf", type=float, default=None,
                        help="--grm: use only variants whose minor-allele frequency among the called samples is at least this, "
                             "in [0, 0.5) (default 0)")
+        p.add_argument("--grm-weights-output-path", type=str, default=None,
+                       help="--grm: write the SNP weight of every variant of the fileset on each of the --num-pc axes of K "
+                            "(pcoa_grm_weights: the left singular vectors of the standardised genotype matrix; smartpca's "
+                            "snpweightoutname, plink2's --pca var-wts) to this file, in the format of --loadings-output-path; a "
+                            "variant that is not used (monomorphic, never called, below --grm-min-maf) prints 0.0")
+        p.add_argument("--grm-project-path", type=str, default=None,
+                       help="--grm: a second PLINK fileset (the study) whose samples are placed onto the axes of the --input-path "
+                            "panel without moving them (pcoa_grm_project): the panel's allele frequencies standardise the "
+                            "study's genotypes, a missing call contributes nothing.  Its .bim must equal the panel's line by "
+                            "line (contig, id, position, both alleles); its rows are emitted after the panel's")
         p.add_argument("--dump-similarity", type=str, default=None,
                        help="write S (N x N int64, little-endian, row-major) to this file (parity tests)")
         p.add_argument("--project-input-path", type=str, nargs="+", default=None,
@@ -956,13 +966,17 @@ class VariantsPcaDriver(object):
     # emitResult, VariantsPca.scala:233-246.  stdout: name, dataset, pc1, pc2 sorted by name, as the reference prints.
     # File: the reference hands the rows to Spark's saveAsTextFile, i.e. a DIRECTORY <output-path>-pca.tsv/ of unsorted
     # part-* files (name, pc1, pc2, dataset per line); here the same lines go, sorted by name, into ONE file of that name.
-    def emitResult(self, result, out=None):
+    def emitResult(self, result, out=None, study=None):
+        """study (--grm-project-path): (callset id, name, pc1, pc2) of the projected samples: their rows follow the panel's,
+        sorted by name among themselves."""
         out = out or sys.stdout
         rows = []
         for (callset_id, pc1, pc2) in result:
             dataset = callset_id.split("-")[0]
             rows.append((self.names[callset_id], pc1, pc2, dataset))
         rows.sort(key=lambda t: t[0])
+        if study:
+            rows += sorted(((name, pc1, pc2, callset_id.split("-")[0]) for (callset_id, name, pc1, pc2) in study), key=lambda t: t[0])
         for (name, pc1, pc2, dataset) in rows:
             out.write("%s\t%s\t%s\t%s\n" % (name, dataset, java_double_to_string(pc1), java_double_to_string(pc2)))
         if self.conf.outputPath:
@@ -1131,13 +1145,20 @@ def check_grm_conf(conf):
     if not conf.grm:
         if conf.grm_min_maf is not None:
             raise SystemExit("VariantsPcaDriver: --grm-min-maf needs --grm (the standardised-genotype PCA is off without it)")
+        if conf.grm_weights_output_path:
+            raise SystemExit("VariantsPcaDriver: --grm-weights-output-path needs --grm (the SNP weights are those of the axes of K; "
+                             "the loadings of the carrier counts go to --loadings-output-path)")
+        if conf.grm_project_path:
+            raise SystemExit("VariantsPcaDriver: --grm-project-path needs --grm (it places a second PLINK fileset on the axes of K; "
+                             "VCFs are placed on the principal coordinates of S by --project-input-path)")
         return
     world = max(conf.gpus, int(os.environ.get("WORLD_SIZE", "1")))
     refused = [
         (world > 1, "runs on one GRM engine: it cannot take --gpus %d" % world),
         (conf.layout == "strips", "holds no similarity matrix to tile: it cannot take --layout strips"),
         (conf.gram == "implicit", "is an operator of its own over 2-bit genotypes: it cannot take --gram implicit"),
-        (bool(conf.project_input_path), "projection onto the coordinates of K is not built: it cannot take --project-input-path"),
+        (bool(conf.project_input_path), "places a second PLINK fileset on the axes of K with --grm-project-path: it cannot take "
+                                        "--project-input-path"),
         (bool(conf.dump_similarity), "never forms a matrix: it cannot take --dump-similarity"),
         (conf.similarity_measure != "shared", "decomposes K, not a measure over the shared counts: it cannot take "
                                               "--similarity-measure %s" % conf.similarity_measure),
@@ -1146,7 +1167,8 @@ def check_grm_conf(conf):
         (conf.related_min_jaccard is not None, "holds no shared counts to screen: it cannot take --related-min-jaccard"),
         (conf.king_cutoff is not None, "holds no genotype-class matrices to screen: it cannot take --king-cutoff"),
         (bool(conf.ld_window), "LD pruning in front of the genotype store is not built: it cannot take --ld-window"),
-        (bool(conf.loadings_output_path), "SNP weights are not built: it cannot take --loadings-output-path"),
+        (bool(conf.loadings_output_path), "writes the SNP weights of K with --grm-weights-output-path: it cannot take "
+                                          "--loadings-output-path"),
     ]
     for hit, why in refused:
         if hit:
@@ -1157,6 +1179,75 @@ def check_grm_conf(conf):
     if conf.synthetic or conf.minAlleleFrequency is not None or len(paths) != 1 or not is_plink_path(paths[0]):
         raise SystemExit("VariantsPcaDriver: --grm reads the genotypes of one PLINK fileset: --input-path must name a single "
                          ".bed / .bim / .fam (dosages from VCF ingest are not built)")
+    if conf.grm_project_path:
+        check_grm_study(paths[0], conf.grm_project_path)
+
+
+def plink_prefix(path):
+    return path[:-4] if path[-4:] in (".bed", ".bim", ".fam") else path
+
+
+def check_grm_study(panel_path, study_path):
+    """--grm-project-path, before any engine exists: the study is a PLINK fileset whose .bim equals the panel's line by line in
+    contig, id, position and both alleles (a fileset with the alleles exchanged is refused, not flipped), and none of its sample
+    names repeats a panel name."""
+    if not is_plink_path(study_path):
+        raise SystemExit("VariantsPcaDriver: --grm --grm-project-path must name a PLINK .bed / .bim / .fam, not %s" % study_path)
+    panel, study = plink_prefix(panel_path), plink_prefix(study_path)
+
+    def bim_lines(prefix):
+        with open(prefix + ".bim") as f:
+            return [ln.split() for ln in f if ln.strip()]
+
+    a, b = bim_lines(panel), bim_lines(study)
+    for k in range(max(len(a), len(b))):
+        if k >= len(a) or k >= len(b):
+            raise SystemExit("VariantsPcaDriver: --grm --grm-project-path: %s.bim and %s.bim differ at line %d: %s.bim ends after "
+                             "%d lines (both filesets must hold the same variants in the same order)"
+                             % (study, panel, k + 1, study if k >= len(b) else panel, min(len(a), len(b))))
+        x, y = a[k], b[k]
+        key_x, key_y = (x[0], x[1], x[3], x[4], x[5]), (y[0], y[1], y[3], y[4], y[5])
+        if key_x != key_y:
+            swapped = key_x[:3] == key_y[:3] and (x[4], x[5]) == (y[5], y[4])
+            raise SystemExit("VariantsPcaDriver: --grm --grm-project-path: %s.bim and %s.bim differ at line %d: study '%s', panel "
+                             "'%s'%s (contig, id, position and both alleles must agree)"
+                             % (study, panel, k + 1, " ".join(key_y), " ".join(key_x),
+                                ": the alleles are exchanged, and genotypes are not flipped" if swapped else ""))
+
+    def fam_names(prefix):
+        with open(prefix + ".fam") as f:
+            return [ln.split()[1] for ln in f if ln.strip()]
+
+    seen = set(fam_names(panel))
+    for name in fam_names(study):
+        if name in seen:
+            raise SystemExit("VariantsPcaDriver: --grm --grm-project-path: the study sample '%s' of %s.fam repeats a sample name of "
+                             "the panel" % (name, study))
+
+
+def grm_project_study(conf, panel_eng, comps, lam, err=None):
+    """--grm-project-path: the study's .bed rows into a GRM study store (the panel's keep mask applies: the .bim files are
+    equal), its samples placed on the panel's axes, and the stderr line.  Returns ([(callset id, name, pc1, pc2)], in the
+    study's .fam order)."""
+    from . import ingest
+    refs = None if conf.all_references else conf.references
+    indexes, names, data = ingest.load_plink(conf.grm_project_path, refs, ref_allele=conf.plink_ref_allele, as_bed=True)
+    _, geno, keep, ref_is_a1 = data[0]
+    nq = len(indexes)
+    with PcoaEngine(nq, device=conf.gpu, grm_study=True) as study:
+        for v0 in range(0, geno.shape[0], PLINK_BLOCK_ROWS):
+            k = keep[v0:v0 + PLINK_BLOCK_ROWS]
+            if k.any():
+                study.accumulate_plink_bed(np.ascontiguousarray(geno[v0:v0 + PLINK_BLOCK_ROWS][k]), ref_is_a1=ref_is_a1)
+        study.finalize()
+        coords, called = panel_eng.grm_project(study, comps, lam)
+    used = panel_eng.grm_info()[1]
+    (err or sys.stderr).write("Projected %d samples over %d used variants (mean call share %.4f)\n"
+                              % (nq, used, float(called.mean()) / used))
+    # the set id as the compiled host assigns it: the second set of the run ('_1' behind a stem the panel has taken)
+    set_id = ingest.set_id_of(conf.grm_project_path, 1, set([ingest.set_id_of(conf.inputPath[0])]))
+    reverse = dict((v, k) for (k, v) in indexes.items())
+    return [("%s-%d" % (set_id, q), names[reverse[q]], float(coords[q, 0]), float(coords[q, 1])) for q in range(nq)]
 
 
 def grm_accumulate(call_rdd, matrix_size, min_maf, device=0, err=None):
@@ -1640,7 +1731,7 @@ def main(args):
         if quiet is not None:
             sys.stdout = quiet
     # (contig, position, id) per row, recorded only with a flag that needs them (--ld-window: the contigs place the breaks)
-    variant_meta = [] if conf.loadings_output_path or conf.ld_window else None
+    variant_meta = [] if conf.loadings_output_path or conf.ld_window or conf.grm_weights_output_path else None
     indexes, names, data = load_dataset(conf, variant_meta)
     driver = VariantsPcaDriver(conf, indexes, names, data)
     filtered = [driver.filterDataset(d) for d in driver.data]
@@ -1659,7 +1750,12 @@ def main(args):
 
     if conf.grm:
         driver.engine = grm_accumulate(calls_rdd, n, conf.grm_min_maf or 0.0, device=conf.gpu)
-        driver.emitResult(driver.computePca(driver.engine))
+        result = driver.computePca(driver.engine)
+        comps, lam = driver.last_pca
+        study = grm_project_study(conf, driver.engine, comps, lam) if conf.grm_project_path else None
+        driver.emitResult(result, study=study)
+        if conf.grm_weights_output_path:
+            write_loadings(conf.grm_weights_output_path, variant_meta, driver.engine.grm_weights(comps, lam, scaled=True))
         driver.reportIoStats(sys.stderr)
         driver.stop()
         return 0
