@@ -183,6 +183,8 @@ int pcoa_create(pcoa_ctx** out, int32_t n_samples, int32_t device_ordinal, uint3
  * all-gather of an N-vector per Lanczos step (pcoa_strip_matvec).  pcoa_gram_read_i64 / _load_i64 / _export / _import
  * move [N][cols] matrices on a strip ctx, pcoa_gram_read_block_i64 takes (row, strip-relative column).
  * pcoa_center_read_f64 / pcoa_compute / pcoa_gram_allreduce_rccl are not available on it (PCOA_ERR_STATE).
+ * Any n_samples >= 1 will do (the smallest owner is n_samples = 1 with the strip (0, 1)); PCOA_ERR_INVALID_ARG for a strip
+ * that is empty or does not lie inside [0, n_samples), and for PCOA_FLAG_GRAM_F32_MFMA.
  * Replaces: the same per-partition matrix of getSimilarityMatrix (VariantsPca.scala:183-189), column-sliced; the
  * reference itself stops at N^2 < 2^31 (DenseMatrix[Int]). */
 int pcoa_create_strip(pcoa_ctx** out, int32_t n_samples, int32_t col0, int32_t cols, int32_t device_ordinal,
@@ -209,7 +211,9 @@ int pcoa_strip_col_sums(pcoa_ctx* ctx, double* out_cols);
 /* y_out[jj] = sum_i B(col0 + jj, i) * v[i] with B(j, i) = ((S(j, i) - means[j]) - means[i]) + matrix_mean -- rows of the
  * double-centred matrix in the reference's operation order (VariantsPca.scala:216-221), evaluated on the fly from the
  * strip (B is never stored).  v, means (= rowSums / N, all N samples) and y_out are host arrays.  One call per owner and
- * Lanczos step; the owners' results concatenate (all-gather) to B v. */
+ * Lanczos step; the owners' results concatenate (all-gather) to B v.  Every operation is an IEEE fp64 one rounded on its own
+ * (no fused multiply-add); the terms of rows i in [256 b, 256 b + 256) are added in order into a partial that starts at 0.0
+ * and the partials in order of b into y_out[jj]: deterministic, and a column's result does not depend on the strip's cut. */
 int pcoa_strip_matvec(pcoa_ctx* ctx, const double* v, const double* means, double matrix_mean, double* y_out);
 
 /* The same mat-vec for a host whose vectors already live on the GPU (e.g. torch tensors exchanged with an RCCL all-gather):
