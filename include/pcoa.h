@@ -35,7 +35,7 @@ extern "C" {
 #endif
 
 #define PCOA_VERSION_MAJOR 0
-#define PCOA_VERSION_MINOR 11
+#define PCOA_VERSION_MINOR 12
 
 typedef struct pcoa_ctx pcoa_ctx;
 
@@ -311,8 +311,8 @@ int pcoa_operator_matvec_device(pcoa_ctx* ctx, const double* v_dev, double* y_de
  *   results are reproducible: the same store, min_maf and x give bit-identical y, run to run and whatever the sizes of the
  *           accumulate calls were (no floating-point atomics; the order of every addition is fixed by N, the segment size
  *           and a row's index in the store).
- * SNP weights and the projection of new samples: pcoa_grm_weights / pcoa_grm_project below.
- * Not built: JNI / Scala natives, LD pruning in front of the store, variant sharding over engines, reading K out. */
+ * SNP weights and the projection of new samples: pcoa_grm_weights / pcoa_grm_project below.  Reading K out: pcoa_grm_block.
+ * Not built: JNI / Scala natives, LD pruning in front of the store, variant sharding over engines. */
 int pcoa_create_grm(pcoa_ctx** out, int32_t n_samples, int32_t device_ordinal, uint32_t flags);
 
 /* Returns 1 for a GRM ctx, 0 otherwise (like pcoa_operator_info).  *variants_out: rows in the store; *used_out: M' under the
@@ -366,6 +366,52 @@ int pcoa_grm_weights(pcoa_ctx* panel, int32_t num_pc, const double* components, 
  * exactly as many rows as the panel, fed in the same order (PCOA_ERR_STATE otherwise). */
 int pcoa_grm_project(pcoa_ctx* panel, pcoa_ctx* study, int32_t num_pc, const double* components, const double* eigenvalues,
                      double* out_coords /* [num_pc][N_study] */, int32_t* out_called /* [N_study] */);
+
+/* ---- reading K out in blocks --------------------------------------------------------------------------------
+ * GCTA --make-grm, plink --make-grm-bin and smartpca also write the matrix they decompose.  pcoa_grm_block returns any
+ * rectangle of it, and of the pair counts, computed from the store on the fp64 matrix cores.  The rule, with c, g, n_v, a_v,
+ * mu_v, used_v, d_v and M' exactly as pcoa_create_grm defines them and a_vi = c_iv ? (double)g_iv - mu_v : 0.0:
+ *   num(i, j) = sum_v (d_v * a_v,lo) * a_v,hi       lo = min(i, j), hi = max(i, j): d rides on the operand of the smaller
+ *                                                   sample index, applied once (not as a square root on both sides)
+ *   n(i, j)   = sum_v used_v * c_iv * c_jv          exact integer: the used variants at which both samples are called
+ *   PCOA_GRM_DIVISOR_USED      (0)   K(i, j) = num(i, j) / (double)M'                      the K that pcoa_compute decomposes
+ *   PCOA_GRM_DIVISOR_PAIRWISE  (1)   K(i, j) = n(i, j) > 0 ? num(i, j) / (double)n(i, j) : 0.0
+ * A missing call contributes 0 to num, so num is the sum over the jointly called used variants of
+ * (g_i - 2p)(g_j - 2p) / (2p(1 - p)): the PAIRWISE form is the pairwise-complete estimator GCTA-style tools store, the USED form
+ * the mean-imputed K above.  The diagonal follows the same expression as every other entry.  This rule is the contract, not
+ * any tool's output (tools differ in how they treat missing calls, the diagonal and the frequency estimate).
+ *   exact symmetry:   K(i, j) and K(j, i) are the same bits (an entry below the diagonal is computed with the operand roles
+ *           exchanged, and the multiplicands of a product commute).
+ *   cut independence: the bits of an entry depend only on the store, min_maf, the divisor and (i, j): not on the rectangle it
+ *           was requested in, the grid, the CU count or the sizes of the accumulate calls.  No floating-point atomics: the
+ *           additions into an entry happen in the order of the variants' indices in the store, four at a time within a segment.
+ *   exactness: where every used mu_v = 1 and d_v = 2 every partial sum is a small integer and num is exact.
+ * Any rectangle inside [0, N)^2; out_k / out_pairs: [rows][cols] row-major, either may be NULL (not both), host memory or, with
+ * is_device_ptr, device memory on the ctx's GPU (both outputs alike).  Synchronising.  The counts and weights are recomputed,
+ * if they are not resident, under the current min_maf, as pcoa_compute does.  Nothing writes the store; the ctx computes the
+ * same bits afterwards.
+ *   PCOA_ERR_INVALID_ARG, found on the host before any device work: ctx NULL (pcoa_last_error(NULL)), rows or cols < 1, a
+ *           rectangle that leaves [0, N), an unknown divisor, both outputs NULL.
+ *   PCOA_ERR_STATE, the ctx stays usable: a ctx that is not from pcoa_create_grm (the message names its kind), a
+ *           pcoa_create_grm_study ctx, M' = 0, M' >= 2^31 (the pair counts are int32).
+ *   memory: rows * cols doubles, plus as many int32 where the pair counts are needed (out_pairs given, or PAIRWISE), in one
+ *           lazily grown buffer of the ctx; a device output is used directly instead.  PCOA_ERR_OUT_OF_MEMORY leaves the ctx
+ *           usable.
+ * Not built: a relatedness cut-off on K, fp32 / bf16 approximations, multi-GPU, a compressed writer, JNI / Scala natives. */
+#define PCOA_GRM_DIVISOR_USED 0
+#define PCOA_GRM_DIVISOR_PAIRWISE 1
+int pcoa_grm_block(pcoa_ctx* ctx, int32_t row0, int32_t rows, int32_t col0, int32_t cols, int32_t divisor,
+                   double* out_k /* [rows][cols] row-major, or NULL */, int32_t* out_pairs /* [rows][cols] n(i, j), or NULL */,
+                   int is_device_ptr /* both outputs: host (0) or device memory on the ctx's GPU (1) */);
+
+/* What pcoa_grm_block did on THIS engine, cumulative since pcoa_create_grm / pcoa_reset_timings.  (A struct of its own, like
+ * pcoa_pairs_stats.)  It grows at its end; out_size = sizeof of the struct the caller compiled against.  Synchronising. */
+typedef struct pcoa_grm_block_stats {
+  double grm_block_seconds;   /* HIP-event time of the segment launches and the finish                                        */
+  int64_t grm_block_calls;
+  double grm_block_flops;     /* 2 * rows * cols * V per float pass launched (num; n where the pair counts are needed)        */
+} pcoa_grm_block_stats;
+int pcoa_get_grm_block_stats(pcoa_ctx* ctx, pcoa_grm_block_stats* out, size_t out_size);
 
 /* ---- PCoA over a sample subset of a stored S ------------------------------------------------------------------------------
  * For a kept index set I, S[I, I] is exactly the similarity matrix of the reduced cohort (an entry counts the variants two

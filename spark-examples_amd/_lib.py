@@ -174,6 +174,17 @@ class PcoaLoadingsStats(ctypes.Structure):
     ]
 
 
+class PcoaGrmBlockStats(ctypes.Structure):
+    """pcoa_grm_block_stats: a struct of its own beside pcoa_timings, like pcoa_pairs_stats."""
+    _fields_ = [
+        ("grm_block_seconds", ctypes.c_double),
+        ("grm_block_calls", ctypes.c_int64),
+        ("grm_block_flops", ctypes.c_double),
+    ]
+
+
+PCOA_GRM_DIVISOR_USED = 0
+PCOA_GRM_DIVISOR_PAIRWISE = 1
 PCOA_LOADINGS_CENTRE = 1
 PCOA_LOADINGS_UNIT = 2
 PCOA_LD_MAX_WINDOW = 1024
@@ -233,6 +244,8 @@ _SIGNATURES = [
     ("pcoa_create_grm_study", ctypes.c_int, [ctypes.POINTER(_vp), _i32, _i32, ctypes.c_uint32]),
     ("pcoa_grm_weights", ctypes.c_int, [_vp, _i32, _vp, _vp, _i32, _i64, _i64, _vp]),
     ("pcoa_grm_project", ctypes.c_int, [_vp, _vp, _i32, _vp, _vp, _vp, _vp]),
+    ("pcoa_grm_block", ctypes.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, ctypes.c_int]),
+    ("pcoa_get_grm_block_stats", ctypes.c_int, [_vp, ctypes.POINTER(PcoaGrmBlockStats), ctypes.c_size_t]),
     ("pcoa_strip_info", ctypes.c_int, [_vp, ctypes.POINTER(_i32), ctypes.POINTER(_i32)]),
     ("pcoa_strip_col_sums", ctypes.c_int, [_vp, _vp]),
     ("pcoa_strip_matvec", ctypes.c_int, [_vp, _vp, _vp, ctypes.c_double, _vp]),

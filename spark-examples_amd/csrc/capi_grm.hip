@@ -218,9 +218,11 @@ void grm_destroy(pcoa_ctx* c) {
   if (c->grm_cnt) dev_free(c->grm_cnt);
   if (c->grm_par) dev_free(c->grm_par);
   if (c->grm_mw) dev_free(c->grm_mw);
+  if (c->grm_blk) dev_free(c->grm_blk);
   c->grm_cnt = nullptr;
   c->grm_par = nullptr;
   c->grm_mw = nullptr;
+  c->grm_blk = nullptr;
 }
 
 }  // namespace pcoa

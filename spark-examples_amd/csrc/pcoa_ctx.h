@@ -12,6 +12,7 @@
 //   capi_operator.hip    the implicit similarity operator: the bit store, its products, computePca over it
 //   capi_grm.hip         the standardised-genotype operator (pcoa_create_grm): the 2-bit store, its counts and weights, K x
 //   capi_grm_project.hip SNP weights of K's axes and the projection of a study store onto them (pcoa_create_grm_study, pcoa_grm_weights / _project)
+//   capi_grm_dense.hip   pcoa_grm_block: a rectangle of K and of the pair counts read out through the fp64 matrix cores
 //   capi_subset.hip      pcoa_create_subset: a new engine whose S is S[I, I] of another
 //   capi_pairs.hip       pcoa_similar_pairs: the screen of S for duplicate and related sample pairs
 //   capi_measure.hip     pcoa_set_similarity / pcoa_get_similarity and the centring of a Jaccard / cosine measure
@@ -27,7 +28,7 @@
 
 #include "pcoa_internal.h"
 
-enum TimeCat { T_GRAM = 0, T_DENSIFY, T_SYNTH, T_FINALIZE, T_CENTER, T_TRIDIAG, T_EIG, T_BACK, T_PACK, T_LANCZOS, T_ALLREDUCE, T_OPERATOR, T_SUBSET, T_REDUCE_PEERS, T_PAIRS, T_LOADINGS, T_LD_COUNT, T_LD_BAND, T_LD_RESOLVE, T_LD_COMPACT, T_KING, T_NCAT };
+enum TimeCat { T_GRAM = 0, T_DENSIFY, T_SYNTH, T_FINALIZE, T_CENTER, T_TRIDIAG, T_EIG, T_BACK, T_PACK, T_LANCZOS, T_ALLREDUCE, T_OPERATOR, T_SUBSET, T_REDUCE_PEERS, T_PAIRS, T_LOADINGS, T_LD_COUNT, T_LD_BAND, T_LD_RESOLVE, T_LD_COMPACT, T_KING, T_GRM_BLOCK, T_NCAT };
 
 struct EventPair {
   hipEvent_t a, b;
@@ -97,6 +98,10 @@ struct pcoa_ctx {
   bool is_grm_study = false;       // pcoa_create_grm_study: a GRM store of study samples with no weights of its own (capi_grm_project.hip)
   double* grm_mw = nullptr;        // pcoa_grm_weights / pcoa_grm_project on a panel: components, t, s, the passes' partials, results (lazy)
   int64_t grm_mw_cap = 0;
+  double* grm_blk = nullptr;       // pcoa_grm_block: [rows][cols] doubles, then as many int32 where the pair counts are needed (lazy)
+  int64_t grm_blk_cap = 0;
+  int64_t grm_block_calls = 0;     // pcoa_grm_block_stats
+  double grm_block_flops = 0;
   int64_t subset_bytes = 0;        // bytes the gathers of pcoa_create_subset moved into this ctx (read + written)
   int64_t pairs_bytes = 0, pairs_calls = 0;   // pcoa_similar_pairs: bytes of S its scan kernels read, calls
   // per-variant loadings (pcoa_loadings_begin .. pcoa_loadings_end, capi_loadings.hip): the prepared vectors stay resident

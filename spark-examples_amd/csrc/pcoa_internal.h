@@ -285,6 +285,15 @@ hipError_t launch_grm_weights_out(const double* t, int64_t tstride, const double
                                   const unsigned long long* mprime, const double* lam, int scaled, int64_t first, int64_t nv,
                                   int32_t num_pc, double* out, hipStream_t stream);
 
+// ---- reading K out (grm_dense.hip): a rectangle of num(i, j) = sum_v (d_v a_v,lo) a_v,hi and of n(i, j) -------------
+// One launch per segment, in the store's order.  out_k / out_n: [nrows][ncols] row-major, either may be NULL (that pass is not
+// instantiated); first = 1: the entries start from 0, otherwise from what out_k / out_n hold.  mu, d, used: the segment's rows.
+hipError_t launch_grm_dense(const uint32_t* seg, int32_t rows, int32_t n, const double* mu, const double* d, const int32_t* used,
+                            int32_t row0, int32_t nrows, int32_t col0, int32_t ncols, int first, double* out_k, int32_t* out_n,
+                            hipStream_t stream);
+// k[i] = divisor 0: k[i] / M'; divisor 1: n[i] > 0 ? k[i] / n[i] : 0.0
+hipError_t launch_grm_dense_finish(double* k, const int32_t* n, int64_t total, int32_t divisor, int64_t mprime, hipStream_t stream);
+
 // ---- per-variant loadings (loadings.hip): out[v * num_pc + c] = (sum_i bit(v, i) u[c * ustride + i]) / div[c] for c in [0, k) ----
 // u: prepared vectors, ustride = 32 ceil(n / 32) doubles each, zero for i >= n (that is what ignores a row's tail bits); div: k
 // divisors or NULL; k must be 1, 2, 4 or 8 (loadings_chunk picks the chunk); out / u / div point at the chunk's first component.

@@ -699,6 +699,64 @@ class PcoaEngine(object):
         self._check(self._lib.pcoa_grm_project(self._ctx, study._ctx, k, _ptr(u), _ptr(lam), _ptr(coords), _ptr(called)))
         return np.ascontiguousarray(coords.T), called
 
+    GRM_DIVISORS = {"used": L.PCOA_GRM_DIVISOR_USED, "pairwise": L.PCOA_GRM_DIVISOR_PAIRWISE}
+
+    def _grm_divisor(self, divisor):
+        if isinstance(divisor, str):
+            if divisor not in self.GRM_DIVISORS:
+                raise ValueError("divisor must be one of used, pairwise, not %r" % (divisor,))
+            return self.GRM_DIVISORS[divisor]
+        return int(divisor)   # (an unknown number is the library's error)
+
+    def grm_block(self, row0, rows, col0, cols, divisor="used", pairs=False, device=False):
+        """K[row0 : row0 + rows, col0 : col0 + cols] of the matrix compute() decomposes (pcoa_grm_block), float64.  divisor:
+        "used" (num / M') or "pairwise" (num / n(i, j), 0 where n is 0); variants_pca.grm_dense_rule is the rule.  pairs=True:
+        returns (K, n) with n the int32 counts of jointly called used variants.  device=True: torch tensors on this engine's
+        GPU, written by the kernels directly; otherwise numpy arrays."""
+        div = self._grm_divisor(divisor)
+        shape = (max(int(rows), 0), max(int(cols), 0))
+        if device:
+            import torch  # plumbing only: device memory handles
+            dev = torch.device("cuda", self.device)
+            k = torch.empty(shape, dtype=torch.float64, device=dev)
+            n = torch.empty(shape, dtype=torch.int32, device=dev) if pairs else None
+            torch.cuda.current_stream(dev).synchronize()   # the engine runs on its own stream
+            kp = ctypes.c_void_p(k.data_ptr()) if k.numel() else None
+            npp = ctypes.c_void_p(n.data_ptr()) if pairs and n.numel() else None
+        else:
+            k = np.zeros(shape, dtype=np.float64)
+            n = np.zeros(shape, dtype=np.int32) if pairs else None
+            kp = _ptr(k) if k.size else None
+            npp = _ptr(n) if pairs and n.size else None
+        self._check(self._lib.pcoa_grm_block(self._ctx, int(row0), int(rows), int(col0), int(cols), div, kp, npp, int(bool(device))))
+        return (k, n) if pairs else k
+
+    def grm_pairs_block(self, row0, rows, col0, cols):
+        """n[row0 : row0 + rows, col0 : col0 + cols] alone (int32 numpy): only the counting pass runs."""
+        n = np.zeros((max(int(rows), 0), max(int(cols), 0)), dtype=np.int32)
+        self._check(self._lib.pcoa_grm_block(self._ctx, int(row0), int(rows), int(col0), int(cols), L.PCOA_GRM_DIVISOR_USED, None,
+                                             _ptr(n) if n.size else None, 0))
+        return n
+
+    def grm_dense(self, divisor="used", block=4096):
+        """The whole N x N matrix as float64 numpy, assembled from blocks of the lower triangle and mirrored (the entries above
+        the diagonal are the same bits as their mirror images, so nothing is lost)."""
+        block = max(int(block), 1)
+        out = np.zeros((self.n, self.n), dtype=np.float64)
+        for r0 in range(0, self.n, block):
+            r = min(block, self.n - r0)
+            for c0 in range(0, r0 + 1, block):
+                c = min(block, self.n - c0)
+                out[r0:r0 + r, c0:c0 + c] = self.grm_block(r0, r, c0, c, divisor)
+        low = np.tril(out, -1)
+        return np.tril(out) + low.T
+
+    def grm_block_stats(self):
+        """pcoa_get_grm_block_stats: grm_block_seconds / grm_block_calls / grm_block_flops."""
+        q = L.PcoaGrmBlockStats()
+        self._check(self._lib.pcoa_get_grm_block_stats(self._ctx, ctypes.byref(q), ctypes.sizeof(q)))
+        return dict((f[0], getattr(q, f[0])) for f in L.PcoaGrmBlockStats._fields_)
+
     # ------------------------------------------------------------------ per-variant loadings
     def loadings(self, components, eigenvalues=None, centre=True, unit=True):
         """Per-variant loadings of the principal coordinates (pcoa_loadings_begin): `components` [N, k] and `eigenvalues` [k] are

@@ -97,6 +97,9 @@ struct Conf {  // PcaConf / GenomicsConf (GenomicsConf.scala:31-101), same flag 
                                         // GCTA, flashpca) through the products K x: no N x N matrix exists
   double grm_min_maf = 0.0;             // --grm-min-maf X: --grm uses only variants whose minor-allele frequency is at least X, in [0, 0.5)
   bool has_grm_min_maf = false;
+  std::string grm_output_path;          // --grm-output-path PREFIX: --grm: K read out band by band into PREFIX.grm.bin / .grm.N.bin / .grm.id
+  std::string grm_output_divisor;       // --grm-output-divisor used|pairwise: num / M' (default) or num / n(i, j)
+  bool has_grm_output_divisor = false;
   std::string grm_weights_output_path;  // --grm-weights-output-path FILE: --grm: the SNP weight of every variant on each of the --num-pc axes of K
   std::string grm_project_path;         // --grm-project-path STUDY.bed: --grm: a second PLINK fileset whose samples are placed onto the panel's axes
   int outlier_iterations = 0;           // --outlier-iterations K: up to K rounds of outlier removal around computePca; a round replaces the engine by
@@ -160,6 +163,9 @@ const char* kUsage =
     "                   format of --loadings-output-path; an unused variant prints 0.0)\n"
     "                   --grm-project-path STUDY.bed (--grm: a second PLINK fileset whose samples are placed onto the panel's axes\n"
     "                   without moving them; its .bim must equal the panel's line by line; its rows follow the panel's)\n"
+    "                   --grm-output-path PREFIX [--grm-output-divisor used|pairwise] (--grm: the matrix that was decomposed, read out\n"
+    "                   band by band: PREFIX.grm.bin (float32 lower triangle with the diagonal), PREFIX.grm.N.bin (jointly called used\n"
+    "                   variants per pair) and PREFIX.grm.id, the layout GCTA and PLINK read; used: num / M', pairwise: num / n(i, j))\n"
     "                   --similarity-measure shared|jaccard|cosine (what computePca decomposes: the counts S as the reference,\n"
     "                   S(i,j) / (S(i,i) + S(j,j) - S(i,j)), or S(i,j) / sqrt(S(i,i) S(j,j)), evaluated on the fly from S; one\n"
     "                   engine, stored S, full layout, no projection)\n"
@@ -249,6 +255,11 @@ Conf parse(int argc, char** argv) {
     else if (a == "--grm") c.grm = true;
     else if (a == "--grm-weights-output-path") c.grm_weights_output_path = one(i);
     else if (a == "--grm-project-path") c.grm_project_path = one(i);
+    else if (a == "--grm-output-path") c.grm_output_path = one(i);
+    else if (a == "--grm-output-divisor") {
+      c.grm_output_divisor = one(i);
+      c.has_grm_output_divisor = true;
+    }
     else if (a == "--grm-min-maf") {
       const std::string v = one(i);
       char* end = nullptr;
@@ -363,6 +374,14 @@ Conf parse(int argc, char** argv) {
   if (!c.grm && !c.grm_project_path.empty())
     die("--grm-project-path needs --grm (it places a second PLINK fileset on the axes of K; VCFs are placed on the principal "
         "coordinates of S by --project-input-path)");
+  if (!c.grm && !c.grm_output_path.empty())
+    die("--grm-output-path needs --grm (it writes the relationship matrix K of the standardised genotypes; the shared counts S go to "
+        "--dump-similarity)");
+  if (!c.grm && c.has_grm_output_divisor) die("--grm-output-divisor needs --grm (and --grm-output-path)");
+  if (c.has_grm_output_divisor && c.grm_output_divisor != "used" && c.grm_output_divisor != "pairwise")
+    die("--grm-output-divisor takes used or pairwise, not '" + c.grm_output_divisor + "'");
+  if (c.has_grm_output_divisor && c.grm_output_path.empty())
+    die("--grm-output-divisor needs --grm-output-path (it chooses the divisor of the matrix written there)");
   if (c.grm) {
     if (c.gpus > 1) die("--grm runs on one GRM engine: it cannot take --gpus " + std::to_string(c.gpus));
     if (c.layout == "strips") die("--grm holds no similarity matrix to tile: it cannot take --layout strips");
@@ -2443,6 +2462,40 @@ int main(int argc, char** argv) {
       out << "\n";
     }
     if (!out) die("cannot write " + conf.grm_weights_output_path);
+  }
+
+  // --grm-output-path: K out of the engine in bands of 1,024 rows, columns 0 .. band end (pcoa_grm_block, host pointers): no
+  // N x N array exists on either side.  Rows are the samples in the engine's index order; the float32 cast is the language's own
+  if (conf.grm && !conf.grm_output_path.empty()) {
+    const int32_t divisor = conf.grm_output_divisor == "pairwise" ? PCOA_GRM_DIVISOR_PAIRWISE : PCOA_GRM_DIVISOR_USED;
+    const int32_t band = 1024;
+    std::ofstream fk(conf.grm_output_path + ".grm.bin", std::ios::binary), fn(conf.grm_output_path + ".grm.N.bin", std::ios::binary);
+    std::vector<double> kb;
+    std::vector<int32_t> nb;
+    std::vector<float> line;
+    long long written = 0;
+    for (int32_t r0 = 0; r0 < n; r0 += band) {
+      const int32_t r = std::min(band, n - r0), cols = r0 + r;
+      kb.resize((size_t)r * (size_t)cols);
+      nb.resize((size_t)r * (size_t)cols);
+      check(ctx, pcoa_grm_block(ctx, r0, r, 0, cols, divisor, kb.data(), nb.data(), 0), "pcoa_grm_block");
+      for (int32_t a = 0; a < r; ++a) {
+        const size_t len = (size_t)(r0 + a) + 1;
+        line.resize(len);
+        for (size_t j = 0; j < len; ++j) line[j] = (float)kb[(size_t)a * (size_t)cols + j];
+        fk.write(reinterpret_cast<const char*>(line.data()), (std::streamsize)(len * sizeof(float)));
+        for (size_t j = 0; j < len; ++j) line[j] = (float)nb[(size_t)a * (size_t)cols + j];
+        fn.write(reinterpret_cast<const char*>(line.data()), (std::streamsize)(len * sizeof(float)));
+        written += 2 * (long long)(len * sizeof(float));
+      }
+    }
+    std::ofstream fi(conf.grm_output_path + ".grm.id");
+    for (int32_t i = 0; i < n; ++i) fi << ids[(size_t)i].substr(0, ids[(size_t)i].find('-')) << "\t" << names[(size_t)i] << "\n";
+    if (!fk || !fn || !fi) die("cannot write " + conf.grm_output_path + ".grm.*");
+    int64_t used = 0;
+    if (pcoa_grm_info(ctx, nullptr, &used, nullptr) != 1) die(std::string("pcoa_grm_info: ") + pcoa_last_error(ctx));
+    std::fprintf(stderr, "GRM written: %d samples, %lld used variants, divisor %s, %lld bytes\n", n, (long long)used,
+                 divisor == PCOA_GRM_DIVISOR_PAIRWISE ? "pairwise" : "used", written);
   }
 
   // --loadings-output-path: w_c = X (J u_c) / sqrt(lambda_c) for every variant the engine was fed, from the eigenpairs above

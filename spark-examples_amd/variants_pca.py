@@ -571,6 +571,14 @@ class PcaConf(object):
                             "panel without moving them (pcoa_grm_project): the panel's allele frequencies standardise the "
                             "study's genotypes, a missing call contributes nothing.  Its .bim must equal the panel's line by "
                             "line (contig, id, position, both alleles); its rows are emitted after the panel's")
+        p.add_argument("--grm-output-path", type=str, default=None,
+                       help="--grm: write the matrix computePca decomposed, read out of the engine band by band "
+                            "(pcoa_grm_block), as PREFIX.grm.bin (float32, lower triangle with the diagonal, row by row), "
+                            "PREFIX.grm.N.bin (the jointly called used variants of each pair, float32, same order) and "
+                            "PREFIX.grm.id (set id <tab> sample name per row): the layout GCTA and PLINK read")
+        p.add_argument("--grm-output-divisor", type=str, default=None,
+                       help="--grm-output-path: used (default): num / M', the mean-imputed K that is decomposed; pairwise: "
+                            "num / n(i, j), the pairwise-complete estimator GCTA-style tools store")
         p.add_argument("--dump-similarity", type=str, default=None,
                        help="write S (N x N int64, little-endian, row-major) to this file (parity tests)")
         p.add_argument("--project-input-path", type=str, nargs="+", default=None,
@@ -1151,7 +1159,17 @@ def check_grm_conf(conf):
         if conf.grm_project_path:
             raise SystemExit("VariantsPcaDriver: --grm-project-path needs --grm (it places a second PLINK fileset on the axes of K; "
                              "VCFs are placed on the principal coordinates of S by --project-input-path)")
+        if conf.grm_output_path:
+            raise SystemExit("VariantsPcaDriver: --grm-output-path needs --grm (it writes the relationship matrix K of the "
+                             "standardised genotypes; the shared counts S go to --dump-similarity)")
+        if conf.grm_output_divisor is not None:
+            raise SystemExit("VariantsPcaDriver: --grm-output-divisor needs --grm (and --grm-output-path)")
         return
+    if conf.grm_output_divisor is not None and conf.grm_output_divisor not in GRM_OUTPUT_DIVISORS:
+        raise SystemExit("VariantsPcaDriver: --grm-output-divisor takes used or pairwise, not '%s'" % conf.grm_output_divisor)
+    if conf.grm_output_divisor is not None and not conf.grm_output_path:
+        raise SystemExit("VariantsPcaDriver: --grm-output-divisor needs --grm-output-path (it chooses the divisor of the matrix "
+                         "written there)")
     world = max(conf.gpus, int(os.environ.get("WORLD_SIZE", "1")))
     refused = [
         (world > 1, "runs on one GRM engine: it cannot take --gpus %d" % world),
@@ -1181,6 +1199,79 @@ def check_grm_conf(conf):
                          ".bed / .bim / .fam (dosages from VCF ingest are not built)")
     if conf.grm_project_path:
         check_grm_study(paths[0], conf.grm_project_path)
+
+
+GRM_OUTPUT_DIVISORS = ("used", "pairwise")
+GRM_OUTPUT_BAND_ROWS = 1024
+
+
+def grm_dense_rule(codes, ref_is_a1, min_maf=0.0, divisor="used"):
+    """The numpy statement of pcoa_grm_block (include/pcoa.h): (K, n) of a cohort given as [V][N] PLINK codes (0 = 00
+    homozygous A1, 1 = 01 missing, 2 = 10 heterozygous, 3 = 11 homozygous A2).  With a_vi = c_iv ? g_iv - mu_v : 0.0:
+    num(i, j) = sum_v (d_v a_v,lo) a_v,hi (d on the operand of the smaller sample index), n(i, j) = sum_v used_v c_iv c_jv;
+    divisor "used": K = num / M', "pairwise": K = n > 0 ? num / n : 0.0.  M' = 0: K is undefined (ValueError)."""
+    if divisor not in GRM_OUTPUT_DIVISORS:
+        raise ValueError("divisor must be one of used, pairwise, not %r" % (divisor,))
+    codes = np.asarray(codes)
+    hom = 3 if ref_is_a1 else 0
+    c = codes != 1
+    g = (codes == 2).astype(np.float64) + 2.0 * (codes == hom).astype(np.float64)
+    nv = c.sum(axis=1).astype(np.int64)
+    av = (codes == 2).sum(axis=1).astype(np.int64) + 2 * (codes == hom).sum(axis=1).astype(np.int64)
+    nf, af = nv.astype(np.float64), av.astype(np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        mu = np.where(nv > 0, af / nf, 0.0)
+        used = (nv > 0) & (av > 0) & (av < 2 * nv) & (np.minimum(av, 2 * nv - av).astype(np.float64) >= min_maf * (2.0 * nf))
+        d = np.where(used, 1.0 / (mu * (1.0 - 0.5 * mu)), 0.0)
+    m = int(used.sum())
+    if m == 0:
+        raise ValueError("none of the %d variants is used: K is undefined" % codes.shape[0])
+    a = np.where(c, g - mu[:, None], 0.0)
+    upper = (d[:, None] * a).T @ a                 # [i][j] = sum_v (d a_i) a_j: the rule where i <= j
+    num = np.triu(upper) + np.triu(upper, 1).T
+    cu = (c & used[:, None]).astype(np.int64)
+    n = cu.T @ c.astype(np.int64)
+    if divisor == "used":
+        k = num / float(m)
+    else:
+        with np.errstate(divide="ignore", invalid="ignore"):
+            k = np.where(n > 0, num / n.astype(np.float64), 0.0)
+    return k, n
+
+
+def write_grm_files(prefix, ids, bands):
+    """PREFIX.grm.bin / PREFIX.grm.N.bin / PREFIX.grm.id, the layout GCTA and PLINK read.  ids: (set id, sample name) per row;
+    bands: an iterable of (row0, K rows [r][>= row0 + r] float64, n rows of the same shape), consecutive from row 0: of row i
+    the entries (i, 0) .. (i, i) are written, as float32.  Returns the bytes written to the two .bin files."""
+    total = 0
+    with open(prefix + ".grm.bin", "wb") as fk, open(prefix + ".grm.N.bin", "wb") as fn:
+        for row0, kb, nb in bands:
+            for r in range(kb.shape[0]):
+                i = row0 + r
+                fk.write(np.asarray(kb[r, :i + 1], dtype=np.float64).astype("<f4").tobytes())
+                fn.write(np.asarray(nb[r, :i + 1]).astype("<f4").tobytes())
+                total += 8 * (i + 1)
+    with open(prefix + ".grm.id", "w") as f:
+        for set_id, name in ids:
+            f.write("%s\t%s\n" % (set_id, name))
+    return total
+
+
+def grm_write_output(conf, eng, ids, err=None):
+    """--grm-output-path: K band by band (GRM_OUTPUT_BAND_ROWS rows, columns 0 .. band end) out of the engine through
+    pcoa_grm_block with host pointers -- no N x N array exists on either side -- and the stderr line."""
+    divisor = conf.grm_output_divisor or "used"
+    n = eng.n
+
+    def bands():
+        for r0 in range(0, n, GRM_OUTPUT_BAND_ROWS):
+            r = min(GRM_OUTPUT_BAND_ROWS, n - r0)
+            kb, nb = eng.grm_block(r0, r, 0, r0 + r, divisor, pairs=True)
+            yield r0, kb, nb
+
+    nbytes = write_grm_files(conf.grm_output_path, ids, bands())
+    (err or sys.stderr).write("GRM written: %d samples, %d used variants, divisor %s, %d bytes\n"
+                              % (n, eng.grm_info()[1], divisor, nbytes))
 
 
 def plink_prefix(path):
@@ -1756,6 +1847,9 @@ def main(args):
         driver.emitResult(result, study=study)
         if conf.grm_weights_output_path:
             write_loadings(conf.grm_weights_output_path, variant_meta, driver.engine.grm_weights(comps, lam, scaled=True))
+        if conf.grm_output_path:
+            order = sorted(driver.indexes.items(), key=lambda kv: kv[1])   # the engine's index order: the .fam's
+            grm_write_output(conf, driver.engine, [(cid.split("-")[0], driver.names[cid]) for cid, _ in order])
         driver.reportIoStats(sys.stderr)
         driver.stop()
         return 0
