@@ -35,7 +35,7 @@ extern "C" {
 #endif
 
 #define PCOA_VERSION_MAJOR 0
-#define PCOA_VERSION_MINOR 12
+#define PCOA_VERSION_MINOR 13
 
 typedef struct pcoa_ctx pcoa_ctx;
 
@@ -312,7 +312,10 @@ int pcoa_operator_matvec_device(pcoa_ctx* ctx, const double* v_dev, double* y_de
  *           accumulate calls were (no floating-point atomics; the order of every addition is fixed by N, the segment size
  *           and a row's index in the store).
  * SNP weights and the projection of new samples: pcoa_grm_weights / pcoa_grm_project below.  Reading K out: pcoa_grm_block.
- * Not built: JNI / Scala natives, LD pruning in front of the store, variant sharding over engines. */
+ * LD pruning: pcoa_grm_ld_prune below prunes the RESIDENT store by the r^2 of the dosages and installs a keep mask that enters
+ * used_v (so d_v and M' too): the product, pcoa_compute, pcoa_grm_weights, pcoa_grm_project, pcoa_grm_block and the
+ * called-sample count see the pruned store; no row is fed twice and none moves.
+ * Not built: JNI / Scala natives, variant sharding over engines. */
 int pcoa_create_grm(pcoa_ctx** out, int32_t n_samples, int32_t device_ordinal, uint32_t flags);
 
 /* Returns 1 for a GRM ctx, 0 otherwise (like pcoa_operator_info).  *variants_out: rows in the store; *used_out: M' under the
@@ -412,6 +415,61 @@ typedef struct pcoa_grm_block_stats {
   double grm_block_flops;     /* 2 * rows * cols * V per float pass launched (num; n where the pair counts are needed)        */
 } pcoa_grm_block_stats;
 int pcoa_get_grm_block_stats(pcoa_ctx* ctx, pcoa_grm_block_stats* out, size_t out_size);
+
+/* ---- LD pruning of the resident GRM store by dosage r^2 ------------------------------------------------------
+ * smartpca, plink --pca, GCTA and flashpca workflows LD-prune the variants in front of the PCA; the accepted pair statistic
+ * (plink --indep-pairwise) is the squared Pearson correlation of the DOSAGES over the samples called at both variants -- not the
+ * r^2 of carrier indicators that pcoa_ld_* tests.  The rule, all integers up to the last comparison.  Rows are the store's rows
+ * in feed order; g_iv in {0, 1, 2} is the dosage and c_iv the called indicator as the store codes them (00 / 10 / 11: g = 0 /
+ * 1 / 2; 01: not called).  For two rows u < v let J be the samples called at both; over i in J, in int64:
+ *   n = |J|     s_u = sum g_iu     s_v = sum g_iv     q_u = sum g_iu^2     q_v = sum g_iv^2     p = sum g_iu g_iv
+ *   cov = n p - s_u s_v      var_u = n q_u - s_u^2      var_v = n q_v - s_v^2
+ *   exceeds(u, v)  <=>  (double)cov * (double)cov  >  t * ((double)var_u * (double)var_v)
+ * -- three fp64 products and one comparison, no sum and no contraction.  A pair with n = 0, or with a row that is constant on
+ * J, has cov = 0 and never exceeds.  A row is a CANDIDATE iff used_v holds under the ctx's current min_maf (the expression of
+ * pcoa_create_grm, judged WITHOUT an installed mask).  The pass is the forward greedy pass of pcoa_ld_*: a non-candidate is
+ * removed and blocks nobody; a candidate v is kept iff no KEPT u has exceeds(u, v), where v - window <= u < v and u lies behind
+ * the last break at or before v.  window counts store rows, not candidates.
+ * This is NOT plink --indep-pairwise to the bit: plink slides a window with a step and removes the lower-MAF member of an
+ * exceeding pair; here the earlier kept row wins, as in pcoa_ld_*.  The pair statistic is plink's.
+ *
+ * pcoa_grm_ld_prune: 1 <= window <= PCOA_LD_MAX_WINDOW, 0 <= r2_max <= 1 (NaN refused); breaks: a host array of n_breaks strictly
+ * increasing row indices in (0, V) -- "a break lies in front of row b" -- or NULL with n_breaks = 0.  Computes the counts and
+ * weights under the current min_maf if they are not resident, runs the pass over the whole store, installs the mask and marks
+ * the weights stale, so that the next consumer sees the pruned used_v, d_v (0 for a removed row; mu_v unchanged) and M' (the
+ * kept rows).  Synchronising.  *candidates_out / *kept_out (either may be NULL): the candidates and the kept rows; V = 0 gives 0
+ * and 0.  A second call replaces the mask; candidates are always judged without the old one.
+ * pcoa_grm_ld_mask: out[v - first_variant] = 1 for a kept row, 0 for a removed one (non-candidates included); host memory;
+ * PCOA_ERR_STATE without an installed mask.
+ * Lifetime: the mask is a statement about the store as it was pruned.  It is dropped by pcoa_grm_ld_clear, pcoa_reset, any
+ * pcoa_accumulate_plink_bed that appends at least one row, and pcoa_grm_set_min_maf with a value other than the current one
+ * (the same value keeps it).  After a drop pcoa_grm_info reports the unpruned M' again.
+ * Errors, all leaving the ctx, the store and an earlier mask as they were:
+ *   PCOA_ERR_STATE        a ctx that is not from pcoa_create_grm (the message names its kind); a pcoa_create_grm_study ctx
+ *   PCOA_ERR_INVALID_ARG  the ranges above, a NULL breaks with n_breaks > 0, breaks not increasing or out of range, N >= 2^28
+ *                         (the sums of a pair are int32 per entry)
+ *   PCOA_ERR_OUT_OF_MEMORY the work buffers: [window + C][pitch] row words, C <= 65,536 rows and <= 256 MiB, C band rows of
+ *                         ceil(window / 32) words, and V bytes
+ * pcoa_ld_* on a GRM ctx stay PCOA_ERR_STATE.  pcoa_grm_project needs nothing new: the study is placed with the panel's pruned
+ * used_v.  Not built: plink's step and MAF-ordered removal, windows in base pairs, JNI / Scala natives. */
+int pcoa_grm_ld_prune(pcoa_ctx* ctx, int32_t window, double r2_max, const int64_t* breaks, int64_t n_breaks,
+                      int64_t* candidates_out, int64_t* kept_out);
+int pcoa_grm_ld_mask(pcoa_ctx* ctx, int64_t first_variant, int64_t n_variants, uint8_t* out /* host */);
+int pcoa_grm_ld_clear(pcoa_ctx* ctx);
+
+/* What the LAST pcoa_grm_ld_prune of this engine did, and the HIP-event time of the pass's kernels, cumulative since
+ * pcoa_create_grm / pcoa_reset_timings.  (A struct of its own, sized like pcoa_ld_stats: it grows at its end; out_size = sizeof
+ * of the struct the caller compiled against.)  Synchronising. */
+typedef struct pcoa_grm_ld_stats {
+  int64_t grm_ld_variants;        /* rows of the store the pass went over                                                    */
+  int64_t grm_ld_candidates;      /* of them candidates (used_v under min_maf)                                               */
+  int64_t grm_ld_kept;            /* of them kept                                                                            */
+  int64_t grm_ld_pairs;           /* in-window pairs (u, v) behind the breaks, candidates or not: what the band kernel tested */
+  double grm_ld_band_seconds;     /* reach + band kernel                                                                     */
+  double grm_ld_resolve_seconds;  /* the greedy pass (one wave)                                                              */
+  double grm_ld_scan_seconds;     /* keep flags to bytes, counts                                                             */
+} pcoa_grm_ld_stats;
+int pcoa_get_grm_ld_stats(pcoa_ctx* ctx, pcoa_grm_ld_stats* out, size_t out_size);
 
 /* ---- PCoA over a sample subset of a stored S ------------------------------------------------------------------------------
  * For a kept index set I, S[I, I] is exactly the similarity matrix of the reduced cohort (an entry counts the variants two

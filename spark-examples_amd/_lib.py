@@ -183,6 +183,19 @@ class PcoaGrmBlockStats(ctypes.Structure):
     ]
 
 
+class PcoaGrmLdStats(ctypes.Structure):
+    """pcoa_grm_ld_stats: what the last pcoa_grm_ld_prune did, and the HIP-event time of its kernels."""
+    _fields_ = [
+        ("grm_ld_variants", ctypes.c_int64),
+        ("grm_ld_candidates", ctypes.c_int64),
+        ("grm_ld_kept", ctypes.c_int64),
+        ("grm_ld_pairs", ctypes.c_int64),
+        ("grm_ld_band_seconds", ctypes.c_double),
+        ("grm_ld_resolve_seconds", ctypes.c_double),
+        ("grm_ld_scan_seconds", ctypes.c_double),
+    ]
+
+
 PCOA_GRM_DIVISOR_USED = 0
 PCOA_GRM_DIVISOR_PAIRWISE = 1
 PCOA_LOADINGS_CENTRE = 1
@@ -246,6 +259,10 @@ _SIGNATURES = [
     ("pcoa_grm_project", ctypes.c_int, [_vp, _vp, _i32, _vp, _vp, _vp, _vp]),
     ("pcoa_grm_block", ctypes.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, ctypes.c_int]),
     ("pcoa_get_grm_block_stats", ctypes.c_int, [_vp, ctypes.POINTER(PcoaGrmBlockStats), ctypes.c_size_t]),
+    ("pcoa_grm_ld_prune", ctypes.c_int, [_vp, _i32, ctypes.c_double, _vp, _i64, ctypes.POINTER(_i64), ctypes.POINTER(_i64)]),
+    ("pcoa_grm_ld_mask", ctypes.c_int, [_vp, _i64, _i64, _vp]),
+    ("pcoa_grm_ld_clear", ctypes.c_int, [_vp]),
+    ("pcoa_get_grm_ld_stats", ctypes.c_int, [_vp, ctypes.POINTER(PcoaGrmLdStats), ctypes.c_size_t]),
     ("pcoa_strip_info", ctypes.c_int, [_vp, ctypes.POINTER(_i32), ctypes.POINTER(_i32)]),
     ("pcoa_strip_col_sums", ctypes.c_int, [_vp, _vp]),
     ("pcoa_strip_matvec", ctypes.c_int, [_vp, _vp, _vp, ctypes.c_double, _vp]),

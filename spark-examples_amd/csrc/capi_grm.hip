@@ -79,20 +79,27 @@ int grm_counts(pcoa_ctx* c) {
   return PCOA_OK;
 }
 
-// mu, d, used and M' from the counts and min_maf; resident until either changes.  The host learns M' here.
-int grm_weights(pcoa_ctx* c) {
-  int rc = grm_counts(c);
-  if (rc != PCOA_OK) return rc;
-  if (c->grm_weights_set) return PCOA_OK;
+// mu, d, used and M' from the counts, min_maf and (with_mask) the LD keep mask, into the resident arrays.  The host learns M' here.
+int weights_pass(pcoa_ctx* c, bool with_mask) {
   const GrmWeights w = weights_of(c);
   {
     ScopedTimer t(c, T_CENTER);
     HIP_TRY(c, hipMemsetAsync(w.mprime, 0, sizeof(unsigned long long), c->stream));
-    HIP_TRY(c, launch_grm_weights(w.cnt, c->op_variants, c->grm_min_maf, w.mu, w.d, w.used, w.mprime, c->stream));
+    HIP_TRY(c, launch_grm_weights(w.cnt, c->op_variants, c->grm_min_maf, with_mask ? c->grm_keep : nullptr, w.mu, w.d, w.used, w.mprime,
+                                  c->stream));
   }
   HIP_TRY(c, hipMemcpyAsync(&c->hw->grm[0], w.mprime, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   c->grm_used = c->hw->grm[0];
+  return PCOA_OK;
+}
+
+// the weights under the counts, min_maf and the keep mask where one is installed; resident until one of them changes
+int grm_weights(pcoa_ctx* c) {
+  int rc = grm_counts(c);
+  if (rc != PCOA_OK) return rc;
+  if (c->grm_weights_set) return PCOA_OK;
+  if ((rc = weights_pass(c, c->grm_keep_set)) != PCOA_OK) return rc;
   c->grm_weights_set = true;
   return PCOA_OK;
 }
@@ -150,6 +157,18 @@ int no_weights_on_study(pcoa_ctx* c, const char* call) {
 namespace pcoa {
 
 int64_t grm_store_ranges(const pcoa_ctx* c) { return store_ranges(c); }
+
+int grm_unmasked_used(pcoa_ctx* c, const int32_t** used_out) {
+  int rc = grm_counts(c);
+  if (rc != PCOA_OK) return rc;
+  if (c->grm_keep_set || !c->grm_weights_set) {
+    c->grm_weights_set = false;
+    if ((rc = weights_pass(c, false)) != PCOA_OK) return rc;
+    c->grm_weights_set = !c->grm_keep_set;
+  }
+  *used_out = weights_of(c).used;
+  return PCOA_OK;
+}
 
 int grm_resident_params(pcoa_ctx* c, GrmParams* out, int64_t* used_out) {
   const int rc = grm_weights(c);
@@ -219,6 +238,9 @@ void grm_destroy(pcoa_ctx* c) {
   if (c->grm_par) dev_free(c->grm_par);
   if (c->grm_mw) dev_free(c->grm_mw);
   if (c->grm_blk) dev_free(c->grm_blk);
+  if (c->grm_keep) dev_free(c->grm_keep);
+  c->grm_keep = nullptr;
+  c->grm_keep_set = false;
   c->grm_cnt = nullptr;
   c->grm_par = nullptr;
   c->grm_mw = nullptr;
@@ -254,7 +276,10 @@ int pcoa_grm_set_min_maf(pcoa_ctx* c, double maf) {
   if (c->is_grm_study) return no_weights_on_study(c, "pcoa_grm_set_min_maf");
   if (!(maf >= 0.0 && maf < 0.5))
     return fail(c, PCOA_ERR_INVALID_ARG, "pcoa_grm_set_min_maf: maf = " + std::to_string(maf) + " is outside [0, 0.5)");
-  if (maf != c->grm_min_maf) c->grm_weights_set = false;
+  if (maf != c->grm_min_maf) {
+    c->grm_weights_set = false;
+    grm_ld_drop(c);   // the mask was judged under the old min_maf
+  }
   c->grm_min_maf = maf;
   return PCOA_OK;
 }

@@ -165,6 +165,7 @@ int store_append(pcoa_ctx* c, int64_t nv, const std::function<hipError_t(int64_t
     done += cur;
   }
   c->op_centering_set = false;
+  grm_ld_drop(c);   // a keep mask (pcoa_grm_ld_prune) described the store without these rows
   return PCOA_OK;
 }
 
@@ -185,6 +186,7 @@ int operator_reset(pcoa_ctx* c) {
   if (!c->op_segs.empty()) c->op_segs[0].rows = 0;
   c->op_variants = 0;
   c->op_centering_set = false;
+  grm_ld_drop(c);
   HIP_TRY(c, hipMemsetAsync(c->err_flag, 0, 16, c->stream));
   return PCOA_OK;
 }

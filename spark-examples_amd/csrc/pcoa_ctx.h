@@ -13,6 +13,7 @@
 //   capi_grm.hip         the standardised-genotype operator (pcoa_create_grm): the 2-bit store, its counts and weights, K x
 //   capi_grm_project.hip SNP weights of K's axes and the projection of a study store onto them (pcoa_create_grm_study, pcoa_grm_weights / _project)
 //   capi_grm_dense.hip   pcoa_grm_block: a rectangle of K and of the pair counts read out through the fp64 matrix cores
+//   capi_grm_ld.hip      pcoa_grm_ld_*: LD pruning of the resident GRM store by dosage r^2, as a keep mask that enters used_v
 //   capi_subset.hip      pcoa_create_subset: a new engine whose S is S[I, I] of another
 //   capi_pairs.hip       pcoa_similar_pairs: the screen of S for duplicate and related sample pairs
 //   capi_measure.hip     pcoa_set_similarity / pcoa_get_similarity and the centring of a Jaccard / cosine measure
@@ -28,7 +29,7 @@
 
 #include "pcoa_internal.h"
 
-enum TimeCat { T_GRAM = 0, T_DENSIFY, T_SYNTH, T_FINALIZE, T_CENTER, T_TRIDIAG, T_EIG, T_BACK, T_PACK, T_LANCZOS, T_ALLREDUCE, T_OPERATOR, T_SUBSET, T_REDUCE_PEERS, T_PAIRS, T_LOADINGS, T_LD_COUNT, T_LD_BAND, T_LD_RESOLVE, T_LD_COMPACT, T_KING, T_GRM_BLOCK, T_NCAT };
+enum TimeCat { T_GRAM = 0, T_DENSIFY, T_SYNTH, T_FINALIZE, T_CENTER, T_TRIDIAG, T_EIG, T_BACK, T_PACK, T_LANCZOS, T_ALLREDUCE, T_OPERATOR, T_SUBSET, T_REDUCE_PEERS, T_PAIRS, T_LOADINGS, T_LD_COUNT, T_LD_BAND, T_LD_RESOLVE, T_LD_COMPACT, T_KING, T_GRM_BLOCK, T_GRM_LD_BAND, T_GRM_LD_RESOLVE, T_GRM_LD_SCAN, T_NCAT };
 
 struct EventPair {
   hipEvent_t a, b;
@@ -102,6 +103,12 @@ struct pcoa_ctx {
   int64_t grm_blk_cap = 0;
   int64_t grm_block_calls = 0;     // pcoa_grm_block_stats
   double grm_block_flops = 0;
+  // LD pruning of the store (pcoa_grm_ld_prune, capi_grm_ld.hip): the keep mask is a statement about the store as it was
+  // pruned under grm_min_maf; an append, pcoa_reset, another min_maf and pcoa_grm_ld_clear drop it (grm_ld_drop)
+  uint8_t* grm_keep = nullptr;     // [V] 1 = kept, 0 = removed or no candidate
+  int64_t grm_keep_cap = 0;
+  bool grm_keep_set = false;
+  int64_t grm_ld_rows = 0, grm_ld_cand = 0, grm_ld_kept = 0, grm_ld_pairs = 0;   // the last prune, for pcoa_get_grm_ld_stats
   int64_t subset_bytes = 0;        // bytes the gathers of pcoa_create_subset moved into this ctx (read + written)
   int64_t pairs_bytes = 0, pairs_calls = 0;   // pcoa_similar_pairs: bytes of S its scan kernels read, calls
   // per-variant loadings (pcoa_loadings_begin .. pcoa_loadings_end, capi_loadings.hip): the prepared vectors stay resident
@@ -482,6 +489,13 @@ struct GrmParams {
 };
 int grm_resident_params(pcoa_ctx* c, GrmParams* out, int64_t* used_out);
 int64_t grm_store_ranges(const pcoa_ctx* c);   // ranges of kGrmRangeRows rows over the segments of c's store
+// the counts, then mu / d / used / M' under the current min_maf WITHOUT the keep mask: *used_out[v] = 1 for a candidate of the LD
+// prune.  The resident weights are marked stale where a mask is installed, so the next consumer computes them with it
+int grm_unmasked_used(pcoa_ctx* c, const int32_t** used_out);
+inline void grm_ld_drop(pcoa_ctx* c) {   // the keep mask no longer describes the store: the weights are the unpruned ones again
+  if (c->grm_keep_set) c->grm_weights_set = false;
+  c->grm_keep_set = false;
+}
 
 // ---- capi_loadings.hip
 void loadings_destroy(pcoa_ctx* c);

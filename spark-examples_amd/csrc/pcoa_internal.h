@@ -243,9 +243,10 @@ int32_t grm_groups(int32_t n);
 hipError_t launch_grm_append(const uint8_t* src, int64_t row_bytes, int64_t nv, int32_t n, int swap, uint32_t* dst, hipStream_t stream);
 // cnt[r * 3 + {0, 1, 2}] = called, het, hom non-reference of row r
 hipError_t launch_grm_counts(const uint32_t* seg, int32_t rows, int32_t n, int32_t* cnt, hipStream_t stream);
-// mu, d, used per variant; *mprime (zeroed by the caller) += the used variants
-hipError_t launch_grm_weights(const int32_t* cnt, int64_t rows, double min_maf, double* mu, double* d, int32_t* used,
-                              unsigned long long* mprime, hipStream_t stream);
+// mu, d, used per variant; *mprime (zeroed by the caller) += the used variants.  keep: NULL, or [rows] bytes of an LD keep mask
+// (0: the row is not used whatever its counts say)
+hipError_t launch_grm_weights(const int32_t* cnt, int64_t rows, double min_maf, const uint8_t* keep, double* mu, double* d,
+                              int32_t* used, unsigned long long* mprime, hipStream_t stream);
 // tpart[g * vstride + r] = the part of (A x)[r] from sample group g, r in [0, rows) of this segment (mu: the segment's first row)
 hipError_t launch_grm_ax(const uint32_t* seg, int32_t rows, int32_t n, const double* mu, const double* x, double* tpart,
                          int64_t vstride, hipStream_t stream);
@@ -320,6 +321,17 @@ hipError_t launch_ld_scan(const uint32_t* kbits, int64_t g0, const int32_t* cnt_
                           int32_t* pos, int64_t* out2, hipStream_t stream);
 hipError_t launch_ld_gather(const uint32_t* wb_rows, const uint8_t* keep, const int32_t* pos, int64_t vc, int32_t n, uint32_t* out,
                             hipStream_t stream);
+
+// ---- LD pruning of the GRM store by dosage r^2 (grm_ld.hip).  wb: [window + vc][grm_pitch_words(n)] store rows,
+// the chunk's first row at row `window`, the rows in front of it before that; reach[r]: the distances at which an earlier row
+// exists for chunk row r (<= window; breaks: sorted global row indices on the device, g0: the global index of the chunk's first
+// row); ex: band words in launch_ld_band's format, so launch_ld_resolve / launch_ld_scan take them as they are ----
+int32_t grm_ld_band_tile_rows();        // target rows a band workgroup owns
+int32_t grm_ld_band_chunk_samples();    // samples of the sample axis it stages at a time
+hipError_t launch_grm_ld_reach(const int64_t* breaks, int64_t n_breaks, int64_t g0, int64_t vc, int32_t window, int32_t* reach,
+                               hipStream_t stream);
+hipError_t launch_grm_ld_band(const uint32_t* wb, const int32_t* reach, int64_t vc, int32_t n, int32_t window, double t, uint32_t* ex,
+                              hipStream_t stream);
 
 // ---- centring (center.hip) --------------------------------------------------------------------
 // s = s32 + (s64 ? s64 : 0).  row_sums[n] (fp64), stats[0] = matrix sum, stats[1] = matrix mean,

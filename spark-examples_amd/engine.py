@@ -757,6 +757,39 @@ class PcoaEngine(object):
         self._check(self._lib.pcoa_get_grm_block_stats(self._ctx, ctypes.byref(q), ctypes.sizeof(q)))
         return dict((f[0], getattr(q, f[0])) for f in L.PcoaGrmBlockStats._fields_)
 
+    # ------------------------------------------------------------------ LD pruning of the GRM store
+    def grm_ld_prune(self, window, r2_max, breaks=()):
+        """LD-prunes the resident genotype store by the r^2 of the dosages over the jointly called samples (pcoa_grm_ld_prune;
+        include/pcoa.h states the rule, tests/grm_ld_cohort.py is its numpy form): forward and greedy over the store's rows, a candidate (a variant used under the
+        current min MAF) is removed when a KEPT row among the `window` rows before it, behind the last break, exceeds r2_max.
+        breaks: strictly increasing row indices, a break lies in front of row b.  Installs the keep mask -- compute, grm_weights,
+        grm_project, grm_block and grm_info see the pruned store until an append, reset, another min MAF or grm_ld_clear --
+        and returns (candidates, kept)."""
+        br = np.ascontiguousarray(np.asarray(list(breaks), dtype=np.int64).reshape(-1))
+        cand, kept = ctypes.c_int64(0), ctypes.c_int64(0)
+        self._check(self._lib.pcoa_grm_ld_prune(self._ctx, int(window), float(r2_max), _ptr(br) if br.size else None, int(br.size),
+                                                ctypes.byref(cand), ctypes.byref(kept)))
+        return int(cand.value), int(kept.value)
+
+    def grm_ld_mask(self, first=0, n=None):
+        """bool [n]: True for a row the installed prune kept, False for a removed one (non-candidates included)."""
+        if n is None:
+            info = self.grm_info()   # (None: not a GRM engine -- the call itself says so)
+            n = info[0] - int(first) if info else 0
+        out = np.zeros(max(int(n), 0), dtype=np.uint8)
+        self._check(self._lib.pcoa_grm_ld_mask(self._ctx, int(first), int(n), _ptr(out) if out.size else None))
+        return out.astype(bool)
+
+    def grm_ld_clear(self):
+        """Drops the keep mask: the store counts unpruned again."""
+        self._check(self._lib.pcoa_grm_ld_clear(self._ctx))
+
+    def grm_ld_stats(self):
+        """pcoa_get_grm_ld_stats: rows / candidates / kept / in-window pairs of the last prune, seconds of band / resolve / scan."""
+        q = L.PcoaGrmLdStats()
+        self._check(self._lib.pcoa_get_grm_ld_stats(self._ctx, ctypes.byref(q), ctypes.sizeof(q)))
+        return dict((f[0], getattr(q, f[0])) for f in L.PcoaGrmLdStats._fields_)
+
     # ------------------------------------------------------------------ per-variant loadings
     def loadings(self, components, eigenvalues=None, centre=True, unit=True):
         """Per-variant loadings of the principal coordinates (pcoa_loadings_begin): `components` [N, k] and `eigenvalues` [k] are

@@ -123,6 +123,10 @@ struct Conf {  // PcaConf / GenomicsConf (GenomicsConf.scala:31-101), same flag 
                                         // principal coordinates, w_c = X (J u_c) / sqrt(lambda_c) (pcoa_loadings_*), one line per variant in feed
                                         // order.  --gram implicit reads the resident store; a stored S takes a second streaming pass over a
                                         // single PLINK fileset
+  int grm_ld_window = 0;                // --grm-ld-window W: --grm: LD-prune the resident store by dosage r^2 (pcoa_grm_ld_prune), W store rows; 0 = off
+  double grm_ld_r2 = 0.2;               // --grm-ld-r2 X: its threshold (the default of --ld-r2)
+  bool grm_ld_r2_given = false;
+  std::string grm_ld_output_path;       // --grm-ld-output-path FILE: one line per variant of the store: index, contig, position, id, 1 (kept) or 0
   int ld_window = 0;                    // --ld-window W: LD pruning in front of the accumulation (pcoa_ld_*), W fed variants; 0 = off
   double ld_r2 = 0.2;                   // --ld-r2 X: a variant is removed when a kept one inside the window has r^2 of the carrier indicators above X
   bool ld_r2_given = false;
@@ -166,6 +170,10 @@ const char* kUsage =
     "                   --grm-output-path PREFIX [--grm-output-divisor used|pairwise] (--grm: the matrix that was decomposed, read out\n"
     "                   band by band: PREFIX.grm.bin (float32 lower triangle with the diagonal), PREFIX.grm.N.bin (jointly called used\n"
     "                   variants per pair) and PREFIX.grm.id, the layout GCTA and PLINK read; used: num / M', pairwise: num / n(i, j))\n"
+    "                   --grm-ld-window W [--grm-ld-r2 X, default 0.2] [--grm-ld-output-path FILE] (--grm: LD-prune the resident store\n"
+    "                   before computePca: forward and greedy, a used variant is removed when a kept one among the W rows before it\n"
+    "                   on the same contig has r^2 of the dosages over the jointly called samples above X -- plink's pair statistic,\n"
+    "                   the earlier kept variant wins; FILE: index, contig, position, id, 1 (kept) or 0 per variant)\n"
     "                   --similarity-measure shared|jaccard|cosine (what computePca decomposes: the counts S as the reference,\n"
     "                   S(i,j) / (S(i,i) + S(j,j) - S(i,j)), or S(i,j) / sqrt(S(i,i) S(j,j)), evaluated on the fly from S; one\n"
     "                   engine, stored S, full layout, no projection)\n"
@@ -346,6 +354,24 @@ Conf parse(int argc, char** argv) {
       c.ld_r2_given = true;
     }
     else if (a == "--ld-output-path") c.ld_output_path = one(i);
+    else if (a == "--grm-ld-window") {
+      const std::string v = one(i);
+      char* end = nullptr;
+      const long w = std::strtol(v.c_str(), &end, 10);
+      if (v.empty() || *end || w < 0 || w > PCOA_LD_MAX_WINDOW)
+        die("--grm-ld-window (the LD pruning of --grm) takes a number of variants in [1, " + std::to_string(PCOA_LD_MAX_WINDOW) +
+            "] (0: off), not '" + v + "'");
+      c.grm_ld_window = (int)w;
+    }
+    else if (a == "--grm-ld-r2") {
+      const std::string v = one(i);
+      char* end = nullptr;
+      c.grm_ld_r2 = std::strtod(v.c_str(), &end);
+      if (v.empty() || *end || !(c.grm_ld_r2 >= 0.0 && c.grm_ld_r2 <= 1.0))
+        die("--grm-ld-r2 (the threshold of --grm-ld-window) takes a value in [0, 1], not '" + v + "'");
+      c.grm_ld_r2_given = true;
+    }
+    else if (a == "--grm-ld-output-path") c.grm_ld_output_path = one(i);
     else if (a == "--parse-only") c.parse_only = true;
     else if (a == "--dump-similarity") c.dump_similarity = one(i);
     else if (a == "--ingest-threads") c.ingest_threads = std::atoi(one(i).c_str());
@@ -378,6 +404,14 @@ Conf parse(int argc, char** argv) {
     die("--grm-output-path needs --grm (it writes the relationship matrix K of the standardised genotypes; the shared counts S go to "
         "--dump-similarity)");
   if (!c.grm && c.has_grm_output_divisor) die("--grm-output-divisor needs --grm (and --grm-output-path)");
+  {
+    const char* why = " needs --grm (it prunes the genotype store of the standardised-genotype PCA; the carrier counts S are pruned by --ld-window)";
+    if (!c.grm && c.grm_ld_window != 0) die(std::string("--grm-ld-window") + why);
+    if (!c.grm && c.grm_ld_r2_given) die(std::string("--grm-ld-r2") + why);
+    if (!c.grm && !c.grm_ld_output_path.empty()) die(std::string("--grm-ld-output-path") + why);
+    if (c.grm_ld_window == 0 && c.grm_ld_r2_given) die("--grm-ld-r2 needs --grm-ld-window W (the pruning is off without it)");
+    if (c.grm_ld_window == 0 && !c.grm_ld_output_path.empty()) die("--grm-ld-output-path needs --grm-ld-window W (the pruning is off without it)");
+  }
   if (c.has_grm_output_divisor && c.grm_output_divisor != "used" && c.grm_output_divisor != "pairwise")
     die("--grm-output-divisor takes used or pairwise, not '" + c.grm_output_divisor + "'");
   if (c.has_grm_output_divisor && c.grm_output_path.empty())
@@ -394,7 +428,9 @@ Conf parse(int argc, char** argv) {
     if (c.outlier_iterations != 0) die("--grm holds no matrix to subset: it cannot take --outlier-iterations");
     if (c.related) die("--grm holds no shared counts to screen: it cannot take --related-min-jaccard");
     if (c.king) die("--grm holds no genotype-class matrices to screen: it cannot take --king-cutoff");
-    if (c.ld_window > 0) die("--grm: LD pruning in front of the genotype store is not built: it cannot take --ld-window");
+    if (c.ld_window > 0)
+      die("--grm prunes its genotype store by dosage r^2 with --grm-ld-window: it cannot take --ld-window (the carrier-indicator pruner "
+          "in front of an accumulation)");
     if (!c.loadings_output_path.empty()) die("--grm writes the SNP weights of K with --grm-weights-output-path: it cannot take --loadings-output-path");
     if (c.carrier_format == "lists") die("--grm stores 2-bit genotypes: it cannot take --carrier-format lists");
     const std::string ext = c.input_path.size() == 1 && c.input_path[0].size() >= 4 ? c.input_path[0].substr(c.input_path[0].size() - 4) : "";
@@ -1817,7 +1853,7 @@ int main(int argc, char** argv) {
   g_ld.on = conf.ld_window > 0;
   g_calls.on = conf.missing_calls == "pairwise";
   g_king.on = conf.king;
-  g_want_meta = want_loadings || g_ld.on || !conf.grm_weights_output_path.empty();   // (--ld-window: the contigs place the breaks)
+  g_want_meta = want_loadings || g_ld.on || !conf.grm_weights_output_path.empty() || conf.grm_ld_window > 0;   // (--ld-window: the contigs place the breaks)
   if (conf.input_path.empty())
     die("--input-path <file.vcf[.gz]> [more files] or one PLINK fileset (<prefix>.bed) is required: the Google Genomics API the reference read "
         "from has been shut down");
@@ -2215,6 +2251,33 @@ int main(int argc, char** argv) {
     if (pcoa_grm_info(ctx, &variants, &used, &store) != 1) die(std::string("pcoa_grm_info: ") + pcoa_last_error(ctx));
     std::fprintf(stderr, "Standardised genotypes: %lld of %lld variants used (min MAF %g), store %lld bytes\n", (long long)used,
                  (long long)variants, conf.grm_min_maf, (long long)store);
+    if (conf.grm_ld_window > 0) {   // --grm-ld-window: the resident store is pruned, a break in front of the first variant of every new contig
+      const bool known = fed_meta_known && (int64_t)fed_meta.size() == variants;
+      std::vector<int64_t> breaks;
+      if (known)
+        for (int64_t v = 1; v < variants; ++v)
+          if (fed_meta[(size_t)v].contig != fed_meta[(size_t)v - 1].contig) breaks.push_back(v);
+      int64_t cand = 0, kept = 0;
+      check(ctx, pcoa_grm_ld_prune(ctx, conf.grm_ld_window, conf.grm_ld_r2, breaks.empty() ? nullptr : breaks.data(), (int64_t)breaks.size(),
+                                   &cand, &kept), "pcoa_grm_ld_prune");
+      std::printf("GRM LD pruning: kept %lld of %lld candidate variants (%lld in the store), window %d, r2 %g\n", (long long)kept,
+                  (long long)cand, (long long)variants, conf.grm_ld_window, conf.grm_ld_r2);
+      pcoa_grm_ld_stats gs;
+      check(ctx, pcoa_get_grm_ld_stats(ctx, &gs, sizeof(gs)), "pcoa_get_grm_ld_stats");
+      std::fprintf(stderr, "GRM LD pruning: %lld pairs; band %.3f ms, resolve %.3f ms, scan %.3f ms\n", (long long)gs.grm_ld_pairs,
+                   1e3 * gs.grm_ld_band_seconds, 1e3 * gs.grm_ld_resolve_seconds, 1e3 * gs.grm_ld_scan_seconds);
+      if (!conf.grm_ld_output_path.empty()) {
+        std::vector<uint8_t> keep((size_t)std::max<int64_t>(variants, 1));
+        check(ctx, pcoa_grm_ld_mask(ctx, 0, variants, keep.data()), "pcoa_grm_ld_mask");
+        std::ofstream out(conf.grm_ld_output_path);
+        for (int64_t v = 0; v < variants; ++v) {
+          if (known) out << v << "\t" << fed_meta[(size_t)v].contig << "\t" << fed_meta[(size_t)v].pos << "\t" << fed_meta[(size_t)v].id;
+          else out << v << "\t.\t.\t.";
+          out << "\t" << (keep[(size_t)v] ? 1 : 0) << "\n";
+        }
+        if (!out) die("cannot write " + conf.grm_ld_output_path);
+      }
+    }
   }
   if (g_ld.on) {
     pcoa_ld_stats ls;

@@ -576,6 +576,17 @@ class PcaConf(object):
                             "(pcoa_grm_block), as PREFIX.grm.bin (float32, lower triangle with the diagonal, row by row), "
                             "PREFIX.grm.N.bin (the jointly called used variants of each pair, float32, same order) and "
                             "PREFIX.grm.id (set id <tab> sample name per row): the layout GCTA and PLINK read")
+        p.add_argument("--grm-ld-window", type=int, default=0,
+                       help="--grm: LD-prune the resident genotype store before computePca (pcoa_grm_ld_prune): forward and "
+                            "greedy in feed order, a used variant is removed when a KEPT variant among the W rows before it, on "
+                            "the same contig, has r^2 of the DOSAGES over the jointly called samples (the pair statistic of "
+                            "plink --indep-pairwise; the earlier kept variant wins, there is no step and no MAF order) above "
+                            "--grm-ld-r2.  0: off; at most %d" % LD_MAX_WINDOW)
+        p.add_argument("--grm-ld-r2", type=float, default=None,
+                       help="the r^2 threshold of --grm-ld-window, in [0, 1] (default %g, as --ld-r2)" % LD_DEFAULT_R2)
+        p.add_argument("--grm-ld-output-path", type=str, default=None,
+                       help="--grm-ld-window: one line per variant of the store in feed order -- 0-based index, contig, "
+                            "position, variant id, 1 (kept) or 0, tab-separated (the columns of --ld-output-path)")
         p.add_argument("--grm-output-divisor", type=str, default=None,
                        help="--grm-output-path: used (default): num / M', the mean-imputed K that is decomposed; pairwise: "
                             "num / n(i, j), the pairwise-complete estimator GCTA-style tools store")
@@ -1164,7 +1175,26 @@ def check_grm_conf(conf):
                              "standardised genotypes; the shared counts S go to --dump-similarity)")
         if conf.grm_output_divisor is not None:
             raise SystemExit("VariantsPcaDriver: --grm-output-divisor needs --grm (and --grm-output-path)")
+        for given, flag in ((conf.grm_ld_window != 0, "--grm-ld-window"), (conf.grm_ld_r2 is not None, "--grm-ld-r2"),
+                            (bool(conf.grm_ld_output_path), "--grm-ld-output-path")):
+            if given:
+                raise SystemExit("VariantsPcaDriver: %s needs --grm (it prunes the genotype store of the standardised-genotype "
+                                 "PCA; the carrier counts S are pruned by --ld-window)" % flag)
         return
+    if conf.grm_ld_window == 0:
+        if conf.grm_ld_r2 is not None:
+            raise SystemExit("VariantsPcaDriver: --grm-ld-r2 needs --grm-ld-window W (the pruning is off without it)")
+        if conf.grm_ld_output_path:
+            raise SystemExit("VariantsPcaDriver: --grm-ld-output-path needs --grm-ld-window W (the pruning is off without it)")
+    else:
+        if not 1 <= conf.grm_ld_window <= LD_MAX_WINDOW:
+            raise SystemExit("VariantsPcaDriver: --grm-ld-window (the LD pruning of --grm) takes a number of variants in [1, %d] (0: off), not '%d'"
+                             % (LD_MAX_WINDOW, conf.grm_ld_window))
+        if conf.grm_ld_r2 is None:
+            conf.grm_ld_r2 = LD_DEFAULT_R2
+        if not 0.0 <= conf.grm_ld_r2 <= 1.0:      # (NaN fails both comparisons)
+            raise SystemExit("VariantsPcaDriver: --grm-ld-r2 (the threshold of --grm-ld-window) takes a value in [0, 1], not '%s'"
+                             % conf.grm_ld_r2)
     if conf.grm_output_divisor is not None and conf.grm_output_divisor not in GRM_OUTPUT_DIVISORS:
         raise SystemExit("VariantsPcaDriver: --grm-output-divisor takes used or pairwise, not '%s'" % conf.grm_output_divisor)
     if conf.grm_output_divisor is not None and not conf.grm_output_path:
@@ -1184,7 +1214,8 @@ def check_grm_conf(conf):
         (conf.outlier_iterations != 0, "holds no matrix to subset: it cannot take --outlier-iterations"),
         (conf.related_min_jaccard is not None, "holds no shared counts to screen: it cannot take --related-min-jaccard"),
         (conf.king_cutoff is not None, "holds no genotype-class matrices to screen: it cannot take --king-cutoff"),
-        (bool(conf.ld_window), "LD pruning in front of the genotype store is not built: it cannot take --ld-window"),
+        (bool(conf.ld_window), "prunes its genotype store by dosage r^2 with --grm-ld-window: it cannot take --ld-window (the "
+                               "carrier-indicator pruner in front of an accumulation)"),
         (bool(conf.loadings_output_path), "writes the SNP weights of K with --grm-weights-output-path: it cannot take "
                                           "--loadings-output-path"),
     ]
@@ -1361,6 +1392,19 @@ def grm_accumulate(call_rdd, matrix_size, min_maf, device=0, err=None):
     (err or sys.stderr).write("Standardised genotypes: %d of %d variants used (min MAF %g), store %d bytes\n"
                               % (used, variants, min_maf, store))
     return eng
+
+
+def grm_ld_prune(conf, eng, meta, out=None):
+    """--grm-ld-window: pcoa_grm_ld_prune over the fed store with a break in front of the first variant of every new contig
+    (meta: (contig, position, id) per row), the stdout line, and the --grm-ld-output-path file."""
+    total = eng.grm_info()[0]
+    contigs = [m[0] for m in meta] if meta and len(meta) == total else None
+    breaks = [v for v in range(1, total) if contigs[v] != contigs[v - 1]] if contigs else []
+    cand, kept = eng.grm_ld_prune(conf.grm_ld_window, conf.grm_ld_r2, breaks)
+    (out or sys.stdout).write("GRM LD pruning: kept %d of %d candidate variants (%d in the store), window %d, r2 %g\n"
+                              % (kept, cand, total, conf.grm_ld_window, conf.grm_ld_r2))
+    if conf.grm_ld_output_path:
+        write_ld_mask(conf.grm_ld_output_path, meta if contigs else None, eng.grm_ld_mask())
 
 
 def check_gram_conf(conf):
@@ -1822,7 +1866,7 @@ def main(args):
         if quiet is not None:
             sys.stdout = quiet
     # (contig, position, id) per row, recorded only with a flag that needs them (--ld-window: the contigs place the breaks)
-    variant_meta = [] if conf.loadings_output_path or conf.ld_window or conf.grm_weights_output_path else None
+    variant_meta = [] if conf.loadings_output_path or conf.ld_window or conf.grm_weights_output_path or conf.grm_ld_window else None
     indexes, names, data = load_dataset(conf, variant_meta)
     driver = VariantsPcaDriver(conf, indexes, names, data)
     filtered = [driver.filterDataset(d) for d in driver.data]
@@ -1841,6 +1885,8 @@ def main(args):
 
     if conf.grm:
         driver.engine = grm_accumulate(calls_rdd, n, conf.grm_min_maf or 0.0, device=conf.gpu)
+        if conf.grm_ld_window:
+            grm_ld_prune(conf, driver.engine, variant_meta)
         result = driver.computePca(driver.engine)
         comps, lam = driver.last_pca
         study = grm_project_study(conf, driver.engine, comps, lam) if conf.grm_project_path else None
