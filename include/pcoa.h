@@ -35,7 +35,7 @@ extern "C" {
 #endif
 
 #define PCOA_VERSION_MAJOR 0
-#define PCOA_VERSION_MINOR 13
+#define PCOA_VERSION_MINOR 14
 
 typedef struct pcoa_ctx pcoa_ctx;
 
@@ -470,6 +470,50 @@ typedef struct pcoa_grm_ld_stats {
   double grm_ld_scan_seconds;     /* keep flags to bytes, counts                                                             */
 } pcoa_grm_ld_stats;
 int pcoa_get_grm_ld_stats(pcoa_ctx* ctx, pcoa_grm_ld_stats* out, size_t out_size);
+
+/* ---- sample subsets of the resident GRM store -----------------------------------------------------------------
+ * smartpca removes outliers in rounds and re-estimates the allele frequencies on the survivors; the usual biobank recipe computes
+ * the axes on an unrelated subset and projects the excluded samples.  A GRM ctx keeps 2 bits per genotype and nothing else, so
+ * the reduced cohort's engine is the same rows with the removed samples' columns taken out: one gather over the store, no
+ * variant is fed twice.
+ *
+ * pcoa_create_grm_subset creates a NEW GRM ctx over n_keep samples on src's device, with src's create flags and src's min_maf:
+ * as from pcoa_create_grm (PCOA_GRM_SUBSET_PANEL, n_keep >= 32) or from pcoa_create_grm_study (PCOA_GRM_SUBSET_STUDY, n_keep >=
+ * 1).  Its store holds as many rows as src's, in the same order; slot a of row v is slot keep[a] of src's row v, in the store's
+ * one coding at the result's own pitch (ceil(n_keep / 4) bytes rounded up to 16); every slot at index >= n_keep, the pitch's
+ * padding included, holds 01, exactly as the append leaves a store.  An engine created with n_keep samples and fed the same rows
+ * re-packed on the host with ref_is_a1 = 1 is indistinguishable from it, bit for bit, in every later call: the counts, weights
+ * and M' are not resident and are computed lazily from its own columns (n_v, mu_v, used_v, d_v, M' of the kept samples).
+ *   keep:   a host array of n_keep strictly increasing indices in [0, N_src), consumed on return (pcoa_create_subset's rules).
+ *   src:    either GRM kind, a result of this call included.  It is synchronised and otherwise unchanged: it may be fed further,
+ *           subset again or destroyed.  A keep mask installed by pcoa_grm_ld_prune on src is NOT inherited (it is a statement
+ *           about src's frequencies).  An empty src store gives an empty result.
+ *   memory: src's store plus the result's at the peak; all of the result's segments are allocated before the first row moves.
+ *   errors are reported on src (pcoa_last_error(src)); *out = NULL and src stays usable:
+ *           PCOA_ERR_INVALID_ARG, found on the host before any device work: out / src / keep NULL, an unknown kind, n_keep below
+ *             the kind's minimum, an index outside [0, N_src), indices not strictly increasing
+ *           PCOA_ERR_STATE: src is not a GRM ctx (the message names its kind)
+ *           PCOA_ERR_OUT_OF_MEMORY: the result's segments
+ * pcoa_create_subset, the strip calls and every other stored-S call on a GRM ctx stay PCOA_ERR_STATE.
+ *
+ * pcoa_grm_rows reads rows [first_variant, first_variant + n_variants) of the store back as .bed rows of ceil(N / 4) bytes, in
+ * the store's coding, which is a .bed row with ref_is_a1 = 1 (00 g = 0, 01 missing, 10 g = 1, 11 g = 2); the unused slots of the
+ * last byte are 00, PLINK's convention.  Either GRM kind.  Feeding the output to a fresh engine with ref_is_a1 = 1 reproduces the
+ * store.  Synchronising; no kernel runs.  PCOA_ERR_INVALID_ARG: a window outside the store, a NULL out.
+ * Not built: JNI / Scala natives, a KING screen that feeds a GRM engine in one run. */
+#define PCOA_GRM_SUBSET_PANEL 0   /* result as from pcoa_create_grm       (n_keep >= 32) */
+#define PCOA_GRM_SUBSET_STUDY 1   /* result as from pcoa_create_grm_study (n_keep >= 1)  */
+int pcoa_create_grm_subset(pcoa_ctx** out, pcoa_ctx* src, const int32_t* keep, int32_t n_keep, int32_t kind);
+int pcoa_grm_rows(pcoa_ctx* ctx, int64_t first_variant, int64_t n_variants, uint8_t* out /* host, [n_variants][ceil(N/4)] */);
+
+/* What pcoa_create_grm_subset did with THIS engine as src, cumulative since its creation / pcoa_reset_timings.  (A struct of its
+ * own; it grows at its end; out_size = sizeof of the struct the caller compiled against.)  Synchronising. */
+typedef struct pcoa_grm_subset_stats {
+  double grm_subset_seconds;   /* HIP-event time of the gather launches                                                      */
+  int64_t grm_subset_calls;
+  int64_t grm_subset_bytes;    /* rows * (src pitch + result pitch) bytes per call: what an ideal gather reads and writes   */
+} pcoa_grm_subset_stats;
+int pcoa_get_grm_subset_stats(pcoa_ctx* ctx, pcoa_grm_subset_stats* out, size_t out_size);
 
 /* ---- PCoA over a sample subset of a stored S ------------------------------------------------------------------------------
  * For a kept index set I, S[I, I] is exactly the similarity matrix of the reduced cohort (an entry counts the variants two

@@ -183,6 +183,15 @@ class PcoaGrmBlockStats(ctypes.Structure):
     ]
 
 
+class PcoaGrmSubsetStats(ctypes.Structure):
+    """pcoa_grm_subset_stats: what pcoa_create_grm_subset did with this engine as its source."""
+    _fields_ = [
+        ("grm_subset_seconds", ctypes.c_double),
+        ("grm_subset_calls", ctypes.c_int64),
+        ("grm_subset_bytes", ctypes.c_int64),
+    ]
+
+
 class PcoaGrmLdStats(ctypes.Structure):
     """pcoa_grm_ld_stats: what the last pcoa_grm_ld_prune did, and the HIP-event time of its kernels."""
     _fields_ = [
@@ -198,6 +207,8 @@ class PcoaGrmLdStats(ctypes.Structure):
 
 PCOA_GRM_DIVISOR_USED = 0
 PCOA_GRM_DIVISOR_PAIRWISE = 1
+PCOA_GRM_SUBSET_PANEL = 0
+PCOA_GRM_SUBSET_STUDY = 1
 PCOA_LOADINGS_CENTRE = 1
 PCOA_LOADINGS_UNIT = 2
 PCOA_LD_MAX_WINDOW = 1024
@@ -263,6 +274,9 @@ _SIGNATURES = [
     ("pcoa_grm_ld_mask", ctypes.c_int, [_vp, _i64, _i64, _vp]),
     ("pcoa_grm_ld_clear", ctypes.c_int, [_vp]),
     ("pcoa_get_grm_ld_stats", ctypes.c_int, [_vp, ctypes.POINTER(PcoaGrmLdStats), ctypes.c_size_t]),
+    ("pcoa_create_grm_subset", ctypes.c_int, [ctypes.POINTER(_vp), _vp, _vp, _i32, _i32]),
+    ("pcoa_grm_rows", ctypes.c_int, [_vp, _i64, _i64, _vp]),
+    ("pcoa_get_grm_subset_stats", ctypes.c_int, [_vp, ctypes.POINTER(PcoaGrmSubsetStats), ctypes.c_size_t]),
     ("pcoa_strip_info", ctypes.c_int, [_vp, ctypes.POINTER(_i32), ctypes.POINTER(_i32)]),
     ("pcoa_strip_col_sums", ctypes.c_int, [_vp, _vp]),
     ("pcoa_strip_matvec", ctypes.c_int, [_vp, _vp, _vp, ctypes.c_double, _vp]),

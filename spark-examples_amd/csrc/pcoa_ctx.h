@@ -14,6 +14,7 @@
 //   capi_grm_project.hip SNP weights of K's axes and the projection of a study store onto them (pcoa_create_grm_study, pcoa_grm_weights / _project)
 //   capi_grm_dense.hip   pcoa_grm_block: a rectangle of K and of the pair counts read out through the fp64 matrix cores
 //   capi_grm_ld.hip      pcoa_grm_ld_*: LD pruning of the resident GRM store by dosage r^2, as a keep mask that enters used_v
+//   capi_grm_subset.hip  pcoa_create_grm_subset: a new GRM ctx over a sample subset of another's store; pcoa_grm_rows reads rows back
 //   capi_subset.hip      pcoa_create_subset: a new engine whose S is S[I, I] of another
 //   capi_pairs.hip       pcoa_similar_pairs: the screen of S for duplicate and related sample pairs
 //   capi_measure.hip     pcoa_set_similarity / pcoa_get_similarity and the centring of a Jaccard / cosine measure
@@ -29,7 +30,7 @@
 
 #include "pcoa_internal.h"
 
-enum TimeCat { T_GRAM = 0, T_DENSIFY, T_SYNTH, T_FINALIZE, T_CENTER, T_TRIDIAG, T_EIG, T_BACK, T_PACK, T_LANCZOS, T_ALLREDUCE, T_OPERATOR, T_SUBSET, T_REDUCE_PEERS, T_PAIRS, T_LOADINGS, T_LD_COUNT, T_LD_BAND, T_LD_RESOLVE, T_LD_COMPACT, T_KING, T_GRM_BLOCK, T_GRM_LD_BAND, T_GRM_LD_RESOLVE, T_GRM_LD_SCAN, T_NCAT };
+enum TimeCat { T_GRAM = 0, T_DENSIFY, T_SYNTH, T_FINALIZE, T_CENTER, T_TRIDIAG, T_EIG, T_BACK, T_PACK, T_LANCZOS, T_ALLREDUCE, T_OPERATOR, T_SUBSET, T_REDUCE_PEERS, T_PAIRS, T_LOADINGS, T_LD_COUNT, T_LD_BAND, T_LD_RESOLVE, T_LD_COMPACT, T_KING, T_GRM_BLOCK, T_GRM_LD_BAND, T_GRM_LD_RESOLVE, T_GRM_LD_SCAN, T_GRM_SUBSET, T_NCAT };
 
 struct EventPair {
   hipEvent_t a, b;
@@ -109,6 +110,7 @@ struct pcoa_ctx {
   int64_t grm_keep_cap = 0;
   bool grm_keep_set = false;
   int64_t grm_ld_rows = 0, grm_ld_cand = 0, grm_ld_kept = 0, grm_ld_pairs = 0;   // the last prune, for pcoa_get_grm_ld_stats
+  int64_t grm_subset_calls = 0, grm_subset_bytes = 0;   // pcoa_create_grm_subset with this ctx as src (pcoa_get_grm_subset_stats)
   int64_t subset_bytes = 0;        // bytes the gathers of pcoa_create_subset moved into this ctx (read + written)
   int64_t pairs_bytes = 0, pairs_calls = 0;   // pcoa_similar_pairs: bytes of S its scan kernels read, calls
   // per-variant loadings (pcoa_loadings_begin .. pcoa_loadings_end, capi_loadings.hip): the prepared vectors stay resident

@@ -333,6 +333,13 @@ hipError_t launch_grm_ld_reach(const int64_t* breaks, int64_t n_breaks, int64_t 
 hipError_t launch_grm_ld_band(const uint32_t* wb, const int32_t* reach, int64_t vc, int32_t n, int32_t window, double t, uint32_t* ex,
                               hipStream_t stream);
 
+// ---- sample subsets of the GRM store (grm_subset.hip): rows x grm_pitch_words(n_src) words -> rows x
+// grm_pitch_words(n_keep) words, slot a of a row = slot keep[a] of the source row, 01 behind n_keep.  keep: n_keep device indices,
+// strictly increasing, inside [0, n_src) (checked by the caller) ----
+int32_t grm_subset_tile_rows();   // rows a lane keeps in flight
+hipError_t launch_grm_subset(const uint32_t* src, int64_t rows, int32_t n_src, const int32_t* keep, int32_t n_keep, uint32_t* dst,
+                             int32_t num_cu, hipStream_t stream);
+
 // ---- centring (center.hip) --------------------------------------------------------------------
 // s = s32 + (s64 ? s64 : 0).  row_sums[n] (fp64), stats[0] = matrix sum, stats[1] = matrix mean,
 // nz[0] = #rows with sum > 0.  b = centred matrix fp64 [n][n].

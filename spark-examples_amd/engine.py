@@ -790,6 +790,45 @@ class PcoaEngine(object):
         self._check(self._lib.pcoa_get_grm_ld_stats(self._ctx, ctypes.byref(q), ctypes.sizeof(q)))
         return dict((f[0], getattr(q, f[0])) for f in L.PcoaGrmLdStats._fields_)
 
+    # ------------------------------------------------------------------ sample subsets of the GRM store
+    def grm_subset(self, keep, study=False):
+        """A new GRM PcoaEngine over the samples `keep` (strictly increasing indices into this engine's samples) whose store is
+        this one's rows with the other samples' columns taken out, gathered on the device (pcoa_create_grm_subset): the engine
+        of the reduced cohort without feeding a variant again.  study=False: as from grm=True (32 samples or more), with this
+        engine's min MAF; study=True: as from grm_study=True (1 sample or more), to be placed by grm_project.  Its counts and
+        weights are its own samples'; an LD mask is not inherited.  This engine is unchanged; the peak is both stores resident."""
+        idx = np.ascontiguousarray(keep, dtype=np.int32)
+        if idx.ndim != 1:
+            raise ValueError("keep must be one-dimensional")
+        ctx = ctypes.c_void_p()
+        kind = L.PCOA_GRM_SUBSET_STUDY if study else L.PCOA_GRM_SUBSET_PANEL
+        self._check(self._lib.pcoa_create_grm_subset(ctypes.byref(ctx), self._ctx, _ptr(idx) if idx.size else None, int(idx.size),
+                                                     int(kind)))
+        sub = object.__new__(PcoaEngine)
+        sub._lib, sub._ctx = self._lib, ctx
+        sub.strip, sub.operator = None, False
+        sub.grm, sub.grm_study = True, bool(study)
+        sub.n = sub.cols = int(idx.size)
+        sub.device = self.device
+        sub._keepalive = []
+        return sub
+
+    def grm_rows(self, first=0, n=None):
+        """uint8 [n, ceil(N / 4)]: the store's rows as .bed rows in the store's coding, which is ref_is_a1=True (pcoa_grm_rows);
+        the unused slots of a row's last byte are 00.  Fed to a fresh engine with ref_is_a1=True they reproduce the store."""
+        if n is None:
+            info = self.grm_info()   # (None: not a GRM engine -- the call itself says so)
+            n = info[0] - int(first) if info else 0
+        out = np.zeros((max(int(n), 0), (self.n + 3) // 4), dtype=np.uint8)
+        self._check(self._lib.pcoa_grm_rows(self._ctx, int(first), int(n), _ptr(out) if out.size else _ptr(np.zeros(1, np.uint8))))
+        return out
+
+    def grm_subset_stats(self):
+        """pcoa_get_grm_subset_stats of the SOURCE engine: grm_subset_seconds / grm_subset_calls / grm_subset_bytes."""
+        q = L.PcoaGrmSubsetStats()
+        self._check(self._lib.pcoa_get_grm_subset_stats(self._ctx, ctypes.byref(q), ctypes.sizeof(q)))
+        return dict((f[0], getattr(q, f[0])) for f in L.PcoaGrmSubsetStats._fields_)
+
     # ------------------------------------------------------------------ per-variant loadings
     def loadings(self, components, eigenvalues=None, centre=True, unit=True):
         """Per-variant loadings of the principal coordinates (pcoa_loadings_begin): `components` [N, k] and `eigenvalues` [k] are

@@ -102,6 +102,13 @@ struct Conf {  // PcaConf / GenomicsConf (GenomicsConf.scala:31-101), same flag 
   bool has_grm_output_divisor = false;
   std::string grm_weights_output_path;  // --grm-weights-output-path FILE: --grm: the SNP weight of every variant on each of the --num-pc axes of K
   std::string grm_project_path;         // --grm-project-path STUDY.bed: --grm: a second PLINK fileset whose samples are placed onto the panel's axes
+  std::string grm_keep_samples;         // --grm-keep-samples FILE: --grm: one sample name per line; the PCA runs on the engine's subset over these samples
+  std::string grm_remove_samples;       // --grm-remove-samples FILE: the same, the file names the samples that are taken out
+  int grm_outlier_iterations = 0;       // --grm-outlier-iterations K: --grm: the rounds of --outlier-iterations with the engine replaced by its
+                                        // pcoa_create_grm_subset over the kept samples
+  double grm_outlier_sigma = 6.0;       // --grm-outlier-sigma X: their threshold
+  bool grm_outlier_sigma_given = false;
+  bool grm_project_removed = false;     // --grm-project-removed: the samples a list or a round removed are placed on the final axes
   int outlier_iterations = 0;           // --outlier-iterations K: up to K rounds of outlier removal around computePca; a round replaces the engine by
                                         // its subset over the kept samples (pcoa_create_subset: one gather of S, no variant read twice).  0 = off
   double outlier_sigma = 6.0;           // --outlier-sigma X: a sample further than X population standard deviations from the mean of an axis goes
@@ -170,6 +177,11 @@ const char* kUsage =
     "                   --grm-output-path PREFIX [--grm-output-divisor used|pairwise] (--grm: the matrix that was decomposed, read out\n"
     "                   band by band: PREFIX.grm.bin (float32 lower triangle with the diagonal), PREFIX.grm.N.bin (jointly called used\n"
     "                   variants per pair) and PREFIX.grm.id, the layout GCTA and PLINK read; used: num / M', pairwise: num / n(i, j))\n"
+    "                   --grm-keep-samples FILE | --grm-remove-samples FILE (--grm: one sample name per line; the PCA runs on the engine's\n"
+    "                   subset over the kept samples, one gather of the 2-bit store, with their own allele frequencies)\n"
+    "                   --grm-outlier-iterations K [--grm-outlier-sigma X, default 6] (--grm: the rounds of --outlier-iterations on subsets\n"
+    "                   of the genotype store; --grm-ld-window prunes every round's engine again)\n"
+    "                   --grm-project-removed (--grm: the samples a list or a round removed are placed on the final axes)\n"
     "                   --grm-ld-window W [--grm-ld-r2 X, default 0.2] [--grm-ld-output-path FILE] (--grm: LD-prune the resident store\n"
     "                   before computePca: forward and greedy, a used variant is removed when a kept one among the W rows before it\n"
     "                   on the same contig has r^2 of the dosages over the jointly called samples above X -- plink's pair statistic,\n"
@@ -275,6 +287,24 @@ Conf parse(int argc, char** argv) {
       c.has_grm_min_maf = true;
       if (v.empty() || *end != 0 || !(c.grm_min_maf >= 0.0 && c.grm_min_maf < 0.5))
         die("--grm-min-maf takes a frequency in [0, 0.5), not '" + v + "'");
+    }
+    else if (a == "--grm-keep-samples") c.grm_keep_samples = one(i);
+    else if (a == "--grm-remove-samples") c.grm_remove_samples = one(i);
+    else if (a == "--grm-project-removed") c.grm_project_removed = true;
+    else if (a == "--grm-outlier-iterations") {
+      const std::string v = one(i);
+      char* end = nullptr;
+      errno = 0;
+      const long k = std::strtol(v.c_str(), &end, 10);
+      if (v.empty() || *end != 0 || errno != 0 || k > 1000000 || k < -1000000) die("--grm-outlier-iterations takes an integer >= 0 (0 = off), not '" + v + "'");
+      c.grm_outlier_iterations = (int)k;
+    }
+    else if (a == "--grm-outlier-sigma") {
+      const std::string v = one(i);
+      char* end = nullptr;
+      c.grm_outlier_sigma = std::strtod(v.c_str(), &end);
+      c.grm_outlier_sigma_given = true;
+      if (v.empty() || *end != 0) die("--grm-outlier-sigma (the threshold of --grm-outlier-iterations) takes a number, not '" + v + "'");
     }
     else if (a == "--outlier-iterations") {   // a value that does not parse must not silently mean "off"
       const std::string v = one(i);
@@ -411,6 +441,20 @@ Conf parse(int argc, char** argv) {
     if (!c.grm && !c.grm_ld_output_path.empty()) die(std::string("--grm-ld-output-path") + why);
     if (c.grm_ld_window == 0 && c.grm_ld_r2_given) die("--grm-ld-r2 needs --grm-ld-window W (the pruning is off without it)");
     if (c.grm_ld_window == 0 && !c.grm_ld_output_path.empty()) die("--grm-ld-output-path needs --grm-ld-window W (the pruning is off without it)");
+  }
+  {
+    const char* why = " needs --grm (it subsets the genotype store of the standardised-genotype PCA; a stored similarity matrix is subset by "
+                      "--outlier-iterations / --remove-related)";
+    if (!c.grm && !c.grm_keep_samples.empty()) die(std::string("--grm-keep-samples") + why);
+    if (!c.grm && !c.grm_remove_samples.empty()) die(std::string("--grm-remove-samples") + why);
+    if (!c.grm && c.grm_outlier_iterations != 0) die(std::string("--grm-outlier-iterations") + why);
+    if (!c.grm && c.grm_outlier_sigma_given) die(std::string("--grm-outlier-sigma") + why);
+    if (!c.grm && c.grm_project_removed) die(std::string("--grm-project-removed") + why);
+    if (!c.grm_keep_samples.empty() && !c.grm_remove_samples.empty())
+      die("--grm-keep-samples and --grm-remove-samples exclude each other (one list names the cohort)");
+    if (c.grm_outlier_iterations < 0) die("--grm-outlier-iterations must be >= 0 (0 = off)");
+    if (!(c.grm_outlier_sigma > 0) || !std::isfinite(c.grm_outlier_sigma))
+      die("--grm-outlier-sigma must be a finite number > 0 (the threshold of --grm-outlier-iterations)");
   }
   if (c.has_grm_output_divisor && c.grm_output_divisor != "used" && c.grm_output_divisor != "pairwise")
     die("--grm-output-divisor takes used or pairwise, not '" + c.grm_output_divisor + "'");
@@ -1797,6 +1841,38 @@ void check_grm_study(const std::string& panel_path, const std::string& study_pat
       die("--grm --grm-project-path: the study sample '" + t[1] + "' of " + study + ".fam repeats a sample name of the panel");
 }
 
+// --grm-keep-samples / --grm-remove-samples, before any engine exists: names are the fileset's sample names in index order.
+// Returns false without a list, else *kept = the kept indices, increasing.  An unknown or repeated name is refused.
+bool grm_sample_list(const Conf& conf, const std::vector<std::string>& names, std::vector<int32_t>* kept) {
+  const bool keeping = !conf.grm_keep_samples.empty();
+  const std::string flag = keeping ? "--grm-keep-samples" : "--grm-remove-samples";
+  const std::string& path = keeping ? conf.grm_keep_samples : conf.grm_remove_samples;
+  if (path.empty()) return false;
+  std::unordered_map<std::string, int32_t> index;
+  for (size_t i = 0; i < names.size(); ++i) index[names[i]] = (int32_t)i;
+  std::ifstream in(path);
+  if (!in) die(flag + ": cannot read " + path);
+  std::vector<char> listed(names.size(), 0);
+  std::string line;
+  while (std::getline(in, line)) {
+    const size_t a = line.find_first_not_of(" \t\r\n"), b = line.find_last_not_of(" \t\r\n");
+    if (a == std::string::npos) continue;
+    const std::string name = line.substr(a, b - a + 1);
+    const auto it = index.find(name);
+    if (it == index.end()) die("--grm " + flag + ": '" + name + "' of " + path + " is not a sample of the fileset");
+    if (listed[(size_t)it->second]) die("--grm " + flag + ": '" + name + "' is listed twice in " + path);
+    listed[(size_t)it->second] = 1;
+  }
+  kept->clear();
+  for (size_t i = 0; i < names.size(); ++i)
+    if ((listed[i] != 0) == keeping) kept->push_back((int32_t)i);
+  const int32_t least = std::max(32, conf.num_pc + 1);
+  if ((int32_t)kept->size() < least)
+    die("--grm " + flag + " leaves " + std::to_string(kept->size()) + " of " + std::to_string(names.size()) + " samples, fewer than the " +
+        std::to_string(least) + " a GRM engine with " + std::to_string(conf.num_pc) + " principal components needs");
+  return true;
+}
+
 // --grm-project-path: the study's kept .bed rows into a GRM study store, block by block, and its samples onto the panel's axes.
 // comps / lam: what pcoa_compute returned on the panel.  Returns the study's rows in .fam order; *called_share: the mean over
 // the samples of (used variants at which the sample is called) / (used variants)
@@ -1885,6 +1961,9 @@ int main(int argc, char** argv) {
     ids = plink.ids;
     names = plink.names;
   }
+  std::vector<int32_t> grm_listed;   // --grm-keep-samples / --grm-remove-samples: the kept indices; a wrong list is refused here
+  const bool grm_has_list = conf.grm && grm_sample_list(conf, names, &grm_listed);
+  const bool grm_rounds = conf.grm && (grm_has_list || conf.grm_outlier_iterations > 0);
   // A single VCF is streamed as well (r05): the header gives the callsets, then every 16-MiB block is parsed by the thread
   // pool, filtered (--references, --min-allele-frequency) and handed to the engine as carrier lists while the next one is
   // read -- the records of the whole file are never held (VariantsRDD.compute is an iterator, rdd/VariantsRDD.scala:205-235).
@@ -2245,30 +2324,36 @@ int main(int argc, char** argv) {
   if (stream_plink) fed_meta = plink.meta;                 // one engine: every kept line, in file order
   if (stream_join || data.size() > 1) fed_meta_known = false;
   for (pcoa_ctx* o : owners) check(o, pcoa_gram_finalize(o), "getSimilarityMatrix");
-  if (conf.grm) {
+  // --grm: what the engine will decompose (again after every subset, for the reduced cohort)
+  auto grm_report = [&](pcoa_ctx* eng) {
     int64_t variants = 0, used = 0, store = 0;
-    check(ctx, pcoa_grm_set_min_maf(ctx, conf.grm_min_maf), "pcoa_grm_set_min_maf");
-    if (pcoa_grm_info(ctx, &variants, &used, &store) != 1) die(std::string("pcoa_grm_info: ") + pcoa_last_error(ctx));
+    if (pcoa_grm_info(eng, &variants, &used, &store) != 1) die(std::string("pcoa_grm_info: ") + pcoa_last_error(eng));
     std::fprintf(stderr, "Standardised genotypes: %lld of %lld variants used (min MAF %g), store %lld bytes\n", (long long)used,
                  (long long)variants, conf.grm_min_maf, (long long)store);
-    if (conf.grm_ld_window > 0) {   // --grm-ld-window: the resident store is pruned, a break in front of the first variant of every new contig
+  };
+  // --grm-ld-window: the resident store is pruned, a break in front of the first variant of every new contig (with
+  // --grm-keep-samples / --grm-remove-samples / --grm-outlier-iterations: every round's engine, whose frequencies name the candidates)
+  auto grm_ld_prune_now = [&](pcoa_ctx* eng) {
+    int64_t variants = 0;
+    if (pcoa_grm_info(eng, &variants, nullptr, nullptr) != 1) die(std::string("pcoa_grm_info: ") + pcoa_last_error(eng));
+    {
       const bool known = fed_meta_known && (int64_t)fed_meta.size() == variants;
       std::vector<int64_t> breaks;
       if (known)
         for (int64_t v = 1; v < variants; ++v)
           if (fed_meta[(size_t)v].contig != fed_meta[(size_t)v - 1].contig) breaks.push_back(v);
       int64_t cand = 0, kept = 0;
-      check(ctx, pcoa_grm_ld_prune(ctx, conf.grm_ld_window, conf.grm_ld_r2, breaks.empty() ? nullptr : breaks.data(), (int64_t)breaks.size(),
+      check(eng, pcoa_grm_ld_prune(eng, conf.grm_ld_window, conf.grm_ld_r2, breaks.empty() ? nullptr : breaks.data(), (int64_t)breaks.size(),
                                    &cand, &kept), "pcoa_grm_ld_prune");
       std::printf("GRM LD pruning: kept %lld of %lld candidate variants (%lld in the store), window %d, r2 %g\n", (long long)kept,
                   (long long)cand, (long long)variants, conf.grm_ld_window, conf.grm_ld_r2);
       pcoa_grm_ld_stats gs;
-      check(ctx, pcoa_get_grm_ld_stats(ctx, &gs, sizeof(gs)), "pcoa_get_grm_ld_stats");
+      check(eng, pcoa_get_grm_ld_stats(eng, &gs, sizeof(gs)), "pcoa_get_grm_ld_stats");
       std::fprintf(stderr, "GRM LD pruning: %lld pairs; band %.3f ms, resolve %.3f ms, scan %.3f ms\n", (long long)gs.grm_ld_pairs,
                    1e3 * gs.grm_ld_band_seconds, 1e3 * gs.grm_ld_resolve_seconds, 1e3 * gs.grm_ld_scan_seconds);
       if (!conf.grm_ld_output_path.empty()) {
         std::vector<uint8_t> keep((size_t)std::max<int64_t>(variants, 1));
-        check(ctx, pcoa_grm_ld_mask(ctx, 0, variants, keep.data()), "pcoa_grm_ld_mask");
+        check(eng, pcoa_grm_ld_mask(eng, 0, variants, keep.data()), "pcoa_grm_ld_mask");
         std::ofstream out(conf.grm_ld_output_path);
         for (int64_t v = 0; v < variants; ++v) {
           if (known) out << v << "\t" << fed_meta[(size_t)v].contig << "\t" << fed_meta[(size_t)v].pos << "\t" << fed_meta[(size_t)v].id;
@@ -2278,6 +2363,11 @@ int main(int argc, char** argv) {
         if (!out) die("cannot write " + conf.grm_ld_output_path);
       }
     }
+  };
+  if (conf.grm) {
+    check(ctx, pcoa_grm_set_min_maf(ctx, conf.grm_min_maf), "pcoa_grm_set_min_maf");
+    grm_report(ctx);
+    if (conf.grm_ld_window > 0 && !grm_rounds) grm_ld_prune_now(ctx);
   }
   if (g_ld.on) {
     pcoa_ld_stats ls;
@@ -2454,7 +2544,61 @@ int main(int argc, char** argv) {
                  java_double(conf.king_cutoff).c_str(), gone.size(), gone_names.c_str());
     drop_samples(gone, "--king-remove", "--king-cutoff");
   }
-  if (!strips.empty()) {
+  pcoa_ctx* const grm_full = conf.grm ? ctx : nullptr;   // the engine of the whole fileset (--grm-project-removed subsets it once more)
+  // pcoa_create_grm_subset of src (n_src samples) over keep, and the stderr lines: what was gathered and, for a panel, what the
+  // reduced cohort's engine will decompose
+  auto grm_subset = [&](pcoa_ctx* src, int32_t n_src, const std::vector<int32_t>& keep, int32_t kind) {
+    pcoa_grm_subset_stats s0, s1;
+    check(src, pcoa_get_grm_subset_stats(src, &s0, sizeof(s0)), "pcoa_get_grm_subset_stats");
+    pcoa_ctx* sub = nullptr;
+    check(src, pcoa_create_grm_subset(&sub, src, keep.data(), (int32_t)keep.size(), kind), "pcoa_create_grm_subset");
+    check(src, pcoa_get_grm_subset_stats(src, &s1, sizeof(s1)), "pcoa_get_grm_subset_stats");
+    std::fprintf(stderr, "GRM subset: kept %zu of %d samples, %lld bytes gathered\n", keep.size(), n_src,
+                 (long long)(s1.grm_subset_bytes - s0.grm_subset_bytes));
+    if (kind == PCOA_GRM_SUBSET_PANEL) grm_report(sub);
+    return sub;
+  };
+  // the cohort's engine is replaced; the whole fileset's stays while --grm-project-removed needs it
+  auto grm_replace = [&](pcoa_ctx* sub) {
+    if (ctx != grm_full || !conf.grm_project_removed) pcoa_destroy(ctx);
+    ctx = owners[0] = sub;
+  };
+  if (grm_rounds) {
+    // --grm-keep-samples / --grm-remove-samples, then the loop of --outlier-iterations below with pcoa_create_grm_subset in
+    // pcoa_create_subset's place and the smallest cohort a GRM engine takes
+    if (grm_has_list) {
+      grm_replace(grm_subset(ctx, n, grm_listed, PCOA_GRM_SUBSET_PANEL));
+      kept = grm_listed;
+    }
+    for (int done = 0;;) {
+      const int32_t m = (int32_t)kept.size();
+      if (conf.grm_ld_window > 0) grm_ld_prune_now(ctx);
+      check(ctx, pcoa_compute(ctx, conf.num_pc, comps.data(), lam.data(), &nonzero), "computePca");
+      if (done == conf.grm_outlier_iterations) break;
+      const std::vector<char> removed = outlier_rule(comps.data(), conf.num_pc, m, conf.grm_outlier_sigma);
+      std::vector<int32_t> keep, kept_next;
+      std::string gone_names;
+      for (int32_t a = 0; a < m; ++a) {
+        if (removed[(size_t)a]) {
+          gone_names += (gone_names.empty() ? ": " : ", ") + names[(size_t)kept[(size_t)a]];
+        } else {
+          keep.push_back(a);
+          kept_next.push_back(kept[(size_t)a]);
+        }
+      }
+      const int32_t gone = m - (int32_t)keep.size();
+      std::fprintf(stderr, "Outlier round %d: removed %d sample(s)%s\n", done + 1, gone, gone_names.c_str());
+      if (gone == 0) break;
+      const int32_t least = std::max(32, conf.num_pc + 1);
+      if ((int32_t)keep.size() < least)
+        die("--grm-outlier-iterations: round " + std::to_string(done + 1) + " would leave " + std::to_string(keep.size()) + " of " +
+            std::to_string(m) + " samples, fewer than the " + std::to_string(least) + " a GRM engine with " + std::to_string(conf.num_pc) +
+            " principal components needs; raise --grm-outlier-sigma");
+      grm_replace(grm_subset(ctx, m, keep, PCOA_GRM_SUBSET_PANEL));
+      kept.swap(kept_next);
+      ++done;
+    }
+  } else if (!strips.empty()) {
     check(ctx, pcoa_compute_strips(owners.data(), (int32_t)owners.size(), conf.num_pc, comps.data(), lam.data(), &nonzero), "computePca");
   } else {
     // --outlier-iterations K: computePca, the rule, and while something is removed and fewer than K rounds have removed
@@ -2508,6 +2652,34 @@ int main(int argc, char** argv) {
     rows.insert(rows.end(), study_rows.begin(), study_rows.end());
     n_study = study_rows.size();
   }
+  if (conf.grm && conf.grm_project_removed) {
+    // every sample of the fileset that is not in the final cohort: one study subset of the ORIGINAL engine on the final axes
+    std::vector<int32_t> gone;
+    size_t k = 0;
+    for (int32_t i = 0; i < n; ++i) {
+      if (k < kept.size() && kept[k] == i) ++k;
+      else gone.push_back(i);
+    }
+    if (!gone.empty()) {
+      const int32_t nq = (int32_t)gone.size();
+      pcoa_ctx* study = grm_subset(grm_full, n, gone, PCOA_GRM_SUBSET_STUDY);
+      std::vector<double> coords((size_t)conf.num_pc * (size_t)nq);
+      std::vector<int32_t> called((size_t)nq);
+      check(ctx, pcoa_grm_project(ctx, study, conf.num_pc, comps.data(), lam.data(), coords.data(), called.data()), "pcoa_grm_project");
+      pcoa_destroy(study);
+      int64_t used = 0, total_called = 0;
+      if (pcoa_grm_info(ctx, nullptr, &used, nullptr) != 1) die(std::string("pcoa_grm_info: ") + pcoa_last_error(ctx));
+      for (int32_t c : called) total_called += c;
+      std::fprintf(stderr, "Projected %d removed samples over %lld used variants (mean call share %.4f)\n", nq, (long long)used,
+                   (double)total_called / (double)nq / (double)used);
+      for (int32_t q = 0; q < nq; ++q) {
+        const size_t i = (size_t)gone[(size_t)q];
+        rows.push_back({names[i], ids[i].substr(0, ids[i].find('-')), coords[(size_t)q], coords[(size_t)q + (size_t)nq]});
+      }
+      n_study += gone.size();
+    }
+    if (grm_full != ctx) pcoa_destroy(grm_full);
+  }
   emit_result(conf, rows, n_study);
 
   // --grm-weights-output-path: the left singular vectors of the standardised genotype matrix, one line per variant of the store
@@ -2537,8 +2709,8 @@ int main(int argc, char** argv) {
     std::vector<int32_t> nb;
     std::vector<float> line;
     long long written = 0;
-    for (int32_t r0 = 0; r0 < n; r0 += band) {
-      const int32_t r = std::min(band, n - r0), cols = r0 + r;
+    for (int32_t r0 = 0; r0 < n_out; r0 += band) {
+      const int32_t r = std::min(band, n_out - r0), cols = r0 + r;
       kb.resize((size_t)r * (size_t)cols);
       nb.resize((size_t)r * (size_t)cols);
       check(ctx, pcoa_grm_block(ctx, r0, r, 0, cols, divisor, kb.data(), nb.data(), 0), "pcoa_grm_block");
@@ -2553,11 +2725,14 @@ int main(int argc, char** argv) {
       }
     }
     std::ofstream fi(conf.grm_output_path + ".grm.id");
-    for (int32_t i = 0; i < n; ++i) fi << ids[(size_t)i].substr(0, ids[(size_t)i].find('-')) << "\t" << names[(size_t)i] << "\n";
+    for (int32_t a = 0; a < n_out; ++a) {   // the final cohort's samples, in the engine's index order
+      const size_t i = (size_t)kept[(size_t)a];
+      fi << ids[i].substr(0, ids[i].find('-')) << "\t" << names[i] << "\n";
+    }
     if (!fk || !fn || !fi) die("cannot write " + conf.grm_output_path + ".grm.*");
     int64_t used = 0;
     if (pcoa_grm_info(ctx, nullptr, &used, nullptr) != 1) die(std::string("pcoa_grm_info: ") + pcoa_last_error(ctx));
-    std::fprintf(stderr, "GRM written: %d samples, %lld used variants, divisor %s, %lld bytes\n", n, (long long)used,
+    std::fprintf(stderr, "GRM written: %d samples, %lld used variants, divisor %s, %lld bytes\n", n_out, (long long)used,
                  divisor == PCOA_GRM_DIVISOR_PAIRWISE ? "pairwise" : "used", written);
   }
 

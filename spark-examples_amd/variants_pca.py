@@ -587,6 +587,24 @@ class PcaConf(object):
         p.add_argument("--grm-ld-output-path", type=str, default=None,
                        help="--grm-ld-window: one line per variant of the store in feed order -- 0-based index, contig, "
                             "position, variant id, 1 (kept) or 0, tab-separated (the columns of --ld-output-path)")
+        p.add_argument("--grm-keep-samples", type=str, default=None,
+                       help="--grm: a file with one sample name per line (the names of PREFIX.grm.id's second column): the "
+                            "fileset is streamed once into the engine and the PCA runs on these samples only, on the engine's "
+                            "subset over them (pcoa_create_grm_subset: one gather of the 2-bit store; the allele frequencies are "
+                            "those of the kept samples).  Excludes --grm-remove-samples")
+        p.add_argument("--grm-remove-samples", type=str, default=None,
+                       help="--grm: as --grm-keep-samples, the file names the samples that are taken out")
+        p.add_argument("--grm-outlier-iterations", type=int, default=0,
+                       help="--grm: K > 0: up to K rounds of outlier removal around computePca (smartpca's loop, the rule of "
+                            "--outlier-iterations): the engine is replaced by its subset over the kept samples, whose allele "
+                            "frequencies standardise the next round; --grm-ld-window prunes every round's engine again.  Rows "
+                            "go out for the kept samples only")
+        p.add_argument("--grm-outlier-sigma", type=float, default=None,
+                       help="--grm-outlier-iterations: the threshold, in population standard deviations of an axis (default %g)"
+                            % GRM_OUTLIER_SIGMA)
+        p.add_argument("--grm-project-removed", action="store_true",
+                       help="--grm: every sample a list or an outlier round removed is placed on the final axes "
+                            "(pcoa_grm_project over a study subset of the whole fileset's engine); its rows follow the kept samples'")
         p.add_argument("--grm-output-divisor", type=str, default=None,
                        help="--grm-output-path: used (default): num / M', the mean-imputed K that is decomposed; pairwise: "
                             "num / n(i, j), the pairwise-complete estimator GCTA-style tools store")
@@ -676,6 +694,8 @@ class PcaConf(object):
 
 
 RELATED_MAX_PAIRS = 1 << 20   # default of --related-max-pairs
+GRM_OUTLIER_SIGMA = 6.0       # default of --grm-outlier-sigma
+GRM_MIN_COHORT = 32           # a GRM engine's computePca is the Lanczos iteration, which starts at 32 samples
 
 
 def java_float_to_string(f):
@@ -1175,12 +1195,27 @@ def check_grm_conf(conf):
                              "standardised genotypes; the shared counts S go to --dump-similarity)")
         if conf.grm_output_divisor is not None:
             raise SystemExit("VariantsPcaDriver: --grm-output-divisor needs --grm (and --grm-output-path)")
+        for given, flag in ((bool(conf.grm_keep_samples), "--grm-keep-samples"), (bool(conf.grm_remove_samples), "--grm-remove-samples"),
+                            (conf.grm_outlier_iterations != 0, "--grm-outlier-iterations"),
+                            (conf.grm_outlier_sigma is not None, "--grm-outlier-sigma"),
+                            (conf.grm_project_removed, "--grm-project-removed")):
+            if given:
+                raise SystemExit("VariantsPcaDriver: %s needs --grm (it subsets the genotype store of the standardised-genotype PCA; "
+                                 "a stored similarity matrix is subset by --outlier-iterations / --remove-related)" % flag)
         for given, flag in ((conf.grm_ld_window != 0, "--grm-ld-window"), (conf.grm_ld_r2 is not None, "--grm-ld-r2"),
                             (bool(conf.grm_ld_output_path), "--grm-ld-output-path")):
             if given:
                 raise SystemExit("VariantsPcaDriver: %s needs --grm (it prunes the genotype store of the standardised-genotype "
                                  "PCA; the carrier counts S are pruned by --ld-window)" % flag)
         return
+    if conf.grm_keep_samples and conf.grm_remove_samples:
+        raise SystemExit("VariantsPcaDriver: --grm-keep-samples and --grm-remove-samples exclude each other (one list names the cohort)")
+    if conf.grm_outlier_iterations < 0:
+        raise SystemExit("VariantsPcaDriver: --grm-outlier-iterations must be >= 0 (0 = off)")
+    if conf.grm_outlier_sigma is None:
+        conf.grm_outlier_sigma = GRM_OUTLIER_SIGMA
+    if not (conf.grm_outlier_sigma > 0 and np.isfinite(conf.grm_outlier_sigma)):
+        raise SystemExit("VariantsPcaDriver: --grm-outlier-sigma must be a finite number > 0 (the threshold of --grm-outlier-iterations)")
     if conf.grm_ld_window == 0:
         if conf.grm_ld_r2 is not None:
             raise SystemExit("VariantsPcaDriver: --grm-ld-r2 needs --grm-ld-window W (the pruning is off without it)")
@@ -1392,6 +1427,113 @@ def grm_accumulate(call_rdd, matrix_size, min_maf, device=0, err=None):
     (err or sys.stderr).write("Standardised genotypes: %d of %d variants used (min MAF %g), store %d bytes\n"
                               % (used, variants, min_maf, store))
     return eng
+
+
+def grm_sample_list(conf, names):
+    """--grm-keep-samples / --grm-remove-samples, before any engine exists: `names` are the fileset's sample names in index
+    order.  Returns the kept indices (increasing), or None without a list.  An unknown or repeated name is refused."""
+    flag, path = ("--grm-keep-samples", conf.grm_keep_samples) if conf.grm_keep_samples else ("--grm-remove-samples", conf.grm_remove_samples)
+    if not path:
+        return None
+    index = dict((name, i) for i, name in enumerate(names))
+    try:
+        with open(path) as f:
+            listed = [ln.strip() for ln in f if ln.strip()]
+    except IOError as e:
+        raise SystemExit("VariantsPcaDriver: %s: cannot read %s (%s)" % (flag, path, e.strerror))
+    seen = set()
+    for name in listed:
+        if name not in index:
+            raise SystemExit("VariantsPcaDriver: --grm %s: '%s' of %s is not a sample of the fileset" % (flag, name, path))
+        if name in seen:
+            raise SystemExit("VariantsPcaDriver: --grm %s: '%s' is listed twice in %s" % (flag, name, path))
+        seen.add(name)
+    picked = np.array(sorted(index[name] for name in listed), dtype=np.int64)
+    kept = picked if conf.grm_keep_samples else np.setdiff1d(np.arange(len(names)), picked)
+    least = max(GRM_MIN_COHORT, conf.numPc + 1)
+    if kept.size < least:
+        raise SystemExit("VariantsPcaDriver: --grm %s leaves %d of %d samples, fewer than the %d a GRM engine with %d principal "
+                         "components needs" % (flag, kept.size, len(names), least, conf.numPc))
+    return kept
+
+
+def grm_subset_engine(src, keep, min_maf, study=False, err=None):
+    """pcoa_create_grm_subset of `src` over its samples `keep`, and the stderr lines: what was gathered, and (a panel) what the
+    reduced cohort's engine will decompose."""
+    err = err or sys.stderr
+    before = src.grm_subset_stats()["grm_subset_bytes"]
+    sub = src.grm_subset(keep, study=study)
+    err.write("GRM subset: kept %d of %d samples, %d bytes gathered\n"
+              % (len(keep), src.n, src.grm_subset_stats()["grm_subset_bytes"] - before))
+    if not study:
+        variants, used, store = sub.grm_info()
+        err.write("Standardised genotypes: %d of %d variants used (min MAF %g), store %d bytes\n" % (used, variants, min_maf, store))
+    return sub
+
+
+def grm_compute_rounds(driver, full, kept, meta, err=None):
+    """computePca of --grm around --grm-keep-samples / --grm-remove-samples (`kept`: the list's indices, or None) and
+    --grm-outlier-iterations K: the loop of computePcaOutlierRounds with the engine replaced by its grm_subset over the kept
+    samples; --grm-ld-window prunes every round's engine, because the candidates follow the cohort's frequencies.  `full`, the
+    engine of the whole fileset, is closed as soon as it is replaced unless --grm-project-removed needs it.  Returns (rows of
+    the kept samples, the final engine, their original indices); driver.engine and driver.last_pca follow."""
+    conf, err = driver.conf, err or sys.stderr
+    if conf.numPc < 2:
+        raise IndexError("computePca emits exactly PC1 and PC2 (VariantsPca.scala:229-230); --num-pc must be >= 2")
+    min_maf = conf.grm_min_maf or 0.0
+    reverse = dict((v, k) for (k, v) in driver.indexes.items())
+    eng = full
+
+    def replace(sub):
+        if eng is not full or not conf.grm_project_removed:
+            eng.close()
+        driver.engine = sub
+        return sub
+
+    if kept is None:
+        kept = np.arange(len(driver.indexes))
+    else:
+        eng = replace(grm_subset_engine(eng, kept, min_maf, err=err))
+    done, iterations, sigma = 0, conf.grm_outlier_iterations, conf.grm_outlier_sigma
+    while True:
+        if conf.grm_ld_window:
+            grm_ld_prune(conf, eng, meta)
+        comps, lam, nonzero = eng.compute(conf.numPc)
+        if done == iterations:
+            break
+        removed = outlier_rule(comps.T, sigma)
+        gone = kept[removed]
+        err.write("Outlier round %d: removed %d sample(s)%s\n"
+                  % (done + 1, gone.size, (": " + ", ".join(driver.names[reverse[int(i)]] for i in gone)) if gone.size else ""))
+        if gone.size == 0:
+            break
+        least = max(GRM_MIN_COHORT, conf.numPc + 1)
+        if kept.size - gone.size < least:
+            raise SystemExit("VariantsPcaDriver: --grm-outlier-iterations: round %d would leave %d of %d samples, fewer than the "
+                             "%d a GRM engine with %d principal components needs; raise --grm-outlier-sigma"
+                             % (done + 1, kept.size - gone.size, kept.size, least, conf.numPc))
+        eng = replace(grm_subset_engine(eng, np.nonzero(~removed)[0], min_maf, err=err))
+        kept = kept[~removed]
+        done += 1
+    driver.last_pca = (comps, lam)
+    print("Non zero rows in matrix: %d / %d." % (nonzero, kept.size))  # :208, once, for the final cohort
+    return [(reverse[int(i)], float(comps[a, 0]), float(comps[a, 1])) for a, i in enumerate(kept)], eng, kept
+
+
+def grm_project_removed(driver, full, eng, kept, err=None):
+    """--grm-project-removed: the samples of the whole fileset that are not in the final cohort, as one study subset of the
+    ORIGINAL engine, on the final panel's axes.  Returns [(callset id, name, pc1, pc2)] in index order."""
+    removed = np.setdiff1d(np.arange(len(driver.indexes)), kept)
+    if removed.size == 0:
+        return []
+    comps, lam = driver.last_pca
+    with grm_subset_engine(full, removed, 0.0, study=True, err=err) as study:
+        coords, called = eng.grm_project(study, comps, lam)
+    used = eng.grm_info()[1]
+    (err or sys.stderr).write("Projected %d removed samples over %d used variants (mean call share %.4f)\n"
+                              % (removed.size, used, float(called.mean()) / used))
+    reverse = dict((v, k) for (k, v) in driver.indexes.items())
+    return [(reverse[int(i)], driver.names[reverse[int(i)]], float(coords[q, 0]), float(coords[q, 1])) for q, i in enumerate(removed)]
 
 
 def grm_ld_prune(conf, eng, meta, out=None):
@@ -1868,6 +2010,10 @@ def main(args):
     # (contig, position, id) per row, recorded only with a flag that needs them (--ld-window: the contigs place the breaks)
     variant_meta = [] if conf.loadings_output_path or conf.ld_window or conf.grm_weights_output_path or conf.grm_ld_window else None
     indexes, names, data = load_dataset(conf, variant_meta)
+    grm_order, grm_listed = None, None
+    if conf.grm:   # --grm-keep-samples / --grm-remove-samples: a wrong list is refused before anything is printed or any engine exists
+        grm_order = sorted(indexes.items(), key=lambda kv: kv[1])   # the engine's index order: the .fam's
+        grm_listed = grm_sample_list(conf, [names[cid] for cid, _ in grm_order])
     driver = VariantsPcaDriver(conf, indexes, names, data)
     filtered = [driver.filterDataset(d) for d in driver.data]
     calls_rdd = driver.getCallsRdd(filtered, variant_meta)
@@ -1884,18 +2030,25 @@ def main(args):
         return engine
 
     if conf.grm:
-        driver.engine = grm_accumulate(calls_rdd, n, conf.grm_min_maf or 0.0, device=conf.gpu)
-        if conf.grm_ld_window:
-            grm_ld_prune(conf, driver.engine, variant_meta)
-        result = driver.computePca(driver.engine)
+        order, listed = grm_order, grm_listed
+        full = driver.engine = grm_accumulate(calls_rdd, n, conf.grm_min_maf or 0.0, device=conf.gpu)
+        if listed is None and conf.grm_outlier_iterations == 0:
+            if conf.grm_ld_window:
+                grm_ld_prune(conf, driver.engine, variant_meta)
+            result, kept = driver.computePca(driver.engine), np.arange(n)
+        else:
+            result, _, kept = grm_compute_rounds(driver, full, listed, variant_meta)
         comps, lam = driver.last_pca
-        study = grm_project_study(conf, driver.engine, comps, lam) if conf.grm_project_path else None
-        driver.emitResult(result, study=study)
+        study = grm_project_study(conf, driver.engine, comps, lam) if conf.grm_project_path else []
+        if conf.grm_project_removed:
+            study = study + grm_project_removed(driver, full, driver.engine, kept)
+            if full is not driver.engine:
+                full.close()
+        driver.emitResult(result, study=study or None)
         if conf.grm_weights_output_path:
             write_loadings(conf.grm_weights_output_path, variant_meta, driver.engine.grm_weights(comps, lam, scaled=True))
         if conf.grm_output_path:
-            order = sorted(driver.indexes.items(), key=lambda kv: kv[1])   # the engine's index order: the .fam's
-            grm_write_output(conf, driver.engine, [(cid.split("-")[0], driver.names[cid]) for cid, _ in order])
+            grm_write_output(conf, driver.engine, [(order[int(i)][0].split("-")[0], driver.names[order[int(i)][0]]) for i in kept])
         driver.reportIoStats(sys.stderr)
         driver.stop()
         return 0
