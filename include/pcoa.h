@@ -35,7 +35,7 @@ extern "C" {
 #endif
 
 #define PCOA_VERSION_MAJOR 0
-#define PCOA_VERSION_MINOR 14
+#define PCOA_VERSION_MINOR 15
 
 typedef struct pcoa_ctx pcoa_ctx;
 
@@ -400,7 +400,7 @@ int pcoa_grm_project(pcoa_ctx* panel, pcoa_ctx* study, int32_t num_pc, const dou
  *   memory: rows * cols doubles, plus as many int32 where the pair counts are needed (out_pairs given, or PAIRWISE), in one
  *           lazily grown buffer of the ctx; a device output is used directly instead.  PCOA_ERR_OUT_OF_MEMORY leaves the ctx
  *           usable.
- * Not built: a relatedness cut-off on K, fp32 / bf16 approximations, multi-GPU, a compressed writer, JNI / Scala natives. */
+ * Not built: fp32 / bf16 approximations, multi-GPU, a compressed writer, JNI / Scala natives. */
 #define PCOA_GRM_DIVISOR_USED 0
 #define PCOA_GRM_DIVISOR_PAIRWISE 1
 int pcoa_grm_block(pcoa_ctx* ctx, int32_t row0, int32_t rows, int32_t col0, int32_t cols, int32_t divisor,
@@ -415,6 +415,48 @@ typedef struct pcoa_grm_block_stats {
   double grm_block_flops;     /* 2 * rows * cols * V per float pass launched (num; n where the pair counts are needed)        */
 } pcoa_grm_block_stats;
 int pcoa_get_grm_block_stats(pcoa_ctx* ctx, pcoa_grm_block_stats* out, size_t out_size);
+
+/* ---- the relatedness cut-off on K ----------------------------------------------------------------------------
+ * gcta --grm-cutoff and plink --rel-cutoff find the pairs of samples whose relationship exceeds a threshold.  pcoa_grm_pairs
+ * screens the upper triangle of K on the device, a band of rows at a time, and returns only the pairs: no N x N matrix leaves
+ * the device.  The rule, with K(i, j) EXACTLY the bits pcoa_grm_block returns for the same ctx, min_maf, keep mask and divisor:
+ *   the pair (i, j), i < j, is REPORTED iff K(i, j) >= cutoff
+ * one fp64 comparison on the value already divided (variants_pca.py's grm_pairs_rule is the numpy statement).  Pairs come out
+ * in increasing (i, j) order, written in order and not sorted.  Content and order are a function of the store, min_maf, the LD
+ * keep mask, the divisor and the cutoff alone: not of band_rows, the grid, the CU count or the sizes of the accumulate calls.
+ *   band_rows: rows of K held at a time, a multiple of 64; 0 = 1,024.  The band [r0, r0 + band_rows) x [64 floor(r0 / 64), N) is
+ *           computed by pcoa_grm_block's kernels into the ctx's workspace, then counted, scanned and written (csrc/grm_pairs.hip);
+ *           one launch chain per band, no host synchronisation between bands.
+ *   out_pairs / capacity / *n_found_out: as pcoa_similar_pairs -- the first min(n_found, capacity) pairs, entries behind them
+ *           untouched; capacity 0 is the count-only call; *n_found_out is always the full count.
+ *   a pair's n: n(i, j) under PCOA_GRM_DIVISOR_PAIRWISE, M' under PCOA_GRM_DIVISOR_USED.
+ *   out_diag: N doubles or NULL: K(i, i) under the same divisor (the band holds its diagonal tiles).
+ * Synchronising.  Nothing writes the store; the ctx computes the same bits afterwards.
+ *   PCOA_ERR_INVALID_ARG, found on the host before any device work: ctx NULL (pcoa_last_error(NULL)), n_found_out NULL, a cutoff
+ *           that is not finite, an unknown divisor, band_rows negative or not a multiple of 64, capacity < 0, capacity > 0 with
+ *           out_pairs NULL.
+ *   PCOA_ERR_STATE, the ctx stays usable: as pcoa_grm_block -- a ctx that is not from pcoa_create_grm, a pcoa_create_grm_study
+ *           ctx, M' = 0, M' >= 2^31.
+ *   memory: band_rows * 64 ceil(N / 64) doubles, plus as many int32 under PAIRWISE, in the lazily grown buffer pcoa_grm_block
+ *           uses; the (row, tile) counts, the row offsets and min(capacity, N (N - 1) / 2) records for the length of the call,
+ *           all allocated before the first launch.  PCOA_ERR_OUT_OF_MEMORY leaves the ctx usable.
+ * Not built: a threshold fused into the dense product's epilogue, skipping the tiles of a band's first block that lie below
+ * the diagonal, a KING screen over the 2-bit store, multi-GPU, GCTA's own removal order, JNI / Scala natives. */
+typedef struct pcoa_grm_pair { int32_t i, j; double k; int64_t n; } pcoa_grm_pair;   /* i < j, k = K(i, j); 24 bytes */
+int pcoa_grm_pairs(pcoa_ctx* ctx, double cutoff, int32_t divisor, int32_t band_rows /* 0: 1,024 */, pcoa_grm_pair* out_pairs,
+                   int64_t capacity, int64_t* n_found_out, double* out_diag /* N doubles, or NULL */);
+
+/* What pcoa_grm_pairs did on THIS engine, cumulative since pcoa_create_grm / pcoa_reset_timings.  (A struct of its own, like
+ * pcoa_pairs_stats.)  It grows at its end; out_size = sizeof of the struct the caller compiled against.  Synchronising. */
+typedef struct pcoa_grm_pairs_stats {
+  double grm_pairs_seconds;          /* HIP-event time of every launch of the calls: the dense bands and the screen          */
+  double grm_pairs_screen_seconds;   /* of which the count, scan and write kernels                                           */
+  int64_t grm_pairs_calls;
+  int64_t grm_pairs_bands;
+  double grm_pairs_flops;            /* 2 * band rows * band columns * V per float pass of the dense part                    */
+  int64_t grm_pairs_bytes;           /* bytes of the bands the count and write kernels read                                  */
+} pcoa_grm_pairs_stats;
+int pcoa_get_grm_pairs_stats(pcoa_ctx* ctx, pcoa_grm_pairs_stats* out, size_t out_size);
 
 /* ---- LD pruning of the resident GRM store by dosage r^2 ------------------------------------------------------
  * smartpca, plink --pca, GCTA and flashpca workflows LD-prune the variants in front of the PCA; the accepted pair statistic

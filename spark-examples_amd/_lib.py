@@ -183,6 +183,28 @@ class PcoaGrmBlockStats(ctypes.Structure):
     ]
 
 
+class PcoaGrmPair(ctypes.Structure):
+    """pcoa_grm_pair: one reported pair of pcoa_grm_pairs, i < j, k = K(i, j), n = n(i, j) or M'; 24 bytes."""
+    _fields_ = [
+        ("i", ctypes.c_int32),
+        ("j", ctypes.c_int32),
+        ("k", ctypes.c_double),
+        ("n", ctypes.c_int64),
+    ]
+
+
+class PcoaGrmPairsStats(ctypes.Structure):
+    """pcoa_grm_pairs_stats: a struct of its own beside pcoa_timings, like pcoa_pairs_stats."""
+    _fields_ = [
+        ("grm_pairs_seconds", ctypes.c_double),
+        ("grm_pairs_screen_seconds", ctypes.c_double),
+        ("grm_pairs_calls", ctypes.c_int64),
+        ("grm_pairs_bands", ctypes.c_int64),
+        ("grm_pairs_flops", ctypes.c_double),
+        ("grm_pairs_bytes", ctypes.c_int64),
+    ]
+
+
 class PcoaGrmSubsetStats(ctypes.Structure):
     """pcoa_grm_subset_stats: what pcoa_create_grm_subset did with this engine as its source."""
     _fields_ = [
@@ -270,6 +292,8 @@ _SIGNATURES = [
     ("pcoa_grm_project", ctypes.c_int, [_vp, _vp, _i32, _vp, _vp, _vp, _vp]),
     ("pcoa_grm_block", ctypes.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, ctypes.c_int]),
     ("pcoa_get_grm_block_stats", ctypes.c_int, [_vp, ctypes.POINTER(PcoaGrmBlockStats), ctypes.c_size_t]),
+    ("pcoa_grm_pairs", ctypes.c_int, [_vp, ctypes.c_double, _i32, _i32, _vp, _i64, ctypes.POINTER(_i64), _vp]),
+    ("pcoa_get_grm_pairs_stats", ctypes.c_int, [_vp, ctypes.POINTER(PcoaGrmPairsStats), ctypes.c_size_t]),
     ("pcoa_grm_ld_prune", ctypes.c_int, [_vp, _i32, ctypes.c_double, _vp, _i64, ctypes.POINTER(_i64), ctypes.POINTER(_i64)]),
     ("pcoa_grm_ld_mask", ctypes.c_int, [_vp, _i64, _i64, _vp]),
     ("pcoa_grm_ld_clear", ctypes.c_int, [_vp]),

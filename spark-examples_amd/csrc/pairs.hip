@@ -298,11 +298,16 @@ hipError_t launch_pairs_count(const int32_t* s32, const int64_t* s64_or_null, in
   return hipGetLastError();
 }
 
+hipError_t launch_pairs_row_scan(int32_t* cnt, int32_t rows, int32_t ntiles, int64_t* rowoff, hipStream_t stream) {
+  if (rows <= 0 || rows > kPairsMaxSamples || ntiles <= 0) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(pairs_row_scan_kernel, dim3((unsigned)((rows + kPairsWaves - 1) / kPairsWaves)), dim3(kPairsThreads), 0, stream,
+                     cnt, rows, ntiles, rowoff);
+  return hipGetLastError();
+}
+
 hipError_t launch_pairs_scan(int32_t* cnt, int32_t n, int64_t* rowoff, hipStream_t stream) {
   if (n <= 0 || n > kPairsMaxSamples) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(pairs_row_scan_kernel, dim3((unsigned)((n + kPairsWaves - 1) / kPairsWaves)), dim3(kPairsThreads), 0, stream,
-                     cnt, n, pairs_tiles(n), rowoff);
-  hipError_t e = hipGetLastError();
+  hipError_t e = launch_pairs_row_scan(cnt, n, pairs_tiles(n), rowoff, stream);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(pairs_offset_scan_kernel, dim3(1), dim3(kPairsScanThreads), 0, stream, rowoff, n);
   return hipGetLastError();

@@ -30,7 +30,7 @@
 
 #include "pcoa_internal.h"
 
-enum TimeCat { T_GRAM = 0, T_DENSIFY, T_SYNTH, T_FINALIZE, T_CENTER, T_TRIDIAG, T_EIG, T_BACK, T_PACK, T_LANCZOS, T_ALLREDUCE, T_OPERATOR, T_SUBSET, T_REDUCE_PEERS, T_PAIRS, T_LOADINGS, T_LD_COUNT, T_LD_BAND, T_LD_RESOLVE, T_LD_COMPACT, T_KING, T_GRM_BLOCK, T_GRM_LD_BAND, T_GRM_LD_RESOLVE, T_GRM_LD_SCAN, T_GRM_SUBSET, T_NCAT };
+enum TimeCat { T_GRAM = 0, T_DENSIFY, T_SYNTH, T_FINALIZE, T_CENTER, T_TRIDIAG, T_EIG, T_BACK, T_PACK, T_LANCZOS, T_ALLREDUCE, T_OPERATOR, T_SUBSET, T_REDUCE_PEERS, T_PAIRS, T_LOADINGS, T_LD_COUNT, T_LD_BAND, T_LD_RESOLVE, T_LD_COMPACT, T_KING, T_GRM_BLOCK, T_GRM_LD_BAND, T_GRM_LD_RESOLVE, T_GRM_LD_SCAN, T_GRM_SUBSET, T_GRM_PAIRS_DENSE, T_GRM_PAIRS_SCREEN, T_NCAT };
 
 struct EventPair {
   hipEvent_t a, b;
@@ -104,6 +104,8 @@ struct pcoa_ctx {
   int64_t grm_blk_cap = 0;
   int64_t grm_block_calls = 0;     // pcoa_grm_block_stats
   double grm_block_flops = 0;
+  int64_t grm_pairs_calls = 0, grm_pairs_bands = 0, grm_pairs_bytes = 0;   // pcoa_grm_pairs_stats (the bands live in grm_blk)
+  double grm_pairs_flops = 0;
   // LD pruning of the store (pcoa_grm_ld_prune, capi_grm_ld.hip): the keep mask is a statement about the store as it was
   // pruned under grm_min_maf; an append, pcoa_reset, another min_maf and pcoa_grm_ld_clear drop it (grm_ld_drop)
   uint8_t* grm_keep = nullptr;     // [V] 1 = kept, 0 = removed or no candidate

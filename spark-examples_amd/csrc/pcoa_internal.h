@@ -180,6 +180,8 @@ hipError_t launch_pairs_diag(const int32_t* s32, const int64_t* s64_or_null, int
 hipError_t launch_pairs_count(const int32_t* s32, const int64_t* s64_or_null, int32_t n, const int64_t* diag, double x,
                               int32_t* cnt, hipStream_t stream);
 hipError_t launch_pairs_scan(int32_t* cnt, int32_t n, int64_t* rowoff, hipStream_t stream);   // both scans
+// the row scan alone, over any [rows][ntiles] counts: cnt[r][.] := its exclusive prefix, rowoff[r] := the row's total
+hipError_t launch_pairs_row_scan(int32_t* cnt, int32_t rows, int32_t ntiles, int64_t* rowoff, hipStream_t stream);
 // out[p] for the list positions p < capacity (capacity >= 1 entries allocated), in increasing (i, j) order.  *entries_read
 // (optional, zeroed by the caller) grows by the entries of S the pass reads again: the widths of the (row, tile) cells it visits
 hipError_t launch_pairs_write(const int32_t* s32, const int64_t* s64_or_null, int32_t n, const int64_t* diag, double x,
@@ -294,6 +296,26 @@ hipError_t launch_grm_dense(const uint32_t* seg, int32_t rows, int32_t n, const 
                             hipStream_t stream);
 // k[i] = divisor 0: k[i] / M'; divisor 1: n[i] > 0 ? k[i] / n[i] : 0.0
 hipError_t launch_grm_dense_finish(double* k, const int32_t* n, int64_t total, int32_t divisor, int64_t mprime, hipStream_t stream);
+
+// ---- the relatedness cut-off on K (grm_pairs.hip): the screen of one row band of K as launch_grm_dense /
+// launch_grm_dense_finish leave it.  k (and nb, the pair counts, or NULL): rows [r0, r0 + nrows) of K x columns [c0, c0 + pitch)
+// at `pitch` elements a row, c0 a multiple of 64 at or below r0, pitch >= n - c0; a pitch that is a multiple of 4 on a 16-byte
+// aligned k takes the 16-byte loads.  A workgroup takes kGrmPairsRows rows x kGrmPairsTileCols columns.  cnt: nrows *
+// grm_pairs_tiles(n - c0) int32; rowoff: nrows + 1 int64; total_io: one int64, the pairs of the bands before on entry and with
+// this band's on exit (the list position the band's first pair takes)
+constexpr int32_t kGrmPairsTileCols = 1024;
+constexpr int32_t kGrmPairsRows = 64;
+int32_t grm_pairs_tiles(int32_t width);
+int64_t grm_pairs_count_pass_entries(int32_t r0, int32_t nrows, int32_t c0, int32_t n);   // entries the count pass loads
+// cnt[row][tile] = the columns j > i of the tile with K >= cutoff; diag_or_null[i] = K(i, i) for the band's rows
+hipError_t launch_grm_pairs_count(const double* k, int64_t pitch, int32_t r0, int32_t nrows, int32_t c0, int32_t n, double cutoff,
+                                  int32_t* cnt, double* diag_or_null, hipStream_t stream);
+hipError_t launch_grm_pairs_scan(int32_t* cnt, int32_t nrows, int32_t ntiles, int64_t* rowoff, int64_t* total_io, hipStream_t stream);
+// out[p] for the list positions p < capacity; n of a record = nb's entry, or mprime where nb is NULL.  *entries_read (optional,
+// zeroed by the caller) grows by the entries of the band the pass reads again
+hipError_t launch_grm_pairs_write(const double* k, const int32_t* nb_or_null, int64_t pitch, int32_t r0, int32_t nrows, int32_t c0,
+                                  int32_t n, double cutoff, int64_t mprime, const int32_t* prefix, const int64_t* rowoff,
+                                  int64_t capacity, pcoa_grm_pair* out, unsigned long long* entries_read, hipStream_t stream);
 
 // ---- per-variant loadings (loadings.hip): out[v * num_pc + c] = (sum_i bit(v, i) u[c * ustride + i]) / div[c] for c in [0, k) ----
 // u: prepared vectors, ustride = 32 ceil(n / 32) doubles each, zero for i >= n (that is what ignores a row's tail bits); div: k

@@ -757,6 +757,33 @@ class PcoaEngine(object):
         self._check(self._lib.pcoa_get_grm_block_stats(self._ctx, ctypes.byref(q), ctypes.sizeof(q)))
         return dict((f[0], getattr(q, f[0])) for f in L.PcoaGrmBlockStats._fields_)
 
+    # ------------------------------------------------------------------ the relatedness cut-off on K
+    GRM_PAIR_DTYPE = np.dtype([("i", np.int32), ("j", np.int32), ("k", np.float64), ("n", np.int64)])   # pcoa_grm_pair
+
+    def grm_pairs(self, cutoff, divisor="used", band_rows=0, capacity=1 << 20, diag=False):
+        """The relatedness screen of the matrix compute() decomposes (pcoa_grm_pairs): the pairs i < j with K(i, j) >= cutoff,
+        K(i, j) the bits grm_block returns under `divisor`, found on the device a band of `band_rows` rows (0: 1,024; a multiple
+        of 64) at a time; variants_pca.grm_pairs_rule is the rule.  Returns (pairs, n_found), or (pairs, n_found, diag) with
+        diag=True: `pairs` a structured array (fields i, j, k, n) of the first min(n_found, capacity) pairs in increasing (i, j)
+        order, n = n(i, j) under "pairwise" and M' under "used"; `n_found` the full count whatever the capacity; `diag` K(i, i),
+        float64 [N]."""
+        div = self._grm_divisor(divisor)
+        cap = int(capacity)
+        pairs = np.zeros(max(cap, 0), dtype=self.GRM_PAIR_DTYPE)
+        d = np.zeros(self.n, dtype=np.float64) if diag else None
+        found = ctypes.c_int64(0)
+        self._check(self._lib.pcoa_grm_pairs(self._ctx, float(cutoff), div, int(band_rows), _ptr(pairs) if cap > 0 else None, cap,
+                                             ctypes.byref(found), _ptr(d) if diag else None))
+        n_found = int(found.value)
+        return (pairs[:min(n_found, cap)], n_found, d) if diag else (pairs[:min(n_found, cap)], n_found)
+
+    def grm_pairs_stats(self):
+        """pcoa_get_grm_pairs_stats: grm_pairs_seconds / grm_pairs_screen_seconds / grm_pairs_calls / grm_pairs_bands /
+        grm_pairs_flops / grm_pairs_bytes."""
+        q = L.PcoaGrmPairsStats()
+        self._check(self._lib.pcoa_get_grm_pairs_stats(self._ctx, ctypes.byref(q), ctypes.sizeof(q)))
+        return dict((f[0], getattr(q, f[0])) for f in L.PcoaGrmPairsStats._fields_)
+
     # ------------------------------------------------------------------ LD pruning of the GRM store
     def grm_ld_prune(self, window, r2_max, breaks=()):
         """LD-prunes the resident genotype store by the r^2 of the dosages over the jointly called samples (pcoa_grm_ld_prune;

@@ -108,6 +108,14 @@ struct Conf {  // PcaConf / GenomicsConf (GenomicsConf.scala:31-101), same flag 
                                         // pcoa_create_grm_subset over the kept samples
   double grm_outlier_sigma = 6.0;       // --grm-outlier-sigma X: their threshold
   bool grm_outlier_sigma_given = false;
+  bool grm_cutoff_given = false;        // --grm-cutoff X given: --grm: the relatedness screen of K before computePca (pcoa_grm_pairs): a pair is
+  double grm_cutoff = 0.0;              // reported when K(i, j) >= X
+  std::string grm_cutoff_text;          // X as it was typed (for the refusal of a value that is not a finite number)
+  std::string grm_cutoff_divisor;       // --grm-cutoff-divisor used|pairwise: the K that is screened: num / M' (default) or num / n(i, j)
+  bool has_grm_cutoff_divisor = false;
+  std::string grm_related_output_path;  // --grm-related-output-path FILE: the reported pairs, one line each
+  bool has_grm_related_output_path = false;
+  bool grm_cutoff_remove = false;       // --grm-cutoff-remove: drop one sample of every reported pair, go on with pcoa_create_grm_subset over the rest
   bool grm_project_removed = false;     // --grm-project-removed: the samples a list or a round removed are placed on the final axes
   int outlier_iterations = 0;           // --outlier-iterations K: up to K rounds of outlier removal around computePca; a round replaces the engine by
                                         // its subset over the kept samples (pcoa_create_subset: one gather of S, no variant read twice).  0 = off
@@ -182,6 +190,10 @@ const char* kUsage =
     "                   --grm-outlier-iterations K [--grm-outlier-sigma X, default 6] (--grm: the rounds of --outlier-iterations on subsets\n"
     "                   of the genotype store; --grm-ld-window prunes every round's engine again)\n"
     "                   --grm-project-removed (--grm: the samples a list or a round removed are placed on the final axes)\n"
+    "                   --grm-cutoff X [--grm-cutoff-divisor used|pairwise] [--grm-related-output-path FILE] [--grm-cutoff-remove]\n"
+    "                   (--grm: screen K for related pairs before computePca, behind the sample list and one LD prune: a pair is reported\n"
+    "                   when K(i, j) >= X; FILE: name_i, name_j, K, n per pair; --grm-cutoff-remove drops one sample of every pair by the\n"
+    "                   rule of --remove-related and goes on with the engine's subset over the rest)\n"
     "                   --grm-ld-window W [--grm-ld-r2 X, default 0.2] [--grm-ld-output-path FILE] (--grm: LD-prune the resident store\n"
     "                   before computePca: forward and greedy, a used variant is removed when a kept one among the W rows before it\n"
     "                   on the same contig has r^2 of the dosages over the jointly called samples above X -- plink's pair statistic,\n"
@@ -291,6 +303,22 @@ Conf parse(int argc, char** argv) {
     else if (a == "--grm-keep-samples") c.grm_keep_samples = one(i);
     else if (a == "--grm-remove-samples") c.grm_remove_samples = one(i);
     else if (a == "--grm-project-removed") c.grm_project_removed = true;
+    else if (a == "--grm-cutoff") {
+      c.grm_cutoff_text = one(i);
+      char* end = nullptr;
+      c.grm_cutoff = std::strtod(c.grm_cutoff_text.c_str(), &end);
+      c.grm_cutoff_given = true;
+      if (c.grm_cutoff_text.empty() || *end != 0) die("--grm-cutoff takes a number, not '" + c.grm_cutoff_text + "'");
+    }
+    else if (a == "--grm-cutoff-divisor") {
+      c.grm_cutoff_divisor = one(i);
+      c.has_grm_cutoff_divisor = true;
+    }
+    else if (a == "--grm-related-output-path") {
+      c.grm_related_output_path = one(i);
+      c.has_grm_related_output_path = true;
+    }
+    else if (a == "--grm-cutoff-remove") c.grm_cutoff_remove = true;
     else if (a == "--grm-outlier-iterations") {
       const std::string v = one(i);
       char* end = nullptr;
@@ -435,6 +463,14 @@ Conf parse(int argc, char** argv) {
         "--dump-similarity)");
   if (!c.grm && c.has_grm_output_divisor) die("--grm-output-divisor needs --grm (and --grm-output-path)");
   {
+    const char* why = " needs --grm (it screens the relationship matrix K of the standardised genotypes; a stored similarity matrix is "
+                      "screened by --related-min-jaccard / --king-cutoff)";
+    if (!c.grm && c.grm_cutoff_given) die(std::string("--grm-cutoff") + why);
+    if (!c.grm && c.has_grm_cutoff_divisor) die(std::string("--grm-cutoff-divisor") + why);
+    if (!c.grm && c.has_grm_related_output_path) die(std::string("--grm-related-output-path") + why);
+    if (!c.grm && c.grm_cutoff_remove) die(std::string("--grm-cutoff-remove") + why);
+  }
+  {
     const char* why = " needs --grm (it prunes the genotype store of the standardised-genotype PCA; the carrier counts S are pruned by --ld-window)";
     if (!c.grm && c.grm_ld_window != 0) die(std::string("--grm-ld-window") + why);
     if (!c.grm && c.grm_ld_r2_given) die(std::string("--grm-ld-r2") + why);
@@ -455,6 +491,16 @@ Conf parse(int argc, char** argv) {
     if (c.grm_outlier_iterations < 0) die("--grm-outlier-iterations must be >= 0 (0 = off)");
     if (!(c.grm_outlier_sigma > 0) || !std::isfinite(c.grm_outlier_sigma))
       die("--grm-outlier-sigma must be a finite number > 0 (the threshold of --grm-outlier-iterations)");
+  }
+  if (!c.grm_cutoff_given) {
+    const char* why = " needs --grm-cutoff X (the screen is off without it)";
+    if (c.has_grm_cutoff_divisor) die(std::string("--grm-cutoff-divisor") + why);
+    if (c.has_grm_related_output_path) die(std::string("--grm-related-output-path") + why);
+    if (c.grm_cutoff_remove) die(std::string("--grm-cutoff-remove") + why);
+  } else {
+    if (!std::isfinite(c.grm_cutoff)) die("--grm-cutoff must be a finite number (the K at or above which a pair is reported)");
+    if (c.has_grm_cutoff_divisor && c.grm_cutoff_divisor != "used" && c.grm_cutoff_divisor != "pairwise")
+      die("--grm-cutoff-divisor takes used or pairwise, not '" + c.grm_cutoff_divisor + "'");
   }
   if (c.has_grm_output_divisor && c.grm_output_divisor != "used" && c.grm_output_divisor != "pairwise")
     die("--grm-output-divisor takes used or pairwise, not '" + c.grm_output_divisor + "'");
@@ -1963,7 +2009,7 @@ int main(int argc, char** argv) {
   }
   std::vector<int32_t> grm_listed;   // --grm-keep-samples / --grm-remove-samples: the kept indices; a wrong list is refused here
   const bool grm_has_list = conf.grm && grm_sample_list(conf, names, &grm_listed);
-  const bool grm_rounds = conf.grm && (grm_has_list || conf.grm_outlier_iterations > 0);
+  const bool grm_rounds = conf.grm && (grm_has_list || conf.grm_outlier_iterations > 0 || conf.grm_cutoff_given);
   // A single VCF is streamed as well (r05): the header gives the callsets, then every 16-MiB block is parsed by the thread
   // pool, filtered (--references, --min-allele-frequency) and handed to the engine as carrier lists while the next one is
   // read -- the records of the whole file are never held (VariantsRDD.compute is an iterator, rdd/VariantsRDD.scala:205-235).
@@ -2570,9 +2616,63 @@ int main(int argc, char** argv) {
       grm_replace(grm_subset(ctx, n, grm_listed, PCOA_GRM_SUBSET_PANEL));
       kept = grm_listed;
     }
+    bool pruned = false;   // ctx carries the prune of --grm-ld-window already
+    if (conf.grm_cutoff_given) {
+      // --grm-cutoff X: the screen sees the K that would be decomposed: behind the list's subset and one prune of that engine.
+      // The rule, as pcoa.h and variants_pca.py's grm_pairs_rule state it: the pair (i, j), i < j, is reported iff K(i, j) >= X.
+      // Then the pair file, one stderr line, and with --grm-cutoff-remove the removal rule of --remove-related and the subset
+      if (conf.grm_ld_window > 0) {
+        grm_ld_prune_now(ctx);
+        pruned = true;
+      }
+      const int32_t m = (int32_t)kept.size();
+      const int32_t divisor = conf.grm_cutoff_divisor == "pairwise" ? PCOA_GRM_DIVISOR_PAIRWISE : PCOA_GRM_DIVISOR_USED;
+      std::vector<pcoa_grm_pair> found((size_t)std::min<int64_t>(1048576, (int64_t)m * (m - 1) / 2));
+      int64_t n_found = 0;
+      check(ctx, pcoa_grm_pairs(ctx, conf.grm_cutoff, divisor, 0, found.empty() ? nullptr : found.data(), (int64_t)found.size(), &n_found,
+                                nullptr), "pcoa_grm_pairs");
+      if (n_found > (int64_t)found.size()) {   // more than the first call's room: the count is known now
+        found.resize((size_t)n_found);
+        check(ctx, pcoa_grm_pairs(ctx, conf.grm_cutoff, divisor, 0, found.data(), (int64_t)found.size(), &n_found, nullptr), "pcoa_grm_pairs");
+      }
+      found.resize((size_t)n_found);
+      if (conf.has_grm_related_output_path) {
+        std::ofstream out(conf.grm_related_output_path);
+        out << "name_i\tname_j\tk\tn\n";
+        for (const pcoa_grm_pair& p : found)
+          out << names[(size_t)kept[(size_t)p.i]] << "\t" << names[(size_t)kept[(size_t)p.j]] << "\t" << java_double(p.k) << "\t" << p.n << "\n";
+        if (!out) die("cannot write " + conf.grm_related_output_path);
+      }
+      std::vector<pcoa_pair> pairs(found.size());
+      for (size_t k = 0; k < found.size(); ++k) pairs[k] = pcoa_pair{found[k].i, found[k].j, 0};
+      const std::vector<int32_t> gone = conf.grm_cutoff_remove ? related_removal(pairs, m) : std::vector<int32_t>();
+      std::fprintf(stderr, "GRM relatedness: %lld pair(s) with K >= %s (divisor %s), removed %zu sample(s)\n", (long long)n_found,
+                   java_double(conf.grm_cutoff).c_str(), divisor == PCOA_GRM_DIVISOR_PAIRWISE ? "pairwise" : "used", gone.size());
+      if (!gone.empty()) {
+        const int32_t least = std::max(32, conf.num_pc + 1);
+        if (m - (int32_t)gone.size() < least)
+          die("--grm --grm-cutoff-remove leaves " + std::to_string(m - (int32_t)gone.size()) + " of " + std::to_string(m) +
+              " samples, fewer than the " + std::to_string(least) + " a GRM engine with " + std::to_string(conf.num_pc) +
+              " principal components needs");
+        std::vector<int32_t> stay, kept_next;
+        size_t g = 0;
+        for (int32_t a = 0; a < m; ++a) {
+          if (g < gone.size() && gone[g] == a) {
+            ++g;
+          } else {
+            stay.push_back(a);
+            kept_next.push_back(kept[(size_t)a]);
+          }
+        }
+        grm_replace(grm_subset(ctx, m, stay, PCOA_GRM_SUBSET_PANEL));
+        kept.swap(kept_next);
+        pruned = false;
+      }
+    }
     for (int done = 0;;) {
       const int32_t m = (int32_t)kept.size();
-      if (conf.grm_ld_window > 0) grm_ld_prune_now(ctx);
+      if (conf.grm_ld_window > 0 && !pruned) grm_ld_prune_now(ctx);
+      pruned = false;
       check(ctx, pcoa_compute(ctx, conf.num_pc, comps.data(), lam.data(), &nonzero), "computePca");
       if (done == conf.grm_outlier_iterations) break;
       const std::vector<char> removed = outlier_rule(comps.data(), conf.num_pc, m, conf.grm_outlier_sigma);

@@ -605,6 +605,18 @@ class PcaConf(object):
         p.add_argument("--grm-project-removed", action="store_true",
                        help="--grm: every sample a list or an outlier round removed is placed on the final axes "
                             "(pcoa_grm_project over a study subset of the whole fileset's engine); its rows follow the kept samples'")
+        p.add_argument("--grm-cutoff", type=float, default=None,
+                       help="--grm: X: screen K for related sample pairs before computePca (pcoa_grm_pairs: gcta --grm-cutoff, "
+                            "plink --rel-cutoff): a pair is reported when K(i, j) >= X, K as --grm-output-path writes it, after "
+                            "--grm-keep-samples / --grm-remove-samples and one --grm-ld-window prune; no N x N matrix leaves the device")
+        p.add_argument("--grm-cutoff-divisor", type=str, default=None,
+                       help="--grm-cutoff: used (default): num / M', the K that is decomposed; pairwise: num / n(i, j)")
+        p.add_argument("--grm-related-output-path", type=str, default=None,
+                       help="--grm-cutoff: write the reported pairs to this file, one line per pair in (i, j) order: "
+                            "name_i, name_j, K, n")
+        p.add_argument("--grm-cutoff-remove", action="store_true",
+                       help="--grm-cutoff: drop one sample of every reported pair (the rule of --remove-related) and go on with "
+                            "the engine's subset over the rest; --grm-project-removed places the dropped samples too")
         p.add_argument("--grm-output-divisor", type=str, default=None,
                        help="--grm-output-path: used (default): num / M', the mean-imputed K that is decomposed; pairwise: "
                             "num / n(i, j), the pairwise-complete estimator GCTA-style tools store")
@@ -1202,6 +1214,12 @@ def check_grm_conf(conf):
             if given:
                 raise SystemExit("VariantsPcaDriver: %s needs --grm (it subsets the genotype store of the standardised-genotype PCA; "
                                  "a stored similarity matrix is subset by --outlier-iterations / --remove-related)" % flag)
+        for given, flag in ((conf.grm_cutoff is not None, "--grm-cutoff"), (conf.grm_cutoff_divisor is not None, "--grm-cutoff-divisor"),
+                            (conf.grm_related_output_path is not None, "--grm-related-output-path"),
+                            (conf.grm_cutoff_remove, "--grm-cutoff-remove")):
+            if given:
+                raise SystemExit("VariantsPcaDriver: %s needs --grm (it screens the relationship matrix K of the standardised "
+                                 "genotypes; a stored similarity matrix is screened by --related-min-jaccard / --king-cutoff)" % flag)
         for given, flag in ((conf.grm_ld_window != 0, "--grm-ld-window"), (conf.grm_ld_r2 is not None, "--grm-ld-r2"),
                             (bool(conf.grm_ld_output_path), "--grm-ld-output-path")):
             if given:
@@ -1230,6 +1248,17 @@ def check_grm_conf(conf):
         if not 0.0 <= conf.grm_ld_r2 <= 1.0:      # (NaN fails both comparisons)
             raise SystemExit("VariantsPcaDriver: --grm-ld-r2 (the threshold of --grm-ld-window) takes a value in [0, 1], not '%s'"
                              % conf.grm_ld_r2)
+    if conf.grm_cutoff is None:
+        for given, flag in ((conf.grm_cutoff_divisor is not None, "--grm-cutoff-divisor"),
+                            (conf.grm_related_output_path is not None, "--grm-related-output-path"),
+                            (conf.grm_cutoff_remove, "--grm-cutoff-remove")):
+            if given:
+                raise SystemExit("VariantsPcaDriver: %s needs --grm-cutoff X (the screen is off without it)" % flag)
+    else:
+        if not np.isfinite(conf.grm_cutoff):
+            raise SystemExit("VariantsPcaDriver: --grm-cutoff must be a finite number (the K at or above which a pair is reported)")
+        if conf.grm_cutoff_divisor is not None and conf.grm_cutoff_divisor not in GRM_OUTPUT_DIVISORS:
+            raise SystemExit("VariantsPcaDriver: --grm-cutoff-divisor takes used or pairwise, not '%s'" % conf.grm_cutoff_divisor)
     if conf.grm_output_divisor is not None and conf.grm_output_divisor not in GRM_OUTPUT_DIVISORS:
         raise SystemExit("VariantsPcaDriver: --grm-output-divisor takes used or pairwise, not '%s'" % conf.grm_output_divisor)
     if conf.grm_output_divisor is not None and not conf.grm_output_path:
@@ -1303,6 +1332,25 @@ def grm_dense_rule(codes, ref_is_a1, min_maf=0.0, divisor="used"):
         with np.errstate(divide="ignore", invalid="ignore"):
             k = np.where(n > 0, num / n.astype(np.float64), 0.0)
     return k, n
+
+
+GRM_PAIR_DTYPE = np.dtype([("i", np.int32), ("j", np.int32), ("k", np.float64), ("n", np.int64)])   # pcoa_grm_pair (include/pcoa.h)
+
+
+def grm_pairs_rule(k, cutoff, n=0):
+    """The rule of --grm-cutoff and of pcoa_grm_pairs (include/pcoa.h): `k` is the N x N matrix K as grm_dense_rule or
+    pcoa_grm_block return it; the pair (i, j), i < j, is reported iff k[i, j] >= cutoff -- one comparison in double on the value
+    already divided.  `n`: the N x N pair counts (the PAIRWISE divisor) or one integer (M', the USED divisor) for the records'
+    last field.  Returns the reported pairs in increasing (i, j) order as a structured array GRM_PAIR_DTYPE."""
+    k = np.asarray(k, dtype=np.float64)
+    if k.ndim != 2 or k.shape[0] != k.shape[1]:
+        raise ValueError("k must be N x N")
+    hit = (k >= np.float64(cutoff)) & np.triu(np.ones(k.shape, dtype=bool), 1)
+    i, j = np.nonzero(hit)                      # row-major: increasing (i, j)
+    out = np.zeros(i.size, dtype=GRM_PAIR_DTYPE)
+    out["i"], out["j"], out["k"] = i, j, k[i, j]
+    out["n"] = np.asarray(n)[i, j] if np.ndim(n) == 2 else int(n)
+    return out
 
 
 def write_grm_files(prefix, ids, bands):
@@ -1471,6 +1519,34 @@ def grm_subset_engine(src, keep, min_maf, study=False, err=None):
     return sub
 
 
+GRM_CUTOFF_CAPACITY = 1 << 20
+
+
+def write_grm_related(path, pairs, names):
+    """--grm-related-output-path: one line per reported pair, in the order given: name_i, name_j, K, n (`names`: the names of
+    the screened engine's samples in index order).  K is written as Java's Double.toString does, like the kinship of
+    --king-output-path."""
+    with open(path, "w") as f:
+        f.write("name_i\tname_j\tk\tn\n")
+        for p in pairs:
+            f.write("%s\t%s\t%s\t%d\n" % (names[int(p["i"])], names[int(p["j"])], java_double_to_string(float(p["k"])), int(p["n"])))
+
+
+def grm_screen_related(conf, eng, names, err=None):
+    """--grm-cutoff X on the engine that is about to be decomposed (pcoa_grm_pairs): the pair file, the stderr line and, with
+    --grm-cutoff-remove, the samples related_removal takes out (indices of `eng`, sorted; empty otherwise)."""
+    divisor = conf.grm_cutoff_divisor or "used"
+    pairs, n_found = eng.grm_pairs(conf.grm_cutoff, divisor, capacity=GRM_CUTOFF_CAPACITY)
+    if n_found > pairs.size:   # more than the first call's room: the count is known now
+        pairs, n_found = eng.grm_pairs(conf.grm_cutoff, divisor, capacity=n_found)
+    if conf.grm_related_output_path:
+        write_grm_related(conf.grm_related_output_path, pairs, names)
+    gone = related_removal(pairs, eng.n) if conf.grm_cutoff_remove else np.zeros(0, dtype=np.int64)
+    (err or sys.stderr).write("GRM relatedness: %d pair(s) with K >= %s (divisor %s), removed %d sample(s)\n"
+                              % (n_found, java_double_to_string(conf.grm_cutoff), divisor, gone.size))
+    return gone
+
+
 def grm_compute_rounds(driver, full, kept, meta, err=None):
     """computePca of --grm around --grm-keep-samples / --grm-remove-samples (`kept`: the list's indices, or None) and
     --grm-outlier-iterations K: the loop of computePcaOutlierRounds with the engine replaced by its grm_subset over the kept
@@ -1494,10 +1570,27 @@ def grm_compute_rounds(driver, full, kept, meta, err=None):
         kept = np.arange(len(driver.indexes))
     else:
         eng = replace(grm_subset_engine(eng, kept, min_maf, err=err))
-    done, iterations, sigma = 0, conf.grm_outlier_iterations, conf.grm_outlier_sigma
-    while True:
+    pruned = False   # eng carries the prune of --grm-ld-window already
+    if conf.grm_cutoff is not None:
+        # --grm-cutoff: the screen sees the K that would be decomposed: behind the list's subset and one prune of that engine
         if conf.grm_ld_window:
             grm_ld_prune(conf, eng, meta)
+            pruned = True
+        gone = grm_screen_related(conf, eng, [driver.names[reverse[int(i)]] for i in kept], err=err)
+        if gone.size:
+            least = max(GRM_MIN_COHORT, conf.numPc + 1)
+            if kept.size - gone.size < least:
+                raise SystemExit("VariantsPcaDriver: --grm --grm-cutoff-remove leaves %d of %d samples, fewer than the %d a GRM "
+                                 "engine with %d principal components needs" % (kept.size - gone.size, kept.size, least, conf.numPc))
+            stay = np.setdiff1d(np.arange(kept.size), gone)
+            eng = replace(grm_subset_engine(eng, stay, min_maf, err=err))
+            kept = kept[stay]
+            pruned = False
+    done, iterations, sigma = 0, conf.grm_outlier_iterations, conf.grm_outlier_sigma
+    while True:
+        if conf.grm_ld_window and not pruned:
+            grm_ld_prune(conf, eng, meta)
+        pruned = False
         comps, lam, nonzero = eng.compute(conf.numPc)
         if done == iterations:
             break
@@ -2032,7 +2125,7 @@ def main(args):
     if conf.grm:
         order, listed = grm_order, grm_listed
         full = driver.engine = grm_accumulate(calls_rdd, n, conf.grm_min_maf or 0.0, device=conf.gpu)
-        if listed is None and conf.grm_outlier_iterations == 0:
+        if listed is None and conf.grm_outlier_iterations == 0 and conf.grm_cutoff is None:
             if conf.grm_ld_window:
                 grm_ld_prune(conf, driver.engine, variant_meta)
             result, kept = driver.computePca(driver.engine), np.arange(n)
