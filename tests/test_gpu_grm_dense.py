@@ -12,7 +12,8 @@ import numpy as np
 import pytest
 
 from conftest import ROOT, align_sign, load_golden, load_pkg, write_golden_plink
-from test_grm_cpu import balding_nichols, dosage, edge_rows, exact_cohort, pack_bed, random_codes, spec_grm_bound, spec_grm_counts, \
+from grm_walk import entry_bound
+from test_grm_cpu import balding_nichols, edge_rows, exact_cohort, pack_bed, random_codes, spec_grm_bound, spec_grm_counts, \
     spec_grm_weights
 
 pytestmark = pytest.mark.gpu
@@ -131,18 +132,6 @@ def test_blocks_across_segment_boundaries():
 
 
 # ---- 3. and 4. rounded cohorts ----------------------------------------------------------------------------------------------
-def entry_bound(codes, ref_is_a1, min_maf, n_pairs, divisor):
-    """(V + 16) 2^-52 (|A|^T diag(d) |A|)_ij / divisor_ij: the standard bound of a sum of V products, each rounded after the
-    scaling by d, the 16 covering the roundings of mu, d and the division, doubled to cover numpy's own error."""
-    g, c = dosage(codes, ref_is_a1)
-    mu, d, used, m = spec_grm_weights(spec_grm_counts(codes, ref_is_a1), min_maf)
-    a = np.abs(np.where(c == 1, g.astype(np.float64) - mu[:, None], 0.0))
-    w = (a.T * d) @ a
-    with np.errstate(divide="ignore", invalid="ignore"):
-        w = w / float(m) if divisor == "used" else np.where(n_pairs > 0, w / n_pairs.astype(np.float64), 0.0)
-    return (codes.shape[0] + 16) * 2.0 ** -52 * w
-
-
 @pytest.fixture(scope="module")
 def rounded():
     rng = np.random.default_rng(260)

@@ -266,10 +266,12 @@ def test_every_grm_consumer_sees_the_pruned_store(P):
 
 # ---- the life of the mask -------------------------------------------------------------------------------------------------------
 def test_mask_lifetime(P):
+    from test_gpu_grm import product
     n, v = 70, 700
     g = cohort(n, v)
     unpruned = int(C.candidates(g).sum())
     rows = pack_bed(C.to_codes(g))
+    x = np.random.default_rng(5).standard_normal(n)
     with P.PcoaEngine(n, grm=True) as eng:
         fill(eng, g)
 
@@ -281,31 +283,56 @@ def test_mask_lifetime(P):
                 eng.grm_ld_mask()
             return ei.value.code == P._lib.PCOA_ERR_STATE and "no keep mask" in str(ei.value)
 
+        def twin_product(store, window=None, min_maf=0.0):
+            """a product of this engine, right after a transition, has the bits of a fresh engine brought straight to the same
+            state: the store's rows in one call, min_maf, and the prune where one is installed"""
+            with P.PcoaEngine(n, grm=True) as twin:
+                if store.shape[0]:
+                    fill(twin, store)
+                twin.grm_set_min_maf(min_maf)
+                if window is not None:
+                    twin.grm_ld_prune(window, .2)
+                want = product(twin, x)
+            return product(eng, x).tobytes() == want.tobytes()
+
         assert dropped() and eng.grm_info()[1] == unpruned                   # nothing installed yet
+        assert twin_product(g)
         first = prune()
+        assert twin_product(g, 7)
         eng.grm_set_min_maf(0.0)                                             # the same value keeps it
+        assert twin_product(g, 7)
         eng.compute(2)
         assert np.array_equal(eng.grm_ld_mask(), first) and eng.grm_info()[1] == first.sum()
+        assert twin_product(g, 7)
         check(eng, want_of(n, v, 64, .2), 64, .2)                            # a second prune is a first prune with that window
+        assert twin_product(g, 64)
         prune()
+        assert twin_product(g, 7)
         eng.grm_ld_clear()
+        assert twin_product(g)
         assert dropped() and eng.grm_info()[1] == unpruned
         prune()
         eng.grm_set_min_maf(0.05)                                            # another value drops it
+        assert twin_product(g, min_maf=0.05)
         assert dropped() and eng.grm_info()[1] == int(C.candidates(g, 0.05).sum())
         eng.grm_set_min_maf(0.0)
+        assert twin_product(g)
         prune()
         eng.accumulate_plink_bed(np.ascontiguousarray(rows[:3]))             # an append drops it
+        assert twin_product(np.concatenate([g, g[:3]]))
         assert dropped() and eng.grm_info()[:2] == (v + 3, unpruned + int(C.candidates(g[:3]).sum()))
         eng.reset()
         fill(eng, g)
         prune()
         eng.reset()                                                          # and so does a reset
+        assert twin_product(g[:0])
         assert dropped() and eng.grm_info()[0] == 0
         assert eng.grm_ld_prune(5, .5) == (0, 0) and eng.grm_ld_mask().size == 0   # V = 0
         fill(eng, g)
+        assert twin_product(g)
         assert dropped()
         prune()
+        assert twin_product(g, 7)
 
 
 # ---- errors ---------------------------------------------------------------------------------------------------------------------
