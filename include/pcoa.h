@@ -966,7 +966,12 @@ void pcoa_destroy(pcoa_ctx* ctx);
  * Replaces: the JVM exception message. */
 const char* pcoa_last_error(const pcoa_ctx* ctx);
 
-/* Zeroes the accumulated similarity matrix (a fresh getSimilarityMatrix run). */
+/* Zeroes the accumulated similarity matrix (a fresh getSimilarityMatrix run).  Afterwards the ctx is, for every call that
+ * reads S, a ctx fresh from pcoa_create with the same flags: S = 0 in the int32 matrix, NO int64 part whatever S was before
+ * (pcoa_timings.gram_i64_live = 0; the matrix is kept as the spare the next fold takes), the bound of the int32 entries zero,
+ * buffered or in-flight operands and an LD pruner's carried rows dropped.  What it keeps: the create flags, the similarity
+ * measure, the companion binding (and the companion's own S), the stream, every workspace -- and the counters of pcoa_timings,
+ * gram_variants among them, which are cumulative since pcoa_create / pcoa_reset_timings and not a statement about S. */
 int pcoa_reset(pcoa_ctx* ctx);
 
 int pcoa_n_samples(const pcoa_ctx* ctx);
@@ -1141,7 +1146,9 @@ int pcoa_gram_reduce_from(pcoa_ctx* dst, pcoa_ctx* src);
  * of the matrix at a time, every engine takes part, and nothing is staged: no exchange buffer of any size beside S (the chain
  * of pcoa_gram_reduce_from calls sends k - 1 whole matrices into engine 0, one after the other, through an N^2 staging buffer).
  *   root_only == 0: on return every engine holds the total (what pcoa_gram_allreduce_rccl leaves behind).
- *   root_only != 0: ctxs[0] holds the total; every other engine comes back as after pcoa_reset -- S zero, books zero, usable.
+ *   root_only != 0: ctxs[0] holds the total; every other engine comes back as after pcoa_reset -- S zero, no int64 part, the
+ *                   bound of the int32 entries zero, usable -- and, beyond what pcoa_reset does, with gram_variants = 0: its
+ *                   variants are counted on ctxs[0] from now on (the sum over the engines), so they are not counted twice.
  *   k == 1: pcoa_gram_finalize.
  *   The sums are integers: the result is, entry for entry, what the pcoa_gram_reduce_from chain gives.  When no engine has an
  *   int64 part and the summed variant weights stay below 2^31 - 1 the int32 matrices are summed in place

@@ -312,7 +312,13 @@ int pcoa_reset(pcoa_ctx* c) {
   if (c->is_operator) return operator_reset(c);
   const size_t nn = s_count(c);
   HIP_TRY(c, hipMemsetAsync(c->s32, 0, sizeof(int32_t) * nn, c->stream));
-  if (c->s64) HIP_TRY(c, hipMemsetAsync(c->s64, 0, sizeof(int64_t) * nn, c->stream));
+  if (c->s64) {
+    // S = 0 needs no int64 part (as the non-roots of pcoa_gram_reduce_peers(root_only)): kept zeroed it would stay "live" for
+    // the rest of the ctx's life, however small the S fed next -- the int64 kernels, the int64 branch of every reduction, and
+    // a companion refused at every centring.  The folds that wrote it are on this stream; the spare's contents are undefined.
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    retire_s64(c);
+  }
   HIP_TRY(c, hipMemsetAsync(c->err_flag, 0, 16, c->stream));
   c->variants_in_s32 = 0;
   c->dirty = false;
