@@ -35,7 +35,7 @@ extern "C" {
 #endif
 
 #define PCOA_VERSION_MAJOR 0
-#define PCOA_VERSION_MINOR 15
+#define PCOA_VERSION_MINOR 16
 
 typedef struct pcoa_ctx pcoa_ctx;
 
@@ -315,6 +315,8 @@ int pcoa_operator_matvec_device(pcoa_ctx* ctx, const double* v_dev, double* y_de
  * LD pruning: pcoa_grm_ld_prune below prunes the RESIDENT store by the r^2 of the dosages and installs a keep mask that enters
  * used_v (so d_v and M' too): the product, pcoa_compute, pcoa_grm_weights, pcoa_grm_project, pcoa_grm_block and the
  * called-sample count see the pruned store; no row is fed twice and none moves.
+ * Variant and sample QC: pcoa_grm_set_variant_filters below adds the missing-share and the Hardy-Weinberg conjunct to used_v
+ * (off by default); pcoa_grm_hwe and pcoa_grm_sample_counts read the statistics out.
  * Not built: JNI / Scala natives, variant sharding over engines. */
 int pcoa_create_grm(pcoa_ctx** out, int32_t n_samples, int32_t device_ordinal, uint32_t flags);
 
@@ -556,6 +558,64 @@ typedef struct pcoa_grm_subset_stats {
   int64_t grm_subset_bytes;    /* rows * (src pitch + result pitch) bytes per call: what an ideal gather reads and writes   */
 } pcoa_grm_subset_stats;
 int pcoa_get_grm_subset_stats(pcoa_ctx* ctx, pcoa_grm_subset_stats* out, size_t out_size);
+
+/* ---- variant and sample QC on the resident GRM store -----------------------------------------------------------
+ * Every smartpca / plink --pca / GCTA recipe starts with four filters: --maf (pcoa_grm_set_min_maf), --geno (variant call rate),
+ * --hwe (Hardy-Weinberg exact test) and --mind (sample call rate).  The two variant filters are properties of a GRM ctx like
+ * min_maf; the sample filter is a host's use of pcoa_grm_sample_counts and pcoa_create_grm_subset.
+ *
+ * pcoa_grm_set_variant_filters: 0 <= max_missing <= 1 (default 1 = off), 0 <= hwe_min_p < 1 (default 0 = off).  used_v of
+ * pcoa_create_grm gains two conjuncts, in exactly these expressions, N the ctx's sample count:
+ *   (double)(N - n_v) <= max_missing * (double)N        plink --geno: removed when the missing share exceeds max_missing
+ *   hwe_min_p == 0  or  p_v >= hwe_min_p                plink --hwe:  removed when p_v is below hwe_min_p
+ * With the defaults used_v is what it is without them, bit for bit.  Like min_maf the filters survive pcoa_reset, are inherited
+ * by pcoa_create_grm_subset (which re-derives counts, p-values and used_v from its own columns), mark the weights stale and drop
+ * an installed LD keep mask when a value other than the current one is set (the same values keep it), and are what
+ * pcoa_grm_ld_prune judges its candidates under.  Every consumer of used_v sees them: the product, pcoa_compute,
+ * pcoa_grm_weights, pcoa_grm_project, pcoa_grm_block, pcoa_grm_pairs and the called-sample count.
+ *   PCOA_ERR_STATE        a pcoa_create_grm_study ctx and every ctx that is not from pcoa_create_grm (the message names the kind)
+ *   PCOA_ERR_INVALID_ARG  NaN or a value outside its range; hwe_min_p > 0 with N >= 2^26 (the tie rule below needs it)
+ *
+ * pcoa_grm_hwe: out[v - first_variant] = p_v of the store's rows [first_variant, first_variant + n_variants); host memory; either
+ * GRM kind; independent of the filters.  The rule (Wigginton, Cutler and Abecasis 2005, without mid-p: plink --hwe's default):
+ * with n = n_v, h = h_v, a = h_v + 2 o_v and R = min(a, 2n - a), for the k of R's parity in [0, R]
+ *   P(k) = n! R! (2n - R)! 2^k / ( ((R - k) / 2)! k! (n - (R + k) / 2)! (2n)! )
+ *   p_v  = sum of P(k) over the k with P(k) <= P(h) * (1 + 2^-24)
+ *   p_v  = 1.0 when n = 0 or R = 0
+ * The tolerance keeps exact ties counted.  Evaluated in fp64 by the recurrence outward from the mode with the mode's term taken
+ * as 1, no contraction; terms that underflow to 0 are dropped.  The p-values are computed only when hwe_min_p > 0 or
+ * pcoa_grm_hwe asks, are resident beside the counts and are dropped with them.
+ *
+ * pcoa_grm_sample_counts: out[i * 3 + {0, 1, 2}] = the rows at which sample i is called, heterozygous, homozygous non-reference;
+ * exact int64; host memory, N * 3 entries.  rows: PCOA_GRM_ROWS_ALL (every row of the store; either GRM kind) or
+ * PCOA_GRM_ROWS_USED (the rows with used_v under min_maf, the filters and an installed LD mask; PCOA_ERR_STATE on a study ctx).
+ * An empty store gives zeros.  Synchronising.  One launch per segment: a lane keeps one word column of 16 samples and counts
+ * the three classes of the rows streaming past it with carry-save adders into bit-sliced counters (csrc/grm_qc.hip).
+ * Every error leaves the ctx usable.
+ * Not built: plink's inbreeding coefficient F, mid-p, per-population HWE, JNI / Scala natives. */
+int pcoa_grm_set_variant_filters(pcoa_ctx* ctx, double max_missing /* [0, 1], default 1 = off */,
+                                 double hwe_min_p /* [0, 1), default 0 = off */);
+int pcoa_grm_get_variant_filters(const pcoa_ctx* ctx, double* max_missing_out, double* hwe_min_p_out);
+int pcoa_grm_hwe(pcoa_ctx* ctx, int64_t first_variant, int64_t n_variants, double* out /* host */);
+#define PCOA_GRM_ROWS_ALL  0
+#define PCOA_GRM_ROWS_USED 1   /* used_v under min_maf, the filters and an installed LD mask; STATE on a study ctx */
+int pcoa_grm_sample_counts(pcoa_ctx* ctx, int32_t rows, int64_t* out /* host, [N][3]: called, het, hom non-reference */);
+
+/* What the QC calls did on THIS engine, cumulative since its creation / pcoa_reset_timings, and the variants of the store that
+ * fail each of the three variant tests under the CURRENT settings, each test judged alone (a variant may fail several; 0 on a
+ * ctx that is not from pcoa_create_grm): MAF = not (n_v > 0 and 0 < a_v < 2 n_v and the min_maf conjunct), so monomorphic and
+ * uncalled variants count there.  Computes the counts, and the p-values where hwe_min_p > 0, if they are not resident.  (A struct
+ * of its own; it grows at its end; out_size = sizeof of the struct the caller compiled against.)  Synchronising. */
+typedef struct pcoa_grm_qc_stats {
+  double grm_qc_hwe_seconds;             /* HIP-event time of the HWE kernel                                                 */
+  int64_t grm_qc_hwe_calls;              /* its launches (once per store contents, not per pcoa_grm_hwe)                     */
+  double grm_qc_sample_counts_seconds;   /* HIP-event time of the sample-count launches and their finish                     */
+  int64_t grm_qc_sample_counts_calls;
+  int64_t grm_qc_fail_maf;
+  int64_t grm_qc_fail_missing;
+  int64_t grm_qc_fail_hwe;
+} pcoa_grm_qc_stats;
+int pcoa_get_grm_qc_stats(pcoa_ctx* ctx, pcoa_grm_qc_stats* out, size_t out_size);
 
 /* ---- PCoA over a sample subset of a stored S ------------------------------------------------------------------------------
  * For a kept index set I, S[I, I] is exactly the similarity matrix of the reduced cohort (an entry counts the variants two

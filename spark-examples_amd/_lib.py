@@ -214,6 +214,19 @@ class PcoaGrmSubsetStats(ctypes.Structure):
     ]
 
 
+class PcoaGrmQcStats(ctypes.Structure):
+    """pcoa_grm_qc_stats: what the QC calls did, and the variants failing each variant test under the current settings."""
+    _fields_ = [
+        ("grm_qc_hwe_seconds", ctypes.c_double),
+        ("grm_qc_hwe_calls", ctypes.c_int64),
+        ("grm_qc_sample_counts_seconds", ctypes.c_double),
+        ("grm_qc_sample_counts_calls", ctypes.c_int64),
+        ("grm_qc_fail_maf", ctypes.c_int64),
+        ("grm_qc_fail_missing", ctypes.c_int64),
+        ("grm_qc_fail_hwe", ctypes.c_int64),
+    ]
+
+
 class PcoaGrmLdStats(ctypes.Structure):
     """pcoa_grm_ld_stats: what the last pcoa_grm_ld_prune did, and the HIP-event time of its kernels."""
     _fields_ = [
@@ -231,6 +244,8 @@ PCOA_GRM_DIVISOR_USED = 0
 PCOA_GRM_DIVISOR_PAIRWISE = 1
 PCOA_GRM_SUBSET_PANEL = 0
 PCOA_GRM_SUBSET_STUDY = 1
+PCOA_GRM_ROWS_ALL = 0
+PCOA_GRM_ROWS_USED = 1
 PCOA_LOADINGS_CENTRE = 1
 PCOA_LOADINGS_UNIT = 2
 PCOA_LD_MAX_WINDOW = 1024
@@ -301,6 +316,11 @@ _SIGNATURES = [
     ("pcoa_create_grm_subset", ctypes.c_int, [ctypes.POINTER(_vp), _vp, _vp, _i32, _i32]),
     ("pcoa_grm_rows", ctypes.c_int, [_vp, _i64, _i64, _vp]),
     ("pcoa_get_grm_subset_stats", ctypes.c_int, [_vp, ctypes.POINTER(PcoaGrmSubsetStats), ctypes.c_size_t]),
+    ("pcoa_grm_set_variant_filters", ctypes.c_int, [_vp, ctypes.c_double, ctypes.c_double]),
+    ("pcoa_grm_get_variant_filters", ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
+    ("pcoa_grm_hwe", ctypes.c_int, [_vp, _i64, _i64, _vp]),
+    ("pcoa_grm_sample_counts", ctypes.c_int, [_vp, _i32, _vp]),
+    ("pcoa_get_grm_qc_stats", ctypes.c_int, [_vp, ctypes.POINTER(PcoaGrmQcStats), ctypes.c_size_t]),
     ("pcoa_strip_info", ctypes.c_int, [_vp, ctypes.POINTER(_i32), ctypes.POINTER(_i32)]),
     ("pcoa_strip_col_sums", ctypes.c_int, [_vp, _vp]),
     ("pcoa_strip_matvec", ctypes.c_int, [_vp, _vp, _vp, ctypes.c_double, _vp]),

@@ -76,17 +76,24 @@ int grm_counts(pcoa_ctx* c) {
   }
   c->op_centering_set = true;
   c->grm_weights_set = false;
+  c->grm_hwe_set = false;   // the p-values are dropped with the counts they were computed from
   return PCOA_OK;
 }
 
-// mu, d, used and M' from the counts, min_maf and (with_mask) the LD keep mask, into the resident arrays.  The host learns M' here.
+// mu, d, used and M' from the counts, min_maf, the variant filters and (with_mask) the LD keep mask, into the resident arrays.
+// The p-values are computed first where the HWE filter is on.  The host learns M' here.
 int weights_pass(pcoa_ctx* c, bool with_mask) {
+  const bool hwe = c->grm_hwe_min_p > 0.0;
+  if (hwe) {
+    const int rc = grm_resident_hwe(c);
+    if (rc != PCOA_OK) return rc;
+  }
   const GrmWeights w = weights_of(c);
   {
     ScopedTimer t(c, T_CENTER);
     HIP_TRY(c, hipMemsetAsync(w.mprime, 0, sizeof(unsigned long long), c->stream));
-    HIP_TRY(c, launch_grm_weights(w.cnt, c->op_variants, c->grm_min_maf, with_mask ? c->grm_keep : nullptr, w.mu, w.d, w.used, w.mprime,
-                                  c->stream));
+    HIP_TRY(c, launch_grm_weights(w.cnt, c->op_variants, c->grm_min_maf, with_mask ? c->grm_keep : nullptr, c->n, c->grm_max_missing,
+                                  c->grm_hwe_min_p, hwe ? c->grm_hwe : nullptr, w.mu, w.d, w.used, w.mprime, c->stream));
   }
   HIP_TRY(c, hipMemcpyAsync(&c->hw->grm[0], w.mprime, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -157,6 +164,9 @@ int no_weights_on_study(pcoa_ctx* c, const char* call) {
 namespace pcoa {
 
 int64_t grm_store_ranges(const pcoa_ctx* c) { return store_ranges(c); }
+int grm_resident_counts(pcoa_ctx* c) { return grm_counts(c); }
+int grm_resident_weights(pcoa_ctx* c) { return grm_weights(c); }
+const int32_t* grm_used_rows(const pcoa_ctx* c) { return weights_of(c).used; }
 
 int grm_unmasked_used(pcoa_ctx* c, const int32_t** used_out) {
   int rc = grm_counts(c);
@@ -239,6 +249,7 @@ void grm_destroy(pcoa_ctx* c) {
   if (c->grm_mw) dev_free(c->grm_mw);
   if (c->grm_blk) dev_free(c->grm_blk);
   if (c->grm_keep) dev_free(c->grm_keep);
+  grm_qc_destroy(c);
   c->grm_keep = nullptr;
   c->grm_keep_set = false;
   c->grm_cnt = nullptr;

@@ -59,6 +59,8 @@ int pcoa_create_grm_subset(pcoa_ctx** out, pcoa_ctx* src, const int32_t* keep, i
                                      : create_grm_study_engine(&sub, n_keep, src->device, src->flags);
   if (rc != PCOA_OK) return fail(src, rc, std::string("pcoa_create_grm_subset: the new engine: ") + pcoa_last_error(nullptr));
   sub->grm_min_maf = src->grm_min_maf;
+  sub->grm_max_missing = src->grm_max_missing;   // the variant filters are inherited like min_maf; the counts, p-values and
+  sub->grm_hwe_min_p = src->grm_hwe_min_p;       // used_v are re-derived from the subset's own columns
   // from here on a failure is reported on src and takes the half-built engine with it
   int32_t* keep_dev = nullptr;
   auto bail = [&](int code, std::string msg) {   // by value: the message usually lives in the engine destroyed below

@@ -92,11 +92,14 @@ __global__ __launch_bounds__(256) void grm_counts_kernel(const uint32_t* __restr
 
 // mu, d, used of every variant from its counts, in the expressions of the definition (no contraction: numpy evaluates the same
 // ones); *mprime += the used variants of this launch (an integer count).  keep (may be NULL): the LD keep mask of the store
-// (pcoa_grm_ld_prune) -- a removed row is not used: d = 0, mu as it was
+// (pcoa_grm_ld_prune) -- a removed row is not used: d = 0, mu as it was.  The variant filters:
+// a row whose missing share of the n samples exceeds max_missing is not used, nor one whose HWE p-value (hwe_p, may be NULL:
+// grm_qc.hip) lies below hwe_min_p; max_missing = 1 and hwe_min_p = 0 leave used as it was without them
 __global__ __launch_bounds__(256) void grm_weights_kernel(const int32_t* __restrict__ cnt, int64_t rows, double min_maf,
-                                                          const uint8_t* __restrict__ keep, double* __restrict__ mu,
-                                                          double* __restrict__ d, int32_t* __restrict__ used,
-                                                          unsigned long long* __restrict__ mprime) {
+                                                          const uint8_t* __restrict__ keep, int32_t n, double max_missing,
+                                                          double hwe_min_p, const double* __restrict__ hwe_p,
+                                                          double* __restrict__ mu, double* __restrict__ d,
+                                                          int32_t* __restrict__ used, unsigned long long* __restrict__ mprime) {
 #pragma clang fp contract(off)
   const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
   int u = 0;
@@ -106,6 +109,8 @@ __global__ __launch_bounds__(256) void grm_weights_kernel(const int32_t* __restr
     if (nv > 0) {
       m = (double)a / (double)nv;
       u = (a > 0 && a < 2 * nv && (double)min(a, 2 * nv - a) >= min_maf * (2.0 * (double)nv)) ? 1 : 0;
+      if (!((double)(n - nv) <= max_missing * (double)n)) u = 0;
+      if (hwe_p && hwe_min_p != 0.0 && !(hwe_p[r] >= hwe_min_p)) u = 0;
       if (keep && !keep[r]) u = 0;
       if (u) w = 1.0 / (m * (1.0 - 0.5 * m));
     }
@@ -323,11 +328,12 @@ hipError_t launch_grm_counts(const uint32_t* seg, int32_t rows, int32_t n, int32
   return hipGetLastError();
 }
 
-hipError_t launch_grm_weights(const int32_t* cnt, int64_t rows, double min_maf, const uint8_t* keep, double* mu, double* d,
-                              int32_t* used, unsigned long long* mprime, hipStream_t stream) {
+hipError_t launch_grm_weights(const int32_t* cnt, int64_t rows, double min_maf, const uint8_t* keep, int32_t n, double max_missing,
+                              double hwe_min_p, const double* hwe_p, double* mu, double* d, int32_t* used,
+                              unsigned long long* mprime, hipStream_t stream) {
   if (rows <= 0) return hipSuccess;
-  hipLaunchKernelGGL(grm_weights_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, stream, cnt, rows, min_maf, keep, mu, d,
-                     used, mprime);
+  hipLaunchKernelGGL(grm_weights_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, stream, cnt, rows, min_maf, keep, n,
+                     max_missing, hwe_min_p, hwe_p, mu, d, used, mprime);
   return hipGetLastError();
 }
 

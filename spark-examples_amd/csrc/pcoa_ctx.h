@@ -14,6 +14,7 @@
 //   capi_grm_project.hip SNP weights of K's axes and the projection of a study store onto them (pcoa_create_grm_study, pcoa_grm_weights / _project)
 //   capi_grm_dense.hip   pcoa_grm_block: a rectangle of K and of the pair counts read out through the fp64 matrix cores
 //   capi_grm_ld.hip      pcoa_grm_ld_*: LD pruning of the resident GRM store by dosage r^2, as a keep mask that enters used_v
+//   capi_grm_qc.hip      pcoa_grm_set_variant_filters, pcoa_grm_hwe, pcoa_grm_sample_counts: variant and sample QC on the resident store
 //   capi_grm_subset.hip  pcoa_create_grm_subset: a new GRM ctx over a sample subset of another's store; pcoa_grm_rows reads rows back
 //   capi_subset.hip      pcoa_create_subset: a new engine whose S is S[I, I] of another
 //   capi_pairs.hip       pcoa_similar_pairs: the screen of S for duplicate and related sample pairs
@@ -30,7 +31,7 @@
 
 #include "pcoa_internal.h"
 
-enum TimeCat { T_GRAM = 0, T_DENSIFY, T_SYNTH, T_FINALIZE, T_CENTER, T_TRIDIAG, T_EIG, T_BACK, T_PACK, T_LANCZOS, T_ALLREDUCE, T_OPERATOR, T_SUBSET, T_REDUCE_PEERS, T_PAIRS, T_LOADINGS, T_LD_COUNT, T_LD_BAND, T_LD_RESOLVE, T_LD_COMPACT, T_KING, T_GRM_BLOCK, T_GRM_LD_BAND, T_GRM_LD_RESOLVE, T_GRM_LD_SCAN, T_GRM_SUBSET, T_GRM_PAIRS_DENSE, T_GRM_PAIRS_SCREEN, T_NCAT };
+enum TimeCat { T_GRAM = 0, T_DENSIFY, T_SYNTH, T_FINALIZE, T_CENTER, T_TRIDIAG, T_EIG, T_BACK, T_PACK, T_LANCZOS, T_ALLREDUCE, T_OPERATOR, T_SUBSET, T_REDUCE_PEERS, T_PAIRS, T_LOADINGS, T_LD_COUNT, T_LD_BAND, T_LD_RESOLVE, T_LD_COMPACT, T_KING, T_GRM_BLOCK, T_GRM_LD_BAND, T_GRM_LD_RESOLVE, T_GRM_LD_SCAN, T_GRM_SUBSET, T_GRM_PAIRS_DENSE, T_GRM_PAIRS_SCREEN, T_GRM_QC_HWE, T_GRM_QC_SAMPLES, T_NCAT };
 
 struct EventPair {
   hipEvent_t a, b;
@@ -112,6 +113,18 @@ struct pcoa_ctx {
   int64_t grm_keep_cap = 0;
   bool grm_keep_set = false;
   int64_t grm_ld_rows = 0, grm_ld_cand = 0, grm_ld_kept = 0, grm_ld_pairs = 0;   // the last prune, for pcoa_get_grm_ld_stats
+  // variant and sample QC (capi_grm_qc.hip): the two filters are properties of the ctx like grm_min_maf -- they survive pcoa_reset,
+  // a subset inherits them, another value marks the weights stale and drops the keep mask.  The p-values are resident beside the
+  // counts (grm_hwe_set: they belong to the current counts) and computed only when hwe_min_p > 0 or pcoa_grm_hwe asks
+  double grm_max_missing = 1.0, grm_hwe_min_p = 0.0;
+  double* grm_hwe = nullptr;       // [V] (lazy)
+  int64_t grm_hwe_cap = 0;
+  bool grm_hwe_set = false;
+  int32_t* grm_qc_part = nullptr;  // pcoa_grm_sample_counts: [ranges][3][pitch * 16] int32 partials (lazy)
+  int64_t grm_qc_part_cap = 0;
+  int64_t* grm_qc_out = nullptr;   // [N][3] results, then the three fail counts of pcoa_get_grm_qc_stats (lazy)
+  int64_t grm_qc_out_cap = 0;
+  int64_t grm_hwe_calls = 0, grm_sample_counts_calls = 0;
   int64_t grm_subset_calls = 0, grm_subset_bytes = 0;   // pcoa_create_grm_subset with this ctx as src (pcoa_get_grm_subset_stats)
   int64_t subset_bytes = 0;        // bytes the gathers of pcoa_create_subset moved into this ctx (read + written)
   int64_t pairs_bytes = 0, pairs_calls = 0;   // pcoa_similar_pairs: bytes of S its scan kernels read, calls
@@ -176,6 +189,7 @@ struct pcoa_ctx {
     int32_t kflag[pcoa::kKingFlagWords];   // the four consistency checks of the kinship screen
     int64_t king[3]; // its V, n_found and the entries the write pass read again
     int64_t grm[2];  // M' of a GRM ctx's weights
+    int64_t qc[3];   // the fail counts of pcoa_get_grm_qc_stats
   };
   HostWords* hw = nullptr;
 
@@ -492,6 +506,9 @@ struct GrmParams {
   const int32_t* used;
 };
 int grm_resident_params(pcoa_ctx* c, GrmParams* out, int64_t* used_out);
+int grm_resident_counts(pcoa_ctx* c);          // n_v, h_v, o_v of every row in c->grm_cnt, computed if the store changed
+int grm_resident_weights(pcoa_ctx* c);         // and mu / d / used / M' under min_maf, the filters and an installed mask
+const int32_t* grm_used_rows(const pcoa_ctx* c);   // used [V] of the resident weights
 int64_t grm_store_ranges(const pcoa_ctx* c);   // ranges of kGrmRangeRows rows over the segments of c's store
 // the counts, then mu / d / used / M' under the current min_maf WITHOUT the keep mask: *used_out[v] = 1 for a candidate of the LD
 // prune.  The resident weights are marked stale where a mask is installed, so the next consumer computes them with it
@@ -500,6 +517,10 @@ inline void grm_ld_drop(pcoa_ctx* c) {   // the keep mask no longer describes th
   if (c->grm_keep_set) c->grm_weights_set = false;
   c->grm_keep_set = false;
 }
+
+// ---- capi_grm_qc.hip
+int grm_resident_hwe(pcoa_ctx* c);   // the counts, then p_v of every row in c->grm_hwe (resident until the counts change)
+void grm_qc_destroy(pcoa_ctx* c);
 
 // ---- capi_loadings.hip
 void loadings_destroy(pcoa_ctx* c);

@@ -246,9 +246,11 @@ hipError_t launch_grm_append(const uint8_t* src, int64_t row_bytes, int64_t nv, 
 // cnt[r * 3 + {0, 1, 2}] = called, het, hom non-reference of row r
 hipError_t launch_grm_counts(const uint32_t* seg, int32_t rows, int32_t n, int32_t* cnt, hipStream_t stream);
 // mu, d, used per variant; *mprime (zeroed by the caller) += the used variants.  keep: NULL, or [rows] bytes of an LD keep mask
-// (0: the row is not used whatever its counts say)
-hipError_t launch_grm_weights(const int32_t* cnt, int64_t rows, double min_maf, const uint8_t* keep, double* mu, double* d,
-                              int32_t* used, unsigned long long* mprime, hipStream_t stream);
+// (0: the row is not used whatever its counts say).  n, max_missing, hwe_min_p, hwe_p (NULL, or [rows] p-values of launch_grm_hwe):
+// the variant filters of pcoa_grm_set_variant_filters
+hipError_t launch_grm_weights(const int32_t* cnt, int64_t rows, double min_maf, const uint8_t* keep, int32_t n, double max_missing,
+                              double hwe_min_p, const double* hwe_p, double* mu, double* d, int32_t* used,
+                              unsigned long long* mprime, hipStream_t stream);
 // tpart[g * vstride + r] = the part of (A x)[r] from sample group g, r in [0, rows) of this segment (mu: the segment's first row)
 hipError_t launch_grm_ax(const uint32_t* seg, int32_t rows, int32_t n, const double* mu, const double* x, double* tpart,
                          int64_t vstride, hipStream_t stream);
@@ -265,6 +267,20 @@ hipError_t launch_grm_finish(const double* ypart, int32_t nranges, int32_t n, co
                              hipStream_t stream);
 // *nz (zeroed by the caller) += the samples whose summed partials are positive
 hipError_t launch_grm_called_finish(const int32_t* ipart, int32_t nranges, int32_t n, int32_t* nz, hipStream_t stream);
+
+// ---- quality control on the store (grm_qc.hip) -----------------------------------------------------------------
+// p[r] = the Hardy-Weinberg exact-test p-value of row r from cnt[r * 3 + {0, 1, 2}] (the rule: pcoa.h at pcoa_grm_hwe)
+hipError_t launch_grm_hwe(const int32_t* cnt, int64_t rows, double* p, hipStream_t stream);
+// fails[0 .. 3) (zeroed by the caller) += the rows that fail the MAF, the missing and the HWE test, each judged alone
+hipError_t launch_grm_qc_fails(const int32_t* cnt, int64_t rows, int32_t n, double min_maf, double max_missing, double hwe_min_p,
+                               const double* hwe_p, unsigned long long* fails, hipStream_t stream);
+// ipart[(q * 3 + class) * pitch * 16 + i] = the rows r of range q of this segment, used[r] != 0 where used is given, at which
+// sample i is missing (class 0), heterozygous (1), homozygous non-reference (2)
+hipError_t launch_grm_sample_counts(const uint32_t* seg, int32_t rows, int32_t n, const int32_t* used, int32_t* ipart,
+                                    hipStream_t stream);
+// out[i * 3 + {0, 1, 2}] = rows_counted - missing, het, hom: the ranges' partials added in order, int64
+hipError_t launch_grm_sample_counts_finish(const int32_t* ipart, int32_t nranges, int32_t n, int64_t rows_counted, int64_t* out,
+                                           hipStream_t stream);
 
 // ---- the two passes for k vectors at once (grm_multi.hip): SNP weights and the projection of new samples ------
 // k must be 1 or 2 (grm_multi_chunk picks the chunk).  Every column is added in the order of the one-vector kernels, so column c

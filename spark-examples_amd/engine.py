@@ -856,6 +856,43 @@ class PcoaEngine(object):
         self._check(self._lib.pcoa_get_grm_subset_stats(self._ctx, ctypes.byref(q), ctypes.sizeof(q)))
         return dict((f[0], getattr(q, f[0])) for f in L.PcoaGrmSubsetStats._fields_)
 
+    # ------------------------------------------------------------------ variant and sample QC on the GRM store
+    def grm_set_variant_filters(self, max_missing=1.0, hwe_min_p=0.0):
+        """The two variant filters beside the min MAF (pcoa_grm_set_variant_filters): a variant is used only if its missing
+        share is at most max_missing (plink --geno; 1 = off) and its Hardy-Weinberg exact-test p-value is at least hwe_min_p
+        (plink --hwe; 0 = off).  Properties of the engine like the min MAF: they survive reset() and a grm_subset inherits
+        them; other values drop an installed LD mask."""
+        self._check(self._lib.pcoa_grm_set_variant_filters(self._ctx, float(max_missing), float(hwe_min_p)))
+
+    def grm_variant_filters(self):
+        """(max_missing, hwe_min_p) as set (pcoa_grm_get_variant_filters)."""
+        a, b = ctypes.c_double(0.0), ctypes.c_double(0.0)
+        self._check(self._lib.pcoa_grm_get_variant_filters(self._ctx, ctypes.byref(a), ctypes.byref(b)))
+        return a.value, b.value
+
+    def grm_hwe(self, first_variant=0, n_variants=None):
+        """float64 [n]: the Hardy-Weinberg exact-test p-values of the store's rows (pcoa_grm_hwe; include/pcoa.h states the rule)."""
+        if n_variants is None:
+            info = self.grm_info()   # (None: not a GRM engine -- the call itself says so)
+            n_variants = (info[0] if info else 0) - int(first_variant)
+        out = np.zeros(max(int(n_variants), 0), dtype=np.float64)
+        self._check(self._lib.pcoa_grm_hwe(self._ctx, int(first_variant), int(n_variants), _ptr(out) if out.size else None))
+        return out
+
+    def grm_sample_counts(self, used=False):
+        """int64 [N, 3]: the rows of the store at which each sample is called, heterozygous, homozygous non-reference
+        (pcoa_grm_sample_counts); used=True: over the rows used under the min MAF, the filters and an installed LD mask."""
+        out = np.zeros((self.n, 3), dtype=np.int64)
+        self._check(self._lib.pcoa_grm_sample_counts(self._ctx, L.PCOA_GRM_ROWS_USED if used else L.PCOA_GRM_ROWS_ALL, _ptr(out)))
+        return out
+
+    def grm_qc_stats(self):
+        """pcoa_get_grm_qc_stats: seconds and calls of the HWE kernel and the sample-count launches, and the variants failing
+        the MAF, missing and HWE test under the current settings."""
+        q = L.PcoaGrmQcStats()
+        self._check(self._lib.pcoa_get_grm_qc_stats(self._ctx, ctypes.byref(q), ctypes.sizeof(q)))
+        return dict((f[0], getattr(q, f[0])) for f in L.PcoaGrmQcStats._fields_)
+
     # ------------------------------------------------------------------ per-variant loadings
     def loadings(self, components, eigenvalues=None, centre=True, unit=True):
         """Per-variant loadings of the principal coordinates (pcoa_loadings_begin): `components` [N, k] and `eigenvalues` [k] are

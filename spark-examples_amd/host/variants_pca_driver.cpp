@@ -97,6 +97,12 @@ struct Conf {  // PcaConf / GenomicsConf (GenomicsConf.scala:31-101), same flag 
                                         // GCTA, flashpca) through the products K x: no N x N matrix exists
   double grm_min_maf = 0.0;             // --grm-min-maf X: --grm uses only variants whose minor-allele frequency is at least X, in [0, 0.5)
   bool has_grm_min_maf = false;
+  double grm_geno = 1.0;                // --grm-geno X: --grm uses only variants whose share of missing calls is at most X, in [0, 1] (plink --geno)
+  double grm_hwe = 0.0;                 // --grm-hwe P: ... and whose Hardy-Weinberg exact-test p-value is at least P, in [0, 1) (plink --hwe)
+  double grm_mind = 1.0;                // --grm-mind X: samples whose share of missing calls exceeds X are taken out before anything else (plink --mind)
+  bool has_grm_geno = false, has_grm_hwe = false, has_grm_mind = false;
+  std::string grm_variant_qc_output_path;   // --grm-variant-qc-output-path FILE: index, contig, position, id, n, het, hom-alt, missing share, HWE p, used
+  std::string grm_sample_qc_output_path;    // --grm-sample-qc-output-path FILE: name, called, het, hom-alt, call rate, het share of called, kept
   std::string grm_output_path;          // --grm-output-path PREFIX: --grm: K read out band by band into PREFIX.grm.bin / .grm.N.bin / .grm.id
   std::string grm_output_divisor;       // --grm-output-divisor used|pairwise: num / M' (default) or num / n(i, j)
   bool has_grm_output_divisor = false;
@@ -198,6 +204,12 @@ const char* kUsage =
     "                   before computePca: forward and greedy, a used variant is removed when a kept one among the W rows before it\n"
     "                   on the same contig has r^2 of the dosages over the jointly called samples above X -- plink's pair statistic,\n"
     "                   the earlier kept variant wins; FILE: index, contig, position, id, 1 (kept) or 0 per variant)\n"
+    "                   --grm-geno X, --grm-hwe P, --grm-mind X (--grm: the quality filters of plink: a variant is used only when its share\n"
+    "                   of missing calls is at most X and its Hardy-Weinberg exact-test p-value (no mid-p) at least P; samples whose\n"
+    "                   share of missing calls exceeds --grm-mind are taken out first and are not placed by --grm-project-removed)\n"
+    "                   --grm-variant-qc-output-path FILE (--grm: index, contig, position, id, called, het, hom-alt, missing share, HWE p,\n"
+    "                   1 (used) or 0 per variant) --grm-sample-qc-output-path FILE (name, called, het, hom-alt, call rate, het share\n"
+    "                   of called, 1 (kept) or 0 per sample)\n"
     "                   --similarity-measure shared|jaccard|cosine (what computePca decomposes: the counts S as the reference,\n"
     "                   S(i,j) / (S(i,i) + S(j,j) - S(i,j)), or S(i,j) / sqrt(S(i,i) S(j,j)), evaluated on the fly from S; one\n"
     "                   engine, stored S, full layout, no projection)\n"
@@ -300,6 +312,23 @@ Conf parse(int argc, char** argv) {
       if (v.empty() || *end != 0 || !(c.grm_min_maf >= 0.0 && c.grm_min_maf < 0.5))
         die("--grm-min-maf takes a frequency in [0, 0.5), not '" + v + "'");
     }
+    else if (a == "--grm-geno" || a == "--grm-hwe" || a == "--grm-mind") {
+      const std::string v = one(i);
+      char* end = nullptr;
+      const double x = std::strtod(v.c_str(), &end);
+      const bool parsed = !v.empty() && *end == 0;
+      if (a == "--grm-hwe") {
+        if (!parsed || !(x >= 0.0 && x < 1.0)) die("--grm-hwe takes a p-value in [0, 1), not '" + v + "'");
+        c.grm_hwe = x;
+        c.has_grm_hwe = true;
+      } else {
+        if (!parsed || !(x >= 0.0 && x <= 1.0)) die(a + " takes a share of missing calls in [0, 1], not '" + v + "'");
+        (a == "--grm-geno" ? c.grm_geno : c.grm_mind) = x;
+        (a == "--grm-geno" ? c.has_grm_geno : c.has_grm_mind) = true;
+      }
+    }
+    else if (a == "--grm-variant-qc-output-path") c.grm_variant_qc_output_path = one(i);
+    else if (a == "--grm-sample-qc-output-path") c.grm_sample_qc_output_path = one(i);
     else if (a == "--grm-keep-samples") c.grm_keep_samples = one(i);
     else if (a == "--grm-remove-samples") c.grm_remove_samples = one(i);
     else if (a == "--grm-project-removed") c.grm_project_removed = true;
@@ -452,6 +481,14 @@ Conf parse(int argc, char** argv) {
   // --grm: one GRM engine holds the 2-bit genotypes of one PLINK fileset: what needs S, carrier bitsets or several engines is
   // refused here, before any file is read or any engine exists, in a message that names --grm and the other flag
   if (!c.grm && c.has_grm_min_maf) die("--grm-min-maf needs --grm (the standardised-genotype PCA is off without it)");
+  {
+    const char* why = " needs --grm (it is quality control on the genotype store of the standardised-genotype PCA)";
+    if (!c.grm && c.has_grm_geno) die(std::string("--grm-geno") + why);
+    if (!c.grm && c.has_grm_hwe) die(std::string("--grm-hwe") + why);
+    if (!c.grm && c.has_grm_mind) die(std::string("--grm-mind") + why);
+    if (!c.grm && !c.grm_variant_qc_output_path.empty()) die(std::string("--grm-variant-qc-output-path") + why);
+    if (!c.grm && !c.grm_sample_qc_output_path.empty()) die(std::string("--grm-sample-qc-output-path") + why);
+  }
   if (!c.grm && !c.grm_weights_output_path.empty())
     die("--grm-weights-output-path needs --grm (the SNP weights are those of the axes of K; the loadings of the carrier counts go to "
         "--loadings-output-path)");
@@ -1975,7 +2012,8 @@ int main(int argc, char** argv) {
   g_ld.on = conf.ld_window > 0;
   g_calls.on = conf.missing_calls == "pairwise";
   g_king.on = conf.king;
-  g_want_meta = want_loadings || g_ld.on || !conf.grm_weights_output_path.empty() || conf.grm_ld_window > 0;   // (--ld-window: the contigs place the breaks)
+  g_want_meta = want_loadings || g_ld.on || !conf.grm_weights_output_path.empty() || conf.grm_ld_window > 0 ||
+                !conf.grm_variant_qc_output_path.empty();   // (--ld-window: the contigs place the breaks)
   if (conf.input_path.empty())
     die("--input-path <file.vcf[.gz]> [more files] or one PLINK fileset (<prefix>.bed) is required: the Google Genomics API the reference read "
         "from has been shut down");
@@ -2007,9 +2045,10 @@ int main(int argc, char** argv) {
     ids = plink.ids;
     names = plink.names;
   }
+  std::vector<int32_t> grm_mind_gone;   // --grm-mind: the samples it took out (never placed by --grm-project-removed)
   std::vector<int32_t> grm_listed;   // --grm-keep-samples / --grm-remove-samples: the kept indices; a wrong list is refused here
-  const bool grm_has_list = conf.grm && grm_sample_list(conf, names, &grm_listed);
-  const bool grm_rounds = conf.grm && (grm_has_list || conf.grm_outlier_iterations > 0 || conf.grm_cutoff_given);
+  bool grm_has_list = conf.grm && grm_sample_list(conf, names, &grm_listed);   // (--grm-mind joins the list after the feed)
+  const bool grm_rounds = conf.grm && (grm_has_list || conf.grm_outlier_iterations > 0 || conf.grm_cutoff_given || conf.has_grm_mind);
   // A single VCF is streamed as well (r05): the header gives the callsets, then every 16-MiB block is parsed by the thread
   // pool, filtered (--references, --min-allele-frequency) and handed to the engine as carrier lists while the next one is
   // read -- the records of the whole file are never held (VariantsRDD.compute is an iterator, rdd/VariantsRDD.scala:205-235).
@@ -2412,7 +2451,88 @@ int main(int argc, char** argv) {
   };
   if (conf.grm) {
     check(ctx, pcoa_grm_set_min_maf(ctx, conf.grm_min_maf), "pcoa_grm_set_min_maf");
+    check(ctx, pcoa_grm_set_variant_filters(ctx, conf.grm_geno, conf.grm_hwe), "pcoa_grm_set_variant_filters");   // every subset inherits them
     grm_report(ctx);
+    if (conf.has_grm_geno || conf.has_grm_hwe || conf.has_grm_mind || !conf.grm_variant_qc_output_path.empty() ||
+        !conf.grm_sample_qc_output_path.empty()) {
+      // --grm-mind and the two QC files, on the engine of the whole fileset straight after the feed: the variant file (counts,
+      // missing share, HWE p and used_v of the fed cohort, in the fp64 expressions of pcoa.h), the sample file (before anyone
+      // is removed), the stderr line
+      int64_t total = 0;
+      if (pcoa_grm_info(ctx, &total, nullptr, nullptr) != 1) die(std::string("pcoa_grm_info: ") + pcoa_last_error(ctx));
+      if (!conf.grm_variant_qc_output_path.empty()) {
+        std::vector<int32_t> cnt((size_t)std::max<int64_t>(total, 1) * 3);
+        std::vector<double> p((size_t)std::max<int64_t>(total, 1));
+        check(ctx, pcoa_grm_counts(ctx, 0, total, cnt.data()), "pcoa_grm_counts");
+        check(ctx, pcoa_grm_hwe(ctx, 0, total, p.data()), "pcoa_grm_hwe");
+        const bool known = fed_meta_known && (int64_t)fed_meta.size() == total;
+        FILE* f = std::fopen(conf.grm_variant_qc_output_path.c_str(), "w");
+        if (!f) die("cannot write " + conf.grm_variant_qc_output_path);
+        for (int64_t v = 0; v < total; ++v) {
+          const int32_t nv = cnt[(size_t)v * 3], h = cnt[(size_t)v * 3 + 1], o = cnt[(size_t)v * 3 + 2];
+          const int64_t a = (int64_t)h + 2 * (int64_t)o;
+          bool used = nv > 0 && a > 0 && a < 2 * (int64_t)nv &&
+                      (double)std::min<int64_t>(a, 2 * (int64_t)nv - a) >= conf.grm_min_maf * (2.0 * (double)nv);
+          used = used && (double)(n - nv) <= conf.grm_geno * (double)n;
+          if (conf.grm_hwe != 0.0) used = used && p[(size_t)v] >= conf.grm_hwe;
+          if (known)
+            std::fprintf(f, "%lld\t%s\t%s\t%s", (long long)v, fed_meta[(size_t)v].contig.c_str(),
+                         std::to_string(fed_meta[(size_t)v].pos).c_str(), fed_meta[(size_t)v].id.c_str());
+          else
+            std::fprintf(f, "%lld\t.\t.\t.", (long long)v);
+          std::fprintf(f, "\t%d\t%d\t%d\t%.6f\t%.17g\t%d\n", nv, h, o, (double)(n - nv) / (double)n, p[(size_t)v], used ? 1 : 0);
+        }
+        if (std::fclose(f) != 0) die("cannot write " + conf.grm_variant_qc_output_path);
+      }
+      int32_t mind_gone = 0;
+      if (conf.has_grm_mind || !conf.grm_sample_qc_output_path.empty()) {
+        std::vector<int64_t> sc((size_t)n * 3);
+        check(ctx, pcoa_grm_sample_counts(ctx, PCOA_GRM_ROWS_ALL, sc.data()), "pcoa_grm_sample_counts");
+        std::vector<char> stay((size_t)n, 1);
+        if (conf.has_grm_mind && total > 0)
+          for (int32_t i = 0; i < n; ++i)
+            stay[(size_t)i] = (double)(total - sc[(size_t)i * 3]) / (double)total > conf.grm_mind ? 0 : 1;
+        if (!conf.grm_sample_qc_output_path.empty()) {
+          FILE* f = std::fopen(conf.grm_sample_qc_output_path.c_str(), "w");
+          if (!f) die("cannot write " + conf.grm_sample_qc_output_path);
+          for (int32_t i = 0; i < n; ++i) {
+            const int64_t called = sc[(size_t)i * 3];
+            std::fprintf(f, "%s\t%lld\t%lld\t%lld\t%.6f\t%.6f\t%d\n", names[(size_t)i].c_str(), (long long)called,
+                         (long long)sc[(size_t)i * 3 + 1], (long long)sc[(size_t)i * 3 + 2],
+                         total ? (double)called / (double)total : 0.0, called ? (double)sc[(size_t)i * 3 + 1] / (double)called : 0.0,
+                         stay[(size_t)i] ? 1 : 0);
+          }
+          if (std::fclose(f) != 0) die("cannot write " + conf.grm_sample_qc_output_path);
+        }
+        if (conf.has_grm_mind) {
+          for (int32_t i = 0; i < n; ++i)
+            if (!stay[(size_t)i]) {
+              ++mind_gone;
+              grm_mind_gone.push_back(i);
+            }
+          if (mind_gone > 0) {   // the samples --grm-mind keeps join (or become) the list
+            std::vector<int32_t> both;
+            if (grm_has_list) {
+              for (int32_t i : grm_listed)
+                if (stay[(size_t)i]) both.push_back(i);
+            } else {
+              for (int32_t i = 0; i < n; ++i)
+                if (stay[(size_t)i]) both.push_back(i);
+            }
+            const int32_t least = std::max(32, conf.num_pc + 1);
+            if ((int32_t)both.size() < least)
+              die("--grm --grm-mind leaves " + std::to_string(both.size()) + " of " + std::to_string(n) + " samples, fewer than the " +
+                  std::to_string(least) + " a GRM engine with " + std::to_string(conf.num_pc) + " principal components needs");
+            grm_listed.swap(both);
+            grm_has_list = true;
+          }
+        }
+      }
+      pcoa_grm_qc_stats qs;
+      check(ctx, pcoa_get_grm_qc_stats(ctx, &qs, sizeof(qs)), "pcoa_get_grm_qc_stats");
+      std::fprintf(stderr, "GRM QC: removed %lld variant(s) by MAF, %lld by missing rate, %lld by HWE; %d sample(s) by call rate\n",
+                   (long long)qs.grm_qc_fail_maf, (long long)qs.grm_qc_fail_missing, (long long)qs.grm_qc_fail_hwe, mind_gone);
+    }
     if (conf.grm_ld_window > 0 && !grm_rounds) grm_ld_prune_now(ctx);
   }
   if (g_ld.on) {
@@ -2758,7 +2878,7 @@ int main(int argc, char** argv) {
     size_t k = 0;
     for (int32_t i = 0; i < n; ++i) {
       if (k < kept.size() && kept[k] == i) ++k;
-      else gone.push_back(i);
+      else if (!std::binary_search(grm_mind_gone.begin(), grm_mind_gone.end(), i)) gone.push_back(i);   // (a sparsely called sample is what a mean-imputed projection misplaces)
     }
     if (!gone.empty()) {
       const int32_t nq = (int32_t)gone.size();

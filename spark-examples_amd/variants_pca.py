@@ -561,6 +561,22 @@ class PcaConf(object):
         p.add_argument("--grm-min-maf", type=float, default=None,
                        help="--grm: use only variants whose minor-allele frequency among the called samples is at least this, "
                             "in [0, 0.5) (default 0)")
+        p.add_argument("--grm-geno", type=float, default=None,
+                       help="--grm: use only variants whose share of missing calls among the samples is at most this, in [0, 1] "
+                            "(plink --geno; pcoa_grm_set_variant_filters; default 1 = off)")
+        p.add_argument("--grm-hwe", type=float, default=None,
+                       help="--grm: use only variants whose Hardy-Weinberg exact-test p-value (Wigginton et al. 2005, no mid-p) is at "
+                            "least this, in [0, 1) (plink --hwe; default 0 = off)")
+        p.add_argument("--grm-mind", type=float, default=None,
+                       help="--grm: take out, before anything else, the samples whose share of missing calls over the fileset's "
+                            "variants exceeds this, in [0, 1] (plink --mind; pcoa_grm_sample_counts, pcoa_create_grm_subset); they "
+                            "are not placed by --grm-project-removed")
+        p.add_argument("--grm-variant-qc-output-path", type=str, default=None,
+                       help="--grm: one line per variant of the fileset: index, contig, position, id, called, het, hom-alt, missing "
+                            "share, HWE p, 1 (used under --grm-min-maf / --grm-geno / --grm-hwe) or 0")
+        p.add_argument("--grm-sample-qc-output-path", type=str, default=None,
+                       help="--grm: one line per sample of the fileset, before --grm-mind removes anyone: name, called, het, hom-alt, "
+                            "call rate, het share of called, 1 (kept) or 0")
         p.add_argument("--grm-weights-output-path", type=str, default=None,
                        help="--grm: write the SNP weight of every variant of the fileset on each of the --num-pc axes of K "
                             "(pcoa_grm_weights: the left singular vectors of the standardised genotype matrix; smartpca's "
@@ -1196,6 +1212,13 @@ def check_grm_conf(conf):
     if not conf.grm:
         if conf.grm_min_maf is not None:
             raise SystemExit("VariantsPcaDriver: --grm-min-maf needs --grm (the standardised-genotype PCA is off without it)")
+        for given, flag in ((conf.grm_geno is not None, "--grm-geno"), (conf.grm_hwe is not None, "--grm-hwe"),
+                            (conf.grm_mind is not None, "--grm-mind"),
+                            (bool(conf.grm_variant_qc_output_path), "--grm-variant-qc-output-path"),
+                            (bool(conf.grm_sample_qc_output_path), "--grm-sample-qc-output-path")):
+            if given:
+                raise SystemExit("VariantsPcaDriver: %s needs --grm (it is quality control on the genotype store of the "
+                                 "standardised-genotype PCA)" % flag)
         if conf.grm_weights_output_path:
             raise SystemExit("VariantsPcaDriver: --grm-weights-output-path needs --grm (the SNP weights are those of the axes of K; "
                              "the loadings of the carrier counts go to --loadings-output-path)")
@@ -1288,6 +1311,12 @@ def check_grm_conf(conf):
             raise SystemExit("VariantsPcaDriver: --grm " + why)
     if conf.grm_min_maf is not None and not (0.0 <= conf.grm_min_maf < 0.5):
         raise SystemExit("VariantsPcaDriver: --grm-min-maf takes a frequency in [0, 0.5), not '%s'" % conf.grm_min_maf)
+    if conf.grm_geno is not None and not (0.0 <= conf.grm_geno <= 1.0):      # (NaN fails both comparisons)
+        raise SystemExit("VariantsPcaDriver: --grm-geno takes a share of missing calls in [0, 1], not '%s'" % conf.grm_geno)
+    if conf.grm_hwe is not None and not (0.0 <= conf.grm_hwe < 1.0):
+        raise SystemExit("VariantsPcaDriver: --grm-hwe takes a p-value in [0, 1), not '%s'" % conf.grm_hwe)
+    if conf.grm_mind is not None and not (0.0 <= conf.grm_mind <= 1.0):
+        raise SystemExit("VariantsPcaDriver: --grm-mind takes a share of missing calls in [0, 1], not '%s'" % conf.grm_mind)
     paths = conf.inputPath or []
     if conf.synthetic or conf.minAlleleFrequency is not None or len(paths) != 1 or not is_plink_path(paths[0]):
         raise SystemExit("VariantsPcaDriver: --grm reads the genotypes of one PLINK fileset: --input-path must name a single "
@@ -1455,12 +1484,14 @@ def grm_project_study(conf, panel_eng, comps, lam, err=None):
     return [("%s-%d" % (set_id, q), names[reverse[q]], float(coords[q, 0]), float(coords[q, 1])) for q in range(nq)]
 
 
-def grm_accumulate(call_rdd, matrix_size, min_maf, device=0, err=None):
+def grm_accumulate(call_rdd, matrix_size, min_maf, device=0, err=None, max_missing=1.0, hwe_min_p=0.0):
     """--grm: the raw .bed rows of a PLINK fileset into one GRM engine, block by block (pcoa_accumulate_plink_bed), and the
-    stderr line that says what the engine will decompose."""
+    stderr line that says what the engine will decompose.  --grm-geno / --grm-hwe are set straight after the create, so that
+    every later step -- and every subset, which inherits them -- honours them."""
     _, geno, keep, ref_is_a1 = call_rdd
     eng = PcoaEngine(matrix_size, device=device, grm=True)
     eng.grm_set_min_maf(min_maf)
+    eng.grm_set_variant_filters(max_missing, hwe_min_p)
     all_kept = bool(keep.all())
     for v0 in range(0, geno.shape[0], PLINK_BLOCK_ROWS):
         rows = geno[v0:v0 + PLINK_BLOCK_ROWS]
@@ -1475,6 +1506,57 @@ def grm_accumulate(call_rdd, matrix_size, min_maf, device=0, err=None):
     (err or sys.stderr).write("Standardised genotypes: %d of %d variants used (min MAF %g), store %d bytes\n"
                               % (used, variants, min_maf, store))
     return eng
+
+
+def grm_qc_used_rule(counts, p, n_samples, min_maf, max_missing, hwe_min_p):
+    """used_v of include/pcoa.h from the counts and p-values an engine returned, without an LD mask: the column of
+    --grm-variant-qc-output-path (both hosts evaluate the same fp64 expressions)."""
+    n = counts[:, 0].astype(np.int64)
+    a = counts[:, 1].astype(np.int64) + 2 * counts[:, 2].astype(np.int64)
+    used = (n > 0) & (a > 0) & (a < 2 * n) & (np.minimum(a, 2 * n - a).astype(np.float64) >= min_maf * (2.0 * n.astype(np.float64)))
+    used &= (n_samples - n).astype(np.float64) <= max_missing * float(n_samples)
+    if hwe_min_p != 0.0:
+        used &= p >= hwe_min_p
+    return used
+
+
+def grm_qc(conf, eng, names, meta, err=None):
+    """--grm-mind and the two QC files, on the engine of the whole fileset straight after the feed: the variant file (counts,
+    missing share, HWE p and used_v of the fed cohort), the sample file (before anyone is removed), the stderr line.  Returns
+    the indices of the samples --grm-mind keeps (increasing), or None without it."""
+    n, (total, _, _) = eng.n, eng.grm_info()
+    min_maf = conf.grm_min_maf or 0.0
+    geno = 1.0 if conf.grm_geno is None else conf.grm_geno
+    hwe = 0.0 if conf.grm_hwe is None else conf.grm_hwe
+    if conf.grm_variant_qc_output_path:
+        counts, p = eng.grm_counts(), eng.grm_hwe()
+        used = grm_qc_used_rule(counts, p, n, min_maf, geno, hwe)
+        labelled = bool(meta) and len(meta) == total
+        with open(conf.grm_variant_qc_output_path, "w") as f:
+            for v in range(total):
+                contig, pos, vid = meta[v] if labelled else (".", ".", ".")
+                f.write("%d\t%s\t%s\t%s\t%d\t%d\t%d\t%.6f\t%.17g\t%d\n"
+                        % (v, contig, pos, vid, counts[v, 0], counts[v, 1], counts[v, 2], float(n - counts[v, 0]) / float(n), p[v],
+                           1 if used[v] else 0))
+    kept, gone = None, 0
+    if conf.grm_mind is not None or conf.grm_sample_qc_output_path:
+        sc = eng.grm_sample_counts()
+        stay = np.ones(n, dtype=bool)
+        if conf.grm_mind is not None and total > 0:
+            stay = ~((total - sc[:, 0]).astype(np.float64) / float(total) > conf.grm_mind)
+        if conf.grm_sample_qc_output_path:
+            with open(conf.grm_sample_qc_output_path, "w") as f:
+                for i in range(n):
+                    called = int(sc[i, 0])
+                    f.write("%s\t%d\t%d\t%d\t%.6f\t%.6f\t%d\n"
+                            % (names[i], called, sc[i, 1], sc[i, 2], float(called) / float(total) if total else 0.0,
+                               float(sc[i, 1]) / float(called) if called else 0.0, 1 if stay[i] else 0))
+        if conf.grm_mind is not None:
+            kept, gone = np.nonzero(stay)[0], int((~stay).sum())
+    st = eng.grm_qc_stats()
+    (err or sys.stderr).write("GRM QC: removed %d variant(s) by MAF, %d by missing rate, %d by HWE; %d sample(s) by call rate\n"
+                              % (st["grm_qc_fail_maf"], st["grm_qc_fail_missing"], st["grm_qc_fail_hwe"], gone))
+    return kept
 
 
 def grm_sample_list(conf, names):
@@ -1613,10 +1695,13 @@ def grm_compute_rounds(driver, full, kept, meta, err=None):
     return [(reverse[int(i)], float(comps[a, 0]), float(comps[a, 1])) for a, i in enumerate(kept)], eng, kept
 
 
-def grm_project_removed(driver, full, eng, kept, err=None):
+def grm_project_removed(driver, full, eng, kept, err=None, never=None):
     """--grm-project-removed: the samples of the whole fileset that are not in the final cohort, as one study subset of the
-    ORIGINAL engine, on the final panel's axes.  Returns [(callset id, name, pc1, pc2)] in index order."""
+    ORIGINAL engine, on the final panel's axes.  never: the samples --grm-mind took out, which are not placed (a sparsely called
+    sample is what a mean-imputed projection misplaces).  Returns [(callset id, name, pc1, pc2)] in index order."""
     removed = np.setdiff1d(np.arange(len(driver.indexes)), kept)
+    if never is not None:
+        removed = np.setdiff1d(removed, never)
     if removed.size == 0:
         return []
     comps, lam = driver.last_pca
@@ -2101,7 +2186,8 @@ def main(args):
         if quiet is not None:
             sys.stdout = quiet
     # (contig, position, id) per row, recorded only with a flag that needs them (--ld-window: the contigs place the breaks)
-    variant_meta = [] if conf.loadings_output_path or conf.ld_window or conf.grm_weights_output_path or conf.grm_ld_window else None
+    variant_meta = [] if (conf.loadings_output_path or conf.ld_window or conf.grm_weights_output_path or conf.grm_ld_window
+                          or conf.grm_variant_qc_output_path) else None
     indexes, names, data = load_dataset(conf, variant_meta)
     grm_order, grm_listed = None, None
     if conf.grm:   # --grm-keep-samples / --grm-remove-samples: a wrong list is refused before anything is printed or any engine exists
@@ -2124,7 +2210,20 @@ def main(args):
 
     if conf.grm:
         order, listed = grm_order, grm_listed
-        full = driver.engine = grm_accumulate(calls_rdd, n, conf.grm_min_maf or 0.0, device=conf.gpu)
+        full = driver.engine = grm_accumulate(calls_rdd, n, conf.grm_min_maf or 0.0, device=conf.gpu,
+                                              max_missing=1.0 if conf.grm_geno is None else conf.grm_geno,
+                                              hwe_min_p=0.0 if conf.grm_hwe is None else conf.grm_hwe)
+        mind_gone = None
+        if (conf.grm_geno is not None or conf.grm_hwe is not None or conf.grm_mind is not None or conf.grm_variant_qc_output_path
+                or conf.grm_sample_qc_output_path):
+            mind_kept = grm_qc(conf, full, [names[cid] for cid, _ in order], variant_meta)
+            if mind_kept is not None and mind_kept.size < n:
+                mind_gone = np.setdiff1d(np.arange(n), mind_kept)
+                listed = mind_kept if listed is None else np.intersect1d(listed, mind_kept)
+                least = max(GRM_MIN_COHORT, conf.numPc + 1)
+                if listed.size < least:
+                    raise SystemExit("VariantsPcaDriver: --grm --grm-mind leaves %d of %d samples, fewer than the %d a GRM engine "
+                                     "with %d principal components needs" % (listed.size, n, least, conf.numPc))
         if listed is None and conf.grm_outlier_iterations == 0 and conf.grm_cutoff is None:
             if conf.grm_ld_window:
                 grm_ld_prune(conf, driver.engine, variant_meta)
@@ -2134,7 +2233,7 @@ def main(args):
         comps, lam = driver.last_pca
         study = grm_project_study(conf, driver.engine, comps, lam) if conf.grm_project_path else []
         if conf.grm_project_removed:
-            study = study + grm_project_removed(driver, full, driver.engine, kept)
+            study = study + grm_project_removed(driver, full, driver.engine, kept, never=mind_gone)
             if full is not driver.engine:
                 full.close()
         driver.emitResult(result, study=study or None)
