@@ -35,7 +35,7 @@ extern "C" {
 #endif
 
 #define PCOA_VERSION_MAJOR 0
-#define PCOA_VERSION_MINOR 16
+#define PCOA_VERSION_MINOR 17
 
 typedef struct pcoa_ctx pcoa_ctx;
 
@@ -355,8 +355,9 @@ int pcoa_grm_matvec_device(pcoa_ctx* ctx, const double* x_dev, double* y_dev);
  * pcoa_create_grm_study: a GRM store of n_samples >= 1 study samples: pcoa_accumulate_plink_bed, pcoa_grm_info (used_out = 0),
  * pcoa_grm_counts, pcoa_reset / reserve / sync / destroy as on a GRM ctx; it has no weights of its own: pcoa_compute,
  * pcoa_grm_matvec_device and pcoa_grm_set_min_maf return PCOA_ERR_STATE with their own message.  Flags as pcoa_create_grm.
- * Not built: a least-squares projection for sparsely called samples (out_called lets a host report the shrinkage), a saved
- * model, allele flipping between the two filesets, multi-GPU, JNI / Scala natives. */
+ * A sample called at a share f of the used variants lands at about f times its position (out_called lets a host report the
+ * shrinkage); pcoa_grm_project_lsq below places it by least squares over the variants it IS called at.
+ * Not built: a saved model, allele flipping between the two filesets, multi-GPU, JNI / Scala natives. */
 int pcoa_create_grm_study(pcoa_ctx** out, int32_t n_samples, int32_t device_ordinal, uint32_t flags);
 
 /* scaled = 0: out[(v - first_variant) * num_pc + c] = t_vc (the vector the projection uses; 0 for an unused variant)
@@ -371,6 +372,54 @@ int pcoa_grm_weights(pcoa_ctx* panel, int32_t num_pc, const double* components, 
  * exactly as many rows as the panel, fed in the same order (PCOA_ERR_STATE otherwise). */
 int pcoa_grm_project(pcoa_ctx* panel, pcoa_ctx* study, int32_t num_pc, const double* components, const double* eigenvalues,
                      double* out_coords /* [num_pc][N_study] */, int32_t* out_called /* [N_study] */);
+
+/* ---- least-squares projection of sparsely called samples ----------------------------------------------------
+ * smartpca's lsqproject.  With the unit weights w_vc = t_vc / sqrt(d_v M' lambda_c) and z_vq = sqrt(d_v) (g_vq - mu_v) / sqrt(M'),
+ * the coordinates of study sample q minimise sum over the used variants q is CALLED at of (z_vq - sum_c w_vc sqrt(lambda_c) x_c)^2.
+ * M' and sqrt(lambda) cancel from the normal equations, so the call takes no eigenvalues.  With K = num_pc, per sample q:
+ *   P_q[c]    = sum_v (g_vq - mu_v c_vq) * t_vc                 the numerator pcoa_grm_project forms: P_q[c] / M' / lambda_c has
+ *                                                               the bits of its output
+ *   p_v[c,c'] = used_v ? (t_vc * t_vc') / d_v : 0.0             in exactly this expression, no contraction;  c' <= c
+ *   H_q[c,c'] = sum_v c_vq * p_v[c,c']                          K (K + 1) / 2 sums; the rows of a range of 512 in order, the ranges
+ *                                                               in (segment, range) order of the STUDY's store, like P
+ *   x_q       = the solution of H_q x = P_q
+ * For a fully called sample and true eigenvectors H_q = diag(M' lambda_c) and x_q is pcoa_grm_project's coordinate.  A pair's sum
+ * has the same bits whatever num_pc is.  The solve is a Cholesky factorisation without pivoting in its square-root-free form
+ * H = L D L^T (so that num_pc = 1 gives x = P / H bit for bit), components in the order c = 0 .. K - 1, in fp64 with every product
+ * and difference rounded on its own (no contraction), in exactly this sequence (h = H_q packed, h[c][j] at c (c + 1) / 2 + j):
+ *   for c = 0 .. K-1:   hcc = h[c][c];                                    undetermined if hcc == 0
+ *     for j = 0 .. c-1: s = h[c][j];  for k = 0 .. j-1: s = s - h[c][k] * h[j][k];   h[c][j] = s          (s = L[c][j] D[j])
+ *     s = hcc;  for k = 0 .. c-1: w = h[c][k];  l = w / h[k][k];  s = s - w * l;  h[c][k] = l            (l = L[c][k])
+ *     pivot_c = s;                                                        undetermined if pivot_c <= 2^-40 * hcc
+ *     h[c][c] = pivot_c                                                                                   (D[c])
+ *   for c = 0 .. K-1:   s = P[c];  for k = 0 .. c-1: s = s - h[c][k] * y[k];   y[c] = s
+ *   for c = 0 .. K-1:   z[c] = y[c] / h[c][c]
+ *   for c = K-1 .. 0:   s = z[c];  for k = c+1 .. K-1: s = s - h[k][c] * x[k];   x[c] = s
+ * An undetermined sample -- one called at fewer than K used variants always is -- gets NaN in all K coordinates and
+ * out_determined[q] = 0; the factorisation stops at the first failing test.
+ * out_coords[c * N_study + q]; out_called as pcoa_grm_project; out_normal (may be NULL): [K (K + 1) / 2 + K][N_study], H_q packed
+ * (entry c (c + 1) / 2 + c') and then P_q, as they were before the solve.  1 <= num_pc <= 16 (136 pair sums).  Preconditions and
+ * error codes are pcoa_grm_project's: PCOA_ERR_STATE for a panel that is not a pcoa_create_grm ctx, a study that is no GRM ctx or
+ * holds another number of rows; PCOA_ERR_INVALID_ARG for another device, num_pc outside [1, 16], M' = 0, NULL components or
+ * out_coords.  Every error leaves both ctxs usable, nothing writes either store, and the panel's counts and weights are
+ * recomputed, if they are not resident, under its current min_maf, filters and LD mask.  pcoa_grm_project is unchanged.
+ * Not built: weights per variant beyond d_v, a ridge term for nearly undetermined samples, more than 16 components, JNI / Scala
+ * natives. */
+int pcoa_grm_project_lsq(pcoa_ctx* panel, pcoa_ctx* study, int32_t num_pc, const double* components /* host [num_pc][N] */,
+                         double* out_coords /* host [num_pc][N_study] */, int32_t* out_called /* [N_study] or NULL */,
+                         int32_t* out_determined /* [N_study] 1 / 0, or NULL */,
+                         double* out_normal /* [num_pc (num_pc + 1) / 2 + num_pc][N_study] or NULL */);
+
+/* What pcoa_grm_project_lsq did with THIS ctx as the panel, cumulative since pcoa_create_grm / pcoa_reset_timings.  It grows at its
+ * end; out_size = sizeof of the struct the caller compiled against.  Synchronising. */
+typedef struct pcoa_grm_lsq_stats {
+  int64_t grm_lsq_calls;
+  int64_t grm_lsq_pair_vectors;     /* product vectors p[c,c'] streamed past the study's store: num_pc (num_pc + 1) / 2 per call */
+  double grm_lsq_pairs_seconds;     /* HIP-event time of the product, pair and finish launches                                   */
+  double grm_lsq_solve_seconds;     /* HIP-event time of the solve                                                               */
+  int64_t grm_lsq_undetermined;     /* undetermined samples of the LAST call                                                     */
+} pcoa_grm_lsq_stats;
+int pcoa_get_grm_lsq_stats(pcoa_ctx* panel, pcoa_grm_lsq_stats* out, size_t out_size);
 
 /* ---- reading K out in blocks --------------------------------------------------------------------------------
  * GCTA --make-grm, plink --make-grm-bin and smartpca also write the matrix they decompose.  pcoa_grm_block returns any

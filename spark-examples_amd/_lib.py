@@ -214,6 +214,17 @@ class PcoaGrmSubsetStats(ctypes.Structure):
     ]
 
 
+class PcoaGrmLsqStats(ctypes.Structure):
+    """pcoa_grm_lsq_stats: what pcoa_grm_project_lsq did with the ctx as the panel."""
+    _fields_ = [
+        ("grm_lsq_calls", ctypes.c_int64),
+        ("grm_lsq_pair_vectors", ctypes.c_int64),
+        ("grm_lsq_pairs_seconds", ctypes.c_double),
+        ("grm_lsq_solve_seconds", ctypes.c_double),
+        ("grm_lsq_undetermined", ctypes.c_int64),
+    ]
+
+
 class PcoaGrmQcStats(ctypes.Structure):
     """pcoa_grm_qc_stats: what the QC calls did, and the variants failing each variant test under the current settings."""
     _fields_ = [
@@ -305,6 +316,8 @@ _SIGNATURES = [
     ("pcoa_create_grm_study", ctypes.c_int, [ctypes.POINTER(_vp), _i32, _i32, ctypes.c_uint32]),
     ("pcoa_grm_weights", ctypes.c_int, [_vp, _i32, _vp, _vp, _i32, _i64, _i64, _vp]),
     ("pcoa_grm_project", ctypes.c_int, [_vp, _vp, _i32, _vp, _vp, _vp, _vp]),
+    ("pcoa_grm_project_lsq", ctypes.c_int, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
+    ("pcoa_get_grm_lsq_stats", ctypes.c_int, [_vp, ctypes.POINTER(PcoaGrmLsqStats), ctypes.c_size_t]),
     ("pcoa_grm_block", ctypes.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, ctypes.c_int]),
     ("pcoa_get_grm_block_stats", ctypes.c_int, [_vp, ctypes.POINTER(PcoaGrmBlockStats), ctypes.c_size_t]),
     ("pcoa_grm_pairs", ctypes.c_int, [_vp, ctypes.c_double, _i32, _i32, _vp, _i64, ctypes.POINTER(_i64), _vp]),

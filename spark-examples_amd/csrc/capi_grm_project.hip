@@ -35,12 +35,11 @@ int check_panel(pcoa_ctx* panel, const char* call, int32_t num_pc, const double*
   return PCOA_OK;
 }
 
-// the front of panel->grm_mw, in doubles: u [P][N] | lam [P] | t [P][V] | s [P][V] | tpart [2][groups][V] | the call's own part
-struct MultiWs {
-  double *u, *lam, *t, *s, *tpart, *rest;
-};
+}  // namespace
 
-int ensure_multi_ws(pcoa_ctx* panel, int32_t num_pc, int64_t rest_doubles, MultiWs* w) {
+namespace pcoa {
+
+int grm_multi_ws(pcoa_ctx* panel, int32_t num_pc, int64_t rest_doubles, GrmMultiWs* w) {
   const int64_t n = panel->n, v = panel->op_variants, groups = grm_groups(panel->n), p = num_pc;
   const int64_t need = p * n + p + 2 * p * v + 2 * groups * v + rest_doubles;
   const int rc = ensure(panel, &panel->grm_mw, &panel->grm_mw_cap, need);
@@ -54,12 +53,12 @@ int ensure_multi_ws(pcoa_ctx* panel, int32_t num_pc, int64_t rest_doubles, Multi
   return PCOA_OK;
 }
 
-// t_c = D A u_c and s_c = -(mu t_c) of every component, two at a time, on the panel's stream (queued)
-int panel_t(pcoa_ctx* panel, const GrmParams& g, const MultiWs& w, int32_t num_pc, const double* components,
-            const double* eigenvalues) {
+int grm_panel_t(pcoa_ctx* panel, const GrmParams& g, const GrmMultiWs& w, int32_t num_pc, const double* components,
+                const double* eigenvalues) {
   const int64_t n = panel->n, v = panel->op_variants, groups = grm_groups(panel->n);
   HIP_TRY(panel, hipMemcpyAsync(w.u, components, sizeof(double) * (size_t)num_pc * (size_t)n, hipMemcpyHostToDevice, panel->stream));
-  HIP_TRY(panel, hipMemcpyAsync(w.lam, eigenvalues, sizeof(double) * (size_t)num_pc, hipMemcpyHostToDevice, panel->stream));
+  if (eigenvalues)
+    HIP_TRY(panel, hipMemcpyAsync(w.lam, eigenvalues, sizeof(double) * (size_t)num_pc, hipMemcpyHostToDevice, panel->stream));
   ScopedTimer timer(panel, T_OPERATOR);
   for (int32_t c0 = 0; c0 < num_pc;) {
     const int32_t k = grm_multi_chunk(num_pc - c0);
@@ -77,7 +76,7 @@ int panel_t(pcoa_ctx* panel, const GrmParams& g, const MultiWs& w, int32_t num_p
   return PCOA_OK;
 }
 
-}  // namespace
+}  // namespace pcoa
 
 extern "C" {
 
@@ -99,9 +98,9 @@ int pcoa_grm_weights(pcoa_ctx* panel, int32_t num_pc, const double* components, 
                                                  std::to_string(v));
   if (n_variants > 0 && !out) return fail(panel, PCOA_ERR_INVALID_ARG, "pcoa_grm_weights: out is NULL");
   if (n_variants == 0) return PCOA_OK;
-  MultiWs w;
-  if ((rc = ensure_multi_ws(panel, num_pc, n_variants * num_pc, &w)) != PCOA_OK) return rc;
-  if ((rc = panel_t(panel, g, w, num_pc, components, eigenvalues)) != PCOA_OK) return rc;
+  GrmMultiWs w;
+  if ((rc = grm_multi_ws(panel, num_pc, n_variants * num_pc, &w)) != PCOA_OK) return rc;
+  if ((rc = grm_panel_t(panel, g, w, num_pc, components, eigenvalues)) != PCOA_OK) return rc;
   HIP_TRY(panel, launch_grm_weights_out(w.t, v, g.d, g.used, g.mprime, w.lam, scaled ? 1 : 0, first_variant, n_variants, num_pc, w.rest,
                                         panel->stream));
   HIP_TRY(panel, hipMemcpyAsync(out, w.rest, sizeof(double) * (size_t)n_variants * (size_t)num_pc, hipMemcpyDeviceToHost, panel->stream));
@@ -137,12 +136,12 @@ int pcoa_grm_project(pcoa_ctx* panel, pcoa_ctx* study, int32_t num_pc, const dou
   // | called [Nq] int32
   const int64_t v = panel->op_variants, nq = study->n, ystride = (int64_t)grm_pitch_words(study->n) * 16;
   const int64_t ranges = grm_store_ranges(study), cstride = ranges * ystride;
-  MultiWs w;
-  if ((rc = ensure_multi_ws(panel, num_pc, 2 * cstride + (int64_t)num_pc * nq + (nq + 1) / 2, &w)) != PCOA_OK) return rc;
+  GrmMultiWs w;
+  if ((rc = grm_multi_ws(panel, num_pc, 2 * cstride + (int64_t)num_pc * nq + (nq + 1) / 2, &w)) != PCOA_OK) return rc;
   double* const ypart = w.rest;
   double* const coords = ypart + 2 * cstride;
   int32_t* const called = reinterpret_cast<int32_t*>(coords + (int64_t)num_pc * nq);
-  if ((rc = panel_t(panel, g, w, num_pc, components, eigenvalues)) != PCOA_OK) return rc;
+  if ((rc = grm_panel_t(panel, g, w, num_pc, components, eigenvalues)) != PCOA_OK) return rc;
   {
     ScopedTimer timer(panel, T_OPERATOR);
     for (int32_t c0 = 0; c0 < num_pc;) {

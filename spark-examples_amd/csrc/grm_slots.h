@@ -1,6 +1,6 @@
-// grm_slots.h -- what the kernels of grm_bits.hip and grm_multi.hip share: the decoding of one word of 16 two-bit genotypes (coding
+// grm_slots.h -- what the kernels of grm_bits.hip, grm_multi.hip and grm_lsq.hip share: the decoding of one word of 16 two-bit genotypes (coding
 // and layout: grm_bits.hip) into its three slot masks, and the AND mask that spends one of their bits on a double.  Private to
-// those two translation units.
+// those translation units.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -441,6 +441,7 @@ int pcoa_reset_timings(pcoa_ctx* c) {
   c->grm_pairs_flops = 0;
   c->grm_subset_calls = c->grm_subset_bytes = 0;
   c->grm_hwe_calls = c->grm_sample_counts_calls = 0;
+  c->grm_lsq_calls = c->grm_lsq_pair_vectors = c->grm_lsq_undetermined = 0;
   c->ld_variants = c->ld_bytes = 0;
   c->ldp_seen = c->ldp_kept = c->ldp_mono = c->ldp_pairs = 0;
   c->reduce_peers_calls = c->reduce_peers_bytes_in = 0;

@@ -12,6 +12,7 @@
 //   capi_operator.hip    the implicit similarity operator: the bit store, its products, computePca over it
 //   capi_grm.hip         the standardised-genotype operator (pcoa_create_grm): the 2-bit store, its counts and weights, K x
 //   capi_grm_project.hip SNP weights of K's axes and the projection of a study store onto them (pcoa_create_grm_study, pcoa_grm_weights / _project)
+//   capi_grm_lsq.hip     pcoa_grm_project_lsq: the least-squares projection of sparsely called study samples (normal equations per sample)
 //   capi_grm_dense.hip   pcoa_grm_block: a rectangle of K and of the pair counts read out through the fp64 matrix cores
 //   capi_grm_ld.hip      pcoa_grm_ld_*: LD pruning of the resident GRM store by dosage r^2, as a keep mask that enters used_v
 //   capi_grm_qc.hip      pcoa_grm_set_variant_filters, pcoa_grm_hwe, pcoa_grm_sample_counts: variant and sample QC on the resident store
@@ -31,7 +32,7 @@
 
 #include "pcoa_internal.h"
 
-enum TimeCat { T_GRAM = 0, T_DENSIFY, T_SYNTH, T_FINALIZE, T_CENTER, T_TRIDIAG, T_EIG, T_BACK, T_PACK, T_LANCZOS, T_ALLREDUCE, T_OPERATOR, T_SUBSET, T_REDUCE_PEERS, T_PAIRS, T_LOADINGS, T_LD_COUNT, T_LD_BAND, T_LD_RESOLVE, T_LD_COMPACT, T_KING, T_GRM_BLOCK, T_GRM_LD_BAND, T_GRM_LD_RESOLVE, T_GRM_LD_SCAN, T_GRM_SUBSET, T_GRM_PAIRS_DENSE, T_GRM_PAIRS_SCREEN, T_GRM_QC_HWE, T_GRM_QC_SAMPLES, T_NCAT };
+enum TimeCat { T_GRAM = 0, T_DENSIFY, T_SYNTH, T_FINALIZE, T_CENTER, T_TRIDIAG, T_EIG, T_BACK, T_PACK, T_LANCZOS, T_ALLREDUCE, T_OPERATOR, T_SUBSET, T_REDUCE_PEERS, T_PAIRS, T_LOADINGS, T_LD_COUNT, T_LD_BAND, T_LD_RESOLVE, T_LD_COMPACT, T_KING, T_GRM_BLOCK, T_GRM_LD_BAND, T_GRM_LD_RESOLVE, T_GRM_LD_SCAN, T_GRM_SUBSET, T_GRM_PAIRS_DENSE, T_GRM_PAIRS_SCREEN, T_GRM_QC_HWE, T_GRM_QC_SAMPLES, T_GRM_LSQ_PAIRS, T_GRM_LSQ_SOLVE, T_NCAT };
 
 struct EventPair {
   hipEvent_t a, b;
@@ -125,6 +126,7 @@ struct pcoa_ctx {
   int64_t* grm_qc_out = nullptr;   // [N][3] results, then the three fail counts of pcoa_get_grm_qc_stats (lazy)
   int64_t grm_qc_out_cap = 0;
   int64_t grm_hwe_calls = 0, grm_sample_counts_calls = 0;
+  int64_t grm_lsq_calls = 0, grm_lsq_pair_vectors = 0, grm_lsq_undetermined = 0;   // pcoa_get_grm_lsq_stats (capi_grm_lsq.hip; the work lives in grm_mw)
   int64_t grm_subset_calls = 0, grm_subset_bytes = 0;   // pcoa_create_grm_subset with this ctx as src (pcoa_get_grm_subset_stats)
   int64_t subset_bytes = 0;        // bytes the gathers of pcoa_create_subset moved into this ctx (read + written)
   int64_t pairs_bytes = 0, pairs_calls = 0;   // pcoa_similar_pairs: bytes of S its scan kernels read, calls
@@ -190,6 +192,7 @@ struct pcoa_ctx {
     int64_t king[3]; // its V, n_found and the entries the write pass read again
     int64_t grm[2];  // M' of a GRM ctx's weights
     int64_t qc[3];   // the fail counts of pcoa_get_grm_qc_stats
+    int32_t lsq;     // the undetermined samples of a pcoa_grm_project_lsq call
   };
   HostWords* hw = nullptr;
 
@@ -517,6 +520,17 @@ inline void grm_ld_drop(pcoa_ctx* c) {   // the keep mask no longer describes th
   if (c->grm_keep_set) c->grm_weights_set = false;
   c->grm_keep_set = false;
 }
+
+// ---- capi_grm_project.hip
+// the front of panel->grm_mw, in doubles: u [P][N] | lam [P] | t [P][V] | s [P][V] | tpart [2][groups][V] | the call's own part
+struct GrmMultiWs {
+  double *u, *lam, *t, *s, *tpart, *rest;
+};
+int grm_multi_ws(pcoa_ctx* panel, int32_t num_pc, int64_t rest_doubles, GrmMultiWs* w);
+// t_c = D A u_c and s_c = -(mu t_c) of every component, two at a time, on the panel's stream (queued); eigenvalues (may be NULL:
+// lam is then left as it is) travel with the components
+int grm_panel_t(pcoa_ctx* panel, const GrmParams& g, const GrmMultiWs& w, int32_t num_pc, const double* components,
+                const double* eigenvalues);
 
 // ---- capi_grm_qc.hip
 int grm_resident_hwe(pcoa_ctx* c);   // the counts, then p_v of every row in c->grm_hwe (resident until the counts change)

@@ -304,6 +304,23 @@ hipError_t launch_grm_weights_out(const double* t, int64_t tstride, const double
                                   const unsigned long long* mprime, const double* lam, int scaled, int64_t first, int64_t nv,
                                   int32_t num_pc, double* out, hipStream_t stream);
 
+// ---- the least-squares projection (grm_lsq.hip): the normal equations H_q x = P_q of every study sample ------
+constexpr int32_t kGrmLsqMaxPc = 16;      // 136 pair sums
+constexpr int32_t kGrmLsqMaxChunk = 4;    // pairs one pass over the study's store carries
+int grm_lsq_chunk(int32_t remaining);     // 4, 2 or 1
+// p[j * rows + v] = used[v] ? (t_c[v] * t_c'[v]) / d[v] : 0.0 for the pairs e = e0 + j, j in [0, nj), e = c (c + 1) / 2 + c', c' <= c
+hipError_t launch_grm_lsq_products(const double* t, int64_t tstride, const double* d, const int32_t* used, int64_t rows, int32_t e0,
+                                   int32_t nj, double* p, hipStream_t stream);
+// hpart[j * cstride + q * pitch * 16 + i] = sum over the rows r of range q of c(r, i) p_j[r]; p_j = p + j * pstride, nj in {1, 2, 4}
+hipError_t launch_grm_lsq_pairs(const uint32_t* seg, int32_t rows, int32_t n, const double* p, int64_t pstride, int32_t nj, double* hpart,
+                                int64_t cstride, hipStream_t stream);
+// out[c * n + i] = the ranges' partials of column c added in order, c in [0, k): nothing is divided
+hipError_t launch_grm_lsq_finish(const double* part, int32_t nranges, int64_t cstride, int32_t n, int32_t k, double* out,
+                                 hipStream_t stream);
+// a: [num_pc (num_pc + 1) / 2 + num_pc][nq], H packed then P; solved in place, the coordinates replace P (NaN, determined[q] = 0
+// and *undetermined += 1 for a sample the rule of pcoa.h calls undetermined)
+hipError_t launch_grm_lsq_solve(double* a, int32_t nq, int32_t num_pc, int32_t* determined, int32_t* undetermined, hipStream_t stream);
+
 // ---- reading K out (grm_dense.hip): a rectangle of num(i, j) = sum_v (d_v a_v,lo) a_v,hi and of n(i, j) -------------
 // One launch per segment, in the store's order.  out_k / out_n: [nrows][ncols] row-major, either may be NULL (that pass is not
 // instantiated); first = 1: the entries start from 0, otherwise from what out_k / out_n hold.  mu, d, used: the segment's rows.

@@ -699,6 +699,34 @@ class PcoaEngine(object):
         self._check(self._lib.pcoa_grm_project(self._ctx, study._ctx, k, _ptr(u), _ptr(lam), _ptr(coords), _ptr(called)))
         return np.ascontiguousarray(coords.T), called
 
+    def grm_project_lsq(self, study, components, normal=False):
+        """(coords [N_study, k] float64, called [N_study] int32, determined [N_study] bool[, normal]): the samples of `study` on
+        the axes `components` [N, k] of this engine, each by least squares over the used variants IT is called at
+        (pcoa_grm_project_lsq; 1 <= k <= 16, no eigenvalues).  An undetermined sample -- called at fewer than k used variants,
+        or with normal equations that are singular to 2^-40 -- has NaN coordinates and determined False.  normal=True: also
+        [k (k + 1) / 2 + k, N_study], the packed H_q (entry c (c + 1) / 2 + c') and then P_q of every sample."""
+        comps = np.asarray(components, dtype=np.float64)
+        if comps.ndim == 1:
+            comps = comps[:, None]
+        if comps.ndim != 2 or comps.shape[0] != self.n:
+            raise ValueError("components must be [N = %d, k], not %s" % (self.n, comps.shape))
+        u, k = np.ascontiguousarray(comps.T), int(comps.shape[1])
+        coords = np.zeros((k, study.n), dtype=np.float64)
+        called = np.zeros(study.n, dtype=np.int32)
+        determined = np.zeros(study.n, dtype=np.int32)
+        nrm = np.zeros((k * (k + 1) // 2 + k, study.n), dtype=np.float64) if normal else None
+        self._check(self._lib.pcoa_grm_project_lsq(self._ctx, study._ctx, k, _ptr(u), _ptr(coords), _ptr(called), _ptr(determined),
+                                                   _ptr(nrm) if normal else None))
+        out = (np.ascontiguousarray(coords.T), called, determined.astype(bool))
+        return out + (nrm,) if normal else out
+
+    def grm_lsq_stats(self):
+        """pcoa_get_grm_lsq_stats: calls, pair vectors, seconds of the pair pass and of the solve, and the undetermined samples of
+        the last grm_project_lsq call with this engine as the panel."""
+        q = L.PcoaGrmLsqStats()
+        self._check(self._lib.pcoa_get_grm_lsq_stats(self._ctx, ctypes.byref(q), ctypes.sizeof(q)))
+        return dict((f[0], getattr(q, f[0])) for f in L.PcoaGrmLsqStats._fields_)
+
     GRM_DIVISORS = {"used": L.PCOA_GRM_DIVISOR_USED, "pairwise": L.PCOA_GRM_DIVISOR_PAIRWISE}
 
     def _grm_divisor(self, divisor):

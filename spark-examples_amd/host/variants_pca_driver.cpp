@@ -122,6 +122,7 @@ struct Conf {  // PcaConf / GenomicsConf (GenomicsConf.scala:31-101), same flag 
   std::string grm_related_output_path;  // --grm-related-output-path FILE: the reported pairs, one line each
   bool has_grm_related_output_path = false;
   bool grm_cutoff_remove = false;       // --grm-cutoff-remove: drop one sample of every reported pair, go on with pcoa_create_grm_subset over the rest
+  bool grm_project_lsq = false;         // --grm-project-lsq: both projections place by least squares over the called variants (pcoa_grm_project_lsq)
   bool grm_project_removed = false;     // --grm-project-removed: the samples a list or a round removed are placed on the final axes
   int outlier_iterations = 0;           // --outlier-iterations K: up to K rounds of outlier removal around computePca; a round replaces the engine by
                                         // its subset over the kept samples (pcoa_create_subset: one gather of S, no variant read twice).  0 = off
@@ -196,6 +197,9 @@ const char* kUsage =
     "                   --grm-outlier-iterations K [--grm-outlier-sigma X, default 6] (--grm: the rounds of --outlier-iterations on subsets\n"
     "                   of the genotype store; --grm-ld-window prunes every round's engine again)\n"
     "                   --grm-project-removed (--grm: the samples a list or a round removed are placed on the final axes)\n"
+    "                   --grm-project-lsq (--grm-project-path / --grm-project-removed: place every sample by least squares over the used\n"
+    "                   variants it is called at, not by mean imputation, which shrinks a sparsely called sample towards the origin;\n"
+    "                   --grm-project-removed then places the samples --grm-mind took out too; at most 16 principal components)\n"
     "                   --grm-cutoff X [--grm-cutoff-divisor used|pairwise] [--grm-related-output-path FILE] [--grm-cutoff-remove]\n"
     "                   (--grm: screen K for related pairs before computePca, behind the sample list and one LD prune: a pair is reported\n"
     "                   when K(i, j) >= X; FILE: name_i, name_j, K, n per pair; --grm-cutoff-remove drops one sample of every pair by the\n"
@@ -332,6 +336,7 @@ Conf parse(int argc, char** argv) {
     else if (a == "--grm-keep-samples") c.grm_keep_samples = one(i);
     else if (a == "--grm-remove-samples") c.grm_remove_samples = one(i);
     else if (a == "--grm-project-removed") c.grm_project_removed = true;
+    else if (a == "--grm-project-lsq") c.grm_project_lsq = true;
     else if (a == "--grm-cutoff") {
       c.grm_cutoff_text = one(i);
       char* end = nullptr;
@@ -523,6 +528,14 @@ Conf parse(int argc, char** argv) {
     if (!c.grm && c.grm_outlier_iterations != 0) die(std::string("--grm-outlier-iterations") + why);
     if (!c.grm && c.grm_outlier_sigma_given) die(std::string("--grm-outlier-sigma") + why);
     if (!c.grm && c.grm_project_removed) die(std::string("--grm-project-removed") + why);
+    if (!c.grm && c.grm_project_lsq)
+      die("--grm-project-lsq needs --grm (it is the least-squares form of --grm-project-path / --grm-project-removed, which place samples on "
+          "the axes of K)");
+    if (c.grm_project_lsq && c.grm_project_path.empty() && !c.grm_project_removed)
+      die("--grm-project-lsq needs --grm-project-path or --grm-project-removed (it chooses how their samples are placed)");
+    if (c.grm_project_lsq && c.num_pc > 16)
+      die("--grm-project-lsq takes at most 16 principal components, not " + std::to_string(c.num_pc) +
+          " (pcoa_grm_project_lsq solves a system of that order per sample)");
     if (!c.grm_keep_samples.empty() && !c.grm_remove_samples.empty())
       die("--grm-keep-samples and --grm-remove-samples exclude each other (one list names the cohort)");
     if (c.grm_outlier_iterations < 0) die("--grm-outlier-iterations must be >= 0 (0 = off)");
@@ -1956,6 +1969,41 @@ bool grm_sample_list(const Conf& conf, const std::vector<std::string>& names, st
   return true;
 }
 
+// The samples of `study` on the panel's axes -- mean-imputed (pcoa_grm_project), or with --grm-project-lsq by least squares
+// (pcoa_grm_project_lsq) -- and the stderr line(s).  labels[q]: the name a message gives sample q.  coords: [num_pc][nq].  Returns
+// placed [nq]: an undetermined sample of the least-squares form is named on stderr and not placed
+std::vector<char> grm_place(const Conf& conf, pcoa_ctx* panel, pcoa_ctx* study, int32_t nq, const std::vector<double>& comps,
+                            const std::vector<double>& lam, const char* what, const std::vector<std::string>& labels,
+                            std::vector<double>& coords) {
+  coords.assign((size_t)conf.num_pc * (size_t)nq, 0.0);
+  std::vector<int32_t> called((size_t)nq), determined((size_t)nq, 1);
+  if (conf.grm_project_lsq)
+    check(panel, pcoa_grm_project_lsq(panel, study, conf.num_pc, comps.data(), coords.data(), called.data(), determined.data(), nullptr),
+          "pcoa_grm_project_lsq");
+  else
+    check(panel, pcoa_grm_project(panel, study, conf.num_pc, comps.data(), lam.data(), coords.data(), called.data()), "pcoa_grm_project");
+  int64_t used = 0, total_called = 0;
+  if (pcoa_grm_info(panel, nullptr, &used, nullptr) != 1) die(std::string("pcoa_grm_info: ") + pcoa_last_error(panel));
+  for (int32_t c : called) total_called += c;
+  const double share = (double)total_called / (double)nq / (double)used;
+  std::vector<char> placed((size_t)nq, 1);
+  if (!conf.grm_project_lsq) {
+    std::fprintf(stderr, "Projected %d %ssamples over %lld used variants (mean call share %.4f)\n", nq, what, (long long)used, share);
+    return placed;
+  }
+  int32_t undetermined = 0;
+  for (int32_t q = 0; q < nq; ++q) undetermined += determined[(size_t)q] ? 0 : 1;
+  std::fprintf(stderr, "Projected %d %ssamples over %lld used variants (mean call share %.4f, least squares, %d undetermined)\n", nq, what,
+               (long long)used, share, undetermined);
+  for (int32_t q = 0; q < nq; ++q) {
+    if (determined[(size_t)q]) continue;
+    placed[(size_t)q] = 0;
+    std::fprintf(stderr, "Not placed: %s is called at %d of %lld used variants, which do not determine %d coordinates\n",
+                 labels[(size_t)q].c_str(), called[(size_t)q], (long long)used, conf.num_pc);
+  }
+  return placed;
+}
+
 // --grm-project-path: the study's kept .bed rows into a GRM study store, block by block, and its samples onto the panel's axes.
 // comps / lam: what pcoa_compute returned on the panel.  Returns the study's rows in .fam order; *called_share: the mean over
 // the samples of (used variants at which the sample is called) / (used variants)
@@ -1988,18 +2036,13 @@ std::vector<OutRow> grm_project_study(const Conf& conf, pcoa_ctx* panel, const P
     }
   }
   check(study, pcoa_gram_finalize(study), "pcoa_gram_finalize (study)");
-  std::vector<double> coords((size_t)conf.num_pc * (size_t)nq);
-  std::vector<int32_t> called((size_t)nq);
-  check(panel, pcoa_grm_project(panel, study, conf.num_pc, comps.data(), lam.data(), coords.data(), called.data()), "pcoa_grm_project");
+  std::vector<double> coords;
+  const std::vector<char> placed = grm_place(conf, panel, study, nq, comps, lam, "", sm.names, coords);
   pcoa_destroy(study);
-  int64_t used = 0, total_called = 0;
-  if (pcoa_grm_info(panel, nullptr, &used, nullptr) != 1) die(std::string("pcoa_grm_info: ") + pcoa_last_error(panel));
-  for (int32_t c : called) total_called += c;
-  std::fprintf(stderr, "Projected %d samples over %lld used variants (mean call share %.4f)\n", nq, (long long)used,
-               (double)total_called / (double)nq / (double)used);
   std::vector<OutRow> rows;
   for (int32_t q = 0; q < nq; ++q)
-    rows.push_back({sm.names[(size_t)q], sm.ids[(size_t)q].substr(0, sm.ids[(size_t)q].find('-')), coords[(size_t)q],
+    if (placed[(size_t)q])
+      rows.push_back({sm.names[(size_t)q], sm.ids[(size_t)q].substr(0, sm.ids[(size_t)q].find('-')), coords[(size_t)q],
                     coords[(size_t)q + (size_t)nq]});
   return rows;
 }
@@ -2878,25 +2921,23 @@ int main(int argc, char** argv) {
     size_t k = 0;
     for (int32_t i = 0; i < n; ++i) {
       if (k < kept.size() && kept[k] == i) ++k;
-      else if (!std::binary_search(grm_mind_gone.begin(), grm_mind_gone.end(), i)) gone.push_back(i);   // (a sparsely called sample is what a mean-imputed projection misplaces)
+      else if (conf.grm_project_lsq || !std::binary_search(grm_mind_gone.begin(), grm_mind_gone.end(), i))
+        gone.push_back(i);   // (a sparsely called sample is what a mean-imputed projection misplaces: least squares places it)
     }
     if (!gone.empty()) {
       const int32_t nq = (int32_t)gone.size();
       pcoa_ctx* study = grm_subset(grm_full, n, gone, PCOA_GRM_SUBSET_STUDY);
-      std::vector<double> coords((size_t)conf.num_pc * (size_t)nq);
-      std::vector<int32_t> called((size_t)nq);
-      check(ctx, pcoa_grm_project(ctx, study, conf.num_pc, comps.data(), lam.data(), coords.data(), called.data()), "pcoa_grm_project");
+      std::vector<std::string> labels;
+      for (int32_t i : gone) labels.push_back(names[(size_t)i]);
+      std::vector<double> coords;
+      const std::vector<char> placed = grm_place(conf, ctx, study, nq, comps, lam, "removed ", labels, coords);
       pcoa_destroy(study);
-      int64_t used = 0, total_called = 0;
-      if (pcoa_grm_info(ctx, nullptr, &used, nullptr) != 1) die(std::string("pcoa_grm_info: ") + pcoa_last_error(ctx));
-      for (int32_t c : called) total_called += c;
-      std::fprintf(stderr, "Projected %d removed samples over %lld used variants (mean call share %.4f)\n", nq, (long long)used,
-                   (double)total_called / (double)nq / (double)used);
       for (int32_t q = 0; q < nq; ++q) {
+        if (!placed[(size_t)q]) continue;
         const size_t i = (size_t)gone[(size_t)q];
         rows.push_back({names[i], ids[i].substr(0, ids[i].find('-')), coords[(size_t)q], coords[(size_t)q + (size_t)nq]});
+        ++n_study;
       }
-      n_study += gone.size();
     }
     if (grm_full != ctx) pcoa_destroy(grm_full);
   }

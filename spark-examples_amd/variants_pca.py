@@ -570,7 +570,7 @@ class PcaConf(object):
         p.add_argument("--grm-mind", type=float, default=None,
                        help="--grm: take out, before anything else, the samples whose share of missing calls over the fileset's "
                             "variants exceeds this, in [0, 1] (plink --mind; pcoa_grm_sample_counts, pcoa_create_grm_subset); they "
-                            "are not placed by --grm-project-removed")
+                            "are not placed by --grm-project-removed, unless --grm-project-lsq is given")
         p.add_argument("--grm-variant-qc-output-path", type=str, default=None,
                        help="--grm: one line per variant of the fileset: index, contig, position, id, called, het, hom-alt, missing "
                             "share, HWE p, 1 (used under --grm-min-maf / --grm-geno / --grm-hwe) or 0")
@@ -621,6 +621,11 @@ class PcaConf(object):
         p.add_argument("--grm-project-removed", action="store_true",
                        help="--grm: every sample a list or an outlier round removed is placed on the final axes "
                             "(pcoa_grm_project over a study subset of the whole fileset's engine); its rows follow the kept samples'")
+        p.add_argument("--grm-project-lsq", action="store_true",
+                       help="--grm-project-path / --grm-project-removed: place every sample by least squares over the used "
+                            "variants it is called at (pcoa_grm_project_lsq, smartpca's lsqproject), not by mean imputation, "
+                            "which shrinks a sparsely called sample towards the origin; --grm-project-removed then places the "
+                            "samples --grm-mind took out too; at most %d principal components" % GRM_LSQ_MAX_PC)
         p.add_argument("--grm-cutoff", type=float, default=None,
                        help="--grm: X: screen K for related sample pairs before computePca (pcoa_grm_pairs: gcta --grm-cutoff, "
                             "plink --rel-cutoff): a pair is reported when K(i, j) >= X, K as --grm-output-path writes it, after "
@@ -1225,6 +1230,9 @@ def check_grm_conf(conf):
         if conf.grm_project_path:
             raise SystemExit("VariantsPcaDriver: --grm-project-path needs --grm (it places a second PLINK fileset on the axes of K; "
                              "VCFs are placed on the principal coordinates of S by --project-input-path)")
+        if conf.grm_project_lsq:
+            raise SystemExit("VariantsPcaDriver: --grm-project-lsq needs --grm (it is the least-squares form of --grm-project-path / "
+                             "--grm-project-removed, which place samples on the axes of K)")
         if conf.grm_output_path:
             raise SystemExit("VariantsPcaDriver: --grm-output-path needs --grm (it writes the relationship matrix K of the "
                              "standardised genotypes; the shared counts S go to --dump-similarity)")
@@ -1282,6 +1290,13 @@ def check_grm_conf(conf):
             raise SystemExit("VariantsPcaDriver: --grm-cutoff must be a finite number (the K at or above which a pair is reported)")
         if conf.grm_cutoff_divisor is not None and conf.grm_cutoff_divisor not in GRM_OUTPUT_DIVISORS:
             raise SystemExit("VariantsPcaDriver: --grm-cutoff-divisor takes used or pairwise, not '%s'" % conf.grm_cutoff_divisor)
+    if conf.grm_project_lsq:
+        if not conf.grm_project_path and not conf.grm_project_removed:
+            raise SystemExit("VariantsPcaDriver: --grm-project-lsq needs --grm-project-path or --grm-project-removed (it chooses how "
+                             "their samples are placed)")
+        if conf.numPc > GRM_LSQ_MAX_PC:
+            raise SystemExit("VariantsPcaDriver: --grm-project-lsq takes at most %d principal components, not %d (pcoa_grm_project_lsq "
+                             "solves a system of that order per sample)" % (GRM_LSQ_MAX_PC, conf.numPc))
     if conf.grm_output_divisor is not None and conf.grm_output_divisor not in GRM_OUTPUT_DIVISORS:
         raise SystemExit("VariantsPcaDriver: --grm-output-divisor takes used or pairwise, not '%s'" % conf.grm_output_divisor)
     if conf.grm_output_divisor is not None and not conf.grm_output_path:
@@ -1326,6 +1341,7 @@ def check_grm_conf(conf):
 
 
 GRM_OUTPUT_DIVISORS = ("used", "pairwise")
+GRM_LSQ_MAX_PC = 16
 GRM_OUTPUT_BAND_ROWS = 1024
 
 
@@ -1459,6 +1475,26 @@ def check_grm_study(panel_path, study_path):
                              "the panel" % (name, study))
 
 
+def grm_place(conf, panel_eng, study, comps, lam, what, labels, err=None):
+    """The samples of `study` on the panel's axes -- mean-imputed (pcoa_grm_project), or with --grm-project-lsq by least squares
+    (pcoa_grm_project_lsq) -- and the stderr line(s).  labels[q]: the name a message gives sample q.  Returns (coords [Nq][k],
+    placed [Nq] bool): an undetermined sample of the least-squares form is named on stderr and not placed."""
+    err = err or sys.stderr
+    used = panel_eng.grm_info()[1]
+    if not conf.grm_project_lsq:
+        coords, called = panel_eng.grm_project(study, comps, lam)
+        err.write("Projected %d %ssamples over %d used variants (mean call share %.4f)\n"
+                  % (study.n, what, used, float(called.mean()) / used))
+        return coords, np.ones(study.n, dtype=bool)
+    coords, called, determined = panel_eng.grm_project_lsq(study, comps)
+    err.write("Projected %d %ssamples over %d used variants (mean call share %.4f, least squares, %d undetermined)\n"
+              % (study.n, what, used, float(called.mean()) / used, int((~determined).sum())))
+    for q in np.nonzero(~determined)[0]:
+        err.write("Not placed: %s is called at %d of %d used variants, which do not determine %d coordinates\n"
+                  % (labels[int(q)], int(called[q]), used, comps.shape[1]))
+    return coords, determined
+
+
 def grm_project_study(conf, panel_eng, comps, lam, err=None):
     """--grm-project-path: the study's .bed rows into a GRM study store (the panel's keep mask applies: the .bim files are
     equal), its samples placed on the panel's axes, and the stderr line.  Returns ([(callset id, name, pc1, pc2)], in the
@@ -1474,14 +1510,11 @@ def grm_project_study(conf, panel_eng, comps, lam, err=None):
             if k.any():
                 study.accumulate_plink_bed(np.ascontiguousarray(geno[v0:v0 + PLINK_BLOCK_ROWS][k]), ref_is_a1=ref_is_a1)
         study.finalize()
-        coords, called = panel_eng.grm_project(study, comps, lam)
-    used = panel_eng.grm_info()[1]
-    (err or sys.stderr).write("Projected %d samples over %d used variants (mean call share %.4f)\n"
-                              % (nq, used, float(called.mean()) / used))
+        reverse = dict((v, k) for (k, v) in indexes.items())
+        coords, placed = grm_place(conf, panel_eng, study, comps, lam, "", [names[reverse[q]] for q in range(nq)], err)
     # the set id as the compiled host assigns it: the second set of the run ('_1' behind a stem the panel has taken)
     set_id = ingest.set_id_of(conf.grm_project_path, 1, set([ingest.set_id_of(conf.inputPath[0])]))
-    reverse = dict((v, k) for (k, v) in indexes.items())
-    return [("%s-%d" % (set_id, q), names[reverse[q]], float(coords[q, 0]), float(coords[q, 1])) for q in range(nq)]
+    return [("%s-%d" % (set_id, q), names[reverse[q]], float(coords[q, 0]), float(coords[q, 1])) for q in range(nq) if placed[q]]
 
 
 def grm_accumulate(call_rdd, matrix_size, min_maf, device=0, err=None, max_missing=1.0, hwe_min_p=0.0):
@@ -1698,20 +1731,19 @@ def grm_compute_rounds(driver, full, kept, meta, err=None):
 def grm_project_removed(driver, full, eng, kept, err=None, never=None):
     """--grm-project-removed: the samples of the whole fileset that are not in the final cohort, as one study subset of the
     ORIGINAL engine, on the final panel's axes.  never: the samples --grm-mind took out, which are not placed (a sparsely called
-    sample is what a mean-imputed projection misplaces).  Returns [(callset id, name, pc1, pc2)] in index order."""
+    sample is what a mean-imputed projection misplaces) unless --grm-project-lsq places by least squares.  Returns [(callset id,
+    name, pc1, pc2)] in index order."""
     removed = np.setdiff1d(np.arange(len(driver.indexes)), kept)
-    if never is not None:
+    if never is not None and not driver.conf.grm_project_lsq:
         removed = np.setdiff1d(removed, never)
     if removed.size == 0:
         return []
     comps, lam = driver.last_pca
-    with grm_subset_engine(full, removed, 0.0, study=True, err=err) as study:
-        coords, called = eng.grm_project(study, comps, lam)
-    used = eng.grm_info()[1]
-    (err or sys.stderr).write("Projected %d removed samples over %d used variants (mean call share %.4f)\n"
-                              % (removed.size, used, float(called.mean()) / used))
     reverse = dict((v, k) for (k, v) in driver.indexes.items())
-    return [(reverse[int(i)], driver.names[reverse[int(i)]], float(coords[q, 0]), float(coords[q, 1])) for q, i in enumerate(removed)]
+    with grm_subset_engine(full, removed, 0.0, study=True, err=err) as study:
+        coords, placed = grm_place(driver.conf, eng, study, comps, lam, "removed ", [driver.names[reverse[int(i)]] for i in removed], err)
+    return [(reverse[int(i)], driver.names[reverse[int(i)]], float(coords[q, 0]), float(coords[q, 1])) for q, i in enumerate(removed)
+            if placed[q]]
 
 
 def grm_ld_prune(conf, eng, meta, out=None):
