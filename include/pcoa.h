@@ -35,7 +35,7 @@ extern "C" {
 #endif
 
 #define PCOA_VERSION_MAJOR 0
-#define PCOA_VERSION_MINOR 17
+#define PCOA_VERSION_MINOR 18
 
 typedef struct pcoa_ctx pcoa_ctx;
 
@@ -492,7 +492,8 @@ int pcoa_get_grm_block_stats(pcoa_ctx* ctx, pcoa_grm_block_stats* out, size_t ou
  *           uses; the (row, tile) counts, the row offsets and min(capacity, N (N - 1) / 2) records for the length of the call,
  *           all allocated before the first launch.  PCOA_ERR_OUT_OF_MEMORY leaves the ctx usable.
  * Not built: a threshold fused into the dense product's epilogue, skipping the tiles of a band's first block that lie below
- * the diagonal, a KING screen over the 2-bit store, multi-GPU, GCTA's own removal order, JNI / Scala natives. */
+ * the diagonal, multi-GPU, GCTA's own removal order, JNI / Scala natives.  (The KING screen over the 2-bit store is
+ * pcoa_grm_king_pairs, below.) */
 typedef struct pcoa_grm_pair { int32_t i, j; double k; int64_t n; } pcoa_grm_pair;   /* i < j, k = K(i, j); 24 bytes */
 int pcoa_grm_pairs(pcoa_ctx* ctx, double cutoff, int32_t divisor, int32_t band_rows /* 0: 1,024 */, pcoa_grm_pair* out_pairs,
                    int64_t capacity, int64_t* n_found_out, double* out_diag /* N doubles, or NULL */);
@@ -593,7 +594,8 @@ int pcoa_get_grm_ld_stats(pcoa_ctx* ctx, pcoa_grm_ld_stats* out, size_t out_size
  * the store's coding, which is a .bed row with ref_is_a1 = 1 (00 g = 0, 01 missing, 10 g = 1, 11 g = 2); the unused slots of the
  * last byte are 00, PLINK's convention.  Either GRM kind.  Feeding the output to a fresh engine with ref_is_a1 = 1 reproduces the
  * store.  Synchronising; no kernel runs.  PCOA_ERR_INVALID_ARG: a window outside the store, a NULL out.
- * Not built: JNI / Scala natives, a KING screen that feeds a GRM engine in one run. */
+ * pcoa_grm_king_pairs on the source, then this call on the samples to keep, is the KING screen that feeds a GRM engine in one run.
+ * Not built: JNI / Scala natives. */
 #define PCOA_GRM_SUBSET_PANEL 0   /* result as from pcoa_create_grm       (n_keep >= 32) */
 #define PCOA_GRM_SUBSET_STUDY 1   /* result as from pcoa_create_grm_study (n_keep >= 1)  */
 int pcoa_create_grm_subset(pcoa_ctx** out, pcoa_ctx* src, const int32_t* keep, int32_t n_keep, int32_t kind);
@@ -902,6 +904,70 @@ typedef struct pcoa_king_stats {
   int64_t king_calls;
 } pcoa_king_stats;
 int pcoa_get_king_stats(pcoa_ctx* plane0, pcoa_king_stats* out, size_t out_size);
+
+/* ---- the KING-robust kinship screen on the resident 2-bit store of a GRM ctx ---------------------------------
+ * K is standardised by cohort-wide allele frequencies, so on a cohort with population structure pcoa_grm_pairs inflates
+ * within-population pairs; the screen the field runs in front of a genotype PCA is plink2 --king-cutoff.  These calls apply
+ * pcoa_king_pairs' rule to the store a GRM ctx already holds: no plane engines, no N x N matrix, no second pass over the
+ * fileset, and the counted rows can be the QC'd, LD-pruned ones.  The rule, on genotype classes: at a row v of the store sample i
+ * is H (heterozygous), R or A (the two homozygotes: KING is symmetric in them, so the store's single coding needs no undoing) or
+ * M (not called; every padding slot is M); C = R u H u A.  Over the COUNTED rows, all exact integers:
+ *   hethet(i, j)  = sum_v H_vi H_vj
+ *   ibs0(i, j)    = sum_v (R_vi A_vj + A_vi R_vj)
+ *   het_sum(i, j) = sum_v (H_vi C_vj + C_vi H_vj)
+ *   the pair (i, j), i < j, is REPORTED iff het_sum > 0 and (double)(hethet - 2 ibs0) >= min_kinship * (double)het_sum
+ * (variants_pca.py's grm_king_rule / grm_king_pairs_rule are the numpy statement).  The diagonal follows the same expressions:
+ * hethet(i, i) = h_i, ibs0(i, i) = 0, het_sum(i, i) = 2 h_i.  Off the diagonal these are the integers pcoa_king_pairs derives from
+ * five plane engines fed the same .bed rows, so the records are the same bytes.
+ *   rows_kind: PCOA_GRM_ROWS_ALL (every row of the store; either GRM kind) or PCOA_GRM_ROWS_USED (the rows with used_v under
+ *           min_maf, the filters and an installed LD mask; PCOA_ERR_STATE on a study ctx), as pcoa_grm_sample_counts.
+ *
+ * pcoa_grm_king_block: the rectangle [row0, row0 + rows) x [col0, col0 + cols) of the three counts, int32, row-major; any output
+ *   may be NULL, not all three; host memory, or device memory of the ctx's device with is_device_ptr.  Four int8 products on
+ *   the matrix cores, fed from the store words (csrc/grm_king.hip), one launch per segment of the store.  Integers: any cut of a
+ *   rectangle gives the same numbers, (i, j) and (j, i) are equal.  Synchronising.
+ * pcoa_grm_king_pairs: walks the upper triangle in bands of band_rows rows (a multiple of 64; 0 = 1,024): the band's counts
+ *   [r0, r0 + band_rows) x [64 floor(r0 / 64), N) go into the ctx's workspace, then count, row scan, offset scan from the running
+ *   total in device memory and the ordered write: one launch chain per band, no host synchronisation between bands.  Pairs come
+ *   out in increasing (i, j) order without a sort.
+ *   min_kinship: finite, in (0, 0.5].
+ *   out_pairs / capacity / *n_found_out: as pcoa_similar_pairs -- the first min(n_found, capacity) pairs, entries behind them
+ *           untouched; capacity 0 is the count-only call; *n_found_out is always the full count.
+ *   *n_rows_out: the counted rows, or NULL.  out_het: N entries h_i over the counted rows (from the bands' diagonal), or NULL.
+ *   Synchronising.  Content and order are a function of the store, the counted rows and min_kinship alone.
+ * Nothing writes the store: pcoa_compute returns the same bits before and after.
+ *   PCOA_ERR_INVALID_ARG, found on the host before any device work: ctx NULL (pcoa_last_error(NULL)), n_found_out NULL, an
+ *           unknown rows_kind, band_rows negative or not a multiple of 64, capacity < 0, capacity > 0 with out_pairs NULL, a
+ *           min_kinship that is not finite or outside (0, 0.5], a rectangle that leaves [0, N)^2, all three outputs NULL.
+ *   PCOA_ERR_STATE, the ctx stays usable: a ctx without a genotype store (the message names its kind), PCOA_GRM_ROWS_USED on a
+ *           study ctx, no counted row, 2^30 or more counted rows (het_sum <= 2 V must fit int32: the plane path's limit).
+ *   memory: 3 * band_rows * 64 ceil(N / 64) int32 (pcoa_grm_king_block with host outputs: one rows * cols int32 per output) in the
+ *           lazily grown buffer pcoa_grm_block uses; the (row, tile) counts, the row offsets, h and min(capacity, N (N - 1) / 2)
+ *           records for the length of the call, all allocated before the first launch.  PCOA_ERR_OUT_OF_MEMORY leaves the ctx
+ *           usable.
+ * Not built: the min-heterozygosity ("between-family") variant, PI_HAT / IBD estimates, a threshold fused into the count kernel's
+ * epilogue, skipping the tiles of a band's first block below the diagonal, a split along variants for small N, multi-GPU,
+ * JNI / Scala natives. */
+int pcoa_grm_king_block(pcoa_ctx* ctx, int32_t rows_kind, int32_t row0, int32_t rows, int32_t col0, int32_t cols,
+                        int32_t* out_hethet, int32_t* out_ibs0, int32_t* out_het_sum /* [rows][cols] each; any may be NULL, not all */,
+                        int is_device_ptr);
+int pcoa_grm_king_pairs(pcoa_ctx* ctx, int32_t rows_kind, double min_kinship, int32_t band_rows /* 0: 1,024; multiple of 64 */,
+                        pcoa_king_pair* out_pairs, int64_t capacity, int64_t* n_found_out,
+                        int64_t* n_rows_out /* counted rows, or NULL */, int64_t* out_het /* N x h_i, or NULL */);
+
+/* What the two calls did on THIS engine, cumulative since pcoa_create_grm / pcoa_reset_timings.  (A struct of its own, like
+ * pcoa_grm_pairs_stats.)  It grows at its end; out_size = sizeof of the struct the caller compiled against.  Synchronising. */
+typedef struct pcoa_grm_king_stats {
+  double grm_king_seconds;          /* HIP-event time of every launch of the calls: the count kernel and the screen            */
+  double grm_king_screen_seconds;   /* of which the screen's count, scan and write kernels                                    */
+  int64_t grm_king_calls;           /* pcoa_grm_king_pairs calls                                                              */
+  int64_t grm_king_bands;
+  double grm_king_macs;             /* int8 multiply-adds the count kernel issued: 4 products * tile rows * tile columns of the
+                                       64 x 64 tiles launched * store rows rounded up to 32 per segment                        */
+  int64_t grm_king_bytes;           /* bytes of the bands the screen's count and write kernels read: 12 per entry              */
+  int64_t grm_king_block_calls;     /* pcoa_grm_king_block calls                                                              */
+} pcoa_grm_king_stats;
+int pcoa_get_grm_king_stats(pcoa_ctx* ctx, pcoa_grm_king_stats* out, size_t out_size);
 
 /* ---- per-variant loadings of the principal coordinates ---------------------------------------------------------------------
  * Which variants drive each axis (smartpca's SNP weights, PLINK 2's --pca var-wts).  With X the V x N carrier bit matrix and

@@ -205,6 +205,19 @@ class PcoaGrmPairsStats(ctypes.Structure):
     ]
 
 
+class PcoaGrmKingStats(ctypes.Structure):
+    """pcoa_grm_king_stats: what pcoa_grm_king_block / pcoa_grm_king_pairs did on the engine."""
+    _fields_ = [
+        ("grm_king_seconds", ctypes.c_double),
+        ("grm_king_screen_seconds", ctypes.c_double),
+        ("grm_king_calls", ctypes.c_int64),
+        ("grm_king_bands", ctypes.c_int64),
+        ("grm_king_macs", ctypes.c_double),
+        ("grm_king_bytes", ctypes.c_int64),
+        ("grm_king_block_calls", ctypes.c_int64),
+    ]
+
+
 class PcoaGrmSubsetStats(ctypes.Structure):
     """pcoa_grm_subset_stats: what pcoa_create_grm_subset did with this engine as its source."""
     _fields_ = [
@@ -322,6 +335,9 @@ _SIGNATURES = [
     ("pcoa_get_grm_block_stats", ctypes.c_int, [_vp, ctypes.POINTER(PcoaGrmBlockStats), ctypes.c_size_t]),
     ("pcoa_grm_pairs", ctypes.c_int, [_vp, ctypes.c_double, _i32, _i32, _vp, _i64, ctypes.POINTER(_i64), _vp]),
     ("pcoa_get_grm_pairs_stats", ctypes.c_int, [_vp, ctypes.POINTER(PcoaGrmPairsStats), ctypes.c_size_t]),
+    ("pcoa_grm_king_block", ctypes.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, ctypes.c_int]),
+    ("pcoa_grm_king_pairs", ctypes.c_int, [_vp, _i32, ctypes.c_double, _i32, _vp, _i64, ctypes.POINTER(_i64), ctypes.POINTER(_i64), _vp]),
+    ("pcoa_get_grm_king_stats", ctypes.c_int, [_vp, ctypes.POINTER(PcoaGrmKingStats), ctypes.c_size_t]),
     ("pcoa_grm_ld_prune", ctypes.c_int, [_vp, _i32, ctypes.c_double, _vp, _i64, ctypes.POINTER(_i64), ctypes.POINTER(_i64)]),
     ("pcoa_grm_ld_mask", ctypes.c_int, [_vp, _i64, _i64, _vp]),
     ("pcoa_grm_ld_clear", ctypes.c_int, [_vp]),

@@ -350,6 +350,22 @@ hipError_t launch_grm_pairs_write(const double* k, const int32_t* nb_or_null, in
                                   int32_t n, double cutoff, int64_t mprime, const int32_t* prefix, const int64_t* rowoff,
                                   int64_t capacity, pcoa_grm_pair* out, unsigned long long* entries_read, hipStream_t stream);
 
+// ---- the KING-robust screen on the 2-bit store (grm_king.hip) ----------------------------------------------------
+// A rectangle of hethet / ibs0 / het_sum (the rule: pcoa.h at pcoa_grm_king_block) as four int8 products on the matrix cores.  One
+// launch per segment; outputs [nrows][ncols] row-major int32, any may be NULL, not all; first = 1: the entries are stored,
+// otherwise added to what the outputs hold.  used_or_null: the segment's used_v, a row with 0 counts as all-missing
+hipError_t launch_grm_king_counts(const uint32_t* seg, int32_t rows, int32_t n, const int32_t* used_or_null, int32_t row0, int32_t nrows,
+                                  int32_t col0, int32_t ncols, int first, int32_t* out_hethet, int32_t* out_ibs0, int32_t* out_het_sum,
+                                  hipStream_t stream);
+// the screen of one row band of the three counts, laid out as launch_grm_pairs_count's band (pitch a multiple of 4, the arrays
+// 16-byte aligned); cnt / rowoff / total_io and the scans are launch_grm_pairs_scan's.  het_or_null[i] = hethet(i, i) = h_i
+hipError_t launch_grm_king_screen_count(const int32_t* hethet, const int32_t* ibs0, const int32_t* het_sum, int64_t pitch, int32_t r0,
+                                        int32_t nrows, int32_t c0, int32_t n, double x, int32_t* cnt, int64_t* het_or_null,
+                                        hipStream_t stream);
+hipError_t launch_grm_king_screen_write(const int32_t* hethet, const int32_t* ibs0, const int32_t* het_sum, int64_t pitch, int32_t r0,
+                                        int32_t nrows, int32_t c0, int32_t n, double x, const int32_t* prefix, const int64_t* rowoff,
+                                        int64_t capacity, pcoa_king_pair* out, unsigned long long* entries_read, hipStream_t stream);
+
 // ---- per-variant loadings (loadings.hip): out[v * num_pc + c] = (sum_i bit(v, i) u[c * ustride + i]) / div[c] for c in [0, k) ----
 // u: prepared vectors, ustride = 32 ceil(n / 32) doubles each, zero for i >= n (that is what ignores a row's tail bits); div: k
 // divisors or NULL; k must be 1, 2, 4 or 8 (loadings_chunk picks the chunk); out / u / div point at the chunk's first component.

@@ -812,6 +812,64 @@ class PcoaEngine(object):
         self._check(self._lib.pcoa_get_grm_pairs_stats(self._ctx, ctypes.byref(q), ctypes.sizeof(q)))
         return dict((f[0], getattr(q, f[0])) for f in L.PcoaGrmPairsStats._fields_)
 
+    # ------------------------------------------------------------------ the KING-robust screen on the 2-bit store
+    GRM_ROWS = {"all": L.PCOA_GRM_ROWS_ALL, "used": L.PCOA_GRM_ROWS_USED}
+
+    def _grm_rows_kind(self, rows):
+        if isinstance(rows, str):
+            if rows not in self.GRM_ROWS:
+                raise ValueError("rows must be one of all, used, not %r" % (rows,))
+            return self.GRM_ROWS[rows]
+        return int(rows)   # (an unknown number is the library's error)
+
+    def grm_king_block(self, row0, rows, col0, cols, rows_kind="all", hethet=True, ibs0=True, het_sum=True, device=False):
+        """The rectangle [row0, row0 + rows) x [col0, col0 + cols) of the three KING counts over the store's counted rows
+        (pcoa_grm_king_block; variants_pca.grm_king_rule is the rule), int32.  rows_kind: "all" (every row of the store) or
+        "used" (used_v under the min MAF, the filters and an installed LD mask).  Returns (hethet, ibs0, het_sum); an output
+        switched off comes back as None and is not computed into.  device=True: torch tensors on this engine's GPU, written by
+        the kernel directly; otherwise numpy arrays."""
+        kind = self._grm_rows_kind(rows_kind)
+        shape = (max(int(rows), 0), max(int(cols), 0))
+        want = (bool(hethet), bool(ibs0), bool(het_sum))
+        if device:
+            import torch  # plumbing only: device memory handles
+            dev = torch.device("cuda", self.device)
+            outs = [torch.empty(shape, dtype=torch.int32, device=dev) if w else None for w in want]
+            torch.cuda.current_stream(dev).synchronize()   # the engine runs on its own stream
+            ptrs = [ctypes.c_void_p(o.data_ptr()) if o is not None and o.numel() else None for o in outs]
+        else:
+            outs = [np.zeros(shape, dtype=np.int32) if w else None for w in want]
+            ptrs = [_ptr(o) if o is not None and o.size else None for o in outs]
+        self._check(self._lib.pcoa_grm_king_block(self._ctx, kind, int(row0), int(rows), int(col0), int(cols), ptrs[0], ptrs[1], ptrs[2],
+                                                  int(bool(device))))
+        return tuple(outs)
+
+    def grm_king_pairs(self, min_kinship, rows="all", band_rows=0, capacity=1 << 20, het=False):
+        """The KING-robust kinship screen on the resident genotype store (pcoa_grm_king_pairs): the pairs i < j with het_sum > 0
+        and hethet - 2 ibs0 >= min_kinship * het_sum over the counted rows (rows: "all" or "used"), found on the device a band
+        of `band_rows` rows (0: 1,024; a multiple of 64) at a time; variants_pca.grm_king_pairs_rule is the rule.  Returns
+        (pairs, n_found, n_rows), or (pairs, n_found, n_rows, h) with het=True: `pairs` a KING_PAIR_DTYPE array of the first
+        min(n_found, capacity) pairs in increasing (i, j) order, `n_found` the full count whatever the capacity, `n_rows` the
+        counted rows, `h` the heterozygous counted rows of every sample, int64 [N]."""
+        kind = self._grm_rows_kind(rows)
+        cap = int(capacity)
+        pairs = np.zeros(max(cap, 0), dtype=self.KING_PAIR_DTYPE)
+        h = np.zeros(self.n, dtype=np.int64) if het else None
+        found = ctypes.c_int64(0)
+        counted = ctypes.c_int64(0)
+        self._check(self._lib.pcoa_grm_king_pairs(self._ctx, kind, float(min_kinship), int(band_rows), _ptr(pairs) if cap > 0 else None,
+                                                  cap, ctypes.byref(found), ctypes.byref(counted), _ptr(h) if het else None))
+        n_found = int(found.value)
+        out = (pairs[:min(n_found, cap)], n_found, int(counted.value))
+        return out + (h,) if het else out
+
+    def grm_king_stats(self):
+        """pcoa_get_grm_king_stats: grm_king_seconds / grm_king_screen_seconds / grm_king_calls / grm_king_bands / grm_king_macs /
+        grm_king_bytes / grm_king_block_calls."""
+        q = L.PcoaGrmKingStats()
+        self._check(self._lib.pcoa_get_grm_king_stats(self._ctx, ctypes.byref(q), ctypes.sizeof(q)))
+        return dict((f[0], getattr(q, f[0])) for f in L.PcoaGrmKingStats._fields_)
+
     # ------------------------------------------------------------------ LD pruning of the GRM store
     def grm_ld_prune(self, window, r2_max, breaks=()):
         """LD-prunes the resident genotype store by the r^2 of the dosages over the jointly called samples (pcoa_grm_ld_prune;

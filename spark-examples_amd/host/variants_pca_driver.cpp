@@ -121,6 +121,15 @@ struct Conf {  // PcaConf / GenomicsConf (GenomicsConf.scala:31-101), same flag 
   bool has_grm_cutoff_divisor = false;
   std::string grm_related_output_path;  // --grm-related-output-path FILE: the reported pairs, one line each
   bool has_grm_related_output_path = false;
+  bool grm_king = false;                // --grm-king-cutoff X given: --grm: the KING-robust kinship screen of the genotype store before computePca
+  double grm_king_cutoff = 0.0;         // (pcoa_grm_king_pairs), where --grm-cutoff runs: a pair is reported when (hethet - 2 ibs0) / het_sum >= X
+  std::string grm_king_rows;            // --grm-king-rows all|used: the counted variants: used_v (default) or every row of the store
+  bool has_grm_king_rows = false;
+  std::string grm_king_output_path;     // --grm-king-output-path FILE: the reported pairs in the format of --king-output-path
+  bool has_grm_king_output_path = false;
+  int64_t grm_king_max_pairs = 1048576; // --grm-king-max-pairs M: the capacity handed to the library; more reported pairs stop the job
+  bool grm_king_max_pairs_given = false;
+  bool grm_king_remove = false;         // --grm-king-remove: drop one sample of every reported pair, go on with pcoa_create_grm_subset over the rest
   bool grm_cutoff_remove = false;       // --grm-cutoff-remove: drop one sample of every reported pair, go on with pcoa_create_grm_subset over the rest
   bool grm_project_lsq = false;         // --grm-project-lsq: both projections place by least squares over the called variants (pcoa_grm_project_lsq)
   bool grm_project_removed = false;     // --grm-project-removed: the samples a list or a round removed are placed on the final axes
@@ -200,6 +209,8 @@ const char* kUsage =
     "                   --grm-project-lsq (--grm-project-path / --grm-project-removed: place every sample by least squares over the used\n"
     "                   variants it is called at, not by mean imputation, which shrinks a sparsely called sample towards the origin;\n"
     "                   --grm-project-removed then places the samples --grm-mind took out too; at most 16 principal components)\n"
+    "                   --grm-king-cutoff X [--grm-king-rows all|used] [--grm-king-output-path FILE] [--grm-king-max-pairs M] [--grm-king-remove]\n"
+    "                   (the KING-robust kinship screen of the genotype store, where --grm-cutoff runs: pcoa_grm_king_pairs)\n"
     "                   --grm-cutoff X [--grm-cutoff-divisor used|pairwise] [--grm-related-output-path FILE] [--grm-cutoff-remove]\n"
     "                   (--grm: screen K for related pairs before computePca, behind the sample list and one LD prune: a pair is reported\n"
     "                   when K(i, j) >= X; FILE: name_i, name_j, K, n per pair; --grm-cutoff-remove drops one sample of every pair by the\n"
@@ -353,6 +364,31 @@ Conf parse(int argc, char** argv) {
       c.has_grm_related_output_path = true;
     }
     else if (a == "--grm-cutoff-remove") c.grm_cutoff_remove = true;
+    else if (a == "--grm-king-cutoff") {
+      const std::string v = one(i);
+      char* end = nullptr;
+      c.grm_king_cutoff = std::strtod(v.c_str(), &end);
+      if (v.empty() || *end != 0) die("--grm-king-cutoff takes a number in (0, 0.5], not '" + v + "'");
+      c.grm_king = true;
+    }
+    else if (a == "--grm-king-rows") {
+      c.grm_king_rows = one(i);
+      c.has_grm_king_rows = true;
+    }
+    else if (a == "--grm-king-output-path") {
+      c.grm_king_output_path = one(i);
+      c.has_grm_king_output_path = true;
+    }
+    else if (a == "--grm-king-max-pairs") {
+      const std::string v = one(i);
+      char* end = nullptr;
+      errno = 0;
+      const long long m = std::strtoll(v.c_str(), &end, 10);
+      if (v.empty() || *end != 0 || errno != 0) die("--grm-king-max-pairs takes an integer >= 0, not '" + v + "'");
+      c.grm_king_max_pairs = (int64_t)m;
+      c.grm_king_max_pairs_given = true;
+    }
+    else if (a == "--grm-king-remove") c.grm_king_remove = true;
     else if (a == "--grm-outlier-iterations") {
       const std::string v = one(i);
       char* end = nullptr;
@@ -513,6 +549,15 @@ Conf parse(int argc, char** argv) {
     if (!c.grm && c.grm_cutoff_remove) die(std::string("--grm-cutoff-remove") + why);
   }
   {
+    const char* why = " needs --grm (it screens the genotype store of the standardised-genotype PCA by KING-robust kinship; a stored "
+                      "similarity matrix is screened by --king-cutoff)";
+    if (!c.grm && c.grm_king) die(std::string("--grm-king-cutoff") + why);
+    if (!c.grm && c.has_grm_king_rows) die(std::string("--grm-king-rows") + why);
+    if (!c.grm && c.has_grm_king_output_path) die(std::string("--grm-king-output-path") + why);
+    if (!c.grm && c.grm_king_max_pairs_given) die(std::string("--grm-king-max-pairs") + why);
+    if (!c.grm && c.grm_king_remove) die(std::string("--grm-king-remove") + why);
+  }
+  {
     const char* why = " needs --grm (it prunes the genotype store of the standardised-genotype PCA; the carrier counts S are pruned by --ld-window)";
     if (!c.grm && c.grm_ld_window != 0) die(std::string("--grm-ld-window") + why);
     if (!c.grm && c.grm_ld_r2_given) die(std::string("--grm-ld-r2") + why);
@@ -551,6 +596,20 @@ Conf parse(int argc, char** argv) {
     if (!std::isfinite(c.grm_cutoff)) die("--grm-cutoff must be a finite number (the K at or above which a pair is reported)");
     if (c.has_grm_cutoff_divisor && c.grm_cutoff_divisor != "used" && c.grm_cutoff_divisor != "pairwise")
       die("--grm-cutoff-divisor takes used or pairwise, not '" + c.grm_cutoff_divisor + "'");
+  }
+  if (!c.grm_king) {
+    const char* why = " needs --grm-king-cutoff X (the screen is off without it)";
+    if (c.has_grm_king_rows) die(std::string("--grm-king-rows") + why);
+    if (c.has_grm_king_output_path) die(std::string("--grm-king-output-path") + why);
+    if (c.grm_king_max_pairs_given) die(std::string("--grm-king-max-pairs") + why);
+    if (c.grm_king_remove) die(std::string("--grm-king-remove") + why);
+  } else {
+    if (!(c.grm_king_cutoff > 0 && c.grm_king_cutoff <= 0.5)) die("--grm-king-cutoff must be a finite number in (0, 0.5]");
+    if (c.has_grm_king_rows && c.grm_king_rows != "all" && c.grm_king_rows != "used")
+      die("--grm-king-rows takes all or used, not '" + c.grm_king_rows + "'");
+    if (c.grm_king_max_pairs < 0) die("--grm-king-max-pairs must be >= 0 (the pairs --grm-king-cutoff may report)");
+    if (c.grm_king_remove && c.grm_cutoff_remove)
+      die("--grm-king-remove and --grm-cutoff-remove exclude each other (one relatedness screen removes samples per run)");
   }
   if (c.has_grm_output_divisor && c.grm_output_divisor != "used" && c.grm_output_divisor != "pairwise")
     die("--grm-output-divisor takes used or pairwise, not '" + c.grm_output_divisor + "'");
@@ -2091,7 +2150,7 @@ int main(int argc, char** argv) {
   std::vector<int32_t> grm_mind_gone;   // --grm-mind: the samples it took out (never placed by --grm-project-removed)
   std::vector<int32_t> grm_listed;   // --grm-keep-samples / --grm-remove-samples: the kept indices; a wrong list is refused here
   bool grm_has_list = conf.grm && grm_sample_list(conf, names, &grm_listed);   // (--grm-mind joins the list after the feed)
-  const bool grm_rounds = conf.grm && (grm_has_list || conf.grm_outlier_iterations > 0 || conf.grm_cutoff_given || conf.has_grm_mind);
+  const bool grm_rounds = conf.grm && (grm_has_list || conf.grm_outlier_iterations > 0 || conf.grm_cutoff_given || conf.grm_king || conf.has_grm_mind);
   // A single VCF is streamed as well (r05): the header gives the callsets, then every 16-MiB block is parsed by the thread
   // pool, filtered (--references, --min-allele-frequency) and handed to the engine as carrier lists while the next one is
   // read -- the records of the whole file are never held (VariantsRDD.compute is an iterator, rdd/VariantsRDD.scala:205-235).
@@ -2815,6 +2874,61 @@ int main(int argc, char** argv) {
         const int32_t least = std::max(32, conf.num_pc + 1);
         if (m - (int32_t)gone.size() < least)
           die("--grm --grm-cutoff-remove leaves " + std::to_string(m - (int32_t)gone.size()) + " of " + std::to_string(m) +
+              " samples, fewer than the " + std::to_string(least) + " a GRM engine with " + std::to_string(conf.num_pc) +
+              " principal components needs");
+        std::vector<int32_t> stay, kept_next;
+        size_t g = 0;
+        for (int32_t a = 0; a < m; ++a) {
+          if (g < gone.size() && gone[g] == a) {
+            ++g;
+          } else {
+            stay.push_back(a);
+            kept_next.push_back(kept[(size_t)a]);
+          }
+        }
+        grm_replace(grm_subset(ctx, m, stay, PCOA_GRM_SUBSET_PANEL));
+        kept.swap(kept_next);
+        pruned = false;
+      }
+    }
+    if (conf.grm_king) {
+      // --grm-king-cutoff X: where --grm-cutoff runs, on the variants that would be decomposed (rows used) or on all of them.  The
+      // rule, as pcoa.h and variants_pca.py's grm_king_pairs_rule state it: the pair (i, j), i < j, is reported iff het_sum > 0
+      // and (double)(hethet - 2 ibs0) >= X * (double)het_sum.  Then the pair file in the format of --king-output-path, one stderr
+      // line, and with --grm-king-remove the removal rule of --remove-related and the subset
+      if (conf.grm_ld_window > 0 && !pruned) {
+        grm_ld_prune_now(ctx);
+        pruned = true;
+      }
+      const int32_t m = (int32_t)kept.size();
+      const bool all_rows = conf.grm_king_rows == "all";
+      std::vector<pcoa_king_pair> found((size_t)std::min<int64_t>(conf.grm_king_max_pairs, (int64_t)m * (m - 1) / 2));
+      int64_t n_found = 0, n_rows = 0;
+      check(ctx, pcoa_grm_king_pairs(ctx, all_rows ? PCOA_GRM_ROWS_ALL : PCOA_GRM_ROWS_USED, conf.grm_king_cutoff, 0,
+                                     found.empty() ? nullptr : found.data(), (int64_t)found.size(), &n_found, &n_rows, nullptr),
+            "pcoa_grm_king_pairs");
+      if (n_found > conf.grm_king_max_pairs)
+        die("--grm-king-cutoff " + java_double(conf.grm_king_cutoff) + " reports " + std::to_string(n_found) +
+            " pairs, more than --grm-king-max-pairs " + std::to_string(conf.grm_king_max_pairs) +
+            " takes; raise --grm-king-max-pairs or the cutoff");
+      found.resize((size_t)n_found);
+      if (conf.has_grm_king_output_path) {
+        std::ofstream out(conf.grm_king_output_path);
+        out << "name_i\tname_j\thethet\tibs0\thet_sum\tkinship\n";
+        for (const pcoa_king_pair& p : found)
+          out << names[(size_t)kept[(size_t)p.i]] << "\t" << names[(size_t)kept[(size_t)p.j]] << "\t" << p.hethet << "\t" << p.ibs0 << "\t"
+              << p.het_sum << "\t" << java_double((double)(p.hethet - 2 * p.ibs0) / (double)p.het_sum) << "\n";
+        if (!out) die("cannot write " + conf.grm_king_output_path);
+      }
+      std::vector<pcoa_pair> pairs(found.size());
+      for (size_t k = 0; k < found.size(); ++k) pairs[k] = pcoa_pair{found[k].i, found[k].j, 0};
+      const std::vector<int32_t> gone = conf.grm_king_remove ? related_removal(pairs, m) : std::vector<int32_t>();
+      std::fprintf(stderr, "GRM KING: %lld pair(s) with kinship >= %s over %lld row(s) (rows %s), removed %zu sample(s)\n",
+                   (long long)n_found, java_double(conf.grm_king_cutoff).c_str(), (long long)n_rows, all_rows ? "all" : "used", gone.size());
+      if (!gone.empty()) {
+        const int32_t least = std::max(32, conf.num_pc + 1);
+        if (m - (int32_t)gone.size() < least)
+          die("--grm --grm-king-remove leaves " + std::to_string(m - (int32_t)gone.size()) + " of " + std::to_string(m) +
               " samples, fewer than the " + std::to_string(least) + " a GRM engine with " + std::to_string(conf.num_pc) +
               " principal components needs");
         std::vector<int32_t> stay, kept_next;

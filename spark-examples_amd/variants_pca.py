@@ -425,6 +425,47 @@ def king_kinship(pairs):
     return (pairs["hethet"] - 2 * pairs["ibs0"]).astype(np.float64) / pairs["het_sum"].astype(np.float64)
 
 
+def grm_king_rule(codes, counted=None):
+    """The counts of pcoa_grm_king_block (include/pcoa.h; csrc/grm_king.hip restates them on the matrix cores): `codes` is
+    [V][N] of 2-bit codes, 1 = not called (M), 2 = heterozygous (H), 0 and 3 the two homozygotes (R, A) -- .bed codes or the
+    store's, the rule is symmetric in the homozygotes -- and `counted` a [V] mask of the counted rows (None: all).  With
+    C = R u H u A, over the counted rows:
+      hethet[i, j]  = sum_v H_vi H_vj
+      ibs0[i, j]    = sum_v (R_vi A_vj + A_vi R_vj)
+      het_sum[i, j] = sum_v (H_vi C_vj + C_vi H_vj)
+    Returns (hethet, ibs0, het_sum), int64 [N][N], diagonal included (h_i, 0, 2 h_i).  Off the diagonal they are king_counts'
+    integers from the five plane Grams of the same codes."""
+    codes = np.asarray(codes, dtype=np.uint8)
+    if codes.ndim != 2 or codes.size and int(codes.max()) > 3:
+        raise ValueError("codes must be [V][N] with values 0 .. 3")
+    if counted is not None:
+        counted = np.asarray(counted).astype(bool)
+        if counted.shape != (codes.shape[0],):
+            raise ValueError("counted must be one flag per row of codes")
+        codes = codes[counted]
+    h = (codes == 2).astype(np.float64)            # 0 / 1 sums in float64: exact far beyond any V, and BLAS does them
+    r = (codes == 0).astype(np.float64)
+    a = (codes == 3).astype(np.float64)
+    c = h + r + a
+    hc = (h.T @ c).astype(np.int64)
+    ra = (r.T @ a).astype(np.int64)
+    return (h.T @ h).astype(np.int64), ra + ra.T, hc + hc.T
+
+
+def grm_king_pairs_rule(codes, x, counted=None):
+    """The rule of --grm-king-cutoff and of pcoa_grm_king_pairs: with the counts of grm_king_rule and num = hethet - 2 ibs0, the
+    pair (i, j), i < j, is reported iff het_sum > 0 and float64(num) >= x * float64(het_sum) -- king_pairs_rule's comparison on
+    the same integers.  Returns the reported pairs in increasing (i, j) order as KING_PAIR_DTYPE."""
+    hethet, ibs0, het_sum = grm_king_rule(codes, counted)
+    num = hethet - 2 * ibs0
+    hit = (het_sum > 0) & (num.astype(np.float64) >= np.float64(x) * het_sum.astype(np.float64))
+    hit &= np.triu(np.ones(hethet.shape, dtype=bool), 1)
+    i, j = np.nonzero(hit)                      # row-major: increasing (i, j)
+    out = np.zeros(i.size, dtype=KING_PAIR_DTYPE)
+    out["i"], out["j"], out["hethet"], out["ibs0"], out["het_sum"] = i, j, hethet[i, j], ibs0[i, j], het_sum[i, j]
+    return out
+
+
 # --------------------------------------------------------------------------------------------- similarity measures
 SIMILARITY_MEASURES =("shared", "jaccard", "cosine")   # PCOA_SIMILARITY_SHARED / _JACCARD / _COSINE = 0 / 1 / 2 (include/pcoa.h)
 
@@ -638,6 +679,23 @@ class PcaConf(object):
         p.add_argument("--grm-cutoff-remove", action="store_true",
                        help="--grm-cutoff: drop one sample of every reported pair (the rule of --remove-related) and go on with "
                             "the engine's subset over the rest; --grm-project-removed places the dropped samples too")
+        p.add_argument("--grm-king-cutoff", type=float, default=None,
+                       help="--grm: X in (0, 0.5]: screen the genotype store for relatives by the KING-robust kinship coefficient "
+                            "before computePca (pcoa_grm_king_pairs: plink2 --king-cutoff), where --grm-cutoff runs: a pair is "
+                            "reported when (hethet - 2 ibs0) / het_sum over the counted variants is at least X.  It does not depend "
+                            "on allele frequencies, so it holds on a cohort with population structure where --grm-cutoff does "
+                            "not; no plane engines, no N x N matrix, no second pass over the fileset")
+        p.add_argument("--grm-king-rows", type=str, default=None,
+                       help="--grm-king-cutoff: used (default): the variants used under the min MAF, --grm-geno, --grm-hwe and the "
+                            "--grm-ld-window prune; all: every variant of the fileset")
+        p.add_argument("--grm-king-output-path", type=str, default=None,
+                       help="--grm-king-cutoff: write the reported pairs to this file in the format of --king-output-path")
+        p.add_argument("--grm-king-max-pairs", type=int, default=None,
+                       help="--grm-king-cutoff: the most pairs the job takes from the library (default 1048576); if more are "
+                            "reported the job stops")
+        p.add_argument("--grm-king-remove", action="store_true",
+                       help="--grm-king-cutoff: drop one sample of every reported pair (the rule of --remove-related) and go on "
+                            "with the engine's subset over the rest; --grm-project-removed places the dropped samples too")
         p.add_argument("--grm-output-divisor", type=str, default=None,
                        help="--grm-output-path: used (default): num / M', the mean-imputed K that is decomposed; pairwise: "
                             "num / n(i, j), the pairwise-complete estimator GCTA-style tools store")
@@ -721,6 +779,9 @@ class PcaConf(object):
         self.related_max_pairs_given = a.related_max_pairs is not None
         if a.related_max_pairs is None:
             self.related_max_pairs = RELATED_MAX_PAIRS
+        self.grm_king_max_pairs_given = a.grm_king_max_pairs is not None
+        if a.grm_king_max_pairs is None:
+            self.grm_king_max_pairs = RELATED_MAX_PAIRS
         self.king_max_pairs_given = a.king_max_pairs is not None
         if a.king_max_pairs is None:
             self.king_max_pairs = RELATED_MAX_PAIRS
@@ -1251,6 +1312,10 @@ def check_grm_conf(conf):
             if given:
                 raise SystemExit("VariantsPcaDriver: %s needs --grm (it screens the relationship matrix K of the standardised "
                                  "genotypes; a stored similarity matrix is screened by --related-min-jaccard / --king-cutoff)" % flag)
+        for given, flag in GRM_KING_FLAGS(conf):
+            if given:
+                raise SystemExit("VariantsPcaDriver: %s needs --grm (it screens the genotype store of the standardised-genotype "
+                                 "PCA by KING-robust kinship; a stored similarity matrix is screened by --king-cutoff)" % flag)
         for given, flag in ((conf.grm_ld_window != 0, "--grm-ld-window"), (conf.grm_ld_r2 is not None, "--grm-ld-r2"),
                             (bool(conf.grm_ld_output_path), "--grm-ld-output-path")):
             if given:
@@ -1290,6 +1355,20 @@ def check_grm_conf(conf):
             raise SystemExit("VariantsPcaDriver: --grm-cutoff must be a finite number (the K at or above which a pair is reported)")
         if conf.grm_cutoff_divisor is not None and conf.grm_cutoff_divisor not in GRM_OUTPUT_DIVISORS:
             raise SystemExit("VariantsPcaDriver: --grm-cutoff-divisor takes used or pairwise, not '%s'" % conf.grm_cutoff_divisor)
+    if conf.grm_king_cutoff is None:
+        for given, flag in GRM_KING_FLAGS(conf)[1:]:
+            if given:
+                raise SystemExit("VariantsPcaDriver: %s needs --grm-king-cutoff X (the screen is off without it)" % flag)
+    else:
+        if not (conf.grm_king_cutoff > 0 and conf.grm_king_cutoff <= 0.5):   # (NaN fails both comparisons)
+            raise SystemExit("VariantsPcaDriver: --grm-king-cutoff must be a finite number in (0, 0.5]")
+        if conf.grm_king_rows is not None and conf.grm_king_rows not in GRM_KING_ROWS:
+            raise SystemExit("VariantsPcaDriver: --grm-king-rows takes all or used, not '%s'" % conf.grm_king_rows)
+        if conf.grm_king_max_pairs < 0:
+            raise SystemExit("VariantsPcaDriver: --grm-king-max-pairs must be >= 0 (the pairs --grm-king-cutoff may report)")
+        if conf.grm_king_remove and conf.grm_cutoff_remove:
+            raise SystemExit("VariantsPcaDriver: --grm-king-remove and --grm-cutoff-remove exclude each other (one relatedness "
+                             "screen removes samples per run)")
     if conf.grm_project_lsq:
         if not conf.grm_project_path and not conf.grm_project_removed:
             raise SystemExit("VariantsPcaDriver: --grm-project-lsq needs --grm-project-path or --grm-project-removed (it chooses how "
@@ -1662,6 +1741,43 @@ def grm_screen_related(conf, eng, names, err=None):
     return gone
 
 
+GRM_KING_ROWS = ("all", "used")   # --grm-king-rows: PCOA_GRM_ROWS_ALL / PCOA_GRM_ROWS_USED
+
+
+def GRM_KING_FLAGS(conf):
+    """(given, flag) of --grm-king-cutoff and its dependants, the cutoff first."""
+    return [(conf.grm_king_cutoff is not None, "--grm-king-cutoff"), (conf.grm_king_rows is not None, "--grm-king-rows"),
+            (conf.grm_king_output_path is not None, "--grm-king-output-path"),
+            (conf.grm_king_max_pairs_given, "--grm-king-max-pairs"), (conf.grm_king_remove, "--grm-king-remove")]
+
+
+def write_king_pairs(path, pairs, names):
+    """The pair file of --king-output-path and --grm-king-output-path: one header line, then name_i, name_j, hethet, ibs0,
+    het_sum, kinship per pair, tab-separated, the kinship as Java's Double.toString writes it."""
+    kinship = king_kinship(pairs)
+    with open(path, "w") as f:
+        f.write("name_i\tname_j\thethet\tibs0\thet_sum\tkinship\n")
+        for p, k in zip(pairs, kinship):
+            f.write("%s\t%s\t%d\t%d\t%d\t%s\n" % (names[int(p["i"])], names[int(p["j"])], p["hethet"], p["ibs0"], p["het_sum"],
+                                                  java_double_to_string(float(k))))
+
+
+def grm_screen_king(conf, eng, names, err=None):
+    """--grm-king-cutoff X on the engine that is about to be decomposed (pcoa_grm_king_pairs): the pair file, the stderr line
+    and, with --grm-king-remove, the samples related_removal takes out (indices of `eng`, sorted; empty otherwise)."""
+    x, cap, rows = conf.grm_king_cutoff, conf.grm_king_max_pairs, conf.grm_king_rows or "used"
+    pairs, n_found, n_rows = eng.grm_king_pairs(x, rows=rows, capacity=cap)
+    if n_found > cap:
+        raise SystemExit("VariantsPcaDriver: --grm-king-cutoff %s reports %d pairs, more than --grm-king-max-pairs %d "
+                         "takes; raise --grm-king-max-pairs or the cutoff" % (java_double_to_string(x), n_found, cap))
+    if conf.grm_king_output_path:
+        write_king_pairs(conf.grm_king_output_path, pairs, names)
+    gone = related_removal(pairs, eng.n) if conf.grm_king_remove else np.zeros(0, dtype=np.int64)
+    (err or sys.stderr).write("GRM KING: %d pair(s) with kinship >= %s over %d row(s) (rows %s), removed %d sample(s)\n"
+                              % (n_found, java_double_to_string(x), n_rows, rows, gone.size))
+    return gone
+
+
 def grm_compute_rounds(driver, full, kept, meta, err=None):
     """computePca of --grm around --grm-keep-samples / --grm-remove-samples (`kept`: the list's indices, or None) and
     --grm-outlier-iterations K: the loop of computePcaOutlierRounds with the engine replaced by its grm_subset over the kept
@@ -1696,6 +1812,21 @@ def grm_compute_rounds(driver, full, kept, meta, err=None):
             least = max(GRM_MIN_COHORT, conf.numPc + 1)
             if kept.size - gone.size < least:
                 raise SystemExit("VariantsPcaDriver: --grm --grm-cutoff-remove leaves %d of %d samples, fewer than the %d a GRM "
+                                 "engine with %d principal components needs" % (kept.size - gone.size, kept.size, least, conf.numPc))
+            stay = np.setdiff1d(np.arange(kept.size), gone)
+            eng = replace(grm_subset_engine(eng, stay, min_maf, err=err))
+            kept = kept[stay]
+            pruned = False
+    if conf.grm_king_cutoff is not None:
+        # --grm-king-cutoff: where --grm-cutoff runs, on the variants that would be decomposed (rows used) or on all of them
+        if conf.grm_ld_window and not pruned:
+            grm_ld_prune(conf, eng, meta)
+            pruned = True
+        gone = grm_screen_king(conf, eng, [driver.names[reverse[int(i)]] for i in kept], err=err)
+        if gone.size:
+            least = max(GRM_MIN_COHORT, conf.numPc + 1)
+            if kept.size - gone.size < least:
+                raise SystemExit("VariantsPcaDriver: --grm --grm-king-remove leaves %d of %d samples, fewer than the %d a GRM "
                                  "engine with %d principal components needs" % (kept.size - gone.size, kept.size, least, conf.numPc))
             stay = np.setdiff1d(np.arange(kept.size), gone)
             eng = replace(grm_subset_engine(eng, stay, min_maf, err=err))
@@ -2256,7 +2387,7 @@ def main(args):
                 if listed.size < least:
                     raise SystemExit("VariantsPcaDriver: --grm --grm-mind leaves %d of %d samples, fewer than the %d a GRM engine "
                                      "with %d principal components needs" % (listed.size, n, least, conf.numPc))
-        if listed is None and conf.grm_outlier_iterations == 0 and conf.grm_cutoff is None:
+        if listed is None and conf.grm_outlier_iterations == 0 and conf.grm_cutoff is None and conf.grm_king_cutoff is None:
             if conf.grm_ld_window:
                 grm_ld_prune(conf, driver.engine, variant_meta)
             result, kept = driver.computePca(driver.engine), np.arange(n)
