@@ -35,7 +35,7 @@ extern "C" {
 #endif
 
 #define PCOA_VERSION_MAJOR 0
-#define PCOA_VERSION_MINOR 18
+#define PCOA_VERSION_MINOR 19
 
 typedef struct pcoa_ctx pcoa_ctx;
 
@@ -968,6 +968,87 @@ typedef struct pcoa_grm_king_stats {
   int64_t grm_king_block_calls;     /* pcoa_grm_king_block calls                                                              */
 } pcoa_grm_king_stats;
 int pcoa_get_grm_king_stats(pcoa_ctx* ctx, pcoa_grm_king_stats* out, size_t out_size);
+
+/* ---- PC-Relate kinship on the resident 2-bit store of a GRM ctx ------------------------------------------------
+ * pcoa_grm_pairs thresholds K, which is standardised by cohort-wide frequencies and inflates every pair that shares ancestry;
+ * pcoa_grm_king_pairs needs no frequencies but is biased downwards for relatives whose ancestry differs.  PC-Relate (Conomos et al.
+ * 2016, GENESIS pcrelate) adjusts the kinship for the ancestry the axes found: the dosages are regressed on an intercept and the
+ * leading axes, the fitted value is the individual's own allele frequency, and the kinship is the residual covariance over the
+ * individual-specific variances.  c_iv, g_iv, n_v, mu_v, used_v are pcoa_create_grm's.  Inputs: n_cov covariates, 1 <= n_cov <= 9
+ * (an intercept and up to 8 axes), as two host matrices basis[n_cov][N] and hat[n_cov][N].
+ *   fit        S_c     = sum_i hat[c][i]                           on the host, i ascending, fp64
+ *              beta_vc = (A hat_c)_v + mu_v * S_c                  (A hat_c)_v: pass 1 of the operator applied to hat_c (A = g - mu c),
+ *                                                                  the sample groups' partials added in group order
+ *              = sum_i hat[c][i] * (c_iv ? g_iv : mu_v): missing calls mean-imputed; defined for EVERY row of the store
+ *   frequency  e_iv  = beta_v0 * basis[0][i];  for c = 1 .. n_cov-1:  e_iv = e_iv + beta_vc * basis[c][i];   mu_iv = 0.5 * e_iv
+ *              every product and sum rounded on its own, no contraction, in exactly this order
+ *   operands   for a threshold t in [0, 0.5), one_minus_t = 1.0 - t:
+ *              m_iv = used_v and c_iv and mu_iv > t and mu_iv < one_minus_t
+ *              a_iv = m_iv ? (double)g_iv - e_iv : 0.0          b_iv = m_iv ? sqrt(mu_iv * (1.0 - mu_iv)) : 0.0   (correctly rounded)
+ *   kinship    num(i,j) = sum_v a_iv a_jv    den(i,j) = sum_v b_iv b_jv    n(i,j) = sum_v m_iv m_jv (exact integer)
+ *              phi(i,j) = den(i,j) > 0 ? num(i,j) / (4.0 * den(i,j)) : 0.0
+ * The diagonal follows the same expression; the inbreeding coefficient is 2 phi(i,i) - 1, the caller's to compute.  The estimator
+ * is symmetric in the two alleles.  variants_pca.py's pcrelate_hat_rule, grm_pcrelate_isaf_rule and grm_pcrelate_rule are the
+ * numpy statements.  As pcoa_grm_block: (i, j) and (j, i) have the same bits (nothing scales an operand, so there are no tile
+ * modes); an entry's bits depend on the store, the fit, used_v, t and (i, j) only, not on the rectangle; no atomics: additions
+ * into an entry happen in the order of the variants' indices in their segment, four at a time (csrc/grm_pcrelate.hip, three fp64
+ * products on v_mfma_f64_16x16x4_f64 with the operands formed in registers; instantiated for 1, 3, 5 and 9 covariates, a fit with
+ * another count is padded with beta = 0, basis = 0, which changes no bit of e but the sign of a zero, and a zero is masked).
+ *
+ * pcoa_pcrelate_hat: pure host arithmetic, no ctx, no device: hat = (basis basis^T)^-1 basis.  G[c][c'] = sum_i basis[c][i] *
+ *   basis[c'][i], i ascending, each product rounded, then added; then the square-root-free L D L^T of pcoa_grm_project_lsq,
+ *   literally that sequence; then its forward / diagonal / backward solve per sample column.  PCOA_ERR_INVALID_ARG, the message
+ *   through pcoa_last_error(NULL): n_cov outside [1, 9], n < n_cov, a non-finite entry, a pivot <= 2^-40 * G[c][c] (collinear
+ *   covariates; c is named).
+ * pcoa_grm_pcrelate_fit: leaves beta [V][n_cov] and the basis resident on the ctx's device; replaces an earlier fit; the counts and
+ *   weights are recomputed if they are not resident.  The fit depends on the store and the two matrices only -- not on min_maf,
+ *   the filters or the LD mask, which enter through used_v when a block is asked for.  hat need not be a pseudo-inverse.
+ *   pcoa_accumulate_plink_bed and pcoa_reset drop the fit; a subset does not inherit it; pcoa_destroy frees it.  Synchronising.
+ * pcoa_grm_pcrelate_beta: beta of the rows [first_variant, first_variant + n_variants), host [n_variants][n_cov].
+ * pcoa_grm_pcrelate_isaf: mu_iv of every sample and row of the window, unmasked, host [n_variants][N] (GENESIS calls it ISAF).
+ * pcoa_grm_pcrelate_block: any rectangle of phi and / or of n, row-major; host memory, or device memory of the ctx's device with
+ *   is_device_ptr; either output may be NULL, not both.  Memory and error conventions are pcoa_grm_block's.  Synchronising.
+ * pcoa_grm_pcrelate_pairs: pcoa_grm_pairs' walk of the upper triangle: bands of band_rows rows (a multiple of 64; 0 = 1,024) x
+ *   [64 floor(r0 / 64), N) sit in the buffer pcoa_grm_block grows -- num, den and n side by side -- one launch chain per band, no
+ *   host synchronisation between bands; the screen is pcoa_grm_pairs' count / scan / write.  The pair (i, j), i < j, is reported
+ *   iff phi(i, j) >= cutoff on the very bits pcoa_grm_pcrelate_block returns; records are pcoa_grm_pair {i, j, k = phi, n = n(i, j)}
+ *   in (i, j) order; capacity and *n_found_out as pcoa_similar_pairs; out_diag[i] = phi(i, i), or NULL.  Synchronising.
+ *   PCOA_ERR_INVALID_ARG, found on the host before any device work: ctx NULL; fit: NULL matrices, n_cov outside [1, 9], a
+ *           non-finite entry; beta / isaf: a window outside the store, NULL out; block: a rectangle that leaves [0, N)^2, both
+ *           outputs NULL; block / pairs: maf_threshold not finite or outside [0, 0.5); pairs: cutoff not finite, band_rows negative
+ *           or not a multiple of 64, capacity < 0, capacity > 0 with out_pairs NULL, n_found_out NULL.
+ *   PCOA_ERR_STATE, the ctx stays usable: not a pcoa_create_grm ctx (the message names its kind), a study ctx, an empty store
+ *           (fit), M' = 0 or M' >= 2^31 (block / pairs), no fit on this ctx (beta / isaf / block / pairs; the message says what
+ *           dropped it when that was an accumulate or a reset).
+ * The inbreeding coefficient's n is n(i, i): read it with pcoa_grm_pcrelate_block's pair counts over diagonal blocks.
+ * Not built: k0 / k2 / IBD-sharing estimates and the dominance product; GENESIS' scale = "overall" correction and its small-sample
+ * correction; maf.bound.method = "truncate"; more than 8 axes; forming e on the matrix cores; removal by PC-Relate kinship and a
+ * second PC-AiR round; a fit inherited by subsets; multi-GPU; JNI / Scala natives. */
+int pcoa_pcrelate_hat(int32_t n_cov, int32_t n, const double* basis /* [n_cov][n] */, double* hat_out /* [n_cov][n] */);
+int pcoa_grm_pcrelate_fit(pcoa_ctx* ctx, int32_t n_cov, const double* basis, const double* hat /* host [n_cov][N] each */);
+int pcoa_grm_pcrelate_beta(pcoa_ctx* ctx, int64_t first_variant, int64_t n_variants, double* out /* host [n_variants][n_cov] */);
+int pcoa_grm_pcrelate_isaf(pcoa_ctx* ctx, int64_t first_variant, int64_t n_variants, double* out /* host [n_variants][N] */);
+int pcoa_grm_pcrelate_block(pcoa_ctx* ctx, int32_t row0, int32_t rows, int32_t col0, int32_t cols, double maf_threshold,
+                            double* out_phi, int32_t* out_pairs /* [rows][cols] each; either may be NULL, not both */,
+                            int is_device_ptr);
+int pcoa_grm_pcrelate_pairs(pcoa_ctx* ctx, double cutoff, double maf_threshold, int32_t band_rows /* 0: 1,024; multiple of 64 */,
+                            pcoa_grm_pair* out_pairs, int64_t capacity, int64_t* n_found_out, double* out_diag /* N, or NULL */);
+
+/* What the PC-Relate calls did on THIS engine, cumulative since pcoa_create_grm / pcoa_reset_timings.  (A struct of its own, like
+ * pcoa_grm_pairs_stats.)  It grows at its end; out_size = sizeof of the struct the caller compiled against.  Synchronising. */
+typedef struct pcoa_grm_pcrelate_stats {
+  int64_t grm_pcrelate_fits;            /* pcoa_grm_pcrelate_fit calls                                                         */
+  int64_t grm_pcrelate_block_calls;     /* pcoa_grm_pcrelate_block calls                                                       */
+  int64_t grm_pcrelate_pairs_calls;     /* pcoa_grm_pcrelate_pairs calls                                                       */
+  int64_t grm_pcrelate_bands;
+  double grm_pcrelate_fit_seconds;      /* HIP-event time of the fits' launches                                                */
+  double grm_pcrelate_dense_seconds;    /* of the dense launches and the division, of both calls                               */
+  double grm_pcrelate_screen_seconds;   /* of the screen's count, scan and write kernels                                       */
+  double grm_pcrelate_flops;            /* issued fp64 flops: 2 * rows * cols * V per product launched (2 or 3 products)       */
+  int64_t grm_pcrelate_bytes;           /* bytes of the bands the screen's count and write kernels read                        */
+  int64_t grm_pcrelate_n_cov;           /* NOT cumulative: n_cov of the resident fit, 0 without one (the width of _beta's rows)  */
+} pcoa_grm_pcrelate_stats;
+int pcoa_get_grm_pcrelate_stats(pcoa_ctx* ctx, pcoa_grm_pcrelate_stats* out, size_t out_size);
 
 /* ---- per-variant loadings of the principal coordinates ---------------------------------------------------------------------
  * Which variants drive each axis (smartpca's SNP weights, PLINK 2's --pca var-wts).  With X the V x N carrier bit matrix and

@@ -14,6 +14,6 @@ The directory name contains '-', so import it with
     importlib.import_module("spark-examples_amd")      (tests/conftest.py and bench.py do this).
 """
 from . import _lib  # noqa: F401  (binding only; the shared library is loaded on first use)
-from .engine import IndexRangeError, PcoaEngine, PcoaError, reduce_peers  # noqa: F401
+from .engine import IndexRangeError, PcoaEngine, PcoaError, pcrelate_hat, reduce_peers  # noqa: F401
 
-__all__ = ["PcoaEngine", "PcoaError", "IndexRangeError", "reduce_peers"]
+__all__ = ["PcoaEngine", "PcoaError", "IndexRangeError", "pcrelate_hat", "reduce_peers"]

@@ -218,6 +218,22 @@ class PcoaGrmKingStats(ctypes.Structure):
     ]
 
 
+class PcoaGrmPcrelateStats(ctypes.Structure):
+    """pcoa_grm_pcrelate_stats: what pcoa_grm_pcrelate_fit / _block / _pairs did on the engine."""
+    _fields_ = [
+        ("grm_pcrelate_fits", ctypes.c_int64),
+        ("grm_pcrelate_block_calls", ctypes.c_int64),
+        ("grm_pcrelate_pairs_calls", ctypes.c_int64),
+        ("grm_pcrelate_bands", ctypes.c_int64),
+        ("grm_pcrelate_fit_seconds", ctypes.c_double),
+        ("grm_pcrelate_dense_seconds", ctypes.c_double),
+        ("grm_pcrelate_screen_seconds", ctypes.c_double),
+        ("grm_pcrelate_flops", ctypes.c_double),
+        ("grm_pcrelate_bytes", ctypes.c_int64),
+        ("grm_pcrelate_n_cov", ctypes.c_int64),
+    ]
+
+
 class PcoaGrmSubsetStats(ctypes.Structure):
     """pcoa_grm_subset_stats: what pcoa_create_grm_subset did with this engine as its source."""
     _fields_ = [
@@ -338,6 +354,13 @@ _SIGNATURES = [
     ("pcoa_grm_king_block", ctypes.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, ctypes.c_int]),
     ("pcoa_grm_king_pairs", ctypes.c_int, [_vp, _i32, ctypes.c_double, _i32, _vp, _i64, ctypes.POINTER(_i64), ctypes.POINTER(_i64), _vp]),
     ("pcoa_get_grm_king_stats", ctypes.c_int, [_vp, ctypes.POINTER(PcoaGrmKingStats), ctypes.c_size_t]),
+    ("pcoa_pcrelate_hat", ctypes.c_int, [_i32, _i32, _vp, _vp]),
+    ("pcoa_grm_pcrelate_fit", ctypes.c_int, [_vp, _i32, _vp, _vp]),
+    ("pcoa_grm_pcrelate_beta", ctypes.c_int, [_vp, _i64, _i64, _vp]),
+    ("pcoa_grm_pcrelate_isaf", ctypes.c_int, [_vp, _i64, _i64, _vp]),
+    ("pcoa_grm_pcrelate_block", ctypes.c_int, [_vp, _i32, _i32, _i32, _i32, ctypes.c_double, _vp, _vp, ctypes.c_int]),
+    ("pcoa_grm_pcrelate_pairs", ctypes.c_int, [_vp, ctypes.c_double, ctypes.c_double, _i32, _vp, _i64, ctypes.POINTER(_i64), _vp]),
+    ("pcoa_get_grm_pcrelate_stats", ctypes.c_int, [_vp, ctypes.POINTER(PcoaGrmPcrelateStats), ctypes.c_size_t]),
     ("pcoa_grm_ld_prune", ctypes.c_int, [_vp, _i32, ctypes.c_double, _vp, _i64, ctypes.POINTER(_i64), ctypes.POINTER(_i64)]),
     ("pcoa_grm_ld_mask", ctypes.c_int, [_vp, _i64, _i64, _vp]),
     ("pcoa_grm_ld_clear", ctypes.c_int, [_vp]),

@@ -249,6 +249,9 @@ void grm_destroy(pcoa_ctx* c) {
   if (c->grm_mw) dev_free(c->grm_mw);
   if (c->grm_blk) dev_free(c->grm_blk);
   if (c->grm_keep) dev_free(c->grm_keep);
+  if (c->grm_pcr) dev_free(c->grm_pcr);
+  c->grm_pcr = nullptr;
+  c->grm_pcr_set = false;
   grm_qc_destroy(c);
   c->grm_keep = nullptr;
   c->grm_keep_set = false;

@@ -166,6 +166,7 @@ int store_append(pcoa_ctx* c, int64_t nv, const std::function<hipError_t(int64_t
   }
   c->op_centering_set = false;
   grm_ld_drop(c);   // a keep mask (pcoa_grm_ld_prune) described the store without these rows
+  grm_pcr_drop(c, 1);   // and so did a PC-Relate fit
   return PCOA_OK;
 }
 
@@ -187,6 +188,7 @@ int operator_reset(pcoa_ctx* c) {
   c->op_variants = 0;
   c->op_centering_set = false;
   grm_ld_drop(c);
+  grm_pcr_drop(c, 2);
   HIP_TRY(c, hipMemsetAsync(c->err_flag, 0, 16, c->stream));
   return PCOA_OK;
 }

@@ -441,6 +441,8 @@ int pcoa_reset_timings(pcoa_ctx* c) {
   c->grm_pairs_flops = 0;
   c->grm_king_calls = c->grm_king_block_calls = c->grm_king_bands = c->grm_king_bytes = 0;
   c->grm_king_macs = 0;
+  c->grm_pcr_fits = c->grm_pcr_block_calls = c->grm_pcr_pairs_calls = c->grm_pcr_bands = c->grm_pcr_bytes = 0;
+  c->grm_pcr_flops = 0;
   c->grm_subset_calls = c->grm_subset_bytes = 0;
   c->grm_hwe_calls = c->grm_sample_counts_calls = 0;
   c->grm_lsq_calls = c->grm_lsq_pair_vectors = c->grm_lsq_undetermined = 0;

@@ -16,6 +16,7 @@
 //   capi_grm_dense.hip   pcoa_grm_block: a rectangle of K and of the pair counts read out through the fp64 matrix cores
 //   capi_grm_ld.hip      pcoa_grm_ld_*: LD pruning of the resident GRM store by dosage r^2, as a keep mask that enters used_v
 //   capi_grm_king.hip    pcoa_grm_king_block / pcoa_grm_king_pairs: the KING-robust kinship screen on the resident 2-bit store
+//   capi_grm_pcrelate.hip pcoa_pcrelate_hat, pcoa_grm_pcrelate_*: PC-Relate kinship from a fit of the dosages on the axes, resident on the ctx
 //   capi_grm_qc.hip      pcoa_grm_set_variant_filters, pcoa_grm_hwe, pcoa_grm_sample_counts: variant and sample QC on the resident store
 //   capi_grm_subset.hip  pcoa_create_grm_subset: a new GRM ctx over a sample subset of another's store; pcoa_grm_rows reads rows back
 //   capi_subset.hip      pcoa_create_subset: a new engine whose S is S[I, I] of another
@@ -33,7 +34,7 @@
 
 #include "pcoa_internal.h"
 
-enum TimeCat { T_GRAM = 0, T_DENSIFY, T_SYNTH, T_FINALIZE, T_CENTER, T_TRIDIAG, T_EIG, T_BACK, T_PACK, T_LANCZOS, T_ALLREDUCE, T_OPERATOR, T_SUBSET, T_REDUCE_PEERS, T_PAIRS, T_LOADINGS, T_LD_COUNT, T_LD_BAND, T_LD_RESOLVE, T_LD_COMPACT, T_KING, T_GRM_BLOCK, T_GRM_LD_BAND, T_GRM_LD_RESOLVE, T_GRM_LD_SCAN, T_GRM_SUBSET, T_GRM_PAIRS_DENSE, T_GRM_PAIRS_SCREEN, T_GRM_QC_HWE, T_GRM_QC_SAMPLES, T_GRM_LSQ_PAIRS, T_GRM_LSQ_SOLVE, T_GRM_KING_COUNTS, T_GRM_KING_SCREEN, T_NCAT };
+enum TimeCat { T_GRAM = 0, T_DENSIFY, T_SYNTH, T_FINALIZE, T_CENTER, T_TRIDIAG, T_EIG, T_BACK, T_PACK, T_LANCZOS, T_ALLREDUCE, T_OPERATOR, T_SUBSET, T_REDUCE_PEERS, T_PAIRS, T_LOADINGS, T_LD_COUNT, T_LD_BAND, T_LD_RESOLVE, T_LD_COMPACT, T_KING, T_GRM_BLOCK, T_GRM_LD_BAND, T_GRM_LD_RESOLVE, T_GRM_LD_SCAN, T_GRM_SUBSET, T_GRM_PAIRS_DENSE, T_GRM_PAIRS_SCREEN, T_GRM_QC_HWE, T_GRM_QC_SAMPLES, T_GRM_LSQ_PAIRS, T_GRM_LSQ_SOLVE, T_GRM_KING_COUNTS, T_GRM_KING_SCREEN, T_GRM_PCR_FIT, T_GRM_PCR_DENSE, T_GRM_PCR_SCREEN, T_NCAT };
 
 struct EventPair {
   hipEvent_t a, b;
@@ -111,6 +112,15 @@ struct pcoa_ctx {
   double grm_pairs_flops = 0;
   int64_t grm_king_calls = 0, grm_king_block_calls = 0, grm_king_bands = 0, grm_king_bytes = 0;   // pcoa_grm_king_stats (the bands live in grm_blk)
   double grm_king_macs = 0;
+  // PC-Relate (capi_grm_pcrelate.hip): the fit is a statement about the store's rows and the two matrices of the fit call alone; an
+  // append and pcoa_reset drop it (grm_pcr_drop), a subset does not inherit it
+  double* grm_pcr = nullptr;       // beta [V][n_cov], then basis [n_cov][N] (sized by the fit)
+  int64_t grm_pcr_cap = 0;
+  bool grm_pcr_set = false;
+  int32_t grm_pcr_cov = 0;         // n_cov of the resident fit
+  int32_t grm_pcr_dropped_by = 0;  // what dropped the last fit: 0 nothing (never fitted), 1 an accumulate call, 2 pcoa_reset, 3 a failed fit
+  int64_t grm_pcr_fits = 0, grm_pcr_block_calls = 0, grm_pcr_pairs_calls = 0, grm_pcr_bands = 0, grm_pcr_bytes = 0;   // pcoa_grm_pcrelate_stats
+  double grm_pcr_flops = 0;
   // LD pruning of the store (pcoa_grm_ld_prune, capi_grm_ld.hip): the keep mask is a statement about the store as it was
   // pruned under grm_min_maf; an append, pcoa_reset, another min_maf and pcoa_grm_ld_clear drop it (grm_ld_drop)
   uint8_t* grm_keep = nullptr;     // [V] 1 = kept, 0 = removed or no candidate
@@ -522,6 +532,11 @@ int grm_unmasked_used(pcoa_ctx* c, const int32_t** used_out);
 inline void grm_ld_drop(pcoa_ctx* c) {   // the keep mask no longer describes the store: the weights are the unpruned ones again
   if (c->grm_keep_set) c->grm_weights_set = false;
   c->grm_keep_set = false;
+}
+
+inline void grm_pcr_drop(pcoa_ctx* c, int32_t by) {   // the PC-Relate fit no longer describes the store
+  if (c->grm_pcr_set) c->grm_pcr_dropped_by = by;
+  c->grm_pcr_set = false;
 }
 
 // ---- capi_grm_project.hip

@@ -366,6 +366,27 @@ hipError_t launch_grm_king_screen_write(const int32_t* hethet, const int32_t* ib
                                         int32_t nrows, int32_t c0, int32_t n, double x, const int32_t* prefix, const int64_t* rowoff,
                                         int64_t capacity, pcoa_king_pair* out, unsigned long long* entries_read, hipStream_t stream);
 
+// ---- PC-Relate kinship on the 2-bit store (grm_pcrelate.hip) ---------------------------------------------------------
+// A rectangle of num / den / n (the rule: pcoa.h at pcoa_grm_pcrelate_block) as three fp64 products on the matrix cores.  One
+// launch per segment, in the store's order; out_num, out_den: [nrows][ncols] row-major, out_n the same in int32 or NULL (that
+// product is not instantiated); first = 1: the entries start from 0, otherwise from what the outputs hold.  used, beta
+// ([rows][n_cov]): the segment's rows; basis: [n_cov][n]; t: the threshold on mu_iv.  The kernel is instantiated for
+// grm_pcrelate_padded_cov(n_cov) covariates: 1, 3, 5 or 9
+constexpr int32_t kGrmPcrelateMaxCov = 9;
+int32_t grm_pcrelate_padded_cov(int32_t n_cov);
+hipError_t launch_grm_pcrelate(const uint32_t* seg, int32_t rows, int32_t n, const int32_t* used, const double* beta, int32_t n_cov,
+                               const double* basis, double t, int32_t row0, int32_t nrows, int32_t col0, int32_t ncols, int first,
+                               double* out_num, double* out_den, int32_t* out_n, hipStream_t stream);
+// num[i] = den[i] > 0 ? num[i] / (4.0 * den[i]) : 0.0
+hipError_t launch_grm_pcrelate_finish(double* num, const double* den, int64_t total, hipStream_t stream);
+// beta[r * n_cov + c0 + c] = (the groups' partials tpart[c * cstride + g * vstride + r] of launch_grm_ax_multi added in group order)
+// + mu[r] * s[c0 + c], c in [0, k), r in [0, rows)
+hipError_t launch_grm_pcrelate_beta(const double* tpart, int64_t vstride, int32_t n, int64_t cstride, int64_t rows, const double* mu,
+                                    const double* s, int32_t c0, int32_t k, int32_t n_cov, double* beta, hipStream_t stream);
+// out[(v - first) * n + i] = mu_iv for the rows [first, first + nv) of beta, unmasked
+hipError_t launch_grm_pcrelate_isaf(const double* beta, int32_t n_cov, const double* basis, int32_t n, int64_t first, int64_t nv,
+                                    double* out, hipStream_t stream);
+
 // ---- per-variant loadings (loadings.hip): out[v * num_pc + c] = (sum_i bit(v, i) u[c * ustride + i]) / div[c] for c in [0, k) ----
 // u: prepared vectors, ustride = 32 ceil(n / 32) doubles each, zero for i >= n (that is what ignores a row's tail bits); div: k
 // divisors or NULL; k must be 1, 2, 4 or 8 (loadings_chunk picks the chunk); out / u / div point at the chunk's first component.

@@ -25,6 +25,22 @@ def _ptr(a):
     return ctypes.c_void_p(a.ctypes.data)
 
 
+def pcrelate_hat(basis):
+    """hat = (basis basis^T)^-1 basis for the covariates `basis` [n_cov, N] of a PC-Relate fit, by pcoa_pcrelate_hat: host
+    arithmetic in the library (no engine, no device), so that every host holds the same bits; variants_pca.pcrelate_hat_rule is
+    the numpy statement.  PcoaError (PCOA_ERR_INVALID_ARG) for n_cov outside [1, 9], N < n_cov, a non-finite entry or collinear
+    covariates."""
+    b = np.ascontiguousarray(basis, dtype=np.float64)
+    if b.ndim != 2:
+        raise ValueError("basis must be [n_cov, N], not %s" % (b.shape,))
+    out = np.zeros(b.shape, dtype=np.float64)
+    lib = L.load()
+    rc = lib.pcoa_pcrelate_hat(int(b.shape[0]), int(b.shape[1]), _ptr(b) if b.size else None, _ptr(out) if out.size else None)
+    if rc != 0:
+        raise PcoaError(rc, (lib.pcoa_last_error(None) or b"").decode())
+    return out
+
+
 _BITS_ROWS = (np.uint32, "int32", "bits must be 2-D [variants][words]")
 _BED_ROWS = (np.uint8, "uint8", "rows must be [variants][row_bytes]")
 
@@ -869,6 +885,91 @@ class PcoaEngine(object):
         q = L.PcoaGrmKingStats()
         self._check(self._lib.pcoa_get_grm_king_stats(self._ctx, ctypes.byref(q), ctypes.sizeof(q)))
         return dict((f[0], getattr(q, f[0])) for f in L.PcoaGrmKingStats._fields_)
+
+    # ------------------------------------------------------------------ PC-Relate kinship on the 2-bit store
+    def grm_pcrelate_fit(self, basis, hat=None):
+        """Regresses the dosages of every row of the store on the covariates `basis` [n_cov, N] (1 <= n_cov <= 9: a row of ones
+        and up to 8 axes) and leaves beta and the basis resident (pcoa_grm_pcrelate_fit).  hat [n_cov, N]: the matrix applied
+        to the mean-imputed dosages; None calls pcrelate_hat(basis).  An accumulate call and reset() drop the fit."""
+        b = np.ascontiguousarray(basis, dtype=np.float64)
+        if b.ndim != 2 or b.shape[1] != self.n:
+            raise ValueError("basis must be [n_cov, N = %d], not %s" % (self.n, b.shape))
+        h = pcrelate_hat(b) if hat is None else np.ascontiguousarray(hat, dtype=np.float64)
+        if h.shape != b.shape:
+            raise ValueError("hat must have the shape of basis %s, not %s" % (b.shape, h.shape))
+        self._check(self._lib.pcoa_grm_pcrelate_fit(self._ctx, int(b.shape[0]), _ptr(b), _ptr(h)))
+
+    def grm_pcrelate_beta(self, first=0, n=None):
+        """beta [n, n_cov] of the rows [first, first + n) of the store under the resident fit (n=None: to the end)."""
+        if n is None:
+            n = self.grm_info()[0] - int(first)
+        k = max(int(self.grm_pcrelate_stats()["grm_pcrelate_n_cov"]), 1)   # the library's own n_cov: the width the call writes
+        out = np.zeros((max(int(n), 0), k), dtype=np.float64)
+        self._check(self._lib.pcoa_grm_pcrelate_beta(self._ctx, int(first), int(n), _ptr(out) if out.size else out.ctypes.data_as(ctypes.c_void_p)))
+        return out
+
+    def grm_pcrelate_isaf(self, first, n):
+        """mu_iv [n, N]: the individual-specific allele frequency of every sample at the rows [first, first + n), unmasked."""
+        out = np.zeros((max(int(n), 0), self.n), dtype=np.float64)
+        self._check(self._lib.pcoa_grm_pcrelate_isaf(self._ctx, int(first), int(n), _ptr(out) if out.size else out.ctypes.data_as(ctypes.c_void_p)))
+        return out
+
+    def grm_pcrelate_block(self, row0, rows, col0, cols, maf_threshold=0.01, pairs=False, device=False):
+        """phi[row0 : row0 + rows, col0 : col0 + cols] under the resident fit (pcoa_grm_pcrelate_block), float64;
+        variants_pca.grm_pcrelate_rule is the rule.  pairs=True: returns (phi, n) with n the int32 counts of variants at which
+        both samples pass the mask.  device=True: torch tensors on this engine's GPU; otherwise numpy arrays."""
+        shape = (max(int(rows), 0), max(int(cols), 0))
+        if device:
+            import torch  # plumbing only: device memory handles
+            dev = torch.device("cuda", self.device)
+            k = torch.empty(shape, dtype=torch.float64, device=dev)
+            n = torch.empty(shape, dtype=torch.int32, device=dev) if pairs else None
+            torch.cuda.current_stream(dev).synchronize()   # the engine runs on its own stream
+            kp = ctypes.c_void_p(k.data_ptr()) if k.numel() else None
+            npp = ctypes.c_void_p(n.data_ptr()) if pairs and n.numel() else None
+        else:
+            k = np.zeros(shape, dtype=np.float64)
+            n = np.zeros(shape, dtype=np.int32) if pairs else None
+            kp = _ptr(k) if k.size else None
+            npp = _ptr(n) if pairs and n.size else None
+        self._check(self._lib.pcoa_grm_pcrelate_block(self._ctx, int(row0), int(rows), int(col0), int(cols), float(maf_threshold), kp, npp,
+                                                      int(bool(device))))
+        return (k, n) if pairs else k
+
+    def grm_pcrelate_dense(self, maf_threshold=0.01, block=4096):
+        """The whole N x N phi as float64 numpy, assembled from blocks of the lower triangle and mirrored (an entry above the
+        diagonal has the bits of its mirror image)."""
+        block = max(int(block), 1)
+        out = np.zeros((self.n, self.n), dtype=np.float64)
+        for r0 in range(0, self.n, block):
+            r = min(block, self.n - r0)
+            for c0 in range(0, r0 + 1, block):
+                c = min(block, self.n - c0)
+                out[r0:r0 + r, c0:c0 + c] = self.grm_pcrelate_block(r0, r, c0, c, maf_threshold)
+        low = np.tril(out, -1)
+        return np.tril(out) + low.T
+
+    def grm_pcrelate_pairs(self, cutoff, maf_threshold=0.01, band_rows=0, capacity=1 << 20, diag=False):
+        """The PC-Relate kinship screen (pcoa_grm_pcrelate_pairs): the pairs i < j with phi(i, j) >= cutoff on the bits
+        grm_pcrelate_block returns, found on the device a band of `band_rows` rows (0: 1,024; a multiple of 64) at a time;
+        variants_pca.grm_pairs_rule(phi, cutoff, n) is the rule.  Returns (pairs, n_found), or (pairs, n_found, diag) with
+        diag=True: `pairs` a GRM_PAIR_DTYPE array (k = phi, n = n(i, j)) of the first min(n_found, capacity) pairs in increasing
+        (i, j) order, `diag` phi(i, i), float64 [N]."""
+        cap = int(capacity)
+        pairs = np.zeros(max(cap, 0), dtype=self.GRM_PAIR_DTYPE)
+        d = np.zeros(self.n, dtype=np.float64) if diag else None
+        found = ctypes.c_int64(0)
+        self._check(self._lib.pcoa_grm_pcrelate_pairs(self._ctx, float(cutoff), float(maf_threshold), int(band_rows),
+                                                      _ptr(pairs) if cap > 0 else None, cap, ctypes.byref(found), _ptr(d) if diag else None))
+        n_found = int(found.value)
+        return (pairs[:min(n_found, cap)], n_found, d) if diag else (pairs[:min(n_found, cap)], n_found)
+
+    def grm_pcrelate_stats(self):
+        """pcoa_get_grm_pcrelate_stats: fits, block / pairs calls, bands, the seconds of the fit, the dense launches and the
+        screen, issued fp64 flops, bytes the screen read, and (not cumulative) n_cov of the resident fit, 0 without one."""
+        q = L.PcoaGrmPcrelateStats()
+        self._check(self._lib.pcoa_get_grm_pcrelate_stats(self._ctx, ctypes.byref(q), ctypes.sizeof(q)))
+        return dict((f[0], getattr(q, f[0])) for f in L.PcoaGrmPcrelateStats._fields_)
 
     # ------------------------------------------------------------------ LD pruning of the GRM store
     def grm_ld_prune(self, window, r2_max, breaks=()):

@@ -129,6 +129,18 @@ struct Conf {  // PcaConf / GenomicsConf (GenomicsConf.scala:31-101), same flag 
   bool has_grm_king_output_path = false;
   int64_t grm_king_max_pairs = 1048576; // --grm-king-max-pairs M: the capacity handed to the library; more reported pairs stop the job
   bool grm_king_max_pairs_given = false;
+  std::string grm_pcrelate_output_path;             // --grm-pcrelate-output-path FILE: --grm: PC-Relate kinship (pcoa_grm_pcrelate_*) behind the last
+  bool has_grm_pcrelate_output_path = false;        // computePca and --grm-project-removed; the pairs at or above the cutoff go to FILE
+  int grm_pcrelate_pcs = 0;                         // --grm-pcrelate-pcs K: the axes beside the intercept, [1, min(8, --num-pc)]; default min(2, --num-pc)
+  bool has_grm_pcrelate_pcs = false;
+  double grm_pcrelate_cutoff = 0.044194173824159216;   // --grm-pcrelate-cutoff X: 2^-4.5
+  bool has_grm_pcrelate_cutoff = false;
+  double grm_pcrelate_maf_threshold = 0.01;         // --grm-pcrelate-maf-threshold T in [0, 0.5)
+  bool has_grm_pcrelate_maf_threshold = false;
+  std::string grm_pcrelate_inbreeding_output_path;  // --grm-pcrelate-inbreeding-output-path FILE: name, f = 2 phi(i, i) - 1, n(i, i)
+  bool has_grm_pcrelate_inbreeding_output_path = false;
+  int64_t grm_pcrelate_max_pairs = 1048576;         // --grm-pcrelate-max-pairs M: the capacity handed to the library; more reported pairs stop the job
+  bool grm_pcrelate_max_pairs_given = false;
   bool grm_king_remove = false;         // --grm-king-remove: drop one sample of every reported pair, go on with pcoa_create_grm_subset over the rest
   bool grm_cutoff_remove = false;       // --grm-cutoff-remove: drop one sample of every reported pair, go on with pcoa_create_grm_subset over the rest
   bool grm_project_lsq = false;         // --grm-project-lsq: both projections place by least squares over the called variants (pcoa_grm_project_lsq)
@@ -211,6 +223,9 @@ const char* kUsage =
     "                   --grm-project-removed then places the samples --grm-mind took out too; at most 16 principal components)\n"
     "                   --grm-king-cutoff X [--grm-king-rows all|used] [--grm-king-output-path FILE] [--grm-king-max-pairs M] [--grm-king-remove]\n"
     "                   (the KING-robust kinship screen of the genotype store, where --grm-cutoff runs: pcoa_grm_king_pairs)\n"
+    "                   --grm-pcrelate-output-path FILE [--grm-pcrelate-pcs K] [--grm-pcrelate-cutoff X] [--grm-pcrelate-maf-threshold T]\n"
+    "                   [--grm-pcrelate-inbreeding-output-path FILE] [--grm-pcrelate-max-pairs M]\n"
+    "                   (PC-Relate kinship over the final cohort and the placed removed samples, behind the last computePca: pcoa_grm_pcrelate_*)\n"
     "                   --grm-cutoff X [--grm-cutoff-divisor used|pairwise] [--grm-related-output-path FILE] [--grm-cutoff-remove]\n"
     "                   (--grm: screen K for related pairs before computePca, behind the sample list and one LD prune: a pair is reported\n"
     "                   when K(i, j) >= X; FILE: name_i, name_j, K, n per pair; --grm-cutoff-remove drops one sample of every pair by the\n"
@@ -389,6 +404,41 @@ Conf parse(int argc, char** argv) {
       c.grm_king_max_pairs_given = true;
     }
     else if (a == "--grm-king-remove") c.grm_king_remove = true;
+    else if (a == "--grm-pcrelate-output-path") {
+      c.grm_pcrelate_output_path = one(i);
+      c.has_grm_pcrelate_output_path = true;
+    }
+    else if (a == "--grm-pcrelate-inbreeding-output-path") {
+      c.grm_pcrelate_inbreeding_output_path = one(i);
+      c.has_grm_pcrelate_inbreeding_output_path = true;
+    }
+    else if (a == "--grm-pcrelate-pcs" || a == "--grm-pcrelate-max-pairs") {
+      const std::string v = one(i);
+      char* end = nullptr;
+      errno = 0;
+      const long long m = std::strtoll(v.c_str(), &end, 10);
+      if (v.empty() || *end != 0 || errno != 0) die(a + " takes an integer, not '" + v + "'");
+      if (a == "--grm-pcrelate-pcs") {
+        c.grm_pcrelate_pcs = (int)std::max<long long>(std::min<long long>(m, 1 << 30), -(1 << 30));
+        c.has_grm_pcrelate_pcs = true;
+      } else {
+        c.grm_pcrelate_max_pairs = (int64_t)m;
+        c.grm_pcrelate_max_pairs_given = true;
+      }
+    }
+    else if (a == "--grm-pcrelate-cutoff" || a == "--grm-pcrelate-maf-threshold") {
+      const std::string v = one(i);
+      char* end = nullptr;
+      const double x = std::strtod(v.c_str(), &end);
+      if (v.empty() || *end != 0) die(a + " takes a number, not '" + v + "'");
+      if (a == "--grm-pcrelate-cutoff") {
+        c.grm_pcrelate_cutoff = x;
+        c.has_grm_pcrelate_cutoff = true;
+      } else {
+        c.grm_pcrelate_maf_threshold = x;
+        c.has_grm_pcrelate_maf_threshold = true;
+      }
+    }
     else if (a == "--grm-outlier-iterations") {
       const std::string v = one(i);
       char* end = nullptr;
@@ -558,6 +608,15 @@ Conf parse(int argc, char** argv) {
     if (!c.grm && c.grm_king_remove) die(std::string("--grm-king-remove") + why);
   }
   {
+    const char* why = " needs --grm (it estimates PC-Relate kinship on the genotype store and the axes of the standardised-genotype PCA)";
+    if (!c.grm && c.has_grm_pcrelate_output_path) die(std::string("--grm-pcrelate-output-path") + why);
+    if (!c.grm && c.has_grm_pcrelate_pcs) die(std::string("--grm-pcrelate-pcs") + why);
+    if (!c.grm && c.has_grm_pcrelate_cutoff) die(std::string("--grm-pcrelate-cutoff") + why);
+    if (!c.grm && c.has_grm_pcrelate_maf_threshold) die(std::string("--grm-pcrelate-maf-threshold") + why);
+    if (!c.grm && c.has_grm_pcrelate_inbreeding_output_path) die(std::string("--grm-pcrelate-inbreeding-output-path") + why);
+    if (!c.grm && c.grm_pcrelate_max_pairs_given) die(std::string("--grm-pcrelate-max-pairs") + why);
+  }
+  {
     const char* why = " needs --grm (it prunes the genotype store of the standardised-genotype PCA; the carrier counts S are pruned by --ld-window)";
     if (!c.grm && c.grm_ld_window != 0) die(std::string("--grm-ld-window") + why);
     if (!c.grm && c.grm_ld_r2_given) die(std::string("--grm-ld-r2") + why);
@@ -610,6 +669,25 @@ Conf parse(int argc, char** argv) {
     if (c.grm_king_max_pairs < 0) die("--grm-king-max-pairs must be >= 0 (the pairs --grm-king-cutoff may report)");
     if (c.grm_king_remove && c.grm_cutoff_remove)
       die("--grm-king-remove and --grm-cutoff-remove exclude each other (one relatedness screen removes samples per run)");
+  }
+  if (!c.has_grm_pcrelate_output_path) {
+    const char* why = " needs --grm-pcrelate-output-path FILE (PC-Relate is off without it)";
+    if (c.has_grm_pcrelate_pcs) die(std::string("--grm-pcrelate-pcs") + why);
+    if (c.has_grm_pcrelate_cutoff) die(std::string("--grm-pcrelate-cutoff") + why);
+    if (c.has_grm_pcrelate_maf_threshold) die(std::string("--grm-pcrelate-maf-threshold") + why);
+    if (c.has_grm_pcrelate_inbreeding_output_path) die(std::string("--grm-pcrelate-inbreeding-output-path") + why);
+    if (c.grm_pcrelate_max_pairs_given) die(std::string("--grm-pcrelate-max-pairs") + why);
+  } else {
+    const int most = std::min(8, c.num_pc);
+    if (c.has_grm_pcrelate_pcs && !(c.grm_pcrelate_pcs >= 1 && c.grm_pcrelate_pcs <= most))
+      die("--grm-pcrelate-pcs must be an integer in [1, " + std::to_string(most) + "] (min(8, --num-pc)), not " +
+          std::to_string(c.grm_pcrelate_pcs));
+    if (!std::isfinite(c.grm_pcrelate_cutoff))
+      die("--grm-pcrelate-cutoff must be a finite number (the kinship at or above which a pair is reported)");
+    if (!(c.grm_pcrelate_maf_threshold >= 0.0 && c.grm_pcrelate_maf_threshold < 0.5))
+      die("--grm-pcrelate-maf-threshold must be a number in [0, 0.5)");
+    if (c.grm_pcrelate_max_pairs < 0) die("--grm-pcrelate-max-pairs must be >= 0 (the pairs --grm-pcrelate-output-path may report)");
+    if (!c.has_grm_pcrelate_pcs) c.grm_pcrelate_pcs = std::min(2, c.num_pc);
   }
   if (c.has_grm_output_divisor && c.grm_output_divisor != "used" && c.grm_output_divisor != "pairwise")
     die("--grm-output-divisor takes used or pairwise, not '" + c.grm_output_divisor + "'");
@@ -3029,6 +3107,8 @@ int main(int argc, char** argv) {
     rows.insert(rows.end(), study_rows.begin(), study_rows.end());
     n_study = study_rows.size();
   }
+  std::vector<int32_t> pcr_placed;   // the removed samples --grm-project-removed placed, and their coordinates: --grm-pcrelate-output-path
+  std::vector<double> pcr_coords;
   if (conf.grm && conf.grm_project_removed) {
     // every sample of the fileset that is not in the final cohort: one study subset of the ORIGINAL engine on the final axes
     std::vector<int32_t> gone;
@@ -3046,6 +3126,14 @@ int main(int argc, char** argv) {
       std::vector<double> coords;
       const std::vector<char> placed = grm_place(conf, ctx, study, nq, comps, lam, "removed ", labels, coords);
       pcoa_destroy(study);
+      for (int32_t q = 0; q < nq; ++q)
+        if (placed[(size_t)q]) pcr_placed.push_back(gone[(size_t)q]);
+      pcr_coords.assign((size_t)conf.num_pc * pcr_placed.size(), 0.0);   // [num_pc][placed]
+      for (int32_t q = 0, w = 0; q < nq; ++q) {
+        if (!placed[(size_t)q]) continue;
+        for (int c = 0; c < conf.num_pc; ++c) pcr_coords[(size_t)c * pcr_placed.size() + (size_t)w] = coords[(size_t)q + (size_t)c * (size_t)nq];
+        ++w;
+      }
       for (int32_t q = 0; q < nq; ++q) {
         if (!placed[(size_t)q]) continue;
         const size_t i = (size_t)gone[(size_t)q];
@@ -3053,8 +3141,85 @@ int main(int argc, char** argv) {
         ++n_study;
       }
     }
-    if (grm_full != ctx) pcoa_destroy(grm_full);
   }
+  if (conf.grm && conf.has_grm_pcrelate_output_path) {
+    // --grm-pcrelate-output-path: the cohort is the final cohort plus the removed samples --grm-project-removed placed, in fileset
+    // index order; its engine is the final one, or a panel subset of the whole-fileset engine over the cohort, pruned under
+    // --grm-ld-window like every round's engine.  The covariates: a row of ones, then the first K coordinates of every cohort
+    // sample (u_c for the final cohort, the projected coordinate for a placed one); the hat matrix is pcoa_pcrelate_hat's.
+    // n(i, i) of the inbreeding file comes from pcoa_grm_pcrelate_block's pair counts over diagonal blocks
+    const int32_t kp = conf.grm_pcrelate_pcs;
+    struct Member { int32_t index; const double* coord; size_t stride; };
+    std::vector<Member> cohort;
+    for (int32_t a = 0; a < n_out; ++a) cohort.push_back({kept[(size_t)a], comps.data() + a, (size_t)n_out});
+    for (size_t q = 0; q < pcr_placed.size(); ++q)
+      cohort.push_back({pcr_placed[q], pcr_coords.data() + q, pcr_placed.size()});
+    std::stable_sort(cohort.begin(), cohort.end(), [](const Member& x, const Member& y) { return x.index < y.index; });
+    const int32_t m = (int32_t)cohort.size();
+    pcoa_ctx* eng = ctx;
+    pcoa_ctx* sub = nullptr;
+    if (!pcr_placed.empty()) {
+      const int32_t least = std::max(32, conf.num_pc + 1);
+      if (m < least)
+        die("--grm-pcrelate-output-path: the cohort holds " + std::to_string(m) + " samples, fewer than the " + std::to_string(least) +
+            " a GRM engine with " + std::to_string(conf.num_pc) + " principal components needs");
+      std::vector<int32_t> idx;
+      for (const Member& mb : cohort) idx.push_back(mb.index);
+      sub = grm_subset(grm_full, n, idx, PCOA_GRM_SUBSET_PANEL);
+      if (conf.grm_ld_window > 0) grm_ld_prune_now(sub);
+      eng = sub;
+    }
+    std::vector<double> basis((size_t)(kp + 1) * (size_t)m), hat((size_t)(kp + 1) * (size_t)m);
+    for (int32_t a = 0; a < m; ++a) {
+      basis[(size_t)a] = 1.0;
+      for (int32_t c = 0; c < kp; ++c) basis[(size_t)(c + 1) * (size_t)m + (size_t)a] = cohort[(size_t)a].coord[(size_t)c * cohort[(size_t)a].stride];
+    }
+    if (pcoa_pcrelate_hat(kp + 1, m, basis.data(), hat.data()) != PCOA_OK) die(std::string("pcoa_pcrelate_hat: ") + pcoa_last_error(nullptr));
+    check(eng, pcoa_grm_pcrelate_fit(eng, kp + 1, basis.data(), hat.data()), "pcoa_grm_pcrelate_fit");
+    std::vector<pcoa_grm_pair> found((size_t)std::min<int64_t>(conf.grm_pcrelate_max_pairs, (int64_t)m * (m - 1) / 2));
+    std::vector<double> diag((size_t)m);
+    int64_t n_found = 0;
+    check(eng, pcoa_grm_pcrelate_pairs(eng, conf.grm_pcrelate_cutoff, conf.grm_pcrelate_maf_threshold, 0, found.empty() ? nullptr : found.data(),
+                                       (int64_t)found.size(), &n_found, diag.data()),
+          "pcoa_grm_pcrelate_pairs");
+    if (n_found > conf.grm_pcrelate_max_pairs)
+      die("--grm-pcrelate-cutoff " + java_double(conf.grm_pcrelate_cutoff) + " reports " + std::to_string(n_found) +
+          " pairs, more than --grm-pcrelate-max-pairs " + std::to_string(conf.grm_pcrelate_max_pairs) +
+          " takes; raise --grm-pcrelate-max-pairs or the cutoff");
+    {
+      std::ofstream out(conf.grm_pcrelate_output_path);
+      out << "name_i\tname_j\tkinship\tn\n";
+      for (int64_t e = 0; e < n_found; ++e) {
+        const pcoa_grm_pair& p = found[(size_t)e];
+        out << names[(size_t)cohort[(size_t)p.i].index] << "\t" << names[(size_t)cohort[(size_t)p.j].index] << "\t" << java_double(p.k) << "\t"
+            << p.n << "\n";
+      }
+      if (!out) die("cannot write " + conf.grm_pcrelate_output_path);
+    }
+    if (conf.has_grm_pcrelate_inbreeding_output_path) {
+      std::vector<int32_t> n_diag((size_t)m), blk;
+      for (int32_t r0 = 0; r0 < m; r0 += 1024) {
+        const int32_t r = std::min(1024, m - r0);
+        blk.assign((size_t)r * (size_t)r, 0);
+        check(eng, pcoa_grm_pcrelate_block(eng, r0, r, r0, r, conf.grm_pcrelate_maf_threshold, nullptr, blk.data(), 0), "pcoa_grm_pcrelate_block");
+        for (int32_t a = 0; a < r; ++a) n_diag[(size_t)(r0 + a)] = blk[(size_t)a * (size_t)r + (size_t)a];
+      }
+      std::ofstream out(conf.grm_pcrelate_inbreeding_output_path);
+      out << "name\tf\tn\n";
+      for (int32_t a = 0; a < m; ++a) {
+        const double twice = 2.0 * diag[(size_t)a];
+        out << names[(size_t)cohort[(size_t)a].index] << "\t" << java_double(twice - 1.0) << "\t" << n_diag[(size_t)a] << "\n";
+      }
+      if (!out) die("cannot write " + conf.grm_pcrelate_inbreeding_output_path);
+    }
+    int64_t used_now = 0;
+    if (pcoa_grm_info(eng, nullptr, &used_now, nullptr) != 1) die(std::string("pcoa_grm_info: ") + pcoa_last_error(eng));
+    std::fprintf(stderr, "GRM PC-Relate: %lld pair(s) with kinship >= %s among %d sample(s), %d %s, %lld used variant(s), threshold %s\n",
+                 (long long)n_found, java_double(conf.grm_pcrelate_cutoff).c_str(), m, kp, kp == 1 ? "axis" : "axes", (long long)used_now,
+                 java_double(conf.grm_pcrelate_maf_threshold).c_str());
+    if (sub) pcoa_destroy(sub);
+  }
+  if (conf.grm && conf.grm_project_removed && grm_full != ctx) pcoa_destroy(grm_full);
   emit_result(conf, rows, n_study);
 
   // --grm-weights-output-path: the left singular vectors of the standardised genotype matrix, one line per variant of the store

@@ -696,6 +696,23 @@ class PcaConf(object):
         p.add_argument("--grm-king-remove", action="store_true",
                        help="--grm-king-cutoff: drop one sample of every reported pair (the rule of --remove-related) and go on "
                             "with the engine's subset over the rest; --grm-project-removed places the dropped samples too")
+        p.add_argument("--grm-pcrelate-output-path", type=str, default=None,
+                       help="--grm: estimate PC-Relate kinship (pcoa_grm_pcrelate_*: kinship adjusted for the ancestry the axes "
+                            "found) behind the last computePca and --grm-project-removed, over the final cohort and the placed "
+                            "removed samples, and write the pairs at or above --grm-pcrelate-cutoff to this file: name_i, name_j, "
+                            "kinship, n")
+        p.add_argument("--grm-pcrelate-pcs", type=int, default=None,
+                       help="--grm-pcrelate-output-path: the axes beside the intercept, in [1, min(8, --num-pc)] (default min(2, --num-pc))")
+        p.add_argument("--grm-pcrelate-cutoff", type=float, default=None,
+                       help="--grm-pcrelate-output-path: report the pairs with kinship at or above this (default 2^-4.5)")
+        p.add_argument("--grm-pcrelate-maf-threshold", type=float, default=None,
+                       help="--grm-pcrelate-output-path: a genotype counts where the individual's own allele frequency lies inside "
+                            "(T, 1 - T), T in [0, 0.5) (default 0.01)")
+        p.add_argument("--grm-pcrelate-inbreeding-output-path", type=str, default=None,
+                       help="--grm-pcrelate-output-path: write name, f = 2 phi(i, i) - 1 and n(i, i) of every sample to this file")
+        p.add_argument("--grm-pcrelate-max-pairs", type=int, default=None,
+                       help="--grm-pcrelate-output-path: the most pairs the job takes from the library (default 1048576); if more "
+                            "are reported the job stops")
         p.add_argument("--grm-output-divisor", type=str, default=None,
                        help="--grm-output-path: used (default): num / M', the mean-imputed K that is decomposed; pairwise: "
                             "num / n(i, j), the pairwise-complete estimator GCTA-style tools store")
@@ -782,6 +799,9 @@ class PcaConf(object):
         self.grm_king_max_pairs_given = a.grm_king_max_pairs is not None
         if a.grm_king_max_pairs is None:
             self.grm_king_max_pairs = RELATED_MAX_PAIRS
+        self.grm_pcrelate_max_pairs_given = a.grm_pcrelate_max_pairs is not None
+        if a.grm_pcrelate_max_pairs is None:
+            self.grm_pcrelate_max_pairs = RELATED_MAX_PAIRS
         self.king_max_pairs_given = a.king_max_pairs is not None
         if a.king_max_pairs is None:
             self.king_max_pairs = RELATED_MAX_PAIRS
@@ -1316,6 +1336,10 @@ def check_grm_conf(conf):
             if given:
                 raise SystemExit("VariantsPcaDriver: %s needs --grm (it screens the genotype store of the standardised-genotype "
                                  "PCA by KING-robust kinship; a stored similarity matrix is screened by --king-cutoff)" % flag)
+        for given, flag in GRM_PCRELATE_FLAGS(conf):
+            if given:
+                raise SystemExit("VariantsPcaDriver: %s needs --grm (it estimates PC-Relate kinship on the genotype store and the "
+                                 "axes of the standardised-genotype PCA)" % flag)
         for given, flag in ((conf.grm_ld_window != 0, "--grm-ld-window"), (conf.grm_ld_r2 is not None, "--grm-ld-r2"),
                             (bool(conf.grm_ld_output_path), "--grm-ld-output-path")):
             if given:
@@ -1369,6 +1393,23 @@ def check_grm_conf(conf):
         if conf.grm_king_remove and conf.grm_cutoff_remove:
             raise SystemExit("VariantsPcaDriver: --grm-king-remove and --grm-cutoff-remove exclude each other (one relatedness "
                              "screen removes samples per run)")
+    if conf.grm_pcrelate_output_path is None:
+        for given, flag in GRM_PCRELATE_FLAGS(conf)[1:]:
+            if given:
+                raise SystemExit("VariantsPcaDriver: %s needs --grm-pcrelate-output-path FILE (PC-Relate is off without it)" % flag)
+    else:
+        most = min(GRM_PCRELATE_MAX_PCS, conf.numPc)
+        if conf.grm_pcrelate_pcs is not None and not 1 <= conf.grm_pcrelate_pcs <= most:
+            raise SystemExit("VariantsPcaDriver: --grm-pcrelate-pcs must be an integer in [1, %d] (min(8, --num-pc)), not %d"
+                             % (most, conf.grm_pcrelate_pcs))
+        if conf.grm_pcrelate_cutoff is not None and not np.isfinite(conf.grm_pcrelate_cutoff):
+            raise SystemExit("VariantsPcaDriver: --grm-pcrelate-cutoff must be a finite number (the kinship at or above which a pair "
+                             "is reported)")
+        if conf.grm_pcrelate_maf_threshold is not None and not (0.0 <= conf.grm_pcrelate_maf_threshold < 0.5):   # (NaN fails)
+            raise SystemExit("VariantsPcaDriver: --grm-pcrelate-maf-threshold must be a number in [0, 0.5)")
+        if conf.grm_pcrelate_max_pairs < 0:
+            raise SystemExit("VariantsPcaDriver: --grm-pcrelate-max-pairs must be >= 0 (the pairs --grm-pcrelate-output-path may "
+                             "report)")
     if conf.grm_project_lsq:
         if not conf.grm_project_path and not conf.grm_project_removed:
             raise SystemExit("VariantsPcaDriver: --grm-project-lsq needs --grm-project-path or --grm-project-removed (it chooses how "
@@ -1475,6 +1516,125 @@ def grm_pairs_rule(k, cutoff, n=0):
     out["i"], out["j"], out["k"] = i, j, k[i, j]
     out["n"] = np.asarray(n)[i, j] if np.ndim(n) == 2 else int(n)
     return out
+
+
+PCRELATE_MAX_COV = 9
+
+
+def pcrelate_hat_rule(basis):
+    """The numpy statement of pcoa_pcrelate_hat (include/pcoa.h), bit for bit: hat = (basis basis^T)^-1 basis for `basis`
+    [n_cov][N], 1 <= n_cov <= 9.  G[c][c'] = sum_i basis[c][i] * basis[c'][i] with i ascending (np.cumsum adds in sequence), the
+    square-root-free L D L^T of pcoa_grm_project_lsq in its sequence, then the forward / diagonal / backward solve of every sample
+    column (vectorised over the samples: every product and difference is one rounded ufunc).  ValueError where the library
+    answers PCOA_ERR_INVALID_ARG."""
+    b = np.ascontiguousarray(basis, dtype=np.float64)
+    if b.ndim != 2:
+        raise ValueError("basis must be [n_cov][N]")
+    k, n = b.shape
+    if not 1 <= k <= PCRELATE_MAX_COV:
+        raise ValueError("n_cov = %d is outside [1, %d]" % (k, PCRELATE_MAX_COV))
+    if n < k:
+        raise ValueError("n = %d samples cannot determine n_cov = %d covariates" % (n, k))
+    if not np.isfinite(b).all():
+        raise ValueError("basis holds a value that is not a finite number")
+    h = [[0.0] * (c + 1) for c in range(k)]
+    for c in range(k):
+        for j in range(c + 1):
+            h[c][j] = float(np.cumsum(b[c] * b[j])[-1])
+    for c in range(k):
+        hcc = h[c][c]
+        for j in range(c):
+            s = h[c][j]
+            for q in range(j):
+                s = s - h[c][q] * h[j][q]
+            h[c][j] = s
+        s = hcc
+        for q in range(c):
+            w = h[c][q]
+            l = w / h[q][q]
+            s = s - w * l
+            h[c][q] = l
+        if not hcc > 0.0 or not np.isfinite(s) or s <= 2.0 ** -40 * hcc:
+            raise ValueError("covariate %d is collinear with the covariates before it" % c)
+        h[c][c] = s
+    y = np.zeros_like(b)
+    for c in range(k):
+        s = b[c].copy()
+        for q in range(c):
+            s = s - h[c][q] * y[q]
+        y[c] = s
+    for c in range(k):
+        y[c] = y[c] / h[c][c]
+    x = np.zeros_like(b)
+    for c in range(k - 1, -1, -1):
+        s = y[c].copy()
+        for q in range(c + 1, k):
+            s = s - h[q][c] * x[q]
+        x[c] = s
+    return x
+
+
+def grm_pcrelate_isaf_rule(beta, basis):
+    """mu_iv [V][N] of pcoa_grm_pcrelate_isaf from beta [V][n_cov] and basis [n_cov][N]: e = beta_v0 * basis[0][i], then
+    e = e + beta_vc * basis[c][i] for c = 1 .. n_cov - 1, every product and sum rounded on its own; mu = 0.5 * e."""
+    beta = np.asarray(beta, dtype=np.float64)
+    basis = np.asarray(basis, dtype=np.float64)
+    if beta.ndim != 2 or basis.ndim != 2 or beta.shape[1] != basis.shape[0]:
+        raise ValueError("beta must be [V][n_cov] and basis [n_cov][N]")
+    e = beta[:, 0:1] * basis[0][None, :]
+    for c in range(1, basis.shape[0]):
+        e = e + beta[:, c:c + 1] * basis[c][None, :]
+    return 0.5 * e
+
+
+def grm_pcrelate_beta_rule(codes, ref_is_a1, hat):
+    """beta [V][n_cov] of pcoa_grm_pcrelate_fit up to the order of its additions: sum_i hat[c][i] * (c_iv ? g_iv : mu_v), for
+    every row of the store."""
+    codes = np.asarray(codes)
+    hom = 3 if ref_is_a1 else 0
+    c = codes != 1
+    g = (codes == 2).astype(np.float64) + 2.0 * (codes == hom).astype(np.float64)
+    nv = c.sum(axis=1).astype(np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        mu = np.where(nv > 0, g.sum(axis=1) / nv, 0.0)
+    return np.where(c, g, mu[:, None]) @ np.asarray(hat, dtype=np.float64).T
+
+
+def grm_pcrelate_rule(codes, ref_is_a1, beta, basis, t, min_maf=0.0, keep=None):
+    """The numpy statement of pcoa_grm_pcrelate_block (include/pcoa.h): (phi, n, num, den) of a cohort given as [V][N] PLINK
+    codes, the fit beta [V][n_cov], the covariates basis [n_cov][N] and the threshold t in [0, 0.5).  used_v is
+    grm_dense_rule's under min_maf, and `keep` ([V] bool, an LD mask) where given.  m = used and called and t < mu < 1 - t;
+    a = m ? g - e : 0; b = m ? sqrt(mu (1 - mu)) : 0; num = a^T a, den = b^T b, n = m^T m; phi = den > 0 ? num / (4 den) : 0."""
+    if not (np.isfinite(t) and 0.0 <= t < 0.5):
+        raise ValueError("t = %r is outside [0, 0.5)" % (t,))
+    codes = np.asarray(codes)
+    hom = 3 if ref_is_a1 else 0
+    c = codes != 1
+    g = (codes == 2).astype(np.float64) + 2.0 * (codes == hom).astype(np.float64)
+    nv = c.sum(axis=1).astype(np.int64)
+    av = (codes == 2).sum(axis=1).astype(np.int64) + 2 * (codes == hom).sum(axis=1).astype(np.int64)
+    used = (nv > 0) & (av > 0) & (av < 2 * nv) & (np.minimum(av, 2 * nv - av).astype(np.float64) >= min_maf * (2.0 * nv.astype(np.float64)))
+    if keep is not None:
+        used = used & np.asarray(keep, dtype=bool)
+    if not used.any():
+        raise ValueError("none of the %d variants is used: phi is undefined" % codes.shape[0])
+    beta, basis = np.asarray(beta, dtype=np.float64), np.asarray(basis, dtype=np.float64)
+    if beta.ndim != 2 or basis.ndim != 2 or beta.shape[1] != basis.shape[0]:
+        raise ValueError("beta must be [V][n_cov] and basis [n_cov][N]")
+    e = beta[:, 0:1] * basis[0][None, :]           # the contract's sequence, as grm_pcrelate_isaf_rule forms it
+    for q in range(1, basis.shape[0]):
+        e = e + beta[:, q:q + 1] * basis[q][None, :]
+    mu = 0.5 * e
+    m = used[:, None] & c & (mu > t) & (mu < 1.0 - t)
+    a = np.where(m, g - e, 0.0)
+    with np.errstate(invalid="ignore"):
+        b = np.where(m, np.sqrt(np.where(m, mu * (1.0 - mu), 0.0)), 0.0)
+    num, den = a.T @ a, b.T @ b
+    mi = m.astype(np.int64)
+    n = mi.T @ mi
+    with np.errstate(divide="ignore", invalid="ignore"):
+        phi = np.where(den > 0, num / (4.0 * den), 0.0)
+    return phi, n, num, den
 
 
 def write_grm_files(prefix, ids, bands):
@@ -1778,6 +1938,93 @@ def grm_screen_king(conf, eng, names, err=None):
     return gone
 
 
+GRM_PCRELATE_MAX_PCS = 8
+GRM_PCRELATE_CUTOFF = 0.044194173824159216   # 2^-4.5, between third and fourth degree (the literal both hosts share)
+GRM_PCRELATE_MAF_THRESHOLD = 0.01
+GRM_PCRELATE_BLOCK = 1024                  # the diagonal blocks n(i, i) is read in
+
+
+def GRM_PCRELATE_FLAGS(conf):
+    """(given, flag) of --grm-pcrelate-output-path and its dependants, the output path first."""
+    return [(conf.grm_pcrelate_output_path is not None, "--grm-pcrelate-output-path"),
+            (conf.grm_pcrelate_pcs is not None, "--grm-pcrelate-pcs"), (conf.grm_pcrelate_cutoff is not None, "--grm-pcrelate-cutoff"),
+            (conf.grm_pcrelate_maf_threshold is not None, "--grm-pcrelate-maf-threshold"),
+            (conf.grm_pcrelate_inbreeding_output_path is not None, "--grm-pcrelate-inbreeding-output-path"),
+            (conf.grm_pcrelate_max_pairs_given, "--grm-pcrelate-max-pairs")]
+
+
+def write_pcrelate_pairs(path, pairs, names):
+    """--grm-pcrelate-output-path: one header line, then name_i, name_j, kinship, n per reported pair in (i, j) order,
+    tab-separated, the kinship as Java's Double.toString writes it."""
+    with open(path, "w") as f:
+        f.write("name_i\tname_j\tkinship\tn\n")
+        for p in pairs:
+            f.write("%s\t%s\t%s\t%d\n" % (names[int(p["i"])], names[int(p["j"])], java_double_to_string(float(p["k"])), int(p["n"])))
+
+
+def write_pcrelate_inbreeding(path, names, phi_diag, n_diag):
+    """--grm-pcrelate-inbreeding-output-path: one header line, then name, f = 2 phi(i, i) - 1 (one product, one difference, as
+    Java's Double.toString writes it) and n(i, i) per sample in cohort order."""
+    with open(path, "w") as f:
+        f.write("name\tf\tn\n")
+        for name, phi, n in zip(names, phi_diag, n_diag):
+            f.write("%s\t%s\t%d\n" % (name, java_double_to_string(2.0 * float(phi) - 1.0), int(n)))
+
+
+def grm_pcrelate(driver, full, eng, kept, meta, err=None):
+    """--grm-pcrelate-output-path, behind the last computePca and --grm-project-removed.  The cohort is the final cohort (`kept`,
+    engine `eng`) plus the removed samples --grm-project-removed placed (driver.last_placed), in fileset index order; its engine
+    is `eng` itself, or a panel subset of the whole-fileset engine `full` over the cohort, pruned under --grm-ld-window like every
+    round's engine.  The covariates are a row of ones and the first K coordinates of every cohort sample -- u_c for the final
+    cohort, the projected coordinate for a placed one -- and the hat matrix is pcoa_pcrelate_hat's.  n(i, i) of the inbreeding
+    file is read with pcoa_grm_pcrelate_block's pair counts over diagonal blocks."""
+    from .engine import pcrelate_hat
+    conf, err = driver.conf, err or sys.stderr
+    k = conf.grm_pcrelate_pcs if conf.grm_pcrelate_pcs is not None else min(2, conf.numPc)
+    x = GRM_PCRELATE_CUTOFF if conf.grm_pcrelate_cutoff is None else conf.grm_pcrelate_cutoff
+    t = GRM_PCRELATE_MAF_THRESHOLD if conf.grm_pcrelate_maf_threshold is None else conf.grm_pcrelate_maf_threshold
+    cap = conf.grm_pcrelate_max_pairs
+    comps, _ = driver.last_pca
+    reverse = dict((v, c) for (c, v) in driver.indexes.items())
+    placed_idx, placed_coords = getattr(driver, "last_placed", None) or (np.zeros(0, dtype=np.int64), np.zeros((0, comps.shape[1])))
+    kept = np.asarray(kept, dtype=np.int64)
+    cohort = np.concatenate([kept, np.asarray(placed_idx, dtype=np.int64)])
+    coords = np.concatenate([np.asarray(comps)[:, :k], np.asarray(placed_coords)[:, :k]], axis=0)
+    order = np.argsort(cohort, kind="stable")
+    cohort, coords = cohort[order], coords[order]
+    sub = None
+    if len(placed_idx):
+        least = max(GRM_MIN_COHORT, conf.numPc + 1)
+        if cohort.size < least:
+            raise SystemExit("VariantsPcaDriver: --grm-pcrelate-output-path: the cohort holds %d samples, fewer than the %d a GRM "
+                             "engine with %d principal components needs" % (cohort.size, least, conf.numPc))
+        sub = grm_subset_engine(full, cohort, conf.grm_min_maf or 0.0, err=err)
+        if conf.grm_ld_window:
+            grm_ld_prune(conf, sub, meta)
+        eng = sub
+    try:
+        names = [driver.names[reverse[int(i)]] for i in cohort]
+        basis = np.ascontiguousarray(np.vstack([np.ones((1, cohort.size)), coords.T]))
+        eng.grm_pcrelate_fit(basis, pcrelate_hat(basis))
+        pairs, n_found, diag = eng.grm_pcrelate_pairs(x, t, capacity=cap, diag=True)
+        if n_found > cap:
+            raise SystemExit("VariantsPcaDriver: --grm-pcrelate-cutoff %s reports %d pairs, more than --grm-pcrelate-max-pairs %d "
+                             "takes; raise --grm-pcrelate-max-pairs or the cutoff" % (java_double_to_string(x), n_found, cap))
+        write_pcrelate_pairs(conf.grm_pcrelate_output_path, pairs, names)
+        if conf.grm_pcrelate_inbreeding_output_path:
+            n_diag = np.zeros(cohort.size, dtype=np.int64)
+            for r0 in range(0, cohort.size, GRM_PCRELATE_BLOCK):
+                r = min(GRM_PCRELATE_BLOCK, cohort.size - r0)
+                n_diag[r0:r0 + r] = np.diagonal(eng.grm_pcrelate_block(r0, r, r0, r, t, pairs=True)[1])
+            write_pcrelate_inbreeding(conf.grm_pcrelate_inbreeding_output_path, names, diag, n_diag)
+        err.write("GRM PC-Relate: %d pair(s) with kinship >= %s among %d sample(s), %d %s, %d used variant(s), threshold %s\n"
+                  % (n_found, java_double_to_string(x), cohort.size, k, "axis" if k == 1 else "axes", eng.grm_info()[1],
+                     java_double_to_string(t)))
+    finally:
+        if sub is not None:
+            sub.close()
+
+
 def grm_compute_rounds(driver, full, kept, meta, err=None):
     """computePca of --grm around --grm-keep-samples / --grm-remove-samples (`kept`: the list's indices, or None) and
     --grm-outlier-iterations K: the loop of computePcaOutlierRounds with the engine replaced by its grm_subset over the kept
@@ -1867,12 +2114,14 @@ def grm_project_removed(driver, full, eng, kept, err=None, never=None):
     removed = np.setdiff1d(np.arange(len(driver.indexes)), kept)
     if never is not None and not driver.conf.grm_project_lsq:
         removed = np.setdiff1d(removed, never)
+    driver.last_placed = None
     if removed.size == 0:
         return []
     comps, lam = driver.last_pca
     reverse = dict((v, k) for (k, v) in driver.indexes.items())
     with grm_subset_engine(full, removed, 0.0, study=True, err=err) as study:
         coords, placed = grm_place(driver.conf, eng, study, comps, lam, "removed ", [driver.names[reverse[int(i)]] for i in removed], err)
+    driver.last_placed = (removed[np.asarray(placed, dtype=bool)], np.asarray(coords)[np.asarray(placed, dtype=bool)])
     return [(reverse[int(i)], driver.names[reverse[int(i)]], float(coords[q, 0]), float(coords[q, 1])) for q, i in enumerate(removed)
             if placed[q]]
 
@@ -2397,8 +2646,10 @@ def main(args):
         study = grm_project_study(conf, driver.engine, comps, lam) if conf.grm_project_path else []
         if conf.grm_project_removed:
             study = study + grm_project_removed(driver, full, driver.engine, kept, never=mind_gone)
-            if full is not driver.engine:
-                full.close()
+        if conf.grm_pcrelate_output_path is not None:
+            grm_pcrelate(driver, full, driver.engine, kept, variant_meta)
+        if conf.grm_project_removed and full is not driver.engine:
+            full.close()
         driver.emitResult(result, study=study or None)
         if conf.grm_weights_output_path:
             write_loadings(conf.grm_weights_output_path, variant_meta, driver.engine.grm_weights(comps, lam, scaled=True))
